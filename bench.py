@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark of the MI355X evaluation hot path.
 
     python bench.py --gpus N --steps K --warmup W [--config 3s|2|5s] [--decimal]
-                    [--scaling weak|strong]
+                    [--scaling weak|strong] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic input that
 is already resident in HBM: for BOTH evaluators (image-level LVISEval and
@@ -34,15 +34,23 @@ all_gather per evaluator.  `--shard category`: every rank evaluates a
 contiguous category block of the union of all shards (no record exchange, but
 every rank flattens the whole input) (tao_amodal_amd/dist.py).
 
+The timed region is exactly K steps after W warm-up steps; `ms_per_step` is
+its wall-clock time over K.  `--dump-outputs DIR` writes what the timed path
+left behind after its last step -- the evaluators' tables, per-detection match
+rows, the track-level IoUs -- as DIR/<name>.npy in float64 (at most 64 MB in
+all: see dump_outputs).  The synthetic input is a function of the arguments
+(--seed), so two builds run with the same arguments can be compared output for
+output.
+
 Prints ONE JSON line on rank 0 (see the driver contract in the task text).
 """
 import argparse
 import json
-import math
 import os
 import subprocess
 import sys
 import time
+import zlib
 
 # (before numpy / torch / the native libraries load libgomp: tao_amodal_amd/__init__.py)
 os.environ.setdefault("OMP_WAIT_POLICY", "PASSIVE")
@@ -54,7 +62,6 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: 8 TB/s spec
-MIN_TIMED_S = 0.25        # floor of the timed region, whatever --steps says
 PROBE_EVERY = 8           # steps between two per-kernel event probes
 
 CONFIGS = {
@@ -114,7 +121,13 @@ def parse():
                         "the printed value counts this rank's pairs only)")
     p.add_argument("--force-dist", action="store_true",
                    help="take the multi-GPU code path even with one rank")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last one computed "
+                        "as DIR/<name>.npy (rank 0; fixed seeded samples of the "
+                        "large tables)")
     a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
     if a.leg == "decimal":
         a.decimal, a.no_wallclock, a.no_decimal_leg = True, True, True
     cfg = CONFIGS[a.config]
@@ -445,6 +458,78 @@ def wallclock_leg(gt, dt):
         shutil.rmtree(d, ignore_errors=True)
 
 
+# --------------------------------------------------------------------------
+# --dump-outputs: what the timed path computed, for output-for-output checks
+# --------------------------------------------------------------------------
+DUMP_SAMPLE = 1 << 19          # elements kept of a larger table (seeded sample)
+DUMP_DETECTIONS = 1 << 15      # detections whose match rows are kept
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _dump_index(name, n, k):
+    """Sorted positions of a fixed sample of k out of n: seeded by the array's
+    name, so every run with the same arguments picks the same ones."""
+    rng = np.random.default_rng([20240807, zlib.crc32(name.encode())])
+    return np.sort(rng.choice(n, size=k, replace=False))
+
+
+def dump_outputs(out_dir, sides):
+    """Write rank 0's result tensors of the last pass as out_dir/<name>.npy,
+    all in float64 (integers below 2^53 and the 32-bit halves of the match
+    words convert exactly).  Per evaluator side (lvis, tao):
+
+      <side>_precision [T,R,K,A], <side>_recall [T,K,A], <side>_num_gt [K,A]
+          whole when they hold at most DUMP_SAMPLE elements, otherwise a seeded
+          sample of DUMP_SAMPLE elements of the flattened (C-order) table with
+          their positions in <name>_index;
+      <side>_matched / <side>_ignored [S, words, 2]: the match bit rows of S
+          sampled detections (input order, positions in <side>_detection_index),
+          every 64-bit word as (low, high) 32-bit halves;
+      tao_iou: the track pairs' 3D IoUs (sampled the same way).
+
+    On the multi-GPU path (dp is None) the assembled precision / recall
+    tables, which every rank holds, are written.  Returns {name: shape}."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+
+    def table(name, t):
+        flat = t.reshape(-1)
+        if flat.numel() <= DUMP_SAMPLE:
+            arrays[name] = t.cpu().numpy().astype(np.float64)
+            return
+        idx = _dump_index(name, flat.numel(), DUMP_SAMPLE)
+        arrays[name] = flat[torch.from_numpy(idx).to(flat.device)].cpu().numpy() \
+            .astype(np.float64)
+        arrays[name + "_index"] = idx.astype(np.float64)
+
+    for side, dp, ws in sides:
+        table(side + "_precision", ws.precision)
+        table(side + "_recall", ws.recall)
+        if dp is None:
+            continue
+        table(side + "_num_gt", ws.num_gt)
+        if dp.kind == "tao":
+            table("tao_iou", ws.iou[:dp.n_iou])
+        n = dp.n_dt
+        if n:
+            det = np.arange(n) if n <= DUMP_DETECTIONS else \
+                _dump_index(side + "_detection_index", n, DUMP_DETECTIONS)
+            d = torch.from_numpy(det).to(ws.dst.device)
+            at = ws.dst[:n][d].long()            # a detection's row sits at dst
+            arrays[side + "_detection_index"] = det.astype(np.float64)
+            for name, rows in (("matched", ws.matched), ("ignored", ws.ignored)):
+                w = rows[at].cpu().numpy().view(np.uint64)
+                arrays[side + "_" + name] = np.stack(
+                    [(w & 0xFFFFFFFF).astype(np.float64),
+                     (w >> np.uint64(32)).astype(np.float64)], axis=-1)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "dump of %d bytes" % total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     args = parse()
     world_env = os.environ.get("WORLD_SIZE")
@@ -461,11 +546,6 @@ def main():
     sys.stdout.flush()
     real_stdout = os.fdopen(os.dup(1), "w")
     os.dup2(2, 1)
-    if world > 1 or args.force_dist:
-        # the category-partitioned step keeps 4 compute streams + the RCCL
-        # stream busy; with the default of 4 hardware queues per process they
-        # alias and serialise (measured 1.25 -> 0.94 ms/step with 8)
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     import torch
     import torch.distributed as dist
     rank = int(os.environ.get("RANK", "0"))
@@ -595,19 +675,9 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    # ---- how many repetitions of the K steps make the timed region >= 0.25 s
-    bracket()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    bracket()
-    calib = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
-    if use_dist:
-        dist.all_reduce(calib, op=dist.ReduceOp.MAX)
-    reps = max(1, int(math.ceil(MIN_TIMED_S / max(float(calib.item()), 1e-6))))
-    timed_steps = reps * args.steps
+    timed_steps = args.steps
 
-    # ---- the timed region: reps x K steps between two barrier + synchronize
+    # ---- the timed region: K steps between two barrier + synchronize
     _lib.kernel_timings()                  # forget anything recorded so far
     # (look-backs of the one-pass sweep that give up anywhere in the region
     # count into this word; the workspaces' own flags are per pass -- an
@@ -653,6 +723,16 @@ def main():
                                  getattr(plan.tao, "sweep_recovered", 0))
     else:
         look_back_timeouts = int(engine.sweep_ok(dpl, wsl)) + int(engine.sweep_ok(dpt, wst))
+    # ---- the last timed step's results, before anything below runs a pass again
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        torch.cuda.synchronize()
+        if use_dist:
+            dumped = dump_outputs(args.dump_outputs, [("lvis", None, plan.lvis),
+                                                      ("tao", None, plan.tao)])
+        else:
+            dumped = dump_outputs(args.dump_outputs, [("lvis", dpl, wsl),
+                                                      ("tao", dpt, wst)])
     # ---- every kernel alone: a few serial steps, one stream, events on
     alone = {}
     if rank == 0 and not use_dist:
@@ -974,6 +1054,7 @@ def main():
                        "parallelism": ("single GPU" if not use_dist else
                                        "%s-sharded x%d" % (args.shard, world))},
             "timed_steps": timed_steps,
+            "dumped_outputs": dumped,
             "timed_region_s": round(elapsed, 4),
             "roofline": roof, "roofline_other": roof_other,
             "step_roofline": step_roof,

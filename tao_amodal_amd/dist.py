@@ -60,12 +60,10 @@ standing in for the kernels.
 """
 import os
 
-# (the by-video step keeps 4 compute streams + RCCL's busy: with the default of
-# 4 hardware queues per process they alias and serialise -- 1.25 -> 0.94 ms/step
-# with GPU_MAX_HW_QUEUES=8.  The HIP runtime reads it when it starts: whoever
-# starts a multi-GPU process sets it before the first device call --
-# evaluation/_dist.init_from_env, bench.py -- importing this module does not
-# touch the environment.)
+# (the by-video step keeps 4 compute streams + RCCL's busy; the streams share
+# the process's hardware queues, which the HIP runtime sizes from its
+# environment when it starts.  Neither this module nor its launchers change
+# that number: importing this module does not touch the environment.)
 
 import numpy as np
 import torch
@@ -740,9 +738,8 @@ class CategoryPlan:
     track-level kernels still run; keeping the longer, image-level chain free
     of cross-stream waits took the one-rank step from 0.63 to 0.57 ms and a
     rank's share of an 8-rank job from 0.72 to 0.60 ms.  Five streams are busy
-    at once (4 + RCCL's): run with GPU_MAX_HW_QUEUES >= 8, the
-    default of 4 hardware queues per process makes them alias (bench.py sets
-    it)."""
+    at once (4 + RCCL's); they share the process's hardware queues, so with
+    fewer queues than streams some of them alias and serialise."""
 
     def __init__(self, dpl, dpt, rank, world, device, backend=None, group=None):
         from . import engine

@@ -54,8 +54,6 @@ def init_from_env():
     """Process group from the launcher's environment (torchrun).  One GPU per
     rank -> RCCL; fewer GPUs than ranks (a development box) -> the ranks share
     GPU 0 and talk over gloo, device tensors staged through the host."""
-    # (read by the HIP runtime when it starts: before the first device call)
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     import torch
     import torch.distributed as dist
     world = int(os.environ["WORLD_SIZE"])

@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 import orclib
-from goldenio import FIXTURES, INTEGER_FIXTURES, load_eval, load_inputs, load_json_gz
+from goldenio import FIXTURES, INTEGER_FIXTURES, load_eval, load_inputs, load_json_gz, path
 from tao_amodal_amd.columns import DTColumns, GTColumns
 from tao_amodal_amd import flatten as fl
 
@@ -170,15 +170,12 @@ def test_thresholds_are_numpy_linspace_bit_for_bit():
 
 
 def test_bb_iou_against_reference_compiled_from_source():
-    """oracle/_ref holds bbIou compiled from the reference's own maskApi.c."""
-    import os
-    if not os.path.exists(orclib.REF_SO):
-        pytest.skip("oracle/_ref not built")
-    rng = np.random.default_rng(5)
-    for scale in (1.0, 0.37):
-        dt = np.c_[rng.integers(-50, 500, (200, 2)), rng.integers(0, 300, (200, 2))] * scale
-        gt = np.c_[rng.integers(-50, 500, (90, 2)), rng.integers(0, 300, (90, 2))] * scale
-        assert np.array_equal(orclib.bb_iou(dt, gt), orclib.ref_bb_iou(dt, gt))
+    """bbIou of the reference's own maskApi.c on seeded boxes, integer and
+    decimal (tests/golden/maskapi, tests/golden/make_golden_maskapi.py)."""
+    z = np.load(path("maskapi", "bb_iou.npz"))
+    for case in ("int", "dec"):
+        dt, gt = z[case + "_dt"], z[case + "_gt"]
+        assert np.array_equal(orclib.bb_iou(dt, gt), z[case + "_iou"])
     assert orclib.bb_iou([[0, 0, 20, 20]], [[0, 0, 10, 10]])[0, 0] == 0.25
 
 

@@ -6,7 +6,7 @@ import pytest
 
 import exchange_ref
 import orclib
-from goldenio import FIXTURES, INTEGER_FIXTURES, load_eval, load_inputs, load_json_gz
+from goldenio import FIXTURES, INTEGER_FIXTURES, load_eval, load_inputs, load_json_gz, path
 from test_flat_oracle_golden import _check_side
 from tao_amodal_amd import flatten as fl
 from tao_amodal_amd.columns import DTColumns, GTColumns
@@ -162,23 +162,21 @@ def test_cells_with_more_than_64_ground_truths():
 
 
 def test_bb_iou_entry_points_match_reference_bbiou():
-    """taoamd_bb_iou[_host] against the C oracle and (when present) the
-    reference's own bbIou compiled from its source (oracle/_ref)."""
-    import ctypes, os
+    """taoamd_bb_iou[_host] against the C oracle and the reference's own
+    bbIou (its answers stored under tests/golden/maskapi)."""
     import torch
     from tao_amodal_amd import _lib
     lib = _lib.load()
-    rng = np.random.default_rng(3)
-    dt = np.c_[rng.integers(-50, 500, (300, 2)), rng.integers(0, 300, (300, 2))] * 0.37
-    gt = np.c_[rng.integers(-50, 500, (77, 2)), rng.integers(0, 300, (77, 2))] * 0.37
-    dt, gt = np.ascontiguousarray(dt), np.ascontiguousarray(gt)
+    # seeded boxes and the reference maskApi.c's bbIou of them
+    # (tests/golden/make_golden_maskapi.py)
+    z = np.load(path("maskapi", "bb_iou.npz"))
+    dt, gt = z["parity_dt"], z["parity_gt"]
     o = np.zeros(300 * 77)
     _lib.check(lib.taoamd_bb_iou_host(dt.ctypes.data, gt.ctypes.data, 300, 77, None,
                                       o.ctypes.data), "bb_iou_host")
     got = o.reshape((300, 77), order="F")
     assert np.array_equal(got, orclib.bb_iou(dt, gt))
-    if os.path.exists(orclib.REF_SO):
-        assert np.array_equal(got, orclib.ref_bb_iou(dt, gt))
+    assert np.array_equal(got, z["parity_iou"])
     d_dt, d_gt = torch.from_numpy(dt).cuda(), torch.from_numpy(gt).cuda()
     d_o = torch.empty(300 * 77, dtype=torch.float64, device="cuda")
     _lib.check(lib.taoamd_bb_iou(d_dt.data_ptr(), d_gt.data_ptr(), 300, 77, None,

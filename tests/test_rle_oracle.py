@@ -1,65 +1,47 @@
 """oracle/rle.py + pyoracle.lvis_eval(iou_type="segm") (test infrastructure)
-pinned to (i) the reference's own maskApi.c compiled where it lies
-(oracle/_ref) and (ii) the golden vectors of fixture F6 -- the reference
-LVISEval run with iou_type="segm" (tests/golden/make_golden_segm.py)."""
+pinned to (i) the answers of the reference's own maskApi.c on seeded cases
+(tests/golden/maskapi, written by tests/golden/make_golden_maskapi.py) and
+(ii) the golden vectors of fixture F6 -- the reference LVISEval run with
+iou_type="segm" (tests/golden/make_golden_segm.py)."""
 import gzip
 import json
-import os
 
 import numpy as np
 import pytest
 
-import orclib
 from goldenio import path
 from oracle import pyoracle, rle
 
-needs_ref = pytest.mark.skipif(not os.path.exists(orclib.REF_SO),
-                               reason="oracle/_ref not built")
+
+def load_maskapi():
+    """The reference maskApi.c's answers on seeded cases
+    (tests/golden/make_golden_maskapi.py)."""
+    with gzip.open(path("maskapi", "rle.json.gz"), "rt") as f:
+        return json.load(f)
 
 
-def _rand_poly(rng, h, w, k=None, spread=0.5):
-    k = k or int(rng.integers(3, 9))
-    cx, cy = rng.uniform(0, w), rng.uniform(0, h)
-    return np.c_[cx + rng.uniform(-w * spread, w * spread, k),
-                 cy + rng.uniform(-h * spread, h * spread, k)].ravel()
-
-
-@needs_ref
 def test_polygon_rasterisation_and_text_form_against_reference_c():
-    rng = np.random.default_rng(1)
-    for it in range(300):
-        h, w = int(rng.integers(5, 60)), int(rng.integers(5, 80))
-        xy = _rand_poly(rng, h, w, spread=0.7)
-        if it % 3 == 0:
-            xy = np.round(xy)
-        if it % 7 == 0:
-            xy[2:4] = xy[0:2]                   # repeated vertex
-        a = rle.fr_poly(xy.tolist(), h, w)
-        assert a == orclib.ref_rle_fr_poly(xy, h, w), it
+    cases = load_maskapi()["poly"]
+    assert len(cases) == 300
+    for it, c in enumerate(cases):
+        h, w = c["h"], c["w"]
+        a = rle.fr_poly(c["xy"], h, w)
+        assert a == c["rle"], it
         s = rle.to_string(a)
-        assert s == orclib.ref_rle_to_string(a)
-        assert rle.fr_string(s, h, w) == a == orclib.ref_rle_fr_string(s, h, w)
-        assert rle.to_bbox(a) == orclib.ref_rle_to_bbox(a)
-        assert rle.area(a) == orclib.ref_rle_area(a)
+        assert s == c["string"]
+        assert rle.fr_string(s, h, w) == a == c["fr_string"]
+        assert rle.to_bbox(a) == c["bbox"]
+        assert rle.area(a) == c["area"]
 
 
-@needs_ref
 def test_merge_and_iou_against_reference_c():
-    rng = np.random.default_rng(2)
-    for it in range(150):
-        h, w = int(rng.integers(8, 50)), int(rng.integers(8, 60))
-        mk = lambda hh=h: rle.fr_poly(_rand_poly(rng, hh, w).tolist(), hh, w)
-        ms = [mk() for _ in range(int(rng.integers(1, 5)))]
-        for inter in (False, True):
-            assert rle.merge(ms, inter) == orclib.ref_rle_merge(ms, inter), it
-        ds, gs = [mk() for _ in range(4)], [mk() for _ in range(3)]
-        if it % 10 == 0:
-            gs[0] = mk(h + 1)                               # another frame size
-        if it % 9 == 0:
-            ds[1] = {"h": h, "w": w, "counts": [h * w]}     # empty mask
-        if it % 8 == 0:
-            ds[2] = {"h": h, "w": w, "counts": [0, h * w]}  # full mask
-        assert np.array_equal(rle.iou_matrix(ds, gs), orclib.ref_rle_iou(ds, gs)), it
+    cases = load_maskapi()["merge"]
+    assert len(cases) == 150
+    for it, c in enumerate(cases):
+        assert rle.merge(c["masks"], False) == c["union"], it
+        assert rle.merge(c["masks"], True) == c["intersection"], it
+        assert np.array_equal(rle.iou_matrix(c["dts"], c["gts"]),
+                              np.asarray(c["iou"], dtype=np.float64)), it
 
 
 def test_known_answers():
