@@ -186,6 +186,40 @@ int taoamd_rle_iou(int64_t n_cells, const int32_t *cell_dt_off,
                    const int32_t *gt_hw, const double *gt_bb, double *iou,
                    void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- 3D IoU of mask tracks (TaoEval iou_type="segm") ------------------------
+ * iou[cell_iou_off[c] + d*G + g] for every cell c, from run-length masks instead
+ * of boxes: replaces compute_iou's three track functions (T/eval.py:51-117,
+ * 306-335) for the "segmentation" annotation type, a path the reference cannot
+ * run (Tao has no ann_to_rle, T/eval.py:173-176).  Tracks are CSR lists of
+ * timeline positions sorted ascending (*_frame_off[n_trk + 1],
+ * *_frame_pos[*_frames]); frame k of a side has mask k of that side (CSR run
+ * lists *_off / *_runs and frame size *_hw[k] = (height, width), as
+ * taoamd_rle_copy produces them; no tight box: see the kernel).  Per shared
+ * position t: i_t = |d_t & g_t|, u_t = |d_t | g_t|, both 0 when the frame sizes
+ * differ.  mode 0 = 3d_iou: sum i_t / (sum u_t + the pixels of the frames only
+ * one track has), integers summed exactly, 0 when the denominator is 0;
+ * 1 = avg_iou: the ratios i_t / u_t (0 where u_t = 0) added in ascending
+ * timeline order, over |F_d u F_g|; 2 = imagenetvid: #{t : i_t > u_t / 2} over
+ * |F_d u F_g|.  n_pairs = cell_iou_off[n_cells].  pair_frames (optional,
+ * int64[1], zeroed by the call) receives the number of shared (pair, frame)
+ * items.  Workspace: taoamd_track_mask_iou_workspace(dt_frames, dt_total,
+ * gt_frames, gt_total) bytes (per-run prefix sums, rebuilt by every call). */
+size_t taoamd_track_mask_iou_workspace(int64_t dt_frames, int64_t dt_total,
+                                       int64_t gt_frames, int64_t gt_total);
+int taoamd_track_mask_iou(int64_t n_cells, const int32_t *cell_dt_off,
+                          const int32_t *cell_gt_off, const int64_t *cell_iou_off,
+                          int64_t n_pairs, const int32_t *dt_frame_off,
+                          const int32_t *dt_frame_pos, int64_t dt_frames,
+                          int64_t dt_total, const int64_t *dt_off,
+                          const uint32_t *dt_runs, const int32_t *dt_hw,
+                          const int32_t *gt_frame_off,
+                          const int32_t *gt_frame_pos, int64_t gt_frames,
+                          int64_t gt_total, const int64_t *gt_off,
+                          const uint32_t *gt_runs, const int32_t *gt_hw,
+                          int32_t mode, double *iou,
+                          int64_t *pair_frames, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
 /* ---- 3D IoU of track pairs --------------------------------------------------
  * iou[cell_iou_off[c] + d*G + g] for every cell c (G = its GT track count).
  * Tracks are CSR lists of (timeline position, box) sorted by position.

@@ -25,7 +25,7 @@
 // are read through the caches.  Integer adds / compares on data read once: no
 // use for the matrix cores; measured bound by instruction issue and LDS
 // latency, not by HBM.
-#include "common.hpp"
+#include "rle_walk.hpp"
 
 using namespace taoamd;
 
@@ -43,47 +43,9 @@ struct RleArgs {
     double *iou;
 };
 
-// one wavefront per mask: inclusive scans of the run lengths and of the
-// lengths of the odd-numbered runs (the ones)
-// (detections are only ever the "A" of a pair: their P is not stored.  Summing
-// their boundaries inside the IoU kernel instead, lazily for the detections
-// that have a pair to walk, was measured slower: 0.56 vs 0.54 ms.)
-template <bool WITH_P>
-__global__ __launch_bounds__(256) void rle_prefix_kernel(int64_t n,
-                                                         const int64_t *off,
-                                                         const uint32_t *runs,
-                                                         void *out, uint32_t *ones)
-{
-    const int lane = lane_id();
-    const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (m >= n) return;
-    const int64_t b = off[m], k = off[m + 1] - b;
-    uint32_t carry_e = 0, carry_p = 0;
-    for (int64_t base = 0; base < k; base += WAVE) {
-        const int64_t i = base + lane;
-        const uint32_t c = i < k ? runs[b + i] : 0;
-        uint32_t e = c, p = (i & 1) ? c : 0;
-#pragma unroll
-        for (int s = 1; s < WAVE; s <<= 1) {
-            const uint32_t ue = __shfl_up(e, s, WAVE), up = __shfl_up(p, s, WAVE);
-            if (lane >= s) { e += ue; p += up; }
-        }
-        e += carry_e;
-        p += carry_p;
-        if (i < k) {
-            if (WITH_P) ((uint2 *)out)[b + i] = make_uint2(e, p);
-            else ((uint32_t *)out)[b + i] = e;
-        }
-        carry_e = __shfl(e, WAVE - 1, WAVE);
-        carry_p = __shfl(p, WAVE - 1, WAVE);
-    }
-    if (lane == 0) ones[m] = carry_p;
-}
-
 #ifndef RLE_THREADS
 #define RLE_THREADS 512         // 8 wavefronts (256: 0.77 ms, 1024: 0.64 ms, 512: 0.57 ms)
 #endif
-#define RLE_RPT 8               // run boundaries of A a lane keeps in registers (even)
 #define RLE_GTILE 64            // ground truths looked at together (one per lane)
 
 // One workgroup = one cell, one wavefront = one detection at a time.  For a
@@ -117,13 +79,7 @@ __device__ __forceinline__ void rle_cell(const RleArgs &a, int32_t d0, int32_t D
         uint32_t xq[RLE_RPT];
         bool use[RLE_RPT];
         auto load_piece = [&](uint32_t piece) {
-#pragma unroll
-            for (int q = 0; q < RLE_RPT; q++) {
-                const uint32_t i = piece * (RLE_RPT * WAVE) + (uint32_t)lane * RLE_RPT + q;
-                use[q] = i < ka && ((i & 1) || i + 1 < ka);
-                // past the end: 0, a boundary that makes the walk below stand still
-                xq[q] = i < ka ? a.dt_end[ab + i] : 0u;
-            }
+            rle_load_piece(piece, lane, a.dt_end + ab, ka, xq, use);
         };
         load_piece(0);
         for (int32_t gbase = 0; gbase < G; gbase += RLE_GTILE) {
@@ -152,48 +108,7 @@ __device__ __forceinline__ void rle_cell(const RleArgs &a, int32_t d0, int32_t D
                 uint32_t acc = 0;
                 for (uint32_t piece = 0; piece < n_pieces; piece++) {
                     if (n_pieces > 1) load_piece(piece);
-                    // one binary search per lane, for its first boundary
-                    // (branch-free: ceil(log2(kb + 1)) halvings) ...
-                    uint32_t lo = 0, hi = kb;
-                    for (uint32_t span = kb; span != 0; span >>= 1) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        const uint32_t e = tab[min(mid, kb - 1)].x;
-                        const bool open = lo < hi, right = e <= xq[0];
-                        lo = (open && right) ? mid + 1 : lo;
-                        hi = (open && !right) ? mid : hi;
-                    }
-                    // ... then B's runs are followed while the lane's own
-                    // boundaries rise: both lists are sorted, so all of it is
-                    // one merge of ~RLE_RPT * (1 + kb / ka) steps per lane.
-                    // (Searching every boundary on its own costs ~10 rounds
-                    // x 12 VALU instructions each: measured 4x slower, the
-                    // kernel is bound by instruction issue, not by the LDS.)
-                    uint32_t r = lo;
-                    uint2 cur = tab[min(r, kb - 1)];
-#pragma unroll
-                    for (int q = 0; q < RLE_RPT; q++) {
-                        if (!use[q]) continue;      // (also the trailing run of zeros)
-                        const uint32_t x = xq[q];
-                        // a few steps usually do; a long stretch of B inside
-                        // one run of A (A in two distant parts, A's last run)
-                        // is crossed by bisection instead
-                        for (int step = 0; step < 4 && r < kb && cur.x <= x; step++) {
-                            r++;
-                            cur = tab[min(r, kb - 1)];
-                        }
-                        if (r < kb && cur.x <= x) {
-                            uint32_t l2 = r + 1, h2 = kb;
-                            while (l2 < h2) {
-                                const uint32_t mid = (l2 + h2) >> 1;
-                                if (tab[mid].x <= x) l2 = mid + 1; else h2 = mid;
-                            }
-                            r = l2;
-                            cur = tab[min(r, kb - 1)];
-                        }
-                        const uint32_t part = (r & 1) ? cur.x - x : 0u;
-                        const uint32_t f = r < kb ? cur.y - part : ones_b;
-                        acc += (q & 1) ? f : 0u - f;
-                    }
+                    rle_lane_walk(xq, use, tab, kb, ones_b, acc);
                 }
 #pragma unroll
                 for (int s = WAVE / 2; s > 0; s >>= 1) acc += __shfl_xor(acc, s, WAVE);

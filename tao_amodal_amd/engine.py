@@ -238,15 +238,20 @@ class DeviceProblem:
         for n in names:
             self.t[n] = on_dev[n].to(self.device) if n in on_dev else \
                 _to_device(flat[n], self.device)
-        # iou_type="segm": run-length masks, row i = detection / ground truth
-        # i of the tables (masks.MaskArrays); the IoU then comes from
-        # taoamd_rle_iou instead of the boxes
-        masks = flat.get("masks") if self.kind == "lvis" else None
+        # iou_type="segm": run-length masks (masks.MaskArrays), row i = detection
+        # / ground truth i of the tables (image level) or frame i of the
+        # *_frame_* lists (track level); the IoU then comes from taoamd_rle_iou
+        # / taoamd_track_mask_iou instead of the boxes
+        masks = flat.get("masks")
         self.mask_iou = masks is not None
-        self.rle_total = {}
+        self.rle_total, self.rle_rows = {}, {}
         if self.mask_iou:
             self.rle_total = {k: int(masks[k].off[-1]) for k in ("dt", "gt")}
-            for side, n_rows in (("dt", self.n_dt), ("gt", self.n_gt)):
+            rows = (("dt", self.n_dt), ("gt", self.n_gt)) if self.kind == "lvis" else \
+                (("dt", int(self.t["dt_frame_pos"].numel())),
+                 ("gt", int(self.t["gt_frame_pos"].numel())))
+            self.rle_rows = dict(rows)
+            for side, n_rows in rows:
                 m = masks[side]
                 if len(m) != n_rows:
                     raise _lib.TaoAmdError(
@@ -337,6 +342,8 @@ class DeviceProblem:
             self.t[k] = None
         if self.device.type != "cuda":     # host-side plumbing tests: no kernels
             return
+        if self.mask_iou:                  # taoamd_track_mask_iou: no plan
+            return
         meta, sides, n_slots = track_meta(flat)
         n_frames = sum(int(getattr(flat, "dev", {})[k].numel())
                        if k in getattr(flat, "dev", {}) and not dict.__contains__(flat, k)
@@ -420,6 +427,7 @@ class DeviceProblem:
         per-frame ratios are rounded divisions.  One-frame tracks have a
         single term in every mode."""
         return (self.kind == "tao" and self.n_iou > 0 and self.iou_mode != 2
+                and not self.mask_iou
                 and not (self.exact_terms and self.iou_mode == 0)
                 and not self.single_frame and self.device.type == "cuda")
 
@@ -525,8 +533,11 @@ class Workspace:
         elif dp.mask_iou:
             self.iou = torch.empty(max(dp.n_iou, 1), dtype=torch.float64,
                                    device=dev)
-            self.rle_bytes = lib.taoamd_rle_iou_workspace(
-                dp.n_dt, dp.rle_total["dt"], dp.n_gt, dp.rle_total["gt"])
+        if dp.mask_iou:
+            ws_bytes = lib.taoamd_rle_iou_workspace if dp.kind == "lvis" else \
+                lib.taoamd_track_mask_iou_workspace
+            self.rle_bytes = ws_bytes(dp.rle_rows["dt"], dp.rle_total["dt"],
+                                      dp.rle_rows["gt"], dp.rle_total["gt"])
             self.rle_ws = buf(self.rle_bytes)
         self.match_gt = None
         self.ious_out = None
@@ -631,11 +642,28 @@ def stage_mask_iou(dp, ws):
         "taoamd_rle_iou")
 
 
+def stage_track_mask_iou(dp, ws):
+    """3D IoU of the mask tracks of every cell (TaoEval iou_type="segm"); the
+    count of shared (pair, frame) items goes to ws.pair_frames."""
+    lib, t, s = _lib.load(), dp.t, _stream()
+    _lib.check(lib.taoamd_track_mask_iou(
+        dp.n_cells, _ptr(t["cell_dt_off"]), _ptr(t["cell_gt_off"]),
+        _ptr(t["cell_iou_off"]), dp.n_iou, _ptr(t["dt_frame_off"]),
+        _ptr(t["dt_frame_pos"]), dp.rle_rows["dt"], dp.rle_total["dt"],
+        _ptr(t["dt_rle_off"]), _ptr(t["dt_rle_runs"]), _ptr(t["dt_rle_hw"]),
+        _ptr(t["gt_frame_off"]), _ptr(t["gt_frame_pos"]), dp.rle_rows["gt"],
+        dp.rle_total["gt"], _ptr(t["gt_rle_off"]), _ptr(t["gt_rle_runs"]),
+        _ptr(t["gt_rle_hw"]), dp.iou_mode, _ptr(ws.iou), _ptr(ws.pair_frames), _ptr(ws.rle_ws),
+        ws.rle_bytes, s), "taoamd_track_mask_iou")
+
+
 def stage_track_iou(dp, ws):
     if dp.kind == "lvis":
         return stage_mask_iou(dp, ws)        # the image level's pre-match IoU
     if dp.kind != "tao" or dp.n_iou == 0:
         return
+    if dp.mask_iou:
+        return stage_track_mask_iou(dp, ws)
     lib, t, s = _lib.load(), dp.t, _stream()
     if dp.single_frame:
         _lib.check(lib.taoamd_track_iou_single(

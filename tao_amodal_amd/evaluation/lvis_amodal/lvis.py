@@ -120,20 +120,8 @@ class LVIS:
         annotation that already holds a compressed RLE comes back as it is.
         Rasterisation, union and the text form are native (csrc/rle.cpp)."""
         img_data = self.imgs[ann["image_id"]]
-        h, w = img_data["height"], img_data["width"]
-        segm = ann["segmentation"]
-        if not isinstance(segm, list) and not isinstance(segm["counts"], list):
-            return segm
-        from ...masks import MaskBatch
-        batch = MaskBatch()
-        try:
-            batch.add(segm, h, w)
-            text = batch.text(0)
-        finally:
-            batch.close()
-        size = [int(h), int(w)] if isinstance(segm, list) else \
-            [int(segm["size"][0]), int(segm["size"][1])]
-        return {"size": size, "counts": text.encode("ascii")}
+        from ...masks import ann_to_rle
+        return ann_to_rle(ann["segmentation"], img_data["height"], img_data["width"])
 
     def ann_to_mask(self, ann):
         """Binary mask of an annotation, uint8 [h, w] in Fortran order like

@@ -2,6 +2,11 @@
 constructor, methods, public state and logged lines as the reference class
 (tao_amodal/evaluation/tao_amodal/eval.py:120-717); the per-(video, category)
 Python loops are replaced by the HIP pipeline over the non-empty cells.
+
+``iou_type="segm"`` (which the reference accepts but cannot run) evaluates
+mask tracks: the three ``iou_3d_type`` metrics over run-length masks
+(csrc/track_mask_iou.hip); a params.vid_ids subset and a multi-GPU run raise
+NotImplementedError there.
 """
 import logging
 from collections import OrderedDict
@@ -110,8 +115,9 @@ class TaoEval:
     def evaluate(self, show_progress=False):
         self.logger.info("Running per video evaluation.")
         self.logger.info("Evaluate annotation type *{}*".format(self.params.iou_type))
-        if self.params.iou_type != "bbox":
-            raise NotImplementedError("only iou_type='bbox' runs on the HIP path")
+        segm = self.params.iou_type == "segm"
+        if segm and self.dist is not None:
+            raise NotImplementedError("multi-GPU runs evaluate iou_type='bbox'")
         if self.params.iou_3d_type not in ("3d_iou", "avg_iou", "imagenetvid"):
             raise ValueError("Unknown iou_3d_type %r" % self.params.iou_3d_type)
         self.params.vid_ids = list(np.unique(self.params.vid_ids))
@@ -122,6 +128,8 @@ class TaoEval:
             self.tao_gt.columns, self.tao_dt.columns_dt, "video",
             self.params.vid_ids, self.params.cat_ids, bool(self.params.use_cats))
         subset = gt_cols is not self.tao_gt.columns
+        if subset and segm:
+            raise NotImplementedError("iou_type='segm' with a params.vid_ids subset")
         if subset:
             if len(gt_cols.ann_id) == 0:
                 raise ValueError("Found no groundtruth annotations for given params")
@@ -129,7 +137,16 @@ class TaoEval:
                 raise ValueError("Found no predicted annotations for given params")
             if self.dist is not None:
                 raise NotImplementedError("params.vid_ids subsets in a multi-GPU run")
-        if not self.params.use_cats:
+        if segm:
+            # the host statement of the tables: it also names the annotation
+            # every frame comes from (*_frame_ann), whose mask the frame takes
+            from ... import flatten
+            self.flat = flatten.flatten_tao(
+                gt_cols, dt_cols, self.tao_dt.max_dets,
+                use_cats=bool(self.params.use_cats))
+            with timed("masks"):
+                self.flat.masks = self._masks(self.flat)
+        elif not self.params.use_cats:
             # class-agnostic cells (reference eval.py:257-260,293-303)
             from ... import flatten
             self.flat = flatten.flatten_tao(
@@ -155,6 +172,43 @@ class TaoEval:
         self.ious = LazyIous(view, P.vid_ids, cats)
         self.eval_vids = _EvalVids(view, len(P.vid_ids), len(cats),
                                    len(P.area_rng), len(P.time_rng))
+
+    def _masks(self, flat):
+        """One run-length mask per frame of the track tables (iou_type="segm"):
+        a ground-truth frame takes Tao.ann_to_rle of its annotation; a
+        prediction its "segmentation" (polygons, uncompressed or compressed
+        RLE), or the polygon of its box where it has none (reference
+        results.py:67-68).  Polygons are rasterised at the image's size."""
+        from ...masks import MaskBatch
+        imgs = self.tao_gt.imgs
+        anns = self.tao_gt.dataset["annotations"]
+        raw = self.tao_dt.raw_results
+
+        def gt_items():
+            for row in np.asarray(flat.gt_frame_ann).tolist():
+                a = anns[row]
+                im = imgs[a["image_id"]]
+                yield a["segmentation"], im["height"], im["width"]
+
+        def dt_items():
+            for row in np.asarray(flat.dt_frame_ann).tolist():
+                r = raw[row]
+                im = imgs[r["image_id"]]
+                if "segmentation" in r:
+                    seg = r["segmentation"]
+                else:
+                    x1, y1, w, h = r["bbox"]
+                    x2, y2 = x1 + w, y1 + h
+                    seg = [[x1, y1, x1, y2, x2, y2, x2, y1]]
+                yield seg, im["height"], im["width"]
+
+        out = {}
+        for side, items in (("gt", gt_items()), ("dt", dt_items())):
+            batch = MaskBatch()
+            batch.add_many(items)       # polygons: one native call, all cores
+            out[side] = batch.arrays()
+            batch.close()
+        return out
 
     @property
     def near_threshold_pairs(self):

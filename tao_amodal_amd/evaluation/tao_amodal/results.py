@@ -6,6 +6,8 @@ building its dicts are performed on arrays: one video per track id
 (results.py:111-119), one category per track (:77-79), image ids known
 (:105-109).  Per-image top-300, track scores (mean of the boxes' scores when
 they differ, :88-98) and ``area = w*h`` happen in ``flatten.flatten_tao``.
+Predictions given as compressed RLE masks without a box (a port extension,
+for iou_type="segm") take area and box from the mask, as LVISResults does.
 """
 import logging
 
@@ -27,16 +29,33 @@ class TaoResults(Tao):
         self.logger = logging.getLogger("tao.results")
         self.logger.info("Loading and preparing results.")
         raw = None
+        self._raw, self._raw_path = None, None
+        # results that bring a compressed RLE and no box: area and bbox come
+        # from the mask as in LVISResults (L/results.py:54-60) -- a port
+        # extension: the reference TaoResults builds no tracks for them
+        # (results.py:60-61 looks at "bbox" only)
+        from ..lvis_amodal.results import LVISResults
         if isinstance(results, DTColumns):
             self.columns_dt = results
         elif isinstance(results, str):
-            self.columns_dt = DTColumns.from_json(results)
+            self._raw_path = results
+            try:
+                self.columns_dt = DTColumns.from_json(results)
+            except KeyError as e:
+                if e.args != ("bbox",):
+                    raise
+                self.columns_dt = LVISResults._from_masks(self.raw_results)
         else:
             self.logger.warning(
                 "Assuming user provided the results in correct format.")
             assert isinstance(results, list), "results is not a list."
-            self.columns_dt = DTColumns.from_json(results)
+            if results and "bbox" not in results[0] \
+                    and "segmentation" in results[0]:
+                self.columns_dt = LVISResults._from_masks(results)
+            else:
+                self.columns_dt = DTColumns.from_json(results)
             raw = results
+            self._raw = results
             # (the caller's dicts: results.py:47-50, before any check)
             from ..lvis_amodal.results import merge_categories_like_reference
             merge_categories_like_reference(
@@ -78,6 +97,20 @@ class TaoResults(Tao):
             # reference's places before it would have touched the kept boxes
             from ..lvis_amodal.results import rewrite_like_reference
             rewrite_like_reference(raw, self.columns_dt, max_dets, tao=True)
+
+    @property
+    def raw_results(self):
+        """The prediction dicts (parsed on demand: only iou_type="segm" and
+        mask-only results look at anything but the columns)."""
+        if self._raw is None:
+            if self._raw_path is None:
+                raise ValueError("the prediction dicts are not available: "
+                                 "TaoResults was built from columns")
+            import json
+            with open(self._raw_path, "r") as f:
+                self._raw = json.load(f)
+            assert isinstance(self._raw, list), "results is not a list."
+        return self._raw
 
     def _flatten(self, max_dets):
         """Cell tables on the device; inputs the reference rejects go through

@@ -143,3 +143,16 @@ class Tao:
 
     def load_vids(self, ids):
         return self._load_helper(self.vids, ids)
+
+    def ann_to_rle(self, ann):
+        """The annotation's mask as a compressed RLE, as ``LVIS.ann_to_rle``
+        (reference lvis_amodal/lvis.py:171-193) makes it: polygon lists and
+        uncompressed RLEs are rasterised at the image's height / width, a
+        compressed RLE comes back as it is.  The reference's Tao has no such
+        method, which leaves its iou_type="segm" path unable to run
+        (tao_amodal/eval.py:173-176); here it feeds TaoEval(iou_type="segm").
+        An annotation without "segmentation" raises KeyError."""
+        from ...masks import ann_to_rle
+        segm = ann["segmentation"]
+        img = self.imgs[ann["image_id"]]
+        return ann_to_rle(segm, img["height"], img["width"])

@@ -955,6 +955,9 @@ def flatten_tao(gt: GTColumns, dt: DTColumns, max_dets=MAX_DETS,
         np.zeros(len(keys_d), dtype=I32)
     f.dt_cell = d_cell.astype(I32)
     f.dt_frame_off, f.dt_frame_pos, f.dt_frame_box = d_foff, d_fpos, d_fbox
+    # row of the prediction (in dt) every frame comes from: the masks of
+    # iou_type="segm" are built per frame (TaoEval._masks)
+    f.dt_frame_ann = d_fbox.index
     f.gt_area = np.ascontiguousarray(g_area[og])
     f.gt_len = g_len[og].astype(I32)
     f.gt_nhp = g_nhp[og].astype(I32)
@@ -966,6 +969,7 @@ def flatten_tao(gt: GTColumns, dt: DTColumns, max_dets=MAX_DETS,
         np.zeros(len(keys_g), dtype=I32)
     f.gt_cell = g_cell.astype(I32)
     f.gt_frame_off, f.gt_frame_pos, f.gt_frame_box = g_foff, g_fpos, g_fbox
+    f.gt_frame_ann = g_fbox.index            # row of the GT annotation (gt.ann_*)
     f.n_pairs = int(iou_off[-1])
     f.track_scores = dict(zip(u.tolist(), trk_score.tolist()))
     f.tl_image_id, f.tl_vid_start = T.tl_image_id, T.tl_vid_start

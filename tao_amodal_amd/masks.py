@@ -176,3 +176,21 @@ class MaskBatch:
         buf = C.create_string_buffer(n + 1)
         self.lib.taoamd_rle_string(self.h, int(i), buf, n + 1)
         return buf.value.decode("ascii")
+
+
+def ann_to_rle(segm, height, width):
+    """``LVIS.ann_to_rle`` (reference lvis.py:171-193: mask_utils.frPyObjects
+    + merge) on an annotation's ``segmentation`` and its image's size: polygons
+    / an uncompressed RLE to a compressed RLE dict {"size": [h, w], "counts":
+    bytes} as pycocotools returns it; a compressed RLE comes back as it is."""
+    if not isinstance(segm, list) and not isinstance(segm["counts"], list):
+        return segm
+    batch = MaskBatch()
+    try:
+        batch.add(segm, height, width)
+        text = batch.text(0)
+    finally:
+        batch.close()
+    size = [int(height), int(width)] if isinstance(segm, list) else \
+        [int(segm["size"][0]), int(segm["size"][1])]
+    return {"size": size, "counts": text.encode("ascii")}

@@ -1,0 +1,310 @@
+"""TaoEval(iou_type="segm") on the GPU: the 3D mask IoU kernel
+(taoamd_track_mask_iou) against the restatement tests/track_segm_ref.py, bit
+for bit in all three modes; the class API on fixture F6; rectangle masks
+against the bbox path; params subsets."""
+import copy
+import json
+
+import numpy as np
+import pytest
+
+import track_segm_ref as ref
+from goldenio import path
+from tao_amodal_amd import flatten
+from tao_amodal_amd.masks import MaskBatch
+
+pytestmark = pytest.mark.gpu
+
+MODES = ("3d_iou", "avg_iou", "imagenetvid")
+
+
+# ----------------------------------------------------------- random problems
+def _rand_counts(rng, h, w, kind):
+    n = h * w
+    if kind == "ones":
+        return [0, n]
+    if kind == "zeros":
+        return [n]
+    k = int(rng.integers(1100, 1500)) if kind == "many" else int(rng.integers(1, 40))
+    k = min(k, n)
+    cuts = np.sort(rng.choice(np.arange(1, n), size=k - 1, replace=False)) if k > 1 \
+        else np.zeros(0, np.int64)
+    runs = np.diff(np.r_[0, cuts, n]).tolist()
+    return ([0] + runs) if rng.random() < 0.3 else runs
+
+
+def _rand_mask(rng, h, w, other_size=False):
+    r = rng.random()
+    if r < 0.03:
+        return {"h": 0, "w": 0, "counts": []}               # no run at all
+    if other_size:
+        h, w = h + 1, w
+    kind = "many" if r < 0.06 else "ones" if r < 0.1 else "zeros" if r < 0.13 else "rand"
+    if kind == "many":
+        h, w = max(h, 40), max(w, 40)
+    return {"h": h, "w": w, "counts": _rand_counts(rng, h, w, kind)}
+
+
+def _problem(rng, shapes):
+    """shapes: per cell (D, G, timeline length, max frames per track)."""
+    cells_d, cells_g, dt_tracks, gt_tracks = [], [], [], []
+    for D, G, T, L in shapes:
+        h, w = int(rng.integers(6, 30)), int(rng.integers(6, 30))
+        half = rng.random() < 0.2            # detections / GT in disjoint halves
+
+        def track(side):
+            lo, hi = (0, T) if not half or T < 2 else \
+                ((0, T // 2) if side == "dt" else (T // 2, T))
+            n = int(rng.integers(1, min(L, hi - lo) + 1))
+            pos = np.sort(rng.choice(np.arange(lo, hi), size=n, replace=False))
+            return {int(p): _rand_mask(rng, h, w, side == "dt" and rng.random() < 0.08)
+                    for p in pos}
+        gt_tracks += [track("gt") for _ in range(G)]
+        dt_tracks += [track("dt") for _ in range(D)]
+        cells_d.append(D)
+        cells_g.append(G)
+    # a 0 x 0 mask only ever meets a frame of another size (two of them on one
+    # frame have nothing to merge in the oracle)
+    for tr in gt_tracks:
+        for p, m in tr.items():
+            if not m["counts"]:
+                tr[p] = {"h": 3, "w": 3, "counts": [9]}
+    return cells_d, cells_g, dt_tracks, gt_tracks
+
+
+def _tables(cells_d, cells_g, dt_tracks, gt_tracks):
+    f = flatten.Flat()
+    f.cell_dt_off = np.r_[0, np.cumsum(cells_d)].astype(np.int32)
+    f.cell_gt_off = np.r_[0, np.cumsum(cells_g)].astype(np.int32)
+    f.cell_iou_off = np.r_[0, np.cumsum(np.asarray(cells_d, np.int64) * cells_g)]
+    out = {}
+    for side, tracks in (("dt", dt_tracks), ("gt", gt_tracks)):
+        off = np.r_[0, np.cumsum([len(t) for t in tracks])].astype(np.int32)
+        pos = np.array([p for t in tracks for p in sorted(t)], np.int32)
+        b = MaskBatch()
+        for t in tracks:
+            for p in sorted(t):
+                m = t[p]
+                b.add({"size": [m["h"], m["w"]], "counts": m["counts"]}, 0, 0)
+        out[side] = (off, pos, b.arrays())
+        b.close()
+    return f, out
+
+
+def _device_iou(f, sides, mode):
+    import torch
+    from tao_amodal_amd import _lib
+    lib = _lib.load()
+    dev = "cuda"
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    head = [t(f.cell_dt_off), t(f.cell_gt_off), t(f.cell_iou_off)]
+    n_pairs = int(f.cell_iou_off[-1])
+    keep, args = [], []
+    for side in ("dt", "gt"):
+        off, pos, m = sides[side]
+        arrs = [t(off), t(pos if len(pos) else np.zeros(1, np.int32))]
+        masks = [t(m.off), t(m.counts.view(np.int32) if len(m.counts) else np.zeros(1, np.int32)),
+                 t(m.hw if len(m) else np.zeros((1, 2), np.int32))]
+        keep += arrs + masks
+        args += [arrs[0].data_ptr(), arrs[1].data_ptr(), len(m), int(m.off[-1])] + \
+            [x.data_ptr() for x in masks]
+    out = torch.full((max(n_pairs, 1),), -7.0, dtype=torch.float64, device=dev)
+    pf = torch.full((1,), -1, dtype=torch.int64, device=dev)
+    nb = lib.taoamd_track_mask_iou_workspace(len(sides["dt"][2]), int(sides["dt"][2].off[-1]),
+                                             len(sides["gt"][2]), int(sides["gt"][2].off[-1]))
+    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+    st = lib.taoamd_track_mask_iou(
+        len(f.cell_dt_off) - 1, *[x.data_ptr() for x in head], n_pairs, *args,
+        MODES.index(mode), out.data_ptr(), pf.data_ptr(), ws.data_ptr(), nb, None)
+    assert st == 0
+    torch.cuda.synchronize()
+    return out.cpu().numpy()[:n_pairs], int(pf.item())
+
+
+def _check(rng, shapes):
+    cells_d, cells_g, dts, gts = _problem(rng, shapes)
+    f, sides = _tables(cells_d, cells_g, dts, gts)
+    terms = {}
+    items = sum(ref.shared_frames(dts[d], gts[g])
+                for c in range(len(cells_d))
+                for d in range(f.cell_dt_off[c], f.cell_dt_off[c + 1])
+                for g in range(f.cell_gt_off[c], f.cell_gt_off[c + 1]))
+    for mode in MODES:
+        got, pairs = _device_iou(f, sides, mode)
+        want = ref.cell_ious(f, dts, gts, mode, terms)
+        assert got.shape == want.shape
+        bad = np.flatnonzero(got.view(np.int64) != want.view(np.int64))
+        assert len(bad) == 0, (mode, bad[:5], got[bad[:5]], want[bad[:5]])
+        assert pairs == items, mode
+    return items
+
+
+def test_track_mask_iou_kernel_equals_the_restatement_on_random_problems():
+    rng = np.random.default_rng(20261015)
+    shapes = [(int(rng.integers(0, 6)), int(rng.integers(0, 6)),
+               int(rng.integers(1, 40)), 30) for _ in range(40)]
+    shapes += [(2, 2, 320, 300),          # tracks up to 300 frames
+               (70, 2, 4, 3),             # more than 64 detection tracks
+               (2, 66, 4, 3),             # more than 64 GT tracks
+               (0, 5, 10, 5), (4, 0, 10, 5)]
+    items = _check(rng, shapes)
+    assert items > 1000
+
+
+def test_track_mask_iou_kernel_long_run_lists_and_no_pairs():
+    rng = np.random.default_rng(5)
+    # every mask a long run list: several 512-boundary pieces per walk
+    cells_d, cells_g, dts, gts = [2], [2], [], []
+    for _ in range(2):
+        dts.append({p: {"h": 50, "w": 60, "counts": _rand_counts(rng, 50, 60, "many")}
+                    for p in range(0, 12, 2)})
+        gts.append({p: {"h": 50, "w": 60, "counts": _rand_counts(rng, 50, 60, "many")}
+                    for p in range(0, 12, 3)})
+    f, sides = _tables(cells_d, cells_g, dts, gts)
+    for mode in MODES:
+        got, pairs = _device_iou(f, sides, mode)
+        want = ref.cell_ious(f, dts, gts, mode)
+        assert np.array_equal(got.view(np.int64), want.view(np.int64)), mode
+        assert pairs == 4 * 2
+    # a problem without pairs: nothing written, no shared frame counted
+    _, _, dts, gts = _problem(rng, [(3, 0, 5, 5), (0, 2, 5, 5)])
+    f, sides = _tables([3, 0], [0, 2], dts, gts)
+    got, pairs = _device_iou(f, sides, "3d_iou")
+    assert len(got) == 0 and pairs == 0
+
+
+# ------------------------------------------------------------- class API, F6
+def _ref_cells(gt, preds, use_cats, mode):
+    from tao_amodal_amd.evaluation.tao_amodal import Tao, TaoResults
+    res = TaoResults(gt, copy.deepcopy(preds))
+    f = flatten.flatten_tao(gt.columns, res.columns_dt, use_cats=use_cats)
+    dm, gm = ref.frame_masks(f, gt.dataset, preds)
+    dts = ref.tracks_of(f.dt_frame_off, f.dt_frame_pos, dm)
+    gts = ref.tracks_of(f.gt_frame_off, f.gt_frame_pos, gm)
+    return f, ref.cell_ious(f, dts, gts, mode)
+
+
+@pytest.mark.parametrize("pred", ["pred_rle.json", "pred.json"])
+@pytest.mark.parametrize("use_cats", [1, 0])
+@pytest.mark.parametrize("mode", MODES)
+def test_tao_eval_segm_ious_equal_the_restatement_on_f6(pred, use_cats, mode):
+    from tao_amodal_amd.evaluation.tao_amodal import Tao, TaoEval
+    gt = Tao(path("f6", "gt.json"))
+    with open(path("f6", pred)) as fh:
+        preds = json.load(fh)
+    ev = TaoEval(gt, path("f6", pred), iou_type="segm", iou_3d_type=mode)
+    ev.params.use_cats = use_cats
+    ev.run()
+    f, want = _ref_cells(gt, preds, bool(use_cats), mode)
+    cats = ev.params.cat_ids if use_cats else [-1]
+    seen = 0
+    for k in range(f.n_cells):
+        vid = int(f.vid_ids[f.cell_unit[k]])
+        cat = int(f.cat_ids[f.cell_cat[k]]) if use_cats else -1
+        assert cat in cats
+        D = f.cell_dt_off[k + 1] - f.cell_dt_off[k]
+        G = f.cell_gt_off[k + 1] - f.cell_gt_off[k]
+        got = np.asarray(ev.ious[vid, cat], dtype=np.float64).reshape(D, G)
+        w = want[f.cell_iou_off[k]:f.cell_iou_off[k + 1]].reshape(D, G)
+        assert np.array_equal(got.view(np.int64), w.view(np.int64)), (vid, cat)
+        seen += D * G
+    assert seen == len(want) and seen > 0
+    assert np.isfinite(ev.eval["precision"]).all()
+    e = ev.eval_vids[(0, 0, 0, 0)]          # detail views work
+    assert e is None or "dt_matches" in e
+
+
+# ------------------------------------------------ rectangles against the boxes
+def _rect_dataset(seed, V=8, F=10, C=2, H=48, W=64):
+    rng = np.random.default_rng(seed)
+    g = {"info": {}, "images": [], "videos": [], "tracks": [], "annotations": [],
+         "categories": [{"id": c + 1, "name": "c%d" % c, "frequency": "cfr"[c % 3]}
+                        for c in range(C)]}
+    preds = []
+
+    def box():
+        x, y = int(rng.integers(0, W - 4)), int(rng.integers(0, H - 4))
+        return [x, y, int(rng.integers(2, W - x + 1)), int(rng.integers(2, H - y + 1))]
+
+    img = trk = ann = 0
+    for v in range(1, V + 1):
+        g["videos"].append({"id": v, "name": "v%d" % v, "neg_category_ids": [],
+                            "not_exhaustive_category_ids": []})
+        ids = []
+        for fi in range(F):
+            img += 1
+            ids.append(img)
+            g["images"].append({"id": img, "video_id": v, "frame_index": fi,
+                                "neg_category_ids": [], "not_exhaustive_category_ids": [],
+                                "height": H, "width": W})
+        for _ in range(int(rng.integers(3, 7))):
+            trk += 1
+            cat = int(rng.integers(1, C + 1))
+            g["tracks"].append({"id": trk, "category_id": cat, "video_id": v})
+            frames = sorted(rng.choice(ids, size=int(rng.integers(1, F + 1)), replace=False))
+            boxes = {}
+            for im in frames:
+                ann += 1
+                b = box()
+                boxes[int(im)] = b
+                g["annotations"].append({
+                    "id": ann, "image_id": int(im), "track_id": trk, "category_id": cat,
+                    "bbox": b, "area": b[2] * b[3], "visibility": float(rng.random()),
+                    "iscrowd": 0, "out_of_frame": False,
+                    "segmentation": ref.box_polygon(b)})
+            # two detection tracks near every GT track
+            for k in range(2):
+                dtrk = trk * 10 + k
+                score = float(np.round(rng.random(), 3))
+                for im, b in boxes.items():
+                    if rng.random() < 0.2:
+                        continue
+                    d = [int(np.clip(b[0] + rng.integers(-3, 4), 0, W - 2)),
+                         int(np.clip(b[1] + rng.integers(-3, 4), 0, H - 2))]
+                    d += [int(np.clip(b[2] + rng.integers(-3, 4), 1, W - d[0])),
+                          int(np.clip(b[3] + rng.integers(-3, 4), 1, H - d[1]))]
+                    preds.append({"image_id": im, "category_id": cat, "bbox": d,
+                                  "score": score, "track_id": dtrk, "video_id": v})
+    return g, preds
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_rectangle_masks_equal_the_bbox_path(mode):
+    from tao_amodal_amd.evaluation.tao_amodal import Tao, TaoEval
+    g, preds = _rect_dataset(11)
+    out = {}
+    for kind in ("bbox", "segm"):
+        gt = Tao(copy.deepcopy(g))
+        ev = TaoEval(gt, copy.deepcopy(preds), iou_type=kind, iou_3d_type=mode)
+        ev.run()
+        out[kind] = ev
+    b, s = out["bbox"], out["segm"]
+    n = 0
+    for key in b.ious:
+        x, y = np.asarray(b.ious[key]), np.asarray(s.ious[key])
+        assert x.shape == y.shape, key
+        if mode == "avg_iou":
+            assert np.allclose(x, y, rtol=0, atol=1e-12), key
+        else:
+            assert np.array_equal(x, y), key
+        n += x.size
+    assert n > 150
+    if mode != "avg_iou":
+        assert np.array_equal(b.eval["precision"], s.eval["precision"])
+        assert np.array_equal(b.eval["recall"], s.eval["recall"])
+        assert list(b.results.items()) == list(s.results.items())
+
+
+def test_cat_ids_subset_selects_columns():
+    from tao_amodal_amd.evaluation.tao_amodal import Tao, TaoEval
+    gt = Tao(path("f6", "gt.json"))
+    whole = TaoEval(gt, path("f6", "pred_rle.json"), iou_type="segm")
+    whole.run()
+    sub = TaoEval(gt, path("f6", "pred_rle.json"), iou_type="segm")
+    cats = sorted(whole.params.cat_ids)
+    pick = [cats[2], cats[0]]
+    sub.params.cat_ids = pick
+    sub.run()
+    pos = [cats.index(c) for c in pick]
+    assert np.array_equal(sub.eval["precision"], whole.eval["precision"][:, :, pos])
+    assert np.array_equal(sub.eval["recall"], whole.eval["recall"][:, pos])
