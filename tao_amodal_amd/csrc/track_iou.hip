@@ -988,7 +988,7 @@ extern "C" int taoamd_pyset_union_order_host(int64_t n_a, const int64_t *a, int6
 // longest start first, and the cells that share a task have similar spans);
 // the detection tracks of a cell by first position.  A task is filled track
 // by track: a detection track brings one pair per GT track of its cell's GT
-// block (<= 32 tracks), the block's rows are added when the task does not
+// block (< TT_ROWS tracks), the block's rows are added when the task does not
 // hold them yet; a task is closed when the next track would exceed 64 pairs or
 // TT_ROWS rows -- so a big cell spills into the next task and the tail of one
 // cell shares a wavefront with the head of the next.
@@ -1060,7 +1060,10 @@ extern "C" int taoamd_track_iou_plan_host(
         std::stable_sort(dts.begin(), dts.end(), [&](int32_t a, int32_t b) {
             return first_of(d0 + a) < first_of(d0 + b);
         });
-        const int32_t gblocks = (G + 31) / 32;
+        // blocks of at most TT_ROWS - 1 GT tracks: a block and one detection
+        // track have to fit into an empty task (a block of 32 GTs -- G = 32,
+        // 63, 64, 94 .. 96, ... -- took 33 rows)
+        const int32_t gblocks = (G + TT_ROWS - 2) / (TT_ROWS - 1);
         for (int32_t gb = 0; gb < gblocks; gb++) {
             const int32_t ga = (int32_t)((int64_t)gb * G / gblocks);
             const int32_t ng = (int32_t)((int64_t)(gb + 1) * G / gblocks) - ga;

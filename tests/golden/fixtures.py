@@ -19,6 +19,9 @@ F8  a down-scaled Config 2 with DECIMAL coordinates (16 videos x 300 frames
     x 10 boxes, 100 categories): tracks of hundreds of frames whose per-frame
     terms are inexact in fp64, i.e. the shape real prediction files have.  Its
     golden 3D IoUs are the reference's set-order sums over up to 600 frames
+F9  rule-dense cells (rule_cells): the greedy match's tie / ignore / threshold
+    / sentinel rules in cells of 2 to 130 GTs, i.e. in every launch route of
+    the match (group, single, big) on both levels
 """
 import os
 import sys
@@ -296,7 +299,224 @@ def f8():
     return gt.to_json(), dt.to_json()
 
 
-ALL = {"f1": f1, "f2": f2, "f3": f3, "f4": f4, "f5": f5, "f7": f7, "f8": f8}
+# --------------------------------------------------------------------------
+# rule-dense cells of any size (F9, tests/test_gpu_match_routes.py)
+# --------------------------------------------------------------------------
+# A motif is a few GT and detection tracks of category 1 in a slot of
+# 128 x 112 pixels no other box reaches, so the image-level cells (frame,
+# category) and the track-level cell (video, category) hold the same rules.
+# Integer boxes: every IoU is a quotient of integers.  Most motifs live on
+# frames 0 and 1, the ones where a detection has two candidate GTs on frame 0
+# only: frame 1's cell takes the group kernel's closed form, frame 0's its
+# sequential greedy.
+T2, T3, F0 = [0, 1], [0, 1, 2], [0]
+SLOT_W, SLOT_H, PAD_Y, PAD_PITCH, PAD_PER_ROW = 128, 112, 360, 12, 85
+
+
+def _m_tie_vis(add):
+    # identical GTs; visibility 0.5 is regular in range [0.1, 0.8] and ignored
+    # in [0.8, 1], 0.9 the other way round: the tie spans the ignore order
+    add.gt([0, 0, 50, 50], F0, vis=0.5)
+    add.gt([0, 0, 50, 50], F0, vis=0.9)
+    add.dt([0, 0, 50, 50], F0, 0.9)
+    add.dt([4, 4, 50, 50], F0, 0.8)
+
+
+def _m_tie_ignored(first):
+    def motif(add):
+        # an ignored and a regular GT with one box, the ignored one first or second
+        add.gt([0, 0, 50, 50], F0, ignore=first)
+        add.gt([0, 0, 50, 50], F0, ignore=not first)
+        add.dt([0, 0, 50, 50], F0, 0.7)
+        add.dt([2, 0, 50, 50], F0, 0.6)
+    return motif
+
+
+def _m_ignored_best(add):
+    # IoU 1 with an ignored GT, 0.8 with a regular one
+    add.gt([0, 0, 20, 20], F0, ignore=True)
+    add.gt([0, 0, 20, 16], F0)
+    add.dt([0, 0, 20, 20], F0, 0.85)
+
+
+def _m_thresholds(ks):
+    def motif(add):
+        # [x, y, k, 1] against [x, y, 20, 1]: IoU exactly k / 20, on every
+        # default threshold (np.linspace: 0.9 meets 0.8999999999999999)
+        for j, k in enumerate(ks):
+            add.gt([0, 4 * j, 20, 1], T2)
+            add.dt([0, 4 * j, k, 1], T2, 0.5 + 0.01 * j)
+    return motif
+
+
+def _m_iou_one(add):
+    # reaches the 1 - 1e-10 clamp of the top threshold
+    add.gt([0, 0, 30, 20], T2)
+    add.dt([0, 0, 30, 20], T2, 0.55)
+
+
+def _m_vis_bounds(add):
+    # visibility exactly on the image level's range bounds, out of frame
+    for x, kw in ((0, {"vis": 0.1}), (24, {"vis": 0.8}), (48, {"vis": 0.0}),
+                  (72, {"oof": True})):
+        add.gt([x, 0, 20, 20], T2, **kw)
+        add.dt([x, 0, 20, 20], T2, 0.65)
+
+
+def _m_area_bounds(add):
+    # mean areas exactly 1024 and 9216 (track level)
+    add.gt([0, 0, 32, 32], T2)
+    add.gt([32, 0, 96, 96], T2)
+    add.dt([0, 0, 32, 32], T2, 0.75)
+    add.dt([31, 1, 96, 96], T2, 0.75)
+
+
+def _m_duration_bounds(add):
+    # durations exactly 3 and 10 (track level)
+    for x, fr in ((0, T3), (24, list(range(10)))):
+        add.gt([x, 0, 20, 20], fr)
+        add.dt([x, 0, 20, 20], fr, 0.6)
+
+
+def _m_hp_bounds(add):
+    # exactly 5 (the HP range ignores the track) and 6 frames below 0.8
+    for x, last in ((0, 0.8), (24, 0.2)):
+        add.gt([x, 0, 20, 20], list(range(6)), vis=[0.1, 0.5, 0.79, 0.3, 0.0, last])
+        add.dt([x + 1, 0, 20, 20], list(range(6)), 0.45)
+
+
+def _m_flags(add):
+    # annotation ignore only, track ignore only, a zero-area annotation
+    add.gt([0, 0, 20, 20], T2, ann_ignore=True)
+    add.gt([24, 0, 20, 20], T2, trk_ignore=True)
+    add.gt([48, 0, 20, 20], T2, zero_at=1)
+    for x in (0, 24, 48):
+        add.dt([x, 0, 20, 20], T2, 0.5)
+
+
+def _m_equal_scores(add):
+    # equal scores: the earlier detection takes the GT
+    add.gt([0, 0, 40, 20], T2)
+    add.dt([0, 0, 40, 20], T2, 0.4)
+    add.dt([0, 0, 40, 20], T2, 0.4)
+
+
+def _m_no_consume(add):
+    # a detection track id <= 0 does not consume its GT (track level)
+    add.gt([0, 0, 40, 20], T2)
+    add.dt([0, 0, 40, 20], T2, 0.95, no_consume=True)
+    add.dt([1, 0, 40, 20], T2, 0.35)
+
+
+def _m_hidden(add):
+    # once per file: GT annotation id 0 (image level) on GT track id -1
+    add.gt([0, 0, 40, 40], T2, hidden=True)
+    add.gt([48, 0, 40, 40], T2)
+    for box, score in (([0, 0], 0.8), ([2, 0], 0.7), ([47, 1], 0.6), ([52, 0], 0.5)):
+        add.dt(box + [40, 40], T2, score, no_consume=score == 0.8)
+
+
+# (GT tracks, builder, frames of the video it needs)
+RULE_MOTIFS = [
+    (2, _m_tie_vis, 2), (5, _m_thresholds(range(10, 15)), 2), (1, _m_equal_scores, 2),
+    (2, _m_tie_ignored(True), 1), (4, _m_vis_bounds, 2), (1, _m_no_consume, 2),
+    (2, _m_ignored_best, 1), (5, _m_thresholds(range(15, 20)), 2), (1, _m_iou_one, 2),
+    (2, _m_tie_ignored(False), 1), (2, _m_area_bounds, 2), (2, _m_duration_bounds, 10),
+    (2, _m_hp_bounds, 6), (3, _m_flags, 2),
+]
+
+
+def rule_cells(sizes, hidden_in=0, negative_ids=True):
+    """(gt, predictions) JSON objects: one video of category 1 per entry of
+    `sizes`, whose track-level cell holds sizes[i] GT tracks and whose frame-0
+    image cell sizes[i] GTs.  Video i takes the motifs in turn from motif i on,
+    each that still fits, and is padded with one-frame GTs and two detections
+    that overlap nothing.  Video `hidden_in` also holds the id sentinels.
+    Non-consuming detections get track ids 0, -1, -2, ... -- only the first
+    one when `negative_ids` is False (the device flatten takes none below 0)."""
+    images, videos, tracks, anns, preds = [], [], [], [], []
+    n = {"img": 0, "trk": 0, "ann": 0, "dtrk": 0, "nc": 0}
+
+    class Add:
+        def __init__(self, vid, ox, oy):
+            self.vid, self.ox, self.oy = vid, ox, oy
+
+        def box(self, b):
+            return [b[0] + self.ox, b[1] + self.oy, b[2], b[3]]
+
+        def gt(self, box, frames, vis=1.0, oof=False, ignore=False,
+               ann_ignore=False, trk_ignore=False, zero_at=None, hidden=False):
+            n["trk"] += 0 if hidden else 1
+            tid = -1 if hidden else n["trk"]
+            tracks.append({"id": tid, "category_id": 1, "video_id": self.vid})
+            if ignore or trk_ignore:
+                tracks[-1]["ignore"] = 1
+            for k, fr in enumerate(frames):
+                b = self.box(box)
+                b[2] = 0 if zero_at == k else b[2]
+                n["ann"] += 0 if hidden and k == 0 else 1
+                anns.append({"id": 0 if hidden and k == 0 else n["ann"],
+                             "image_id": img0 + fr, "track_id": tid,
+                             "category_id": 1, "bbox": b, "area": b[2] * b[3],
+                             "visibility": vis[k] if isinstance(vis, list) else vis,
+                             "out_of_frame": oof})
+                if ignore or ann_ignore:
+                    anns[-1]["ignore"] = 1
+
+        def dt(self, box, frames, score, no_consume=False):
+            if no_consume and (negative_ids or n["nc"] == 0):
+                tid = -n["nc"]       # unique: make_track_ids_unique keeps it
+                n["nc"] += 1
+            else:
+                n["dtrk"] += 1
+                tid = n["dtrk"]
+            for fr in frames:
+                preds.append({"image_id": img0 + fr, "category_id": 1,
+                              "bbox": self.box(box), "score": score,
+                              "track_id": tid, "video_id": self.vid})
+
+    for i, G in enumerate(sizes):
+        vid = i + 1
+        chosen = [(2, _m_hidden, 2)] if i == hidden_in else []
+        for j in range(len(RULE_MOTIFS)):
+            m = RULE_MOTIFS[(i + j) % len(RULE_MOTIFS)]
+            if sum(c[0] for c in chosen) + m[0] <= G:
+                chosen.append(m)
+        n_pad = G - sum(c[0] for c in chosen)
+        if len(chosen) > 8 * (PAD_Y // SLOT_H) or n_pad > PAD_PER_ROW * 50:
+            raise ValueError("cell too large for one image")
+        videos.append({"id": vid, "name": "v%d" % vid, "neg_category_ids": [],
+                       "not_exhaustive_category_ids": []})
+        img0 = n["img"] + 1
+        for fr in range(max(c[2] for c in chosen) if chosen else 1):
+            n["img"] += 1
+            images.append({"id": n["img"], "video_id": vid, "frame_index": fr,
+                           "neg_category_ids": [], "not_exhaustive_category_ids": []})
+        for s, (_, fn, _) in enumerate(chosen):
+            fn(Add(vid, (s % 8) * SLOT_W, (s // 8) * SLOT_H))
+        pad = Add(vid, 0, PAD_Y)
+        for p in range(n_pad):
+            pad.gt([(p % PAD_PER_ROW) * PAD_PITCH, (p // PAD_PER_ROW) * PAD_PITCH, 8, 8], [0])
+        for p in range(2):
+            pad.dt([p * PAD_PITCH, 620, 8, 8], [0], 0.3 + 0.1 * p)
+    gt = {"info": {"description": "rule-dense cells"}, "images": images,
+          "videos": videos, "tracks": tracks, "annotations": anns,
+          "categories": [{"id": 1, "name": "a", "frequency": "f"}]}
+    return gt, preds
+
+
+# F9: runs of group-sized cells (<= 8 GTs), a cell of 64 GTs
+# (match_kernel), 65 / 96 / 97 / 130 GTs (match_big_kernel, either side of the
+# 64-GT and the 32-bit word bounds), both levels
+F9_SIZES = [8, 6, 8, 5, 7, 8, 64, 65, 96, 97, 130]
+
+
+def f9():
+    return rule_cells(F9_SIZES, hidden_in=6, negative_ids=False)
+
+
+ALL = {"f1": f1, "f2": f2, "f3": f3, "f4": f4, "f5": f5, "f7": f7, "f8": f8,
+       "f9": f9}
 # big fixtures: inputs stored gzipped, image level reduced to the integer
 # match counts + precision / recall + results + text (make_golden.py)
 LITE = {"f8"}

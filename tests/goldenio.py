@@ -6,8 +6,8 @@ import os
 import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-FIXTURES = ["f1", "f2", "f3", "f4", "f5"]
-INTEGER_FIXTURES = ["f1", "f2", "f3", "f5"]
+FIXTURES = ["f1", "f2", "f3", "f4", "f5", "f9"]
+INTEGER_FIXTURES = ["f1", "f2", "f3", "f5", "f9"]
 # every 3D IoU within a few ulp of a threshold: only code that adds a track
 # pair's frames in the reference's CPython set order (the Python oracle with
 # frame_order="set", the HIP path behind its frame-order guard) reproduces it

@@ -121,3 +121,22 @@ def test_dense_only_entry_points_refuse_the_pair_layout():
     p = i64.ctypes.data
     assert lib.taoamd_exchange_place(4, 1, 1, base + 8, base + 8, 0, p, p, base + 256,
                                      None) == 2
+
+
+def test_track_iou_plan_keeps_every_task_within_its_rows():
+    """taoamd_track_iou_plan_host (host only) at GT counts whose even split
+    into blocks of 32 left no row for the detection track (32, 63, 64, 96):
+    every task <= 32 tracks and <= 64 pairs, every pair in exactly one task."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import fixtures
+    from tao_amodal_amd import engine, flatten as fl
+    from tao_amodal_amd.columns import DTColumns, GTColumns
+    from test_gpu_parity import _check_plan
+    gtj, predj = fixtures.rule_cells([32, 63, 64, 96, 31, 33])
+    gt, dt = GTColumns.from_json(gtj), DTColumns.from_json(predj)
+    dt.track_id, _ = fl.make_track_ids_unique(dt)
+    f = fl.flatten_tao(gt, dt)
+    assert {32, 63, 64, 96} <= set(np.diff(f.cell_gt_off).tolist())
+    meta = engine.track_meta(f)[0]
+    _check_plan(f, meta, *engine.track_iou_plan(f, meta))

@@ -36,7 +36,7 @@ def test_cli_text_is_identical_to_the_reference(name, tmp_path):
     assert got == want
 
 
-@pytest.mark.parametrize("name", ["f1", "f2"])
+@pytest.mark.parametrize("name", ["f1", "f2", "f9"])
 def test_class_api_state_matches_reference(name):
     from tao_amodal_amd.evaluation.lvis_amodal import LVISEval
     want = load_json_gz(name, "lvis.json.gz")
@@ -67,7 +67,7 @@ def test_class_api_state_matches_reference(name):
     assert ev.eval["dt_pointers"][0][0] == {} or (0, 0) in ptr
 
 
-@pytest.mark.parametrize("name", ["f1", "f2"])
+@pytest.mark.parametrize("name", ["f1", "f2", "f9"])
 def test_tao_class_api_state_matches_reference(name):
     import json
     from tao_amodal_amd import flatten
