@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark of the MI355X evaluation hot path.
 
     python bench.py --gpus N --steps K --warmup W [--config 3s|2|5s] [--decimal]
-                    [--scaling weak|strong] [--dump-outputs DIR]
+                    [--scaling weak|strong] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic input that
 is already resident in HBM: for BOTH evaluators (image-level LVISEval and
@@ -41,6 +41,16 @@ rows, the track-level IoUs -- as DIR/<name>.npy in float64 (at most 64 MB in
 all: see dump_outputs).  The synthetic input is a function of the arguments
 (--seed), so two builds run with the same arguments can be compared output for
 output.
+
+A plain run does only what the headline figure needs: it builds the input,
+warms up, times the K steps, writes the dump if asked and prints the line
+(`value`, `ms_per_step` and the per-kernel durations the timed steps recorded
+themselves, `kernels_ms`).  `--full` adds everything that takes work of its
+own after the timed region: every kernel alone, the stage times and the
+roofline figures, the CPU baselines and the bit-exact check against the C
+oracle, the Python oracle's frame-order sample (--decimal), the drop-in CLI's
+wall clock, the decimal-coordinates leg, and the multi-GPU exchange checks.
+Their fields are null in a plain run.
 
 Prints ONE JSON line on rank 0 (see the driver contract in the task text).
 """
@@ -83,31 +93,39 @@ def parse():
     p.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                    help="N > 1: a shard of the configuration per rank (weak) or "
                         "one fixed set split by video over the ranks (strong)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure and check what the "
+                        "headline figure does not need: kernels alone, stages, "
+                        "roofline, CPU baselines, the oracle check, the CLI's "
+                        "wall clock, the decimal leg, the exchange checks")
     p.add_argument("--no-wallclock", action="store_true",
-                   help="skip the end-to-end leg (the set written as JSON files, "
-                        "the drop-in CLI run on them)")
+                   help="--full: skip the end-to-end leg (the set written as "
+                        "JSON files, the drop-in CLI run on them)")
     p.add_argument("--videos", type=int, default=None)
     p.add_argument("--frames", type=int, default=None)
     p.add_argument("--dets", type=int, default=None)
     p.add_argument("--cats", type=int, default=1203)
     p.add_argument("--seed", type=int, default=20240807)
     p.add_argument("--cpu-sample-videos", type=int, default=2000,
-                   help="videos of the same workload timed through the C "
-                        "oracle for cpu_baseline (rank 0, N=1 only); the whole "
-                        "set when it has no more than that")
+                   help="--full: videos of the same workload timed through "
+                        "the C oracle for cpu_baseline (rank 0, N=1 only); the "
+                        "whole set when it has no more than that")
     p.add_argument("--decimal", action="store_true",
                    help="decimal box coordinates, as real prediction files have: "
                         "the track level runs with the frame-order guard active")
     p.add_argument("--no-decimal-leg", action="store_true",
-                   help="skip the second measurement of the default invocation: "
-                        "the same workload with decimal coordinates (frame-order "
-                        "guard active), 20 steps, in a subprocess")
+                   help="--full: skip the second measurement: the same "
+                        "workload with decimal coordinates (frame-order guard "
+                        "active), 20 steps, in a subprocess")
     p.add_argument("--leg", choices=["decimal"], default=None,
                    help="internal: this process is the decimal leg of another "
-                        "bench run (implies --decimal --no-wallclock; the oracle "
-                        "verifies on all host cores, no cpu_baseline timing)")
-    p.add_argument("--no-cpu", action="store_true")
-    p.add_argument("--no-verify", action="store_true")
+                        "bench run (implies --full --decimal --no-wallclock; the "
+                        "oracle verifies on all host cores, no cpu_baseline "
+                        "timing)")
+    p.add_argument("--no-cpu", action="store_true",
+                   help="--full: no CPU baselines and no oracle checks")
+    p.add_argument("--no-verify", action="store_true",
+                   help="--full: CPU baselines without the oracle checks")
     p.add_argument("--serial", action="store_true",
                    help="run the two evaluator passes back to back on one stream")
     p.add_argument("--shard", choices=["category", "unit"], default="unit",
@@ -129,7 +147,7 @@ def parse():
     if a.steps < 1 or a.warmup < 0:
         p.error("--steps must be >= 1 and --warmup >= 0")
     if a.leg == "decimal":
-        a.decimal, a.no_wallclock, a.no_decimal_leg = True, True, True
+        a.full, a.decimal, a.no_wallclock, a.no_decimal_leg = True, True, True, True
     cfg = CONFIGS[a.config]
     for k in ("videos", "frames", "dets"):
         if getattr(a, k) is None:
@@ -733,9 +751,9 @@ def main():
         else:
             dumped = dump_outputs(args.dump_outputs, [("lvis", dpl, wsl),
                                                       ("tao", dpt, wst)])
-    # ---- every kernel alone: a few serial steps, one stream, events on
+    # ---- (--full) every kernel alone: a few serial steps, one stream, events on
     alone = {}
-    if rank == 0 and not use_dist:
+    if args.full and rank == 0 and not use_dist:
         _lib.kernel_timing(True)
         for _ in range(5):
             engine.run(dpl, wsl)
@@ -762,9 +780,12 @@ def main():
                    else "SYNTH custom", args.videos, args.frames, args.dets,
                    args.cats, ", decimal coordinates" if args.decimal else ""))
 
-    # ---- per-kernel durations inside the timed steps -> dominant kernel
+    # ---- per-kernel durations inside the timed steps; with --full the stages,
+    # the roofline of every kernel and the dominant kernel
     stages, roof, roof_other, kernels_ms, step_roof = None, None, None, None, None
     if rank == 0:
+        kernels_ms = {name: round(tot / calls, 4) for name, (tot, calls) in in_step.items()}
+    if args.full and rank == 0:
         stages = engine.time_stages(dpl, wsl, dpt, wst, reps=10)
         models, strict = {}, {}
         for side, dp, ws in (("lvis", dpl, wsl), ("tao", dpt, wst)):
@@ -773,11 +794,10 @@ def main():
                 models[side + ":" + k] = (v, gg.get(k), vv.get(k))
             for k, v in survey_models(dp, ws).items():
                 strict[side + ":" + k] = v
-        cands, kernels_ms = [], {}
+        cands = []
         probed = max(1, len(range(PROBE_EVERY // 2, timed_steps, PROBE_EVERY)))
         for name, (tot, calls) in in_step.items():
             k_ms = tot / calls
-            kernels_ms[name] = round(k_ms, 4)
             alg, grid, variant = models.get(name, (None, None, None))
             ent = {"bound": "hbm", "kernel": name, "achieved": None,
                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
@@ -855,14 +875,14 @@ def main():
                          "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 5),
                          "note": "SURVEY 8(d) B_alg of both passes / ms_per_step"}
 
-    # ---- multi-GPU: every rank checks the assembled tables against what the
+    # ---- (--full) multi-GPU: every rank checks the assembled tables against what the
     # owners computed.  Own block: the plain single-GPU pass over this rank's
     # shard must give the same precision / recall block, bit for bit.  Other
     # blocks: a checksum of checksums -- each owner publishes the wrapping
     # int64 sum of its block's bit patterns, every rank compares it with the
     # sum over that block of ITS assembled table.
     exchange_ok = None
-    if by_category and not args.emulate:
+    if args.full and by_category and not args.emulate:
         ok = True
         for ev, dp, ws in ((plan.lvis, dpl, wsl), (plan.tao, dpt, wst)):
             engine.run(dp, ws)
@@ -884,7 +904,7 @@ def main():
         flag = torch.tensor([1 if ok else 0], dtype=torch.int64, device=dev)
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
         exchange_ok = bool(flag.item())
-    elif use_dist and not args.emulate:
+    elif args.full and use_dist and not args.emulate:
         # unit partition: all ranks must hold identical assembled tables
         ok = True
         for ev in (plan.lvis, plan.tao):
@@ -896,9 +916,9 @@ def main():
             ok &= bool(torch.equal(lo, hi))
         exchange_ok = ok
 
-    # ---- verification + CPU baseline (C oracle = "port"), rank 0, N=1
+    # ---- (--full) verification + CPU baseline (C oracle = "port"), rank 0, N=1
     cpu, cpu_all, verified, t_host_flatten = None, None, None, None
-    if not use_dist and rank == 0 and not args.no_cpu:
+    if args.full and not use_dist and rank == 0 and not args.no_cpu:
         import orclib
         nv = min(args.cpu_sample_videos, args.videos)
         if args.frames * args.dets < 3000:        # stress shape: many tiny videos
@@ -970,11 +990,11 @@ def main():
                 and np.array_equal(gtt["precision"], ot["precision"])
                 and np.array_equal(gtt["recall"], ot["recall"]))
 
-    # ---- decimal coordinates: a sample of the same workload through the Python
+    # ---- (--full) decimal coordinates: a sample of the same workload through the Python
     # oracle in the reference's own frame order (CPython sets), against the HIP
     # path with its guard -- the C oracle above adds frames in timeline order
     set_order_check = None
-    if args.decimal and not use_dist and rank == 0 and not args.no_cpu \
+    if args.full and args.decimal and not use_dist and rank == 0 and not args.no_cpu \
             and not args.no_verify:
         from oracle import pyoracle
         nv = min(6, args.videos)
@@ -994,19 +1014,19 @@ def main():
             "recall_equal": bool(np.array_equal(
                 gg["recall"].reshape(po["recall"].shape), po["recall"]))}
 
-    # ---- the metric's second half: end-to-end wall-clock of the drop-in CLI
+    # ---- (--full) the metric's second half: end-to-end wall-clock of the drop-in CLI
     # on this very workload as FILES (JSON -> parse -> tables -> kernels ->
     # summaries -> printed text).  Writing the files is not part of it.
     wall = None
-    if not use_dist and rank == 0 and not args.no_wallclock:
+    if args.full and not use_dist and rank == 0 and not args.no_wallclock:
         wall = wallclock_leg(gt, dt)
 
-    # ---- the same workload with DECIMAL coordinates (what real prediction
+    # ---- (--full) the same workload with DECIMAL coordinates (what real prediction
     # files hold: the frame-order guard of the 3D IoU is active), 20 steps, in
     # a subprocess of this very script once this process's GPU work is done
     decimal_leg = None
-    if (not use_dist and rank == 0 and not args.decimal and not args.no_decimal_leg
-            and not args.no_cpu and not args.serial):
+    if (args.full and not use_dist and rank == 0 and not args.decimal
+            and not args.no_decimal_leg and not args.no_cpu and not args.serial):
         import subprocess
         cmd = [sys.executable, os.path.abspath(__file__), "--leg", "decimal",
                "--steps", "20", "--warmup", "3", "--config", args.config,
@@ -1043,6 +1063,7 @@ def main():
             "unit": "Mpair/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True, "scaling": args.scaling if use_dist else "weak",
+            "full": args.full,
             "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
             "config": {"workload": workload,
@@ -1058,10 +1079,11 @@ def main():
             "timed_region_s": round(elapsed, 4),
             "roofline": roof, "roofline_other": roof_other,
             "step_roofline": step_roof,
-            "hbm_delivers": hbm_delivers(),
+            "hbm_delivers": hbm_delivers() if args.full else None,
             "cpu_baseline": cpu, "cpu_baseline_all_cores": cpu_all,
             "kernels_ms": kernels_ms,
-            "kernels_alone_ms": {k: round(t / c, 4) for k, (t, c) in alone.items()},
+            "kernels_alone_ms": ({k: round(t / c, 4) for k, (t, c) in alone.items()}
+                                 if args.full else None),
             "stages_ms": stages,
             "streams": "serial" if args.serial else "4 (image-level || track-level, range masks + num_gt all-reduce aside) + RCCL" if (use_dist and not by_category)
             else "4 (image-level || track-level, ranges/sort || IoU) + RCCL all_gather" if use_dist

@@ -8,8 +8,8 @@ R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/sq_$PREFIX
 rm -rf $OUT; mkdir -p $OUT $R/profiles
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --output-format csv --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVES -d $OUT/pmc -o sq -- python $R/bench.py --steps 6 --warmup 2 --no-cpu --no-wallclock "$@" > /dev/null 2> $OUT/err.log || true
-rocprofv3 --output-format csv --pmc SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE -d $OUT/lds -o lds -- python $R/bench.py --steps 6 --warmup 2 --no-cpu --no-wallclock "$@" > /dev/null 2>> $OUT/err.log || true
+rocprofv3 --output-format csv --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVES -d $OUT/pmc -o sq -- python $R/bench.py --steps 6 --warmup 2 --full --no-cpu --no-wallclock "$@" > /dev/null 2> $OUT/err.log || true
+rocprofv3 --output-format csv --pmc SQ_LDS_IDX_ACTIVE SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE -d $OUT/lds -o lds -- python $R/bench.py --steps 6 --warmup 2 --full --no-cpu --no-wallclock "$@" > /dev/null 2>> $OUT/err.log || true
 cd $R
 python - $OUT profiles/${PREFIX}_sq_counters.txt <<'P'
 import csv, glob, sys, collections, os
