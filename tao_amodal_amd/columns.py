@@ -341,15 +341,24 @@ class GTColumns:
 
 def fingerprint(v):
     """A cheap digest of an array's CONTENT -- ~1000 evenly spaced elements and
-    both ends -- so that the usual in-place edits of an uploaded column between
-    two evaluations (scores rescaled, boxes shifted, ids remapped: ADVICE r3)
-    are seen as well as a rebound column; an edit of single elements between
-    the samples still needs flatten_dev.forget_columns(dt)."""
+    both ends -- so that the usual in-place edits of a column between two
+    evaluations (scores rescaled, boxes shifted, ids remapped: ADVICE r3) are
+    seen.  An edit of single elements between the samples is not: after one,
+    flatten_dev.forget_columns(cols) drops every copy made from the arrays."""
     if not isinstance(v, np.ndarray) or v.size == 0:
         return 0
     flat = v.reshape(-1) if v.flags.c_contiguous else np.ascontiguousarray(v).reshape(-1)
     step = max(1, flat.size // 1024)
     return hash((flat[::step].tobytes(), flat[-1:].tobytes()))
+
+
+def array_key(a):
+    """Identity of an array for everything made from it (device copies, the
+    top-max_dets cut, ground-truth halves): object, buffer, shape, dtype and
+    sampled content -- a rebound column and most in-place edits change it."""
+    if not isinstance(a, np.ndarray):
+        return (id(a),)
+    return (id(a), a.__array_interface__["data"][0], a.shape, a.dtype, fingerprint(a))
 
 
 class DTColumns:
@@ -666,8 +675,8 @@ class DeviceDTColumns(DTColumns):
     column (image_id, track_id, video_id first: what the constructors of the
     Results classes check on the host).  Reading a column waits for its copy;
     assigning one (``dt.score = other``) replaces it and retires the device
-    copy, and an in-place edit of an arrived array is seen by its fingerprint,
-    as for uploaded columns."""
+    copy, an in-place edit of an arrived array is seen by its array_key, as
+    for uploaded columns, and ``forget()`` retires all device copies."""
 
     ORDER = ("image_id", "track_id", "video_id", "category_id", "score", "bbox")
 
@@ -675,29 +684,31 @@ class DeviceDTColumns(DTColumns):
         import threading
         d = self.__dict__
         d["_n"], d["_dev"], d["_device"] = n, dict(tensors), device
-        d["_host"], d["_fp"], d["_error"] = {}, {}, None
+        d["_host"], d["_key"], d["_error"] = {}, {}, None
+        d["_lock"] = threading.Lock()   # (the background copy never overwrites an assignment)
         d["_ready"] = {f: threading.Event() for f in self.FIELDS}
         d["first"], d["total"] = 0, n
-        threading.Thread(target=self._download, daemon=True).start()
+        threading.Thread(target=self._download, args=(dict(tensors),), daemon=True).start()
 
-    def _download(self):
+    def _download(self, tensors):
         try:
             import torch
             with torch.cuda.device(self._device):
                 side = torch.cuda.Stream(device=self._device)
                 with torch.cuda.stream(side):
                     for f in self.ORDER:
-                        t = self._dev.get(f)
+                        t = tensors.pop(f, None)
                         if self._ready[f].is_set() or t is None:
                             continue            # (assigned meanwhile)
                         arr = np.empty(tuple(t.shape), dtype=np.float64
                                        if t.dtype == torch.float64 else np.int64)
                         torch.from_numpy(arr).copy_(t)
                         side.synchronize()
-                        if not self._ready[f].is_set():
-                            self._fp[f] = fingerprint(arr)
-                            self._host[f] = arr
-                            self._ready[f].set()
+                        with self._lock:
+                            if not self._ready[f].is_set():
+                                self._key[f] = array_key(arr)
+                                self._host[f] = arr
+                                self._ready[f].set()
         except BaseException as e:      # (a reader of the columns re-raises it)
             self.__dict__["_error"] = e
             for ev in self._ready.values():
@@ -714,19 +725,26 @@ class DeviceDTColumns(DTColumns):
         return self._host[f]
 
     def _set(self, f, v):
-        if self._ready[f].is_set() and v is self._host.get(f):
-            return                      # (the same array handed back)
-        self._host[f] = v
-        self._dev.pop(f, None)
-        self._fp.pop(f, None)
-        self._ready[f].set()
+        with self._lock:
+            if self._ready[f].is_set() and v is self._host.get(f):
+                return                  # (the same array handed back)
+            self._host[f] = v
+            self._dev.pop(f, None)
+            self._key.pop(f, None)
+            self._ready[f].set()
+
+    def forget(self):
+        """Retire the device tensors: the table builds upload the host arrays
+        from now on (flatten_dev.forget_columns)."""
+        with self._lock:
+            self._dev.clear()
 
     def track_clash_free(self):
         """Whether every track id occurs with ONE video id (what
         make_track_ids_unique asks first, tools/eval_on_tao_amodal.py:44-58),
         answered where the columns were made: a table of the id's video, every
-        row against it.  None: not answerable here (a column replaced, ids
-        negative or in too wide a range) -- the host statement decides."""
+        row against it.  None: not answerable here (a column replaced, the
+        tensors retired, ids negative or too wide) -- the host decides."""
         import torch
         cols = self.device_columns(self._device, ("track_id", "video_id"))
         if cols is None or self._n == 0:
@@ -748,15 +766,16 @@ class DeviceDTColumns(DTColumns):
         if device.type != "cuda" or idx != self._device.index:
             return None
         out = {}
-        for f in names:
-            t = self._dev.get(f)
-            if t is None:
-                return None
-            if self._ready[f].is_set() and (self._error is not None
-                                            or fingerprint(self._host[f]) != self._fp.get(f)):
-                self._dev.pop(f, None)
-                return None
-            out[f] = t
+        with self._lock:
+            for f in names:
+                t = self._dev.get(f)
+                if t is None:
+                    return None
+                if self._ready[f].is_set() and (self._error is not None
+                                                or array_key(self._host[f]) != self._key.get(f)):
+                    self._dev.pop(f, None)
+                    return None
+                out[f] = t
         return out
 
 

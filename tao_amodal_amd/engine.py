@@ -31,33 +31,18 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-_RAW_TABLES = {}     # id(host table) -> (weakref, {device: tensor})
-import threading as _threading
-_RAW_TABLES_LOCK = _threading.Lock()
-
-
 def _to_device(v, device):
     """Upload a table of a flattened problem.  flatten.LazyRows (rows of a raw
-    input table) are gathered on the device from ONE upload of the raw table,
-    shared by every problem built from the same input."""
+    input table) are gathered on the device from ONE upload of the raw table
+    (flatten_dev.device_copy), shared by every problem built from the same input."""
     from .flatten import LazyRows
     if not isinstance(v, LazyRows):
         return torch.from_numpy(np.ascontiguousarray(v)).to(device)
-    import weakref
-    key = id(v.source)
-    dev = torch.device(device)
-    with _RAW_TABLES_LOCK:
-        ent = _RAW_TABLES.get(key)
-        if ent is None or ent[0]() is not v.source:
-            ent = (weakref.ref(v.source, lambda _r, k=key: _RAW_TABLES.pop(k, None)), {})
-            _RAW_TABLES[key] = ent
-        if dev not in ent[1]:
-            # (under the lock: the CLI builds both levels' problems side by side)
-            ent[1][dev] = torch.from_numpy(np.ascontiguousarray(v.source)).to(dev)
+    from .flatten_dev import device_copy
+    src = device_copy(v.source, device)
     if len(v.index) == 0:
-        return torch.zeros((0,) + tuple(v.source.shape[1:]), dtype=ent[1][dev].dtype,
-                           device=dev)
-    return ent[1][dev].index_select(0, torch.from_numpy(v.index).to(dev))
+        return torch.zeros((0,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
+    return src.index_select(0, torch.from_numpy(v.index).to(src.device))
 
 
 def match_plan(cell_dt_off, cell_gt_off, cap_d=64, cap_g=64, cap_cell_g=8):

@@ -40,7 +40,7 @@ import sys
 
 import numpy as np
 
-from .columns import DTColumns, GTColumns
+from .columns import DTColumns, GTColumns, array_key
 
 MAX_DETS = 300
 I32 = np.int32
@@ -216,12 +216,11 @@ def limit_dets_per_image(dt, max_dets=MAX_DETS):
     n = len(dt)
     if n == 0:
         return np.zeros(0, dtype=np.int64)
-    # (the cut is reused for the same arrays: a caller that rebinds a column
-    # gets a fresh one; editing a column in place after a cut is not seen)
-    ident = tuple((id(c), c.__array_interface__["data"][0]) if isinstance(c, np.ndarray)
-                  else id(c) for c in (dt.image_id, dt.score))
+    # (the cut is reused while image_id and score are what they were:
+    # columns.array_key; flatten_dev.forget_columns drops it)
+    ident = (max_dets, n, array_key(dt.image_id), array_key(dt.score))
     cache = getattr(dt, "_limit_cache", None)
-    if cache is not None and cache[0] == (max_dets, n, ident):
+    if cache is not None and cache[0] == ident:
         return cache[1]
     uniq, first, inv = first_inverse(dt.image_id)
     cnt = np.bincount(inv, minlength=len(uniq))
@@ -238,7 +237,7 @@ def limit_dets_per_image(dt, max_dets=MAX_DETS):
     else:
         order = sort_key_score(img_rank)
     try:
-        dt._limit_cache = ((max_dets, n, ident), order)
+        dt._limit_cache = (ident, order)
     except AttributeError:
         pass
     return order

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib, flatten
+from .columns import array_key
 from .flatten import DT_IGNORE_UNMATCHED, Flat, I32, MAX_DETS   # noqa: F401
 
 class Unsupported(Exception):
@@ -74,67 +75,61 @@ class DeviceFlat(Flat):
         return f
 
 
-_RAW = {}      # id(DTColumns) -> (weakref, {device: dict of tensors})
-_RAW_LOCK = threading.Lock()     # (the CLI builds both levels' tables side by side)
+_COPIES = {}    # id(host array) -> (array_key, weakref, lock, {(device, dtype): tensor})
+_COPIES_LOCK = threading.Lock()
 
 
-def _column_key(dt):
-    """Identity of the arrays behind a DTColumns' columns: the cached device
-    copy is that of THESE arrays with THIS content (a sampled digest,
-    _fingerprint) -- a caller that rebinds a column (dt.score = other) or edits
-    one in place gets a fresh upload."""
-    key = []
-    for name in ("image_id", "category_id", "score", "bbox", "video_id", "area"):
-        v = getattr(dt, name, None)
-        key.append(None if v is None else
-                   (id(v), v.__array_interface__["data"][0] if isinstance(v, np.ndarray)
-                    else 0, getattr(v, "shape", None), _fingerprint(v)))
-    return tuple(key)
+def device_copy(a, device, dtype=None):
+    """The host array ``a`` on ``device`` (as ``dtype``): uploaded once and
+    shared by every caller while the array is what it was (columns.array_key),
+    dropped when the array dies or by forget_columns; None stays None.  (Copied
+    on a CPU device too: a tensor sharing the array's memory would keep it alive.)"""
+    if a is None:
+        return None
+    a = a if isinstance(a, np.ndarray) else np.asarray(a)
+    dev, key = torch.device(device), array_key(a)
+    with _COPIES_LOCK:
+        ent = _COPIES.get(id(a))
+        if ent is None or ent[0] != key:
+            ref = weakref.ref(a, lambda _r, k=id(a): _COPIES.pop(k, None))
+            ent = _COPIES[id(a)] = (key, ref, threading.Lock(), {})
+    # (one upload per array and device: the CLI builds both levels side by side)
+    with ent[2]:
+        t = ent[3].get((dev, dtype))
+        if t is None:
+            t = ent[3][(dev, dtype)] = torch.from_numpy(np.ascontiguousarray(
+                a, dtype=dtype)).to(dev, non_blocking=True, copy=True)
+    return t
 
 
-from .columns import fingerprint as _fingerprint   # noqa: E402
+def forget_columns(cols):
+    """Drop everything made from a DTColumns' or GTColumns' arrays -- device
+    copies, the top-max_dets cut, a prepare_gt bundle, the device reader's
+    tensors -- so that an edit fingerprint does not sample is seen."""
+    if hasattr(cols, "forget"):
+        cols.forget()
+    d = vars(cols)
+    for v in list(d.values()) + list(d.get("_host", {}).values()):
+        if isinstance(v, np.ndarray):
+            _COPIES.pop(id(v), None)
+    d.pop("_limit_cache", None)
+    d.pop("_prepared_gt", None)
 
 
-def forget_columns(dt):
-    """Drop the cached device copy of a DTColumns' columns."""
-    _RAW.pop(id(dt), None)
+_RAW_NAMES = ("image_id", "category_id", "score", "bbox", "video_id")
 
 
 def raw_columns(dt, device):
-    """The prediction columns on the device, uploaded once per DTColumns (and
-    set of column arrays) and shared by the image-level and the track-level
-    build."""
-    with _RAW_LOCK:
-        return _raw_columns(dt, device)
-
-
-def _raw_columns(dt, device):
+    """The prediction columns on the device: the device reader's tensors while
+    they hold what the host arrays do, device_copy of the host arrays else."""
     dev = torch.device(device)
+    area = getattr(dt, "area", None)
     born = getattr(dt, "device_columns", None)
-    if born is not None and getattr(dt, "area", None) is None:
-        # columns the device-side reader made (columns.DeviceDTColumns): there
-        # already, unless the caller has replaced or edited one since
-        cols = born(dev, ("image_id", "category_id", "score", "bbox", "video_id"))
-        if cols is not None:
-            cols["area"] = None
-            return cols
-    key = id(dt)
-    cols_key = _column_key(dt)
-    ent = _RAW.get(key)
-    if ent is None or ent[0]() is not dt or ent[2] != cols_key:
-        ent = (weakref.ref(dt, lambda _r, k=key: _RAW.pop(k, None)), {}, cols_key)
-        _RAW[key] = ent
-    if dev not in ent[1]:
-        cols = {}
-        for name in ("image_id", "category_id", "score", "bbox", "video_id"):
-            v = getattr(dt, name, None)
-            cols[name] = None if v is None else torch.from_numpy(
-                np.ascontiguousarray(v)).to(dev, non_blocking=True)
-        area = getattr(dt, "area", None)
-        cols["area"] = None if area is None else torch.from_numpy(
-            np.ascontiguousarray(area, dtype=np.float64)).to(dev)
-        ent[1][dev] = cols
-    return ent[1][dev]
+    cols = born(dev, _RAW_NAMES) if born is not None and area is None else None
+    if cols is None:
+        cols = {name: device_copy(getattr(dt, name, None), dev) for name in _RAW_NAMES}
+    cols["area"] = device_copy(area, dev, np.float64)
+    return cols
 
 
 def _ptr(t):
@@ -209,7 +204,7 @@ def _cells_from_runs(lib, dev, n_keep, dt_key, gkeys_sorted, keys_g):
 # ---------------------------------------------------------------------------
 # ground-truth halves, buildable before the predictions are there: prepare.py
 # (no torch there -- the CLI builds them while torch is still being imported)
-from .prepare import (_gt_key, _gt_ready, _gt_universe, _lvis_gt_ready, _READY,   # noqa: E402,F401
+from .prepare import (_gt_ready, _gt_universe, _lvis_gt_ready, _READY,   # noqa: E402,F401
                       _tao_gt_ready, prepare_gt)
 
 

@@ -7,16 +7,16 @@ sit in front of the first table).  ``flatten_dev`` re-exports everything here.
 import numpy as np
 
 from . import flatten
+from .columns import array_key
 from .flatten import Flat, I32
 
 
 # ---------------------------------------------------------------------------
 # ground-truth halves, buildable before the predictions are there
 # ---------------------------------------------------------------------------
-def _gt_key(gt):
-    """Identity of the arrays behind a GTColumns (see _column_key)."""
-    return tuple((k, id(v), v.__array_interface__["data"][0], v.shape)
-                 for k, v in sorted(vars(gt).items()) if isinstance(v, np.ndarray))
+def _arrays_key(gt):
+    """columns.array_key of every array behind a GTColumns."""
+    return tuple((k, array_key(v)) for k, v in sorted(vars(gt).items()) if isinstance(v, np.ndarray))
 
 
 def _sorted_unique(keys):
@@ -116,7 +116,7 @@ def prepare_gt(gt, kinds=("lvis", "tao"), wait=True):
         else:
             made[k] = pool.submit(build, k)
     pool.shutdown(wait=False)
-    vars(gt)["_prepared_gt"] = (_gt_key(gt), made, parts)
+    vars(gt)["_prepared_gt"] = (_arrays_key(gt), made, parts)
     if wait:
         for f in made.values():
             f.result()
@@ -131,7 +131,7 @@ def _gt_universe(gt):
     key, _made, parts = slot
     fut = parts.pop("tao_universe", None)
     A = fut.result() if fut is not None else None
-    return A if A is not None and key == _gt_key(gt) else None
+    return A if A is not None and key == _arrays_key(gt) else None
 
 
 def _gt_ready(gt, kind):
@@ -143,6 +143,6 @@ def _gt_ready(gt, kind):
             vars(gt).pop("_prepared_gt", None)
         if R is not None:
             R = R.result()              # (a half still being built: wait for it)
-        if R is not None and key == _gt_key(gt):
+        if R is not None and key == _arrays_key(gt):
             return R
     return _READY[kind](gt)

@@ -223,6 +223,50 @@ def test_track_clash_answered_on_the_device(tmp_path):
     assert d.track_clash_free() is None
 
 
+def test_forget_columns_retires_the_readers_tensors(tmp_path):
+    """Edits between the elements fingerprint samples, then forget_columns:
+    raw_columns, the track-id check and both levels use the host arrays."""
+    from tao_amodal_amd import flatten, flatten_dev
+    from tao_amodal_amd.columns import DeviceDTColumns
+    from tao_amodal_amd.evaluation.lvis_amodal import LVIS, LVISEval, LVISResults
+    from tao_amodal_amd.evaluation.tao_amodal import Tao, TaoEval, TaoResults
+    from tao_amodal_amd.synth import synth
+    gt, c = synth(seed=5, V=4, F=40, C=30, dets_per_frame=30, n_present=5)
+    c.track_id, _ = flatten.make_track_ids_unique(c)
+    p = str(tmp_path / "pred.json")
+    c.write_json(p)
+    d = DTColumns.from_file_native(p)
+    assert isinstance(d, DeviceDTColumns)
+    same(d, c)                                      # (waits for the host arrays)
+    assert d.track_clash_free() is True
+    # a kept detection whose score and track id fingerprint does not read
+    step = len(d) // 1024
+    kept = np.asarray(flatten.flatten_lvis(gt, c).dt_row, np.int64)
+    i = next(int(r) for r in kept if r % step and r != len(d) - 1)
+    made = d._dev["score"].data_ptr()
+    d.score[i] = 2.0
+    d.track_id[i] = int(c.track_id.max()) + 1       # a track of its own
+    flatten_dev.forget_columns(d)
+    raw = flatten_dev.raw_columns(d, "cuda")
+    assert raw["score"].data_ptr() != made
+    for f in ("image_id", "category_id", "score", "bbox", "video_id"):
+        assert np.array_equal(raw[f].cpu().numpy(), getattr(d, f)), f
+    assert d.track_clash_free() is None
+    plain = DTColumns(**{f: getattr(d, f).copy() for f in FIELDS})
+    gtj = gt.to_json()
+
+    def run(dt, Gt, Results, Eval):
+        g = Gt(gtj)
+        ev = Eval(g, Results(g, dt), iou_type="bbox")
+        ev.run()
+        return ev
+    for level in ((LVIS, LVISResults, LVISEval), (Tao, TaoResults, TaoEval)):
+        got, want = run(d, *level), run(plain, *level)
+        assert np.array_equal(got.eval["precision"], want.eval["precision"])
+        assert np.array_equal(got.eval["recall"], want.eval["recall"])
+        assert list(got.results.items()) == list(want.results.items())
+
+
 def test_random_files_agree_with_the_host_reader_or_go_to_it(tmp_path):
     """Fuzz: prediction lists with random spellings, spacing, key order, extra
     and missing keys, literals and broken syntax.  The device reader either
