@@ -790,6 +790,25 @@ int taoamd_accumulate_by_order(int64_t n_dt, int32_t n_cat, int32_t n_rng,
                                const int32_t *num_gt, int32_t max_segment,
                                double *precision, double *recall, void *workspace,
                                size_t workspace_bytes, void *stream);
+/* _prepared: on a workspace taoamd_accumulate_prepare planned (the plan depends
+ * on cat_off alone, not on where the rows lie); the one-pass sweep then runs its
+ * gathered kernel: order[] in coalesced pieces, the 16-byte rows of a chunk
+ * gathered in one batch.  _chunked: the chunked kernels whatever the sweep mode
+ * -- what a caller runs again when taoamd_accumulate_error reports a look-back
+ * that gave up (rows still in cell order, order[] still in place; prepare again
+ * afterwards). */
+int taoamd_accumulate_by_order_prepared(int64_t n_dt, int32_t n_cat, int32_t n_rng,
+                               const int32_t *cat_off, const int32_t *order,
+                               const uint64_t *matched, const uint64_t *ignored,
+                               const int32_t *num_gt, int32_t max_segment,
+                               double *precision, double *recall, void *workspace,
+                               size_t workspace_bytes, void *stream);
+int taoamd_accumulate_by_order_chunked(int64_t n_dt, int32_t n_cat, int32_t n_rng,
+                               const int32_t *cat_off, const int32_t *order,
+                               const uint64_t *matched, const uint64_t *ignored,
+                               const int32_t *num_gt, int32_t max_segment,
+                               double *precision, double *recall, void *workspace,
+                               size_t workspace_bytes, void *stream);
 
 /* ---- multi-GPU result exchange (category-partitioned evaluation) -------------------
  * No reference counterpart (the reference is single-process); these carry the

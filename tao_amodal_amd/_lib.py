@@ -170,6 +170,10 @@ SIGNATURES = {
                                     _vp, _vp, _vp, _sz, _vp]),
     "taoamd_accumulate_by_order": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp,
                                              _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "taoamd_accumulate_by_order_prepared": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp,
+                                             _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "taoamd_accumulate_by_order_chunked": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp,
+                                             _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

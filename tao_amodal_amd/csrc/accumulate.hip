@@ -377,12 +377,41 @@ __device__ __forceinline__ uint64_t transpose64(uint64_t x, int lane)
 // offset per lane (global_load_dwordx4 v, v_off, s[base]) and no in-range
 // selects: ~190 VALU instructions of address arithmetic, selects and and-nots
 // a chunk become ~50.
-template <int ACC_BLK_N>
+//
+// GATHER: the rows lie in cell order (the match stored them as whole-wavefront
+// runs and did not wait for the sort) and sorted place p holds row order[p].
+// The full chunk's twin: the wavefront's ACC_BLK_N * 64 places of order[] with
+// coalesced loads from one uniform base (lane = row of a 64-row block, the
+// layout the transposes want, so nothing changes lanes afterwards), all issued
+// before the first is waited for, then all the 16-byte row gathers in one batch
+// (one more dependent round trip than the streaming form, no selects).  A
+// category's rows in cell order are one contiguous piece as well (the cells are
+// category-major), so the gathers of a category's super-chunks, which the XCD
+// order puts behind one L2, stay inside that piece.
+template <int ACC_BLK_N, bool GATHER = false>
 __device__ __forceinline__ void load_chunk_tv(const AccArgs &a, int64_t start, int word, int len,
                                               int lane, uint64_t (&tpw)[ACC_BLK_N],
                                               uint64_t (&vw)[ACC_BLK_N])
 {
-    if (a.wide && a.order == nullptr && len == ACC_BLK_N * WAVE) {
+    if (GATHER && a.wide && len == ACC_BLK_N * WAVE) {
+        const int32_t *__restrict__ ob = a.order + start;              // (uniform)
+        uint32_t at[ACC_BLK_N];
+#pragma unroll
+        for (int blk = 0; blk < ACC_BLK_N; blk++) at[blk] = (uint32_t)ob[blk * WAVE + lane];
+        const char *base = reinterpret_cast<const char *>(a.matched + 2 * word);
+        const uint32_t row_bytes = (uint32_t)a.n_words * 16u;
+        ulonglong2 v[ACC_BLK_N];
+#pragma unroll
+        for (int blk = 0; blk < ACC_BLK_N; blk++)
+            v[blk] = *reinterpret_cast<const ulonglong2 *>(base + (uint64_t)at[blk] * row_bytes);
+#pragma unroll
+        for (int blk = 0; blk < ACC_BLK_N; blk++) {
+            tpw[blk] = v[blk].x & ~v[blk].y;
+            vw[blk] = ~v[blk].y;
+        }
+        return;
+    }
+    if (!GATHER && a.wide && a.order == nullptr && len == ACC_BLK_N * WAVE) {
         const char *base = reinterpret_cast<const char *>(a.matched + 2 * (start * a.n_words + word));
         const uint32_t lane_off = (uint32_t)lane * (uint32_t)a.n_words * 16u;
         const uint32_t blk_off = (uint32_t)WAVE * (uint32_t)a.n_words * 16u;
@@ -1176,7 +1205,9 @@ __global__ void acc_cj_kernel(AccArgs a, RecThr rec)
 // NB = 64-row blocks of a wavefront's chunk (8: 512 rows; the chunked kernels'
 // (NB * WAVE) = 256 rows would be 4 -- 512 is 0.281 against 0.297 ms at 21 M rows:
 // half the wavefronts, half the per-wavefront set-up, still 64 VGPRs)
-template <int SW, int MODE, int NB = SWEEP_NB>
+// GATHER: rows in cell order, fetched through a.order (load_chunk_tv); a kernel
+// of its own, so that the streaming form keeps its code and its registers
+template <int SW, int MODE, bool GATHER = false, int NB = SWEEP_NB>
 __global__ __launch_bounds__(SW * WAVE) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void acc_sweep_kernel(AccArgs a, RecThr rec)
 {
@@ -1217,7 +1248,7 @@ void acc_sweep_kernel(AccArgs a, RecThr rec)
     const bool swept = k >= a.k_begin && k < a.k_end;       // (uniform)
     // ---- rows of my chunk: every load ahead of anything else
     uint64_t tpw[NB], vw[NB];
-    load_chunk_tv(a, start, word, len, lane, tpw, vw);
+    load_chunk_tv<NB, GATHER>(a, start, word, len, lane, tpw, vw);
     const int r_lo = (word * WAVE) / N_THR;
     const int r_hi = min(a.n_rng - 1, (word * WAVE + WAVE - 1) / N_THR);
     if (MODE != 2) {
@@ -1827,7 +1858,13 @@ static int accumulate_compact(int64_t n_dt, int32_t n_cat, int32_t n_rng,
             uint32_t g = ++g_sc_gen;
             a.sc_gen = (g & 0x3fffffffu) ? (g & 0x3fffffffu) : (++g_sc_gen & 0x3fffffffu);
             a.sc_error = tickets;
-            TAO_TIMED("acc_sweep_kernel", s, (acc_sweep_kernel<SWEEP_SW, 0><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
+            if (a.order)
+                TAO_TIMED("acc_sweep_kernel", s, (acc_sweep_kernel<SWEEP_SW, 0, true><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
+            else
+                TAO_TIMED("acc_sweep_kernel", s, (acc_sweep_kernel<SWEEP_SW, 0><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
+        } else if (a.order) {
+            TAO_TIMED("acc_sccount_kernel", s, (acc_sweep_kernel<SWEEP_SW, 2, true><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
+            TAO_TIMED("acc_sweep_kernel", s, (acc_sweep_kernel<SWEEP_SW, 1, true><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
         } else {
             TAO_TIMED("acc_sccount_kernel", s, (acc_sweep_kernel<SWEEP_SW, 2><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
             TAO_TIMED("acc_sweep_kernel", s, (acc_sweep_kernel<SWEEP_SW, 1><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
@@ -1982,6 +2019,43 @@ extern "C" int taoamd_accumulate_by_order(int64_t n_dt, int32_t n_cat, int32_t n
     return accumulate_all(n_dt, n_cat, n_rng, cat_off, order, matched, ignored,
                           num_gt, max_segment, precision, recall, workspace,
                           workspace_bytes, stream);
+}
+
+// ... on a prepared workspace (taoamd_accumulate_prepare: the plan depends on
+// cat_off alone, not on where the rows lie)
+extern "C" int taoamd_accumulate_by_order_prepared(int64_t n_dt, int32_t n_cat, int32_t n_rng,
+                                                   const int32_t *cat_off,
+                                                   const int32_t *order,
+                                                   const uint64_t *matched,
+                                                   const uint64_t *ignored,
+                                                   const int32_t *num_gt, int32_t max_segment,
+                                                   double *precision, double *recall,
+                                                   void *workspace, size_t workspace_bytes,
+                                                   void *stream)
+{
+    if (!order) return TAOAMD_ERR_ARG;
+    return accumulate_all(n_dt, n_cat, n_rng, cat_off, order, matched, ignored,
+                          num_gt, max_segment, precision, recall, workspace,
+                          workspace_bytes, stream, ACC_SWEEP);
+}
+
+// ... and from the chunked kernels whatever the sweep mode: the second sweep of
+// a gathered pass whose look-back gave up (taoamd_accumulate_chunked; the rows
+// are still in cell order, order[] still in place)
+extern "C" int taoamd_accumulate_by_order_chunked(int64_t n_dt, int32_t n_cat, int32_t n_rng,
+                                                  const int32_t *cat_off,
+                                                  const int32_t *order,
+                                                  const uint64_t *matched,
+                                                  const uint64_t *ignored,
+                                                  const int32_t *num_gt, int32_t max_segment,
+                                                  double *precision, double *recall,
+                                                  void *workspace, size_t workspace_bytes,
+                                                  void *stream)
+{
+    if (!order) return TAOAMD_ERR_ARG;
+    return accumulate_all(n_dt, n_cat, n_rng, cat_off, order, matched, ignored,
+                          num_gt, max_segment, precision, recall, workspace,
+                          workspace_bytes, stream, ACC_ALL, SWEEP_CHUNKED);
 }
 
 extern "C" int taoamd_accumulate_prepare(int64_t n_dt, int32_t n_cat, int32_t n_rng,

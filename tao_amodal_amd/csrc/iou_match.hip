@@ -358,7 +358,11 @@ __global__ __launch_bounds__(256) void match_kernel(MatchArgs a, IouThr thr)
 // batch: with the layout decided by run-time (uniform) branches the compiler
 // put an s_waitcnt vmcnt(0) behind each of them, four HBM round trips in a
 // row where two are needed (descriptor, then everything).
-template <bool FUSED, bool FAST = false>
+// SCATTER (FAST only): a detection's row goes to its sorted place dst[d] -- one
+// cache line per store --; false: rows stay in cell order, a run's rows are ONE
+// contiguous piece written by a whole wavefront, dst[] is not read and the match
+// does not depend on the sort (the sweep gathers them through order[]).
+template <bool FUSED, bool FAST = false, bool SCATTER = true>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void match_group_kernel(MatchArgs a, IouThr thr)
 {
     __shared__ double4 s_gt[4][WAVE];
@@ -405,9 +409,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         const int32_t g = g0 + min(lane, max(nG, 1) - 1);
         const uint32_t mt = a.dt_meta[d];
 #ifdef TAOAMD_ABLATE_SCATTER     // (timing experiment: rows stored in detection order)
-        const int32_t row = d + (a.dst[d] & 0);
+        const int32_t row = SCATTER ? d + (a.dst[d] & 0) : d;
 #else
-        const int32_t row = a.dst[d];
+        const int32_t row = SCATTER ? a.dst[d] : d;
 #endif
         const double4 box = reinterpret_cast<const double4 *>(a.dt_box)[d];
         uint32_t gr = 0xffffffffu;
@@ -950,9 +954,10 @@ extern "C" int taoamd_match(int64_t n_cells, const int32_t *cell_dt_off,
     if (planned && n_groups > 0) {
         const unsigned gb = (unsigned)(((int64_t)n_groups * a.n_words + 3) / 4);
         // (one combo word of at most six ranges: the fast kernel's word assembly)
-        const bool fast = fused && a.dt_meta && a.dst && !a.dt_rng && !a.ious_out && !a.match_gt &&
+        const bool fast = fused && a.dt_meta && !a.dt_rng && !a.ious_out && !a.match_gt &&
                           a.n_words == 1 && n_rng <= 6;
-        if (fast) TAO_TIMED("match_group_kernel", s, (match_group_kernel<true, true><<<gb, 256, 0, s>>>(a, match_thr())));
+        if (fast && a.dst) TAO_TIMED("match_group_kernel", s, (match_group_kernel<true, true><<<gb, 256, 0, s>>>(a, match_thr())));
+        else if (fast) TAO_TIMED("match_group_kernel", s, (match_group_kernel<true, true, false><<<gb, 256, 0, s>>>(a, match_thr())));
         else if (fused) TAO_TIMED("match_group_kernel", s, match_group_kernel<true><<<gb, 256, 0, s>>>(a, match_thr()));
         else TAO_TIMED("match_group_kernel", s, match_group_kernel<false><<<gb, 256, 0, s>>>(a, match_thr()));
     }

@@ -451,6 +451,9 @@ class Workspace:
         lib = _lib.load()
         dev = dp.device
         u8 = torch.uint8
+        # rows left in cell order and gathered by the sweep (run_forked) where
+        # that is the faster form; the per-detection views want the rows sorted
+        self.gather = not detail and gathers_rows(dp)
 
         def buf(nbytes):
             return torch.empty(max(int(nbytes), 256), dtype=u8, device=dev)
@@ -461,14 +464,19 @@ class Workspace:
             else torch.empty(max(dp.n_dt, 1), dtype=torch.int32, device=dev)
         self.num_gt = torch.empty((dp.n_cat, dp.n_rng), dtype=torch.int32,
                                   device=dev)
-        # dst[i] = sorted place of detection i is what the pass needs (the match
-        # writes a detection's row there); order[] = its inverse is derived on
-        # demand (the `order` property) unless a caller wants the sort to store
-        # it: 86 MB of stores less per pass at 21 M detections
+        # dst[i] = the place of detection i's row in `rows`.  Scatter form: its
+        # sorted place, stored by the sort (the match writes the row there);
+        # order[] = its inverse is derived on demand (the `order` property)
+        # unless a caller wants the sort to store it: 86 MB of stores less per
+        # pass at 21 M detections.  Gathered form: the sort stores order[] and
+        # nothing else, the rows stay where the detections are and dst[] is the
+        # identity, written once (dst_identity: it still is).
         self.order_buf = torch.empty(max(dp.n_dt, 1), dtype=torch.int32, device=dev) \
-            if (detail or keep_order or _os0.environ.get("TAOAMD_SORT_ASIDE", "0") != "0") else None
+            if (detail or keep_order or self.gather or SORT_ASIDE) else None
         self._n_dt = dp.n_dt
         self.dst = torch.empty(max(dp.n_dt, 1), dtype=torch.int32, device=dev)
+        self.dst_identity = False
+        self.cell_order = False           # the last match left its rows in cell order
         self.sort_bytes = max(lib.taoamd_sort_workspace(dp.n_dt),
                               lib.taoamd_sort_segments_workspace(dp.n_dt),
                               lib.taoamd_sort_sampled_workspace(
@@ -587,8 +595,35 @@ def sort_is_sampled(dp):
     return dp.n_dt >= SORT_SAMPLED_MIN
 
 
+# Image level, Overlap's chain: where the match leaves its rows (run_forked).
+# TAOAMD_SORT_ASIDE unset: cell order + gathering sweep where gathers_rows() says
+# so; =0: the scatter form everywhere; =1: cell order wherever the chain can
+# (A/B timing from one build).  Measured on one MI355X at 21.4 M rows, three runs
+# each: scatter form 1.356-1.361 ms a step, cell order 1.290-1.304 (the sort
+# stores no dst[], the match reads none, stores whole-wavefront runs and runs
+# beside the sort; the one-pass sweep's gathered loader pays part of it back).
+# The round-2 form of the same idea -- generic loader, unprepared plan, the slow
+# match kernel -- was and is a loss: 1.364-1.371 ms.
+_ASIDE_ENV = _os0.environ.get("TAOAMD_SORT_ASIDE", "")
+SORT_ASIDE = None if _ASIDE_ENV == "" else _ASIDE_ENV != "0"
+
+
+def gathers_rows(dp):
+    """Whether Overlap's image-level chain leaves the match's rows in cell
+    order on this problem: box IoU, grouped plan, the sample sort (it can store
+    order[] alone) and the one-pass sweep (it reads every row once: the 6 M-row
+    rule of taoamd_accumulate_plan_kind) on one GPU."""
+    if SORT_ASIDE is not None:
+        return False          # (forced either way: run_forked is told by its caller)
+    return (dp.kind == "lvis" and not dp.mask_iou and dp.grouped and dp.n_dt > 0
+            and dp.device.type == "cuda" and sort_is_sampled(dp)
+            and _plan_key(dp)[1] in (2, 3))
+
+
 def stage_sort(dp, ws, order_only=False):
     lib, t, s = _lib.load(), dp.t, _stream()
+    if not order_only:
+        ws.dst_identity = False
     if dp.grouped and dp.n_dt and sort_is_sampled(dp):
         nc, ns, nt, nb = dp.ss_sizes
         _lib.check(lib.taoamd_sort_sampled(
@@ -768,11 +803,19 @@ def sweep_ok(dp, ws):
         "shared GPU?): this pass is swept again with the chunked kernels")
     lib, t = _lib.load(), dp.t
     with torch.cuda.device(dp.device):
-        _lib.check(lib.taoamd_accumulate_chunked(
-            dp.n_dt, dp.n_cat, dp.n_rng, _ptr(t["cat_off"]), _ptr(ws.matched),
-            _ptr(ws.ignored), _ptr(ws.num_gt), dp.acc_hint, _ptr(ws.precision),
-            _ptr(ws.recall), _ptr(ws.acc_ws), ws.acc_bytes, _stream()),
-            "taoamd_accumulate_chunked")
+        if ws.cell_order:
+            # (the rows are where the match left them, order[] where the sort did)
+            _lib.check(lib.taoamd_accumulate_by_order_chunked(
+                dp.n_dt, dp.n_cat, dp.n_rng, _ptr(t["cat_off"]), _ptr(ws.order),
+                _ptr(ws.matched), _ptr(ws.ignored), _ptr(ws.num_gt), dp.acc_hint,
+                _ptr(ws.precision), _ptr(ws.recall), _ptr(ws.acc_ws), ws.acc_bytes,
+                _stream()), "taoamd_accumulate_by_order_chunked")
+        else:
+            _lib.check(lib.taoamd_accumulate_chunked(
+                dp.n_dt, dp.n_cat, dp.n_rng, _ptr(t["cat_off"]), _ptr(ws.matched),
+                _ptr(ws.ignored), _ptr(ws.num_gt), dp.acc_hint, _ptr(ws.precision),
+                _ptr(ws.recall), _ptr(ws.acc_ws), ws.acc_bytes, _stream()),
+                "taoamd_accumulate_chunked")
     prepare_sweep(dp, ws)
     torch.cuda.synchronize(dp.device)
     ws.sweep_recovered += 1
@@ -873,6 +916,8 @@ def stage_match(dp, ws, scatter=True, groups=None, singles=None):
         if n_g == 0 and n_s == 0:
             return
     fused = dp.kind == "lvis" and not dp.mask_iou
+    if groups is None:
+        ws.cell_order = not scatter
     _lib.check(lib.taoamd_match(
         dp.n_cells, _ptr(t["cell_dt_off"]), _ptr(t["cell_gt_off"]),
         _ptr(t["cell_iou_off"]), dp.max_g,
@@ -891,7 +936,9 @@ def stage_accumulate_by_order(dp, ws):
     """The sweep over rows the match left in cell order (stage_match(scatter=
     False)): gathered through the sort's order[] by the first sweep."""
     lib, t, s = _lib.load(), dp.t, _stream()
-    _lib.check(lib.taoamd_accumulate_by_order(
+    fn = lib.taoamd_accumulate_by_order_prepared if ws.acc_prepared == _plan_key(dp) \
+        else lib.taoamd_accumulate_by_order
+    _lib.check(fn(
         dp.n_dt, dp.n_cat, dp.n_rng, _ptr(t["cat_off"]), _ptr(ws.order),
         _ptr(ws.matched), _ptr(ws.ignored), _ptr(ws.num_gt), dp.acc_hint,
         _ptr(ws.precision), _ptr(ws.recall), _ptr(ws.acc_ws), ws.acc_bytes, s),
@@ -932,11 +979,6 @@ def run(dp, ws):
 
 
 import os as _os
-# Overlap: image-level sort beside ranges + match (see run_forked).  Off: measured
-# slower on one MI355X (0.439 vs 0.421 ms/step at Config 2: the match takes 139
-# instead of 84 us beside the sort -- the step is bound by the sum of its
-# kernels, not by the chain); TAOAMD_SORT_ASIDE=1 switches it on for A/B timing
-SORT_ASIDE = _os.environ.get("TAOAMD_SORT_ASIDE", "0") != "0"
 # A/B: the 3D IoU (the longest kernel) alone ahead of the image level instead of beside it
 TRACK_FIRST = _os.environ.get("TAOAMD_TRACK_FIRST", "0") != "0"
 TRACK_AFTER_SORT = _os.environ.get("TAOAMD_TRACK_AFTER_SORT", "0") != "0"
@@ -1070,25 +1112,39 @@ def _probed(name, fn, dp, ws):
         PROBE.wrap(dp.kind + ":" + name, fn, dp, ws)
 
 
-def run_forked(dp, ws, aux, head_only=False, sort_aside=False, no_match=False,
+def run_forked(dp, ws, aux, head_only=False, sort_aside=None, no_match=False,
                sort_done=None, match_done=None):
     """One evaluator pass on the current stream, its independent head stages
     on the stream `aux` (forked from and joined to the current stream):
     image level  ranges || sort -> match -> accumulate,
     track level  (ranges, sort) || 3D IoU -> match -> accumulate.
-    `sort_aside` (image level): sort || (ranges -> match, rows left in cell
-    order) -> accumulate gathering the rows through order[] -- the match does
-    not wait for the sort and stores full wavefront runs."""
+    `sort_aside` (image level; None: where the workspace was built for it,
+    Workspace.gather): the match leaves its rows in cell order -- it reads no
+    dst[], stores full wavefront runs and the sort stores order[] alone -- and
+    the sweep gathers them through order[]."""
     cur = torch.cuda.current_stream(dp.device)
     aux.wait_stream(cur)
     if _lib.TIMING:
         _lib.kernel_timing_label(dp.kind)
+    if sort_aside is None:
+        sort_aside = ws.gather and _plan_key(dp)[1] in (2, 3)
     if sort_aside and dp.kind == "lvis" and not dp.mask_iou and not head_only \
-            and dp.grouped and dp.n_dt:
+            and not no_match and dp.grouped and dp.n_dt:
+        order_only = sort_is_sampled(dp) and ws.order_buf is not None
+        if order_only and not ws.dst_identity:
+            # nobody stores sorted places: dst[] says where the rows are
+            torch.arange(dp.n_dt, out=ws.dst[:dp.n_dt])
+            ws.dst_identity = True
+        # the match BESIDE the sort (it no longer depends on it), not behind it:
+        # 1.290-1.304 against 1.327-1.335 ms a step at 21 M rows (parent 1.356-1.361)
         with torch.cuda.stream(aux):
-            stage_sort(dp, ws, order_only=sort_is_sampled(dp) and ws.order_buf is not None)
+            stage_sort(dp, ws, order_only=order_only)
+            if sort_done is not None:
+                sort_done.record(aux)
         stage_ranges(dp, ws)
         _probed("match", lambda d, w: stage_match(d, w, scatter=False), dp, ws)
+        if match_done is not None:
+            match_done.record(cur)
         cur.wait_stream(aux)
         stage_accumulate_by_order(dp, ws)
         return
