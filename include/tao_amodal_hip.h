@@ -82,7 +82,7 @@ extern "C" {
 #define TAOAMD_ERR_HIP 1         /* a HIP runtime call failed */
 #define TAOAMD_ERR_ARG 2         /* bad argument */
 #define TAOAMD_ERR_TOO_LARGE 3   /* a cell exceeds a kernel limit */
-#define TAOAMD_ERR_WORKSPACE 4   /* workspace too small */
+#define TAOAMD_ERR_WORKSPACE 4   /* workspace_bytes below what taoamd_*_workspace() reports */
 #define TAOAMD_JSON_FALLBACK 16  /* taoamd_json_pred_open: the host reader should take the file */
 
 const char *taoamd_strerror(int status);
@@ -698,7 +698,10 @@ size_t taoamd_accumulate_workspace(int64_t n_dt, int32_t n_cat, int32_t n_rng);
  * workgroup (<= 4096 rows with one combo word, <= 1024 with four) the sweep
  * is a single fused launch with all intermediates in LDS / registers;
  * otherwise (or with 0) categories are cut into chunks spread over the chip.
- * Workspace of _compact: taoamd_accumulate_workspace (val/rec excluded). */
+ * Workspace of _compact: taoamd_accumulate_workspace; its tables end where
+ * taoamd_accumulate keeps val and rec, so less is accepted (that much less).
+ * Every workspace: any base address (rounded up to 256 bytes inside, the
+ * reported size allows for it); contents need not be initialised. */
 size_t taoamd_compact_elems(int32_t n_cat, int32_t n_rng); /* 8-byte elements in val */
 int taoamd_accumulate_compact(int64_t n_dt, int32_t n_cat, int32_t n_rng,
                               const int32_t *cat_off, const uint64_t *matched,

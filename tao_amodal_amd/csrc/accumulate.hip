@@ -51,6 +51,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "workspace.hpp"
 
 using namespace taoamd;
 
@@ -1586,8 +1587,6 @@ __global__ __launch_bounds__(256) void acc_finalize_kernel(FinArgs a)
     }
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 static int32_t max_chunks(int64_t n_dt, int32_t n_cat)
 {
     return (int32_t)((n_dt + ACC_CH - 1) / ACC_CH + n_cat);
@@ -1680,36 +1679,60 @@ static size_t max_scs(int64_t n_dt, int32_t n_cat)
     return (size_t)(n_dt / (SWEEP_SW * SWEEP_NB * WAVE) + n_cat + 1);
 }
 
-static size_t sc_workspace(int64_t n_dt, int32_t n_cat, size_t nw)
-{
-    const size_t ns = max_scs(n_dt, n_cat);
-    return align256(SC_TICKETS * 4) + align256(ns * nw * WAVE * 16) +
-           align256(ns * nw * WAVE * 8) + align256(ns * nw * WAVE);
-}
-
-static size_t base_workspace(int64_t n_dt, int32_t n_cat, int32_t n_rng)
-{
-    const size_t nw = (size_t)(n_rng * N_THR + 63) / 64;
-    const size_t nc = (size_t)max_chunks(n_dt, n_cat);
-    return sc_workspace(n_dt, n_cat, nw) +
-           align256(((size_t)n_cat + 1) * 4) + align256(64) + align256(nc * 4) +
-           4 * align256(nc * nw * WAVE * 4) +
-           align256(nc * nw * WAVE * 8) +
-           2 * align256(nc * nw * ACC_BLK * WAVE * 8) +
-           align256((size_t)n_cat * n_rng * N_REC * 4) + 4096;
-}
-
 extern "C" size_t taoamd_compact_elems(int32_t n_cat, int32_t n_rng)
 {
     return (size_t)n_cat * n_rng * N_THR * N_REC;
 }
 
+// The tables of the sweep, in buffer order: a function of (n_dt, n_cat, n_rng)
+// alone -- what taoamd_accumulate_prepare writes is read by later passes in
+// any mode and phase.  The pieces every pass uses alike go straight into `a`;
+// the ones whose use depends on mode and phase come back for accumulate_compact.
+struct AccWs {
+    uint32_t *header;     // SC_TICKETS words: word 0 the error flag, then the look-back's tickets
+    size_t head_bytes;    // header + sc_stat: one piece, one memset clears both
+    int32_t *xcd_start, *chunk_tab;
+};
+
+static AccWs acc_layout(Carve &c, int64_t n_dt, int32_t n_cat, int32_t n_rng, AccArgs &a)
+{
+    a.n_words = (n_rng * N_THR + 63) / 64;
+    a.n_chunks_max = max_chunks(n_dt, n_cat);
+    const size_t nw = (size_t)a.n_words, nc = (size_t)a.n_chunks_max;
+    const size_t ns = max_scs(n_dt, n_cat);
+    AccWs t;
+    static_assert(SC_TICKETS * 4 % 256 == 0, "sc_stat starts a 256-byte line");
+    t.head_bytes = SC_TICKETS * 4 + ns * nw * WAVE * 16;
+    t.header = (uint32_t *)c.take<uint64_t>(t.head_bytes / 8);
+    a.sc_stat = (uint64_t *)Carve::at(t.header, SC_TICKETS);
+    a.sc_max = c.take<uint64_t>(ns * nw * WAVE);
+    a.sc_jhi = c.take<uint8_t>(ns * nw * WAVE);
+    a.cat_chunk_off = c.take<int32_t>((size_t)n_cat + 1);
+    t.xcd_start = c.take<int32_t>(N_XCD + 1);
+    t.chunk_tab = c.take<int32_t>(nc);
+    for (uint32_t **p : {&a.cnt_tp, &a.cnt_fp, &a.pre_tp, &a.pre_fp})
+        *p = c.take<uint32_t>(nc * nw * WAVE);
+    a.cmax = c.take<uint64_t>(nc * nw * WAVE);
+    for (uint64_t **p : {&a.t_tp, &a.t_fp}) *p = c.take<uint64_t>(nc * nw * ACC_BLK * WAVE);
+    a.cj = c.take<int32_t>((size_t)n_cat * n_rng * N_REC);
+    return t;
+}
+
+// ... and behind them the records of taoamd_accumulate*: val, rec
+static void acc_full_layout(Carve &c, int64_t n_dt, int32_t n_cat, int32_t n_rng,
+                            double *&val, double *&rec)
+{
+    AccArgs a;
+    acc_layout(c, n_dt, n_cat, n_rng, a);
+    val = c.take<double>(taoamd_compact_elems(n_cat, n_rng));
+    rec = c.take<double>((size_t)n_cat * n_rng * N_THR);
+}
+
 extern "C" size_t taoamd_accumulate_workspace(int64_t n_dt, int32_t n_cat,
                                               int32_t n_rng)
 {
-    return base_workspace(n_dt, n_cat, n_rng) +
-           align256(taoamd_compact_elems(n_cat, n_rng) * 8) +
-           align256((size_t)n_cat * n_rng * N_THR * 8);
+    double *val, *rec;
+    return measure([&](Carve &c) { acc_full_layout(c, n_dt, n_cat, n_rng, val, rec); });
 }
 
 // phases of accumulate_compact: the chunk table depends on cat_off alone, so a
@@ -1729,23 +1752,21 @@ static int accumulate_compact(int64_t n_dt, int32_t n_cat, int32_t n_rng,
     if (k_begin < 0 || k_end > n_cat || k_begin > k_end) return TAOAMD_ERR_ARG;
     if (!cat_off || !workspace) return TAOAMD_ERR_ARG;
     if (phase != ACC_PLAN && (!num_gt || !val || !rec)) return TAOAMD_ERR_ARG;
-    if (workspace_bytes < base_workspace(n_dt, n_cat, n_rng))
-        return TAOAMD_ERR_WORKSPACE;
+    Carve c(workspace);
+    AccArgs a;
+    const AccWs t = acc_layout(c, n_dt, n_cat, n_rng, a);
+    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
     if (k_begin == k_end) return TAOAMD_OK;
     hipStream_t s = (hipStream_t)stream;
-    AccArgs a;
-    a.cat_chunk_off = nullptr; a.chunk_tab = nullptr; a.cnt_tp = a.cnt_fp = a.pre_tp = a.pre_fp = nullptr;
-    a.cmax = a.t_tp = a.t_fp = nullptr; a.cj = nullptr;
+    a.chunk_tab = nullptr;
     a.n_dt = n_dt; a.n_cat = n_cat; a.n_rng = n_rng;
-    a.n_words = (n_rng * N_THR + 63) / 64;
-    a.n_chunks_max = max_chunks(n_dt, n_cat);
     a.cat_off = cat_off; a.matched = matched; a.ignored = ignored; a.order = order;
     a.paired = matched != nullptr && ignored == matched + 1;
     a.wide = a.paired && ((uintptr_t)matched & 15) == 0;
     a.num_gt = num_gt; a.val = (uint64_t *)val; a.rec = rec;
     a.k_begin = k_begin; a.k_end = k_end;
     a.inline_scans = 0;
-    a.sc_rows = 0; a.sc_gen = 0; a.sc_stat = a.sc_max = nullptr; a.sc_jhi = nullptr;
+    a.sc_rows = 0; a.sc_gen = 0;
     a.sc_error = nullptr;
     a.sc_giveups = g_sweep_giveups.load(std::memory_order_relaxed);
     a.xcd_start = nullptr;
@@ -1767,8 +1788,7 @@ static int accumulate_compact(int64_t n_dt, int32_t n_cat, int32_t n_rng,
     // taoamd_accumulate_error -- zero whenever a plan or an unprepared pass
     // starts, whatever path it takes)
     if (phase != ACC_SWEEP)
-        TAO_HIP(hipMemsetAsync((void *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255), 0,
-                               align256(SC_TICKETS * 4), s));
+        TAO_HIP(hipMemsetAsync(t.header, 0, SC_TICKETS * 4, s));
     const int32_t fused_cap = ACC_FUSED_WAVES / a.n_words * ACC_CH;
     const bool all_fused = max_segment > 0 && max_segment <= fused_cap &&
                            (force_mode == SWEEP_CHUNKED || !sweep_mode_explicit_onepass());
@@ -1800,41 +1820,24 @@ static int accumulate_compact(int64_t n_dt, int32_t n_cat, int32_t n_rng,
     // scan kernels are folded into their consumers (four launches on the
     // chain instead of six; all or nothing, like the fused sweep)
     a.inline_scans = max_segment > 0 && max_segment <= ACC_INLINE_CHUNKS * ACC_CH;
-    unsigned char *w = (unsigned char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     const size_t nc = (size_t)a.n_chunks_max, nw = (size_t)a.n_words;
     const int mode = force_mode != SWEEP_AUTO ? force_mode : sweep_mode(n_dt);
-    const size_t ns = max_scs(n_dt, n_cat);
-    uint32_t *tickets = (uint32_t *)w;   w += align256(SC_TICKETS * 4);
-    a.sc_stat = (uint64_t *)w;           w += align256(ns * nw * WAVE * 16);
-    a.sc_max = (uint64_t *)w;            w += align256(ns * nw * WAVE * 8);
-    a.sc_jhi = (uint8_t *)w;             w += align256(ns * nw * WAVE);
     if (mode != SWEEP_CHUNKED) {
         a.sc_rows = SWEEP_SW * SWEEP_NB * WAVE;
         a.inline_scans = 0;
     }
-    a.cat_chunk_off = (int32_t *)w; w += align256(((size_t)n_cat + 1) * 4);
     // (the runs' lengths are bounded only when the longest category is known)
-    if (mode != SWEEP_CHUNKED && max_segment > 0) a.xcd_start = (int32_t *)w;
-    w += align256(64);
-    int32_t *chunk_tab = (int32_t *)w; w += align256(nc * 4);
-    a.chunk_tab = phase == ACC_SWEEP ? chunk_tab : nullptr;
-    a.cnt_tp = (uint32_t *)w; w += align256(nc * nw * WAVE * 4);
-    a.cnt_fp = (uint32_t *)w; w += align256(nc * nw * WAVE * 4);
-    a.pre_tp = (uint32_t *)w; w += align256(nc * nw * WAVE * 4);
-    a.pre_fp = (uint32_t *)w; w += align256(nc * nw * WAVE * 4);
-    a.cmax = (uint64_t *)w; w += align256(nc * nw * WAVE * 8);
-    a.t_tp = (uint64_t *)w; w += align256(nc * nw * ACC_BLK * WAVE * 8);
-    a.t_fp = (uint64_t *)w; w += align256(nc * nw * ACC_BLK * WAVE * 8);
-    a.cj = (int32_t *)w;
+    if (mode != SWEEP_CHUNKED && max_segment > 0) a.xcd_start = t.xcd_start;
+    if (phase == ACC_SWEEP) a.chunk_tab = t.chunk_tab;
     const unsigned chunk_blocks = (unsigned)((nc * nw + 3) / 4);
     const unsigned cat_blocks = (unsigned)((size_t)(k_end - k_begin) * nw);
     if (phase != ACC_SWEEP)
         TAO_TIMED("acc_chunks_kernel", s, acc_chunks_kernel<<<1, 256, 0, s>>>(a));
     if (phase == ACC_PLAN) {
-        TAO_TIMED("acc_chunktab_kernel", s, acc_chunktab_kernel<<<(unsigned)((nc + 255) / 256), 256, 0, s>>>(a, chunk_tab));
+        TAO_TIMED("acc_chunktab_kernel", s, acc_chunktab_kernel<<<(unsigned)((nc + 255) / 256), 256, 0, s>>>(a, t.chunk_tab));
         // (the look-back's ticket slots and status words start from zero)
         if (mode != SWEEP_CHUNKED)
-            TAO_HIP(hipMemsetAsync(tickets, 0, align256(SC_TICKETS * 4) + align256(ns * nw * WAVE * 16), s));
+            TAO_HIP(hipMemsetAsync(t.header, 0, t.head_bytes, s));
         TAO_LAUNCH_CHECK();
         return TAOAMD_OK;
     }
@@ -1854,10 +1857,10 @@ static int accumulate_compact(int64_t n_dt, int32_t n_cat, int32_t n_rng,
         if (mode == SWEEP_LOOKBACK) {
             // an unprepared workspace may hold anything
             if (phase == ACC_ALL)
-                TAO_HIP(hipMemsetAsync(tickets, 0, align256(SC_TICKETS * 4) + align256(ns * nw * WAVE * 16), s));
+                TAO_HIP(hipMemsetAsync(t.header, 0, t.head_bytes, s));
             uint32_t g = ++g_sc_gen;
             a.sc_gen = (g & 0x3fffffffu) ? (g & 0x3fffffffu) : (++g_sc_gen & 0x3fffffffu);
-            a.sc_error = tickets;
+            a.sc_error = t.header;
             if (a.order)
                 TAO_TIMED("acc_sweep_kernel", s, (acc_sweep_kernel<SWEEP_SW, 0, true><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
             else
@@ -1895,7 +1898,10 @@ static int accumulate_compact(int64_t n_dt, int32_t n_cat, int32_t n_rng,
 extern "C" int taoamd_accumulate_error(const void *workspace, void *stream, int32_t *flag_host)
 {
     if (!workspace || !flag_host) return TAOAMD_ERR_ARG;
-    const unsigned char *w = (const unsigned char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    // (the header is the first piece whatever the shape)
+    Carve c((void *)workspace);
+    AccArgs a;
+    const uint32_t *w = acc_layout(c, 0, 1, 1, a).header;
     uint32_t f = 0;
     TAO_HIP(hipMemcpyAsync(&f, w, sizeof f, hipMemcpyDeviceToHost, (hipStream_t)stream));
     TAO_HIP(hipStreamSynchronize((hipStream_t)stream));
@@ -1946,15 +1952,13 @@ static int accumulate_all(int64_t n_dt, int32_t n_cat, int32_t n_rng,
 {
     if (n_cat <= 0 || n_rng < 1 || n_rng > 32) return TAOAMD_ERR_ARG;
     if (!workspace) return TAOAMD_ERR_ARG;
-    if (workspace_bytes < taoamd_accumulate_workspace(n_dt, n_cat, n_rng))
-        return TAOAMD_ERR_WORKSPACE;
-    unsigned char *w = (unsigned char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    const size_t base = base_workspace(n_dt, n_cat, n_rng);
-    double *val = (double *)(w + base);
-    double *rec = val + (align256(taoamd_compact_elems(n_cat, n_rng) * 8) / 8);
+    Carve c(workspace);
+    double *val, *rec;
+    acc_full_layout(c, n_dt, n_cat, n_rng, val, rec);
+    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
     int st = accumulate_compact(n_dt, n_cat, n_rng, cat_off, order, matched, ignored,
-                                num_gt, 0, n_cat, max_segment, val, rec, w, base,
-                                stream, phase, force_mode);
+                                num_gt, 0, n_cat, max_segment, val, rec, workspace,
+                                workspace_bytes, stream, phase, force_mode);
     if (st != TAOAMD_OK || phase == ACC_PLAN) return st;
     return taoamd_finalize(n_cat, n_rng, num_gt, val, rec, precision, recall, stream);
 }

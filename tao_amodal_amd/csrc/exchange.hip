@@ -32,12 +32,11 @@
 // ground truth of a plan does not change between passes); an overflow flag
 // guards against misuse.
 #include "common.hpp"
+#include "workspace.hpp"
 
 using namespace taoamd;
 
 namespace {
-
-__host__ __device__ inline size_t ex_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct NumSrc {             // where the num_gt of a global row lives
     const unsigned char *base;
@@ -135,9 +134,9 @@ inline Chunk chunk_layout(int32_t block_cats, int32_t n_rng, int64_t capacity)
 {
     const size_t rows = (size_t)block_cats * n_rng;
     Chunk c;
-    c.hdr_bytes = ex_align(rows * 8);     // num_gt[rows], off[rows]
-    c.rec_bytes = ex_align(rows * N_THR * 8);
-    c.bytes = c.hdr_bytes + c.rec_bytes + ex_align((size_t)capacity * 8);
+    c.hdr_bytes = align256(rows * 8);     // num_gt[rows], off[rows]
+    c.rec_bytes = align256(rows * N_THR * 8);
+    c.bytes = c.hdr_bytes + c.rec_bytes + align256((size_t)capacity * 8);
     return c;
 }
 
@@ -255,21 +254,21 @@ __global__ __launch_bounds__(256) void ex_unpack_kernel(UnpackArgs a)
     }
 }
 
-size_t ws_bytes(int64_t rows, int32_t world)
+// the maps of `rows` = block_cats * n_rng * world rows
+void ws_layout(Carve &c, int64_t rows, int32_t world, ExWs &w)
 {
-    return ex_align((size_t)rows * N_REC) + 2 * ex_align((size_t)rows * 4) +
-           ex_align((size_t)world * 8) + 256;
+    w.dmap = c.take<uint8_t>((size_t)rows * N_REC);
+    w.nd = c.take<int32_t>((size_t)rows);
+    w.off = c.take<int32_t>((size_t)rows);
+    w.totals = c.take<int64_t>((size_t)world);
 }
 
-ExWs carve(void *workspace, int64_t rows, int32_t world)
+// the layout on the caller's buffer; false: the buffer is too small
+bool carve(void *workspace, size_t workspace_bytes, int64_t rows, int32_t world, ExWs &w)
 {
-    unsigned char *p = (unsigned char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    ExWs w;
-    w.dmap = p; p += ex_align((size_t)rows * N_REC);
-    w.nd = (int32_t *)p; p += ex_align((size_t)rows * 4);
-    w.off = (int32_t *)p; p += ex_align((size_t)rows * 4);
-    w.totals = (int64_t *)p;
-    return w;
+    Carve c(workspace);
+    ws_layout(c, rows, world, w);
+    return c.fits(workspace, workspace_bytes);
 }
 
 bool bad_shape(int32_t block_cats, int32_t n_rng, int32_t world)
@@ -289,7 +288,8 @@ extern "C" size_t taoamd_exchange_chunk_bytes(int32_t block_cats, int32_t n_rng,
 extern "C" size_t taoamd_exchange_workspace(int32_t block_cats, int32_t n_rng,
                                             int32_t world)
 {
-    return ws_bytes((int64_t)block_cats * n_rng * world, world);
+    ExWs w;
+    return measure([&](Carve &c) { ws_layout(c, (int64_t)block_cats * n_rng * world, world, w); });
 }
 
 extern "C" int taoamd_exchange_sizes(int32_t block_cats, int32_t n_rng,
@@ -301,9 +301,9 @@ extern "C" int taoamd_exchange_sizes(int32_t block_cats, int32_t n_rng,
         return TAOAMD_ERR_ARG;
     const int32_t BR = block_cats * n_rng;
     const int64_t rows = (int64_t)BR * world;
-    if (workspace_bytes < ws_bytes(rows, world)) return TAOAMD_ERR_WORKSPACE;
+    ExWs w;
+    if (!carve(workspace, workspace_bytes, rows, world, w)) return TAOAMD_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    ExWs w = carve(workspace, rows, world);
     NumSrc src{(const unsigned char *)num_gt, (int64_t)BR * 4, rows, BR};
     TAO_TIMED("ex_levels_kernel", s, ex_levels_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, s>>>(src, 0, rows, w,
                                                                 rec_thr()));
@@ -329,9 +329,9 @@ extern "C" int taoamd_exchange_pack(int32_t n_cat, int32_t n_rng,
     if (!num_gt || !val || !rec || !chunk || !workspace) return TAOAMD_ERR_ARG;
     const int32_t BR = block_cats * n_rng;
     const int64_t rows = (int64_t)BR * world;
-    if (workspace_bytes < ws_bytes(rows, world)) return TAOAMD_ERR_WORKSPACE;
+    ExWs w;
+    if (!carve(workspace, workspace_bytes, rows, world, w)) return TAOAMD_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    ExWs w = carve(workspace, rows, world);
     const int64_t valid = (int64_t)n_cat * n_rng;
     const int64_t r0 = (int64_t)rank * BR;
     // the local table is addressed by global row: one "block" spanning it all
@@ -369,11 +369,10 @@ extern "C" int taoamd_exchange_unpack(int32_t n_cat, int32_t n_rng,
     if (!chunks || !precision || !recall || !workspace) return TAOAMD_ERR_ARG;
     const int32_t BR = block_cats * n_rng;
     const int64_t rows = (int64_t)BR * world;
-    if (workspace_bytes < ws_bytes(rows, world)) return TAOAMD_ERR_WORKSPACE;
+    UnpackArgs a;
+    if (!carve(workspace, workspace_bytes, rows, world, a.w)) return TAOAMD_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const Chunk c = chunk_layout(block_cats, n_rng, capacity);
-    UnpackArgs a;
-    a.w = carve(workspace, rows, world);
     NumSrc src{(const unsigned char *)chunks, (int64_t)c.bytes, rows, BR};
     if (!maps_ready)
         TAO_TIMED("ex_levels_kernel", s, ex_levels_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, s>>>(src, 0, rows, a.w,

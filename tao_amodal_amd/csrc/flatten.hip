@@ -26,6 +26,7 @@
 //
 // HBM-bound integer work; every pass streams its inputs once.
 #include "common.hpp"
+#include "workspace.hpp"
 
 using namespace taoamd;
 
@@ -378,10 +379,19 @@ extern "C" int taoamd_flat_gather(int64_t n_keep, const int32_t *order,
     return TAOAMD_OK;
 }
 
+// per block of FL_TILE keys: its number of run heads, then where its runs start
+static int64_t flat_runs_layout(Carve &c, int64_t n, int32_t *&block_sum, int32_t *&block_start)
+{
+    const int64_t nb = ((n < 1 ? 1 : n) + FL_TILE - 1) / FL_TILE;
+    block_sum = c.take<int32_t>((size_t)nb + 2);
+    block_start = c.take<int32_t>((size_t)nb + 2);
+    return nb;
+}
+
 extern "C" size_t taoamd_flat_runs_workspace(int64_t n)
 {
-    const size_t nb = (size_t)((n < 1 ? 1 : n) + FL_TILE - 1) / FL_TILE;
-    return 2 * ((nb + 2) * 4 + 256) + 256;
+    int32_t *block_sum, *block_start;
+    return measure([&](Carve &c) { flat_runs_layout(c, n, block_sum, block_start); });
 }
 
 template <typename K>
@@ -395,11 +405,10 @@ static int flat_runs(int64_t n, const K *key, const int32_t *order, int32_t *run
         return TAOAMD_OK;
     }
     if (!key || !run_id || !run_key || !run_start || !workspace) return TAOAMD_ERR_ARG;
-    if (workspace_bytes < taoamd_flat_runs_workspace(n)) return TAOAMD_ERR_WORKSPACE;
-    const int64_t nb = (n + FL_TILE - 1) / FL_TILE;
-    unsigned char *w = (unsigned char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-    int32_t *block_sum = (int32_t *)w;
-    int32_t *block_start = (int32_t *)(w + (((size_t)(nb + 2) * 4 + 255) & ~(size_t)255));
+    Carve c(workspace);
+    int32_t *block_sum, *block_start;
+    const int64_t nb = flat_runs_layout(c, n, block_sum, block_start);
+    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
     TAO_TIMED("fl_heads_kernel", s, fl_heads_kernel<K><<<(unsigned)nb, FL_THREADS, 0, s>>>(
         n, key, order, block_sum));
     // exclusive scan of the block sums; the total lands in block_start[nb]

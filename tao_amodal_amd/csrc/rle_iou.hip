@@ -137,13 +137,11 @@ __global__ __launch_bounds__(RLE_THREADS) void rle_iou_kernel(RleArgs a)
     }
 }
 
-static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 extern "C" size_t taoamd_rle_iou_workspace(int64_t n_dt, int64_t dt_runs,
                                            int64_t n_gt, int64_t gt_runs)
 {
-    return up256((size_t)dt_runs * 4) + up256((size_t)gt_runs * 8) +
-           up256((size_t)n_dt * 4) + up256((size_t)n_gt * 4) + 256;
+    RleArgs a;
+    return measure([&](Carve &c) { rle_layout(c, n_dt, dt_runs, n_gt, gt_runs, a); });
 }
 
 extern "C" int taoamd_rle_iou(int64_t n_cells, const int32_t *cell_dt_off,
@@ -164,15 +162,11 @@ extern "C" int taoamd_rle_iou(int64_t n_cells, const int32_t *cell_dt_off,
         !dt_hw || !dt_bb || !gt_off || !gt_runs || !gt_hw || !gt_bb || !iou ||
         !workspace)
         return TAOAMD_ERR_ARG;
-    if (workspace_bytes < taoamd_rle_iou_workspace(n_dt, dt_total, n_gt, gt_total))
-        return TAOAMD_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    unsigned char *w = (unsigned char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    Carve c(workspace);
     RleArgs a;
-    a.dt_end = (const uint32_t *)w; w += up256((size_t)dt_total * 4);
-    a.gt_pre = (const uint2 *)w; w += up256((size_t)gt_total * 8);
-    a.dt_ones = (const uint32_t *)w; w += up256((size_t)n_dt * 4);
-    a.gt_ones = (const uint32_t *)w;
+    rle_layout(c, n_dt, dt_total, n_gt, gt_total, a);
+    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
     TAO_TIMED("rle_prefix_kernel", s, rle_prefix_kernel<false><<<dim3((unsigned)((n_dt + 3) / 4)), 256, 0, s>>>(
         n_dt, dt_off, dt_runs, (void *)a.dt_end, (uint32_t *)a.dt_ones));
     TAO_LAUNCH_CHECK();

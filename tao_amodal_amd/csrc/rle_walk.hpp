@@ -7,6 +7,7 @@
 // boundaries per lane.
 #pragma once
 #include "common.hpp"
+#include "workspace.hpp"
 
 #define RLE_RPT 8               // run boundaries of A a lane keeps in registers (even)
 
@@ -45,6 +46,18 @@ __global__ __launch_bounds__(256) void rle_prefix_kernel(int64_t n,
         carry_p = __shfl(p, WAVE - 1, WAVE);
     }
     if (lane == 0) ones[m] = carry_p;
+}
+
+// The workspace of both IoU stages: the tables rle_prefix_kernel writes for the
+// n_dt / n_gt masks of dt_runs / gt_runs runs (A: RleArgs, TrackMaskArgs)
+template <class A>
+static void rle_layout(taoamd::Carve &c, int64_t n_dt, int64_t dt_runs, int64_t n_gt,
+                       int64_t gt_runs, A &a)
+{
+    a.dt_end = c.take<uint32_t>((size_t)dt_runs);
+    a.gt_pre = c.take<uint2>((size_t)gt_runs);
+    a.dt_ones = c.take<uint32_t>((size_t)n_dt);
+    a.gt_ones = c.take<uint32_t>((size_t)n_gt);
 }
 
 // A's run boundaries of one piece (RLE_RPT * 64 of them) into the lane's

@@ -22,6 +22,7 @@
 #include <cstring>
 
 #include "common.hpp"
+#include "workspace.hpp"
 
 using namespace taoamd;
 
@@ -237,15 +238,30 @@ __global__ void rs_finish_kernel(SortBufs b, int32_t *__restrict__ order,
     }
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+// the ping-pong buffers of n (key, index) elements: SortBufs, SegArgs
+template <class A> static void key_idx_layout(Carve &c, int64_t n, A &a)
+{
+    for (int i = 0; i < 2; i++) a.key[i] = c.take<uint64_t>((size_t)n);
+    for (int i = 0; i < 2; i++) a.idx[i] = c.take<int32_t>((size_t)n);
+}
+
+static void rs_layout(Carve &c, int64_t n, SortBufs &b)
+{
+    if (n < 1) n = 1;
+    b.n = n;
+    b.n_blocks = (int32_t)((n + RS_TILE - 1) / RS_TILE);
+    key_idx_layout(c, n, b);
+    b.block_hist = c.take<uint32_t>((size_t)b.n_blocks * RS_BINS);
+    b.digit_total = c.take<uint32_t>(RS_PASSES * RS_BINS);
+    // one piece: the kernels find sel right behind skip
+    b.skip = c.take<int32_t>(RS_PASSES + RS_PASSES + 1);
+    b.sel = Carve::at(b.skip, RS_PASSES);
+}
 
 extern "C" size_t taoamd_sort_workspace(int64_t n)
 {
-    if (n < 1) n = 1;
-    size_t nb = (size_t)((n + RS_TILE - 1) / RS_TILE);
-    return 2 * align256((size_t)n * 8) + 2 * align256((size_t)n * 4) +
-           align256(nb * RS_BINS * 4) + align256(RS_PASSES * RS_BINS * 4) +
-           align256(256) + 4096;
+    SortBufs b;
+    return measure([&](Carve &c) { rs_layout(c, n, b); });
 }
 
 extern "C" int taoamd_sort_by_cat_score(int64_t n, const int32_t *dt_cat,
@@ -256,21 +272,12 @@ extern "C" int taoamd_sort_by_cat_score(int64_t n, const int32_t *dt_cat,
     if (n == 0) return TAOAMD_OK;
     if (n > 0x7fffffff) return TAOAMD_ERR_TOO_LARGE;
     if (!dt_cat || !workspace) return TAOAMD_ERR_ARG;
-    if (workspace_bytes < taoamd_sort_workspace(n)) return TAOAMD_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    unsigned char *w = (unsigned char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    Carve c(workspace);
     SortBufs b;
-    b.n = n;
-    b.n_blocks = (int32_t)((n + RS_TILE - 1) / RS_TILE);
+    rs_layout(c, n, b);
+    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
     b.cat = dt_cat;
-    b.key[0] = (uint64_t *)w; w += align256((size_t)n * 8);
-    b.key[1] = (uint64_t *)w; w += align256((size_t)n * 8);
-    b.idx[0] = (int32_t *)w;  w += align256((size_t)n * 4);
-    b.idx[1] = (int32_t *)w;  w += align256((size_t)n * 4);
-    b.block_hist = (uint32_t *)w; w += align256((size_t)b.n_blocks * RS_BINS * 4);
-    b.digit_total = (uint32_t *)w; w += align256(RS_PASSES * RS_BINS * 4);
-    b.skip = (int32_t *)w;
-    b.sel = b.skip + RS_PASSES;
     TAO_HIP(hipMemsetAsync(b.digit_total, 0, RS_PASSES * RS_BINS * 4, s));
     unsigned init_blocks = (unsigned)(b.n_blocks < 2048 ? b.n_blocks : 2048);
     TAO_TIMED("rs_init_kernel", s, rs_init_kernel<<<init_blocks, RS_THREADS, 0, s>>>(b, dt_score));
@@ -921,11 +928,17 @@ __global__ __launch_bounds__(256) void seg_mpass_kernel(SegArgs a, int pass, int
     }
 }
 
-extern "C" size_t taoamd_sort_segments_workspace(int64_t n)
+static void seg_layout(Carve &c, int64_t n, SegArgs &a)
 {
     if (n < 1) n = 1;
-    return 2 * align256((size_t)n * 8) + 2 * align256((size_t)n * 4) +
-           align256(((size_t)n / SEG_TILE + 2) * SEG_BND_PER_SLOT * 4) + 4096;
+    key_idx_layout(c, n, a);
+    a.bnd = c.take<int32_t>(((size_t)n / SEG_TILE + 2) * SEG_BND_PER_SLOT);
+}
+
+extern "C" size_t taoamd_sort_segments_workspace(int64_t n)
+{
+    SegArgs a;
+    return measure([&](Carve &c) { seg_layout(c, n, a); });
 }
 
 extern "C" int taoamd_sort_segments(int64_t n, int32_t n_cat,
@@ -939,17 +952,13 @@ extern "C" int taoamd_sort_segments(int64_t n, int32_t n_cat,
     if (n == 0 || n_cat == 0 || n_tiles == 0) return TAOAMD_OK;
     if (n > 0x7fffffff) return TAOAMD_ERR_TOO_LARGE;
     if (!cat_off || !tile_off || !dt_cat || !dt_score || !workspace) return TAOAMD_ERR_ARG;
-    if (workspace_bytes < taoamd_sort_segments_workspace(n)) return TAOAMD_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    unsigned char *w = (unsigned char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    Carve c(workspace);
     SegArgs a;
+    seg_layout(c, n, a);
+    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
     a.cat_off = cat_off; a.tile_off = tile_off; a.cat = dt_cat; a.score = dt_score;
     a.order = order; a.dst = dst; a.n = n; a.n_cat = n_cat; a.n_tiles = n_tiles;
-    a.key[0] = (uint64_t *)w; w += align256((size_t)n * 8);
-    a.key[1] = (uint64_t *)w; w += align256((size_t)n * 8);
-    a.idx[0] = (int32_t *)w;  w += align256((size_t)n * 4);
-    a.idx[1] = (int32_t *)w;  w += align256((size_t)n * 4);
-    a.bnd = (int32_t *)w;
     TAO_TIMED("seg_tile_kernel", s, seg_tile_kernel<<<(unsigned)n_tiles, SEG_THREADS, 0, s>>>(a));
     if (max_segment > SEG_TILE && max_segment <= (int64_t)SEG_KMERGE_TILES * SEG_TILE) {
         TAO_TIMED("seg_kmerge_kernel", s, seg_kmerge_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(a));
@@ -1841,16 +1850,31 @@ extern "C" int taoamd_sort_plan_host(int32_t n_cat, const int32_t *cat_off_host,
     return TAOAMD_OK;
 }
 
-extern "C" size_t taoamd_sort_sampled_workspace(int64_t n, int64_t n_buckets, int32_t merge)
+// `cursor_ints`: the cursor block -- cursor[n_buckets], then at least 64 spare
+// ints up to a 256-byte boundary; the LAST of them is the redo count, so that
+// it sits right ahead of the redo list (redo[-1]) and one memset clears both
+static size_t ss_layout(Carve &c, int64_t n, int64_t n_buckets, int merge, SsArgs &a, SegArgs &m)
 {
     if (n < 1) n = 1;
     if (n_buckets < 1) n_buckets = 1;
-    size_t b = align256((size_t)n_buckets * 4 + 256)           // cursor, redo count
-               + align256((size_t)n_buckets * 4)                // redo list
-               + align256((size_t)n_buckets * 8) + align256((size_t)n_buckets * 4)
-               + align256((size_t)n_buckets * SS_CAP * 8) + align256((size_t)n_buckets * SS_CAP * 4);
-    if (merge) b += 2 * align256((size_t)n * 8) + 2 * align256((size_t)n * 4);
-    return b + 4096;
+    const size_t nb = (size_t)n_buckets;
+    const size_t cursor_ints = align256((nb + 64) * 4) / 4;
+    a.cursor = c.take<int32_t>(cursor_ints + nb);
+    a.redo = Carve::at(a.cursor, cursor_ints);
+    a.spl_key = c.take<uint64_t>(nb);
+    a.spl_idx = c.take<int32_t>(nb);
+    a.slot_key = c.take<uint64_t>(nb * SS_CAP);
+    a.slot_idx = c.take<int32_t>(nb * SS_CAP);
+    m.key[0] = m.key[1] = nullptr; m.idx[0] = m.idx[1] = nullptr; m.bnd = nullptr;
+    if (merge) key_idx_layout(c, n, m);
+    return cursor_ints;
+}
+
+extern "C" size_t taoamd_sort_sampled_workspace(int64_t n, int64_t n_buckets, int32_t merge)
+{
+    SsArgs a;
+    SegArgs m;
+    return measure([&](Carve &c) { ss_layout(c, n, n_buckets, merge, a, m); });
 }
 
 // The splitter kernel is 0.06 ms of latency at the head of the image level's
@@ -1891,11 +1915,12 @@ extern "C" int taoamd_sort_sampled(int64_t n, int32_t n_cat, const int32_t *cat_
         return TAOAMD_ERR_ARG;
     const int merge = max_segment > SS_CHUNK;
     if (merge && (!tile_off || n_tiles <= 0)) return TAOAMD_ERR_ARG;
-    if (workspace_bytes < taoamd_sort_sampled_workspace(n, n_buckets, merge))
-        return TAOAMD_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    unsigned char *w = (unsigned char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    Carve c(workspace);
     SsArgs a;
+    SegArgs m;
+    const size_t cursor_ints = ss_layout(c, n, n_buckets, merge, a, m);
+    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
     a.score = dt_score; a.chunks = (const SsChunk *)chunks; a.split_list = split_list;
     a.stile_chunk = stile_chunk; a.bucket_chunk = bucket_chunk;
     a.order = order; a.dst = dst; a.n_buckets = n_buckets; a.n_stiles = n_stiles;
@@ -1906,27 +1931,12 @@ extern "C" int taoamd_sort_sampled(int64_t n, int32_t n_cat, const int32_t *cat_
 #else
     a.dbg = 0;
 #endif
-    a.cursor = (int32_t *)w;    w += align256((size_t)n_buckets * 4 + 256);
-    a.redo = (int32_t *)w;      w += align256((size_t)n_buckets * 4);
-    // (the redo count sits in the last int of the cursor block, right ahead of the list)
-    a.spl_key = (uint64_t *)w;  w += align256((size_t)n_buckets * 8);
-    a.spl_idx = (int32_t *)w;   w += align256((size_t)n_buckets * 4);
-    a.slot_key = (uint64_t *)w; w += align256((size_t)n_buckets * SS_CAP * 8);
-    a.slot_idx = (int32_t *)w;  w += align256((size_t)n_buckets * SS_CAP * 4);
-    SegArgs m;
     m.cat_off = cat_off; m.tile_off = tile_off; m.cat = nullptr; m.score = dt_score;
     m.order = order; m.dst = dst; m.n = n; m.n_cat = n_cat; m.n_tiles = n_tiles;
-    m.key[0] = m.key[1] = nullptr; m.idx[0] = m.idx[1] = nullptr; m.bnd = nullptr;
-    a.key_out = nullptr; a.idx_out = nullptr;
-    if (merge) {
-        m.key[0] = (uint64_t *)w; w += align256((size_t)n * 8);
-        m.key[1] = (uint64_t *)w; w += align256((size_t)n * 8);
-        m.idx[0] = (int32_t *)w;  w += align256((size_t)n * 4);
-        m.idx[1] = (int32_t *)w;  w += align256((size_t)n * 4);
-        a.key_out = m.key[SS_FIRST_MERGE_PASS & 1];
-        a.idx_out = m.idx[SS_FIRST_MERGE_PASS & 1];
-    }
-    TAO_HIP(hipMemsetAsync(a.cursor, 0, align256((size_t)n_buckets * 4 + 256), s));
+    // (merge buffers: null without merge passes)
+    a.key_out = m.key[SS_FIRST_MERGE_PASS & 1];
+    a.idx_out = m.idx[SS_FIRST_MERGE_PASS & 1];
+    TAO_HIP(hipMemsetAsync(a.cursor, 0, cursor_ints * 4, s));
     if (n_split > 0) {
         // (TAOAMD_SS_SPLIT=1: one wavefront per chunk, the round-3 kernel, for A/B timing)
         static const bool one_wave = getenv("TAOAMD_SS_SPLIT") && atoi(getenv("TAOAMD_SS_SPLIT")) == 1;

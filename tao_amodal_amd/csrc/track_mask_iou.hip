@@ -178,13 +178,11 @@ __global__ __launch_bounds__(TMI_THREADS) void track_mask_iou_kernel(TrackMaskAr
     }
 }
 
-static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 extern "C" size_t taoamd_track_mask_iou_workspace(int64_t dt_frames, int64_t dt_total,
                                                   int64_t gt_frames, int64_t gt_total)
 {
-    return up256((size_t)dt_total * 4) + up256((size_t)gt_total * 8) +
-           up256((size_t)dt_frames * 4) + up256((size_t)gt_frames * 4) + 256;
+    TrackMaskArgs a;
+    return measure([&](Carve &c) { rle_layout(c, dt_frames, dt_total, gt_frames, gt_total, a); });
 }
 
 extern "C" int taoamd_track_mask_iou(
@@ -208,15 +206,10 @@ extern "C" int taoamd_track_mask_iou(
         !dt_hw || !gt_off || !gt_runs || !gt_hw || !iou ||
         !workspace)
         return TAOAMD_ERR_ARG;
-    if (workspace_bytes < taoamd_track_mask_iou_workspace(dt_frames, dt_total,
-                                                          gt_frames, gt_total))
-        return TAOAMD_ERR_WORKSPACE;
-    unsigned char *w = (unsigned char *)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    Carve c(workspace);
     TrackMaskArgs a;
-    a.dt_end = (const uint32_t *)w; w += up256((size_t)dt_total * 4);
-    a.gt_pre = (const uint2 *)w; w += up256((size_t)gt_total * 8);
-    a.dt_ones = (const uint32_t *)w; w += up256((size_t)dt_frames * 4);
-    a.gt_ones = (const uint32_t *)w;
+    rle_layout(c, dt_frames, dt_total, gt_frames, gt_total, a);
+    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
     if (dt_frames)
         TAO_TIMED("rle_prefix_kernel", s, rle_prefix_kernel<false><<<dim3((unsigned)((dt_frames + 3) / 4)), 256, 0, s>>>(
             dt_frames, dt_off, dt_runs, (void *)a.dt_end, (uint32_t *)a.dt_ones));

@@ -140,3 +140,123 @@ def test_track_iou_plan_keeps_every_task_within_its_rows():
     assert {32, 63, 64, 96} <= set(np.diff(f.cell_gt_off).tolist())
     meta = engine.track_meta(f)[0]
     _check_plan(f, meta, *engine.track_iou_plan(f, meta))
+
+
+# ---- caller-allocated workspaces: one layout function each (csrc/workspace.hpp)
+_WS_N = (0, 1, 2816, 2817, 1_500_000, 21_400_000, 2 ** 31 - 1)
+
+
+def _workspace_shapes():
+    """(size function, arguments) of every workspace over the table of shapes."""
+    for n in _WS_N:
+        yield "taoamd_sort_workspace", (n,)
+        yield "taoamd_sort_segments_workspace", (n,)
+        yield "taoamd_flat_runs_workspace", (n,)
+        for merge in (0, 1):
+            yield "taoamd_sort_sampled_workspace", (n, n // 352 + 1, merge)
+        yield "taoamd_rle_iou_workspace", (n, 4 * n, n // 2, 2 * n)
+        yield "taoamd_track_mask_iou_workspace", (n, 4 * n, n // 2, 2 * n)
+        for n_cat in (1, 100, 1203):
+            for n_rng in (6, 20):
+                yield "taoamd_accumulate_workspace", (n, n_cat, n_rng)
+    for n_cat in (1, 100, 1203):
+        for n_rng in (6, 20):
+            for world in (1, 8):
+                yield "taoamd_exchange_workspace", (n_cat, n_rng, world)
+
+
+# what the commit before the layout functions reported, in _workspace_shapes() order
+_WS_BYTES_BEFORE = {
+    "taoamd_sort_workspace": [18688, 18688, 86272, 87296, 36767488, 524317440, 52613366016],
+    "taoamd_sort_segments_workspace": [7168, 7168, 74752, 75776, 36551168, 521387520, 52320516096],
+    "taoamd_flat_runs_workspace": [792, 792, 800, 800, 6648, 84384, 8389392],
+    "taoamd_sort_sampled_workspace": [17664, 18688, 17664, 18688, 115968, 183552, 115968, 184576, 52461568, 88461824, 748281600, 1261881600, 75088725504, 126628333056],
+    "taoamd_rle_iou_workspace": [256, 1024, 107264, 108032, 57000448, 813200384, 81604378880],
+    "taoamd_track_mask_iou_workspace": [256, 1024, 107264, 108032, 57000448, 813200384, 81604378880],
+    "taoamd_accumulate_workspace": [65792, 212224, 5869312, 20033024, 70531328, 240871168, 71424, 234752, 5874944, 20055552, 70536960, 240893696, 129280, 466432, 5932800, 20287232, 70595072, 241125376, 134912, 488960, 5938432, 20309760, 70600704, 241147904, 34263808, 136934400, 40067584, 156755456, 104729600, 377593600, 487919872, 1950625792, 493723392, 1970446592, 558385664, 2191284736, 48955980544, 195723207680, 48961783808, 195743028480, 49026446080, 195963866624],
+    "taoamd_exchange_workspace": [1792, 5888, 3072, 18432, 66304, 523776, 219136, 1744640, 787456, 6295040, 2623232, 20981248],
+}
+
+
+def test_workspace_sizes_never_grow():
+    """The sizes are measuring runs of the layout functions: the pieces + 256
+    bytes for aligning the base.  The hand-written formulas they replace added
+    up to 4 KB of slack; no size may exceed what those reported."""
+    lib = _lib.load()
+    before = {k: list(v) for k, v in _WS_BYTES_BEFORE.items()}
+    for name, args in _workspace_shapes():
+        new, old = int(getattr(lib, name)(*args)), before[name].pop(0)
+        assert 0 < new <= old, (name, args, new, old)
+    assert not any(before.values())
+
+
+def _compact_bytes(lib, p, n, n_cat, n_rng, full):
+    """Smallest workspace_bytes taoamd_accumulate_compact accepts (its check
+    comes first; k_begin == k_end then returns before any device work)."""
+    def st(nbytes):
+        return lib.taoamd_accumulate_compact(n, n_cat, n_rng, p, p, p + 8, p, 0, 0, 0, p, p,
+                                             p, nbytes, None)
+    assert st(full) == 0
+    lo, hi = 0, full            # st(lo) == 4, st(hi) == 0
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if st(mid) == 0:
+            hi = mid
+        else:
+            assert st(mid) == 4
+            lo = mid
+    return hi
+
+
+def test_accumulate_workspace_holds_val_and_rec_behind_the_compact_tables():
+    lib = _lib.load()
+    buf = np.zeros(64, dtype=np.uint64)
+    for n in _WS_N:
+        for n_cat in (1, 100, 1203):
+            for n_rng in (6, 20):
+                full = int(lib.taoamd_accumulate_workspace(n, n_cat, n_rng))
+                compact = _compact_bytes(lib, buf.ctypes.data, n, n_cat, n_rng, full)
+                records = 8 * (int(lib.taoamd_compact_elems(n_cat, n_rng)) + n_cat * n_rng * 10)
+                assert full - compact >= records, (n, n_cat, n_rng, full, compact)
+
+
+def test_entry_points_refuse_a_workspace_below_the_reported_size():
+    """Every entry point whose workspace check precedes its first device call
+    (this runs without a GPU) answers TAOAMD_ERR_WORKSPACE to one byte less
+    than the size function reports, whatever the pointers."""
+    lib = _lib.load()
+    buf = np.zeros(64, dtype=np.uint64)
+    p = buf.ctypes.data
+    n, K, R = 100000, 7, 6
+    calls = []
+    nb = int(lib.taoamd_sort_workspace(n)) - 1
+    calls.append(("taoamd_sort_by_cat_score", (n, p, p, p, p, p, nb, None)))
+    nb = int(lib.taoamd_sort_segments_workspace(n)) - 1
+    calls.append(("taoamd_sort_segments", (n, K, p, p, 40, n, p, p, p, p, p, nb, None)))
+    for max_segment, merge in ((1000, 0), (n, 1)):      # merge: longer than 16 tiles
+        nb = int(lib.taoamd_sort_sampled_workspace(n, 300, merge)) - 1
+        calls.append(("taoamd_sort_sampled", (n, K, p, p, 40, max_segment, p, 20, p, 5, p, 40,
+                                              p, 300, p, p, p, p, nb, None)))
+    nb = int(lib.taoamd_accumulate_workspace(n, K, R)) - 1
+    for name in ("taoamd_accumulate", "taoamd_accumulate_chunked", "taoamd_accumulate_prepared"):
+        calls.append((name, (n, K, R, p, p, p + 8, p, 0, p, p, p, nb, None)))
+    for name in ("taoamd_accumulate_by_order", "taoamd_accumulate_by_order_prepared",
+                 "taoamd_accumulate_by_order_chunked"):
+        calls.append((name, (n, K, R, p, p, p, p + 8, p, 0, p, p, p, nb, None)))
+    calls.append(("taoamd_accumulate_prepare", (n, K, R, p, 0, p, nb, None)))
+    nb = int(lib.taoamd_rle_iou_workspace(50, 900, 20, 400)) - 1
+    calls.append(("taoamd_rle_iou", (9, p, p, p, 50, 900, p, p, p, p, 20, 400, p, p, p, p,
+                                     p, p, nb, None)))
+    nb = int(lib.taoamd_track_mask_iou_workspace(50, 900, 20, 400)) - 1
+    calls.append(("taoamd_track_mask_iou", (9, p, p, p, 30, p, p, 50, 900, p, p, p,
+                                            p, p, 20, 400, p, p, p, 0, p, None, p, nb, None)))
+    nb = int(lib.taoamd_exchange_workspace(K, R, 4)) - 1
+    calls.append(("taoamd_exchange_sizes", (K, R, 4, p, p, p, nb, None)))
+    calls.append(("taoamd_exchange_pack", (4 * K, R, K, 4, 1, p, p, p, p, 100, p, p, nb, 0, None)))
+    calls.append(("taoamd_exchange_unpack", (4 * K, R, K, 4, p, 100, p, p, p, p, p, nb, 0, None)))
+    nb = int(lib.taoamd_flat_runs_workspace(n)) - 1
+    calls.append(("taoamd_flat_runs", (n, p, p, p, p, p, p, nb, None)))
+    calls.append(("taoamd_flat_runs_by", (n, p, p, p, p, p, p, p, nb, None)))
+    calls.append(("taoamd_flat_runs64_by", (n, p, p, p, p, p, p, p, nb, None)))
+    for name, args in calls:
+        assert getattr(lib, name)(*args) == 4, name

@@ -7,6 +7,7 @@ import json
 import numpy as np
 import pytest
 
+import wsguard
 from goldenio import path
 from oracle import rle
 from tao_amodal_amd.masks import MaskBatch
@@ -38,15 +39,15 @@ def _device_iou(cells_d, cells_g, dt, gt):
                       t(m.hw if len(m) else np.zeros((1, 2), np.int32)),
                       t(m.bbox if len(m) else np.zeros((1, 4)))])
     out = torch.full((max(int(i_off[-1]), 1),), -7.0, dtype=torch.float64, device=dev)
-    nb = lib.taoamd_rle_iou_workspace(len(dt), int(dt.off[-1]), len(gt), int(gt.off[-1]))
-    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    ws = wsguard.Guarded(lib.taoamd_rle_iou_workspace(len(dt), int(dt.off[-1]), len(gt),
+                                                      int(gt.off[-1])), dev)
     st = lib.taoamd_rle_iou(
         len(cells_d), *[x.data_ptr() for x in head],
         len(dt), int(dt.off[-1]), *[x.data_ptr() for x in sides[0]],
         len(gt), int(gt.off[-1]), *[x.data_ptr() for x in sides[1]],
-        out.data_ptr(), ws.data_ptr(), nb, None)
+        out.data_ptr(), ws.data_ptr(), ws.nbytes, None)
     assert st == 0
-    torch.cuda.synchronize()
+    ws.check()
     return out.cpu().numpy()[:int(i_off[-1])], i_off
 
 
@@ -85,6 +86,11 @@ def test_rle_iou_kernel_equals_the_oracle_on_random_cells():
         d0 += D
         g0 += G
     assert n_pos > 100 and n_neg > 3
+
+
+def test_rle_iou_with_the_workspace_base_moved_by_8_bytes(monkeypatch):
+    monkeypatch.setattr(wsguard, "SHIFT", 8)
+    test_rle_iou_kernel_equals_the_oracle_on_random_cells()
 
 
 def test_rle_iou_kernel_long_run_lists():

@@ -6,6 +6,7 @@ import pytest
 
 import exchange_ref
 import orclib
+import wsguard
 from goldenio import FIXTURES, INTEGER_FIXTURES, load_eval, load_inputs, load_json_gz, path
 from test_flat_oracle_golden import _check_side
 from tao_amodal_amd import flatten as fl
@@ -310,12 +311,11 @@ def test_both_sorts_are_the_stable_mergesort_order(n, n_cat, quant):
     d_cat, d_score = torch.from_numpy(cat).cuda(), torch.from_numpy(score).cuda()
     order = torch.empty(n, dtype=torch.int32, device="cuda")
     dst = torch.empty(n, dtype=torch.int32, device="cuda")
-    nb = max(lib.taoamd_sort_workspace(n), lib.taoamd_sort_segments_workspace(n))
-    ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
+    ws = wsguard.Guarded(lib.taoamd_sort_workspace(n))
     _lib.check(lib.taoamd_sort_by_cat_score(n, d_cat.data_ptr(), d_score.data_ptr(),
                                             order.data_ptr(), dst.data_ptr(),
-                                            ws.data_ptr(), nb, None), "radix")
-    torch.cuda.synchronize()
+                                            ws.data_ptr(), ws.nbytes, None), "radix")
+    ws.check()
     assert np.array_equal(order.cpu().numpy(), want)
     assert np.array_equal(dst.cpu().numpy()[want], np.arange(n))
     cat_off = np.zeros(n_cat + 1, np.int32)
@@ -325,17 +325,30 @@ def test_both_sorts_are_the_stable_mergesort_order(n, n_cat, quant):
     np.cumsum(tiles, out=tile_off[1:])
     order.zero_(); dst.zero_()
     d_co, d_to = torch.from_numpy(cat_off).cuda(), torch.from_numpy(tile_off).cuda()
+    ws = wsguard.Guarded(lib.taoamd_sort_segments_workspace(n))
     _lib.check(lib.taoamd_sort_segments(
         n, n_cat, d_co.data_ptr(), d_to.data_ptr(), int(tile_off[-1]),
         int(np.diff(cat_off).max()), d_cat.data_ptr(), d_score.data_ptr(),
-        order.data_ptr(), dst.data_ptr(), ws.data_ptr(), nb, None), "segments")
-    torch.cuda.synchronize()
+        order.data_ptr(), dst.data_ptr(), ws.data_ptr(), ws.nbytes, None), "segments")
+    ws.check()
     assert np.array_equal(order.cpu().numpy(), want)
     assert np.array_equal(dst.cpu().numpy()[want], np.arange(n))
     # the sample sort (what the evaluator passes call)
     o2, d2 = _sampled_sort(cat_off, tile_off, d_score)
     assert np.array_equal(o2, want)
     assert np.array_equal(d2[want], np.arange(n))
+
+
+def test_sorts_with_the_workspace_base_moved_by_8_bytes(monkeypatch):
+    """The three sorts once more, the base of every workspace 8 bytes off its
+    256-byte line: the reported size covers the rounding too (wsguard)."""
+    monkeypatch.setattr(wsguard, "SHIFT", 8)
+    test_both_sorts_are_the_stable_mergesort_order(90000, 2, -2)
+
+
+def test_exchange_with_the_workspace_base_moved_by_8_bytes(monkeypatch):
+    monkeypatch.setattr(wsguard, "SHIFT", 8)
+    test_exchange_chunks_hip_vs_numpy_restatement(3)
 
 
 def _sampled_sort(cat_off, tile_off, d_score, repeat=1):
@@ -350,15 +363,14 @@ def _sampled_sort(cat_off, tile_off, d_score, repeat=1):
     d_to = torch.from_numpy(np.ascontiguousarray(tile_off, np.int32)).cuda()
     order = torch.full((n,), -1, dtype=torch.int32, device="cuda")
     dst = torch.full((n,), -1, dtype=torch.int32, device="cuda")
-    nbytes = lib.taoamd_sort_sampled_workspace(n, nb, int(merge))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
+    ws = wsguard.Guarded(lib.taoamd_sort_sampled_workspace(n, nb, int(merge)))
     for _ in range(repeat):
         _lib.check(lib.taoamd_sort_sampled(
             n, len(cat_off) - 1, d_co.data_ptr(), d_to.data_ptr(), int(tile_off[-1]),
             int(np.diff(cat_off).max()), d_score.data_ptr(), nc, dev[0].data_ptr(), ns,
             dev[1].data_ptr(), nt, dev[2].data_ptr(), nb, dev[3].data_ptr(),
-            order.data_ptr(), dst.data_ptr(), ws.data_ptr(), nbytes, None), "sampled")
-    torch.cuda.synchronize()
+            order.data_ptr(), dst.data_ptr(), ws.data_ptr(), ws.nbytes, None), "sampled")
+    ws.check()
     return order.cpu().numpy(), dst.cpu().numpy()
 
 
@@ -531,8 +543,8 @@ def test_exchange_chunks_hip_vs_numpy_restatement(world):
         _, _, Kb = tdist.category_block(K, 0, world)
         table = torch.zeros((Kb * world, R), dtype=torch.int32, device="cuda")
         table[:K] = ws.num_gt
-        xws = torch.empty(be.exchange_workspace(Kb, R, world), dtype=torch.uint8,
-                          device="cuda")
+        xguard = wsguard.Guarded(be.exchange_workspace(Kb, R, world))
+        xws = xguard.tensor
         totals = torch.zeros(world, dtype=torch.int64, device="cuda")
         be.exchange_sizes(Kb, R, world, table, totals, xws)
         want_sizes = exchange_ref.sizes(Kb, R, world, table.cpu().numpy())
@@ -554,7 +566,7 @@ def test_exchange_chunks_hip_vs_numpy_restatement(world):
         rcl = torch.empty((10, K, R), dtype=torch.float64, device="cuda")
         ng = torch.zeros((K, R), dtype=torch.int32, device="cuda")
         be.exchange_unpack(K, R, Kb, world, chunks, cap, ng, prec, rcl, over, xws)
-        torch.cuda.synchronize()
+        xguard.check()
         assert int(over.item()) == 0
         assert np.array_equal(ng.cpu().numpy(), hn)
         assert np.array_equal(prec.cpu().numpy(), ws.precision.cpu().numpy())
@@ -690,14 +702,13 @@ def test_segment_sort_mixes_the_three_ways_of_finishing_a_category():
     d_co, d_to = torch.from_numpy(cat_off).cuda(), torch.from_numpy(tile_off).cuda()
     order = torch.zeros(n, dtype=torch.int32, device="cuda")
     dst = torch.zeros(n, dtype=torch.int32, device="cuda")
-    nb = lib.taoamd_sort_segments_workspace(n)
-    ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
+    ws = wsguard.Guarded(lib.taoamd_sort_segments_workspace(n))
     for _ in range(2):
         _lib.check(lib.taoamd_sort_segments(
             n, n_cat, d_co.data_ptr(), d_to.data_ptr(), int(tile_off[-1]), max(sizes),
             d_cat.data_ptr(), d_score.data_ptr(), order.data_ptr(), dst.data_ptr(),
-            ws.data_ptr(), nb, None), "segments")
-    torch.cuda.synchronize()
+            ws.data_ptr(), ws.nbytes, None), "segments")
+    ws.check()
     assert np.array_equal(order.cpu().numpy(), want)
     assert np.array_equal(dst.cpu().numpy()[want], np.arange(n))
 

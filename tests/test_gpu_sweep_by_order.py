@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import orclib
+import wsguard
 from goldenio import FIXTURES, load_eval, load_inputs
 from tao_amodal_amd import _lib
 from tao_amodal_amd import flatten as fl
@@ -78,8 +79,8 @@ def _device_tables(cat_off, matched, ignored, num_gt, order, layout, hint, how):
     else:
         d_m = torch.from_numpy(np.ascontiguousarray(m_cell).view(np.int64)).to(dev)
         d_i = torch.from_numpy(np.ascontiguousarray(i_cell).view(np.int64)).to(dev)
-    nbytes = lib.taoamd_accumulate_workspace(n, K, n_rng)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = wsguard.Guarded(lib.taoamd_accumulate_workspace(n, K, n_rng), dev)
+    nbytes = ws.nbytes
     prec = torch.full((N_THR, N_REC, K, n_rng), 7.0, dtype=torch.float64, device=dev)
     rec = torch.full((N_THR, K, n_rng), 7.0, dtype=torch.float64, device=dev)
     s = torch.cuda.current_stream().cuda_stream
@@ -96,6 +97,7 @@ def _device_tables(cat_off, matched, ignored, num_gt, order, layout, hint, how):
         _lib.check(lib.taoamd_accumulate_by_order(*args), "by_order")
     flag = C.c_int32(7)
     _lib.check(lib.taoamd_accumulate_error(ws.data_ptr(), s, C.addressof(flag)), "error")
+    ws.check()
     return prec.cpu().numpy(), rec.cpu().numpy(), flag.value
 
 
@@ -117,6 +119,11 @@ def test_categories_on_every_boundary_of_the_blocking(onepass_mode, n_rng, layou
                 assert flag == 0, what
                 assert np.array_equal(got_r, want_r), what
                 assert np.array_equal(got_p, want_p), what
+
+
+def test_gathered_sweep_with_the_workspace_base_moved_by_8_bytes(onepass_mode, monkeypatch):
+    monkeypatch.setattr(wsguard, "SHIFT", 8)
+    test_categories_on_every_boundary_of_the_blocking(onepass_mode, 20, "paired")
 
 
 @pytest.mark.parametrize("how", ["plain", "prepared"])

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import orclib
+import wsguard
 from goldenio import FIXTURES
 from tao_amodal_amd import _lib
 from tao_amodal_amd import flatten as fl
@@ -146,8 +147,8 @@ def _device_tables(cat_off, matched, ignored, num_gt, layout, hint, prepared=Fal
         if n == 0:
             d_m = torch.zeros((1, nw), dtype=torch.int64, device=dev)
             d_i = torch.zeros((1, nw), dtype=torch.int64, device=dev)
-    nbytes = lib.taoamd_accumulate_workspace(n, K, n_rng)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = wsguard.Guarded(lib.taoamd_accumulate_workspace(n, K, n_rng), dev)
+    nbytes = ws.nbytes
     prec = torch.full((N_THR, N_REC, K, n_rng), 7.0, dtype=torch.float64, device=dev)
     rec = torch.full((N_THR, K, n_rng), 7.0, dtype=torch.float64, device=dev)
     s = torch.cuda.current_stream().cuda_stream
@@ -162,6 +163,7 @@ def _device_tables(cat_off, matched, ignored, num_gt, layout, hint, prepared=Fal
         _lib.check(lib.taoamd_accumulate(*args), "taoamd_accumulate")
     flag = C.c_int32(0)
     _lib.check(lib.taoamd_accumulate_error(ws.data_ptr(), s, C.addressof(flag)), "error")
+    ws.check()
     return prec.cpu().numpy(), rec.cpu().numpy(), flag.value
 
 
@@ -180,6 +182,13 @@ def test_categories_on_every_boundary_of_the_blocking(sweep_mode, n_rng, layout)
             assert flag == 0
             assert np.array_equal(got_r, want_r), (sweep_mode, n_rng, layout, hint, prepared)
             assert np.array_equal(got_p, want_p), (sweep_mode, n_rng, layout, hint, prepared)
+
+
+def test_sweep_with_the_workspace_base_moved_by_8_bytes(sweep_mode, monkeypatch):
+    """Once more with the workspace 8 bytes off its 256-byte line: the reported
+    size covers the rounding too (wsguard), and the error word is found."""
+    monkeypatch.setattr(wsguard, "SHIFT", 8)
+    test_categories_on_every_boundary_of_the_blocking(sweep_mode, 20, "paired")
 
 
 def test_long_categories_through_the_look_back(sweep_mode):
@@ -230,8 +239,8 @@ def test_the_flag_is_raised_and_the_chunked_entry_point_recovers(failing_look_ba
     rows[:, :, 0] = torch.from_numpy(m.view(np.int64)).to(dev)
     rows[:, :, 1] = torch.from_numpy(i.view(np.int64)).to(dev)
     d_off, d_ng = torch.from_numpy(cat_off).to(dev), torch.from_numpy(ng).to(dev)
-    nbytes = lib.taoamd_accumulate_workspace(n, K, n_rng)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws = wsguard.Guarded(lib.taoamd_accumulate_workspace(n, K, n_rng), dev)
+    nbytes = ws.nbytes
     prec = torch.empty((N_THR, N_REC, K, n_rng), dtype=torch.float64, device=dev)
     rec = torch.empty((N_THR, K, n_rng), dtype=torch.float64, device=dev)
     s = torch.cuda.current_stream().cuda_stream
@@ -242,6 +251,7 @@ def test_the_flag_is_raised_and_the_chunked_entry_point_recovers(failing_look_ba
     flag = C.c_int32(7)
     _lib.check(lib.taoamd_accumulate_error(ws.data_ptr(), s, C.addressof(flag)), "error")
     assert flag.value == 0
+    ws.check()
     assert np.array_equal(prec.cpu().numpy(), want_p) and np.array_equal(rec.cpu().numpy(), want_r)
 
 

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import track_segm_ref as ref
+import wsguard
 from goldenio import path
 from tao_amodal_amd import flatten
 from tao_amodal_amd.masks import MaskBatch
@@ -110,14 +111,14 @@ def _device_iou(f, sides, mode):
             [x.data_ptr() for x in masks]
     out = torch.full((max(n_pairs, 1),), -7.0, dtype=torch.float64, device=dev)
     pf = torch.full((1,), -1, dtype=torch.int64, device=dev)
-    nb = lib.taoamd_track_mask_iou_workspace(len(sides["dt"][2]), int(sides["dt"][2].off[-1]),
-                                             len(sides["gt"][2]), int(sides["gt"][2].off[-1]))
-    ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+    ws = wsguard.Guarded(lib.taoamd_track_mask_iou_workspace(
+        len(sides["dt"][2]), int(sides["dt"][2].off[-1]),
+        len(sides["gt"][2]), int(sides["gt"][2].off[-1])), dev)
     st = lib.taoamd_track_mask_iou(
         len(f.cell_dt_off) - 1, *[x.data_ptr() for x in head], n_pairs, *args,
-        MODES.index(mode), out.data_ptr(), pf.data_ptr(), ws.data_ptr(), nb, None)
+        MODES.index(mode), out.data_ptr(), pf.data_ptr(), ws.data_ptr(), ws.nbytes, None)
     assert st == 0
-    torch.cuda.synchronize()
+    ws.check()
     return out.cpu().numpy()[:n_pairs], int(pf.item())
 
 
@@ -149,6 +150,11 @@ def test_track_mask_iou_kernel_equals_the_restatement_on_random_problems():
                (0, 5, 10, 5), (4, 0, 10, 5)]
     items = _check(rng, shapes)
     assert items > 1000
+
+
+def test_track_mask_iou_with_the_workspace_base_moved_by_8_bytes(monkeypatch):
+    monkeypatch.setattr(wsguard, "SHIFT", 8)
+    test_track_mask_iou_kernel_equals_the_restatement_on_random_problems()
 
 
 def test_track_mask_iou_kernel_long_run_lists_and_no_pairs():
