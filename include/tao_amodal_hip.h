@@ -813,6 +813,39 @@ int taoamd_accumulate_by_order_chunked(int64_t n_dt, int32_t n_cat, int32_t n_rn
                                double *precision, double *recall, void *workspace,
                                size_t workspace_bytes, void *stream);
 
+/* ---- score at each recall threshold ----------------------------------------------
+ * pycocotools' eval["scores"] (cocoeval.py accumulate: ss[ri] = dtScoresSorted[pi]):
+ * the detection score at the row where recall first reaches each recall
+ * threshold.  The reference's accumulate computes the index it is read at --
+ * rec_thrs_insert_idx = np.searchsorted(rc, rec_thrs, side="left"),
+ * lvis_amodal/eval.py:406-417 == tao_amodal/eval.py:562-573 -- and keeps only
+ * the precision there.  Inputs as in taoamd_accumulate: cat_off, the rows'
+ * matched / ignored words (either layout), num_gt[n_cat][n_rng], the calling
+ * thread's recall thresholds -- non-decreasing, which taoamd_set_thresholds
+ * enforces (the selection searches the table of crossings along the recall
+ * axis); `order` (optional, int32[n_dt], device): sorted position p -> the row
+ * of matched / ignored that belongs to it (rows in cell order,
+ * taoamd_accumulate_by_order); NULL: row p is that of sorted position p.
+ * `score_order` (optional, likewise): sorted position p -> its element of
+ * `score`; NULL: the rows' numbering (order[p], or p without `order`) -- so rows
+ * in sorted order beside scores per detection pass NULL and the sort's order[].
+ * Output, C order, the layout of precision:
+ *   scores[T][R][n_cat][n_rng]  -1 where num_gt == 0; else score[pi], pi = the
+ *     first row of the category whose inclusive count of true positives
+ *     (matched & ~ignored) reaches the smallest count c with
+ *     fl(c / num_gt) >= rec_thrs[j] (c == 0: the category's first row); 0 where
+ *     the category has no such row (the reference's bare `except`).
+ * A value is a copy of an input score: no arithmetic touches it.
+ * Workspace: taoamd_score_at_recall_workspace(n_dt, n_cat, n_rng); any base
+ * address, contents need not be initialised. */
+size_t taoamd_score_at_recall_workspace(int64_t n_dt, int32_t n_cat, int32_t n_rng);
+int taoamd_score_at_recall(int64_t n_dt, int32_t n_cat, int32_t n_rng,
+                           const int32_t *cat_off, const int32_t *order,
+                           const uint64_t *matched, const uint64_t *ignored,
+                           const double *score, const int32_t *score_order,
+                           const int32_t *num_gt, double *scores, void *workspace, size_t workspace_bytes,
+                           void *stream);
+
 /* ---- multi-GPU result exchange (category-partitioned evaluation) -------------------
  * No reference counterpart (the reference is single-process); these carry the
  * tables of taoamd_accumulate_compact between ranks and end in the layout of

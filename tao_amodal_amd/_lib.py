@@ -174,6 +174,9 @@ SIGNATURES = {
                                              _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     "taoamd_accumulate_by_order_chunked": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp,
                                              _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "taoamd_score_at_recall_workspace": (_sz, [_i64, _i32, _i32]),
+    "taoamd_score_at_recall": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

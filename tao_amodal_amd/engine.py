@@ -957,6 +957,29 @@ def stage_accumulate(dp, ws):
         "taoamd_accumulate")
 
 
+def stage_scores(dp, ws):
+    """eval["scores"] of the pass the workspace holds (after stage_accumulate):
+    ws.scores[T, R, n_cat, n_rng] = the score of the row at which recall first
+    reaches each recall threshold (taoamd_score_at_recall), under the calling
+    thread's thresholds.  Its buffers are allocated on the first call: a
+    workspace that is never asked pays nothing."""
+    lib, t, s = _lib.load(), dp.t, _stream()
+    if getattr(ws, "scores", None) is None:
+        ws.score_bytes = lib.taoamd_score_at_recall_workspace(dp.n_dt, dp.n_cat, dp.n_rng)
+        ws.score_ws = torch.empty(max(int(ws.score_bytes), 256), dtype=torch.uint8,
+                                  device=dp.device)
+        ws.scores = torch.empty((N_THR, N_REC, dp.n_cat, dp.n_rng), dtype=torch.float64,
+                                device=dp.device)
+    # the scores lie where the detections are; so do rows left in cell order,
+    # rows scattered to their sorted places need order[] for the scores alone
+    ws.score_order = ws.order        # (derived on demand: alive while the pass runs)
+    order = _ptr(ws.score_order)
+    _lib.check(lib.taoamd_score_at_recall(
+        dp.n_dt, dp.n_cat, dp.n_rng, _ptr(t["cat_off"]), order if ws.cell_order else None,
+        _ptr(ws.matched), _ptr(ws.ignored), _ptr(t["dt_score"]), order, _ptr(ws.num_gt),
+        _ptr(ws.scores), _ptr(ws.score_ws), ws.score_bytes, s), "taoamd_score_at_recall")
+
+
 def stage_track_iou_guarded(dp, ws):
     stage_track_iou(dp, ws)
     stage_iou_guard(dp, ws)

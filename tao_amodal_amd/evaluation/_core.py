@@ -200,6 +200,43 @@ class GpuRun:
         slot[c.thr_blocks[0][0]] = np.arange(c.T)
         return slot.tolist()
 
+    def score_table(self):
+        """eval["scores"][T, R, K, n_rng] in the caller's order of thresholds:
+        the score of the detection at which recall first reaches each recall
+        threshold (pycocotools' ss[ri] = dtScoresSorted[pi]; the index is the
+        reference's rec_thrs_insert_idx, L/eval.py:406-417), from the rows the
+        workspace holds after accumulate() (engine.stage_scores)."""
+        if self.precision is None:
+            raise RuntimeError("Please run accumulate() first.")
+        c = self.constants
+        if c is not None and not c.single:
+            raise NotImplementedError(
+                "eval['scores'] is kept for up to %d IoU thresholds, %d recall "
+                "thresholds and the reference's number of ranges" % (N_THR, N_REC))
+        with timed("kernels"), applied(c):
+            self.engine.stage_scores(self.dp, self.ws)
+            self.torch.cuda.synchronize(self.device)
+        with timed("download"):
+            s = self.ws.scores.cpu().numpy()
+        if c is None:
+            return s
+        r_idx = c.rec_blocks[0][0]
+        out = np.empty((c.T, c.R) + s.shape[2:])
+        out[:, r_idx] = s[self.thr_slots(), :c.R]
+        if not c.rec_sorted:
+            # the reference fills a row IN THE CALLER'S ORDER and stops at the
+            # first threshold the category never reaches (the bare `except` of
+            # L/eval.py:412-416): what follows stays 0.  Never reached: above
+            # the category's recall, or a category without detections.
+            rec = np.empty(c.R)
+            rec[r_idx] = c.rec_blocks[0][1][:c.R]
+            no_rows = np.diff(np.asarray(self.dp.cat_off_host)) == 0
+            unreached = (rec[None, :, None, None] > self.recall[:, None]) \
+                | no_rows[None, None, :, None]
+            never = np.maximum.accumulate(unreached, axis=1)
+            out[never & (self.recall[:, None] != -1)] = 0
+        return out
+
     def pointer_tables(self):
         """What eval['dt_pointers'] is read from: the detections' ids and
         (matched, ignored) words in the sweep's order (category-major, stable
@@ -412,6 +449,20 @@ class LazyPointers(Mapping):
 
     def __len__(self):
         return self.run.dp.n_cat if self.cat_pos is None else len(self.cat_pos)
+
+
+def operating_points(scores, iou_thrs, rec_thrs, cat_ids, iou_thr, recall):
+    """{category id: score} at one IoU threshold and one recall threshold from
+    scores[T, R, K] (eval["scores"] at one range): the confidence at which the
+    category reaches that recall.  The thresholds are looked up like
+    _summarize's (exact floats, ``thr == params.iou_thrs``); categories without
+    evaluated ground truth (-1) are left out."""
+    t = np.where(iou_thr == np.asarray(iou_thrs))[0]
+    j = np.where(recall == np.asarray(rec_thrs))[0]
+    if len(t) == 0 or len(j) == 0:
+        raise ValueError("iou_thr / recall is not one of params.iou_thrs / params.rec_thrs")
+    col = np.asarray(scores)[t[0], j[0]]
+    return {int(c): float(v) for c, v in zip(cat_ids, col.tolist()) if v != -1}
 
 
 def now():

@@ -415,6 +415,9 @@ class DistRun:
                 "ignored": np.concatenate([e[2] for e in every]),
                 "num_gt": self.sharded.num_gt.cpu().numpy(), "cat_off": cat_off}
 
+    def score_table(self):
+        raise NotImplementedError("eval['scores'] in a multi-GPU run")
+
     def pointer_tables(self):
         if self._pointers is None:
             raise NotImplementedError(

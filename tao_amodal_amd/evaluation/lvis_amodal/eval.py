@@ -13,7 +13,7 @@ import numpy as np
 from ... import flatten
 from .._core import (N_REC, N_THR, CellView, GpuRun, LazyIous, LazyPointers,
                      EvalConstants, restrict_to_params,
-                     masked_mean, now, summaries, timed)
+                     masked_mean, now, operating_points, summaries, timed)
 from .lvis import LVIS
 from .results import LVISResults
 
@@ -218,6 +218,33 @@ class LVISEval:
             "recall": recall,
             "dt_pointers": LazyPointers(self._run, n_rng, (n_rng,), self._cat_pos),
         }
+
+    def score_at_recall(self):
+        """eval["scores"][T, R, K, visibility range], pycocotools' table beside
+        eval["precision"]: the score of the detection at which recall first
+        reaches each recall threshold (-1: no evaluated ground truth, 0: never
+        reached).  Computed on the first call, from what accumulate() left on
+        the device."""
+        if not self.eval:
+            raise RuntimeError("Please run accumulate() first.")
+        if "scores" not in self.eval:
+            scores = self._run.score_table()
+            if self._cat_pos is not None:
+                scores = np.ascontiguousarray(scores[:, :, self._cat_pos])
+            self.eval["scores"] = scores
+        return self.eval["scores"]
+
+    def operating_points(self, iou_thr, recall, rng="all"):
+        """{category id: score threshold} at which the category reaches
+        `recall` at `iou_thr` in the visibility range labelled `rng`, read from
+        eval["scores"] (score_at_recall() first)."""
+        if "scores" not in self.eval:
+            raise RuntimeError("Please run score_at_recall() first.")
+        P = self.params
+        aidx = P.visibility_rng_lbl.index(rng)
+        cats = P.cat_ids if P.use_cats else [-1]
+        return operating_points(self.eval["scores"][..., aidx], P.iou_thrs, P.rec_thrs,
+                                cats, iou_thr, recall)
 
     def _summarize(self, summary_type, iou_thr=None, visibility_rng="all",
                    freq_group_idx=None):

@@ -16,7 +16,7 @@ import numpy as np
 
 from .._core import (N_REC, N_THR, CellView, GpuRun, LazyIous, LazyPointers,
                      EvalConstants,
-                     masked_mean, now, summaries, timed)
+                     masked_mean, now, operating_points, summaries, timed)
 from .results import TaoResults
 from .tao import Tao
 
@@ -250,6 +250,33 @@ class TaoEval:
             "recall": recall.reshape(len(P.iou_thrs), K, A, T),
             "dt_pointers": LazyPointers(self._run, A * T, (A, T), self._cat_pos),
         }
+
+    def score_at_recall(self):
+        """eval["scores"][T, R, K, area range, time range], pycocotools' table
+        beside eval["precision"]: the score of the track at which recall first
+        reaches each recall threshold (-1: no evaluated ground truth, 0: never
+        reached).  Computed on the first call, from what accumulate() left on
+        the device."""
+        if not self.eval:
+            raise RuntimeError("Please run accumulate() first.")
+        if "scores" not in self.eval:
+            scores = self._run.score_table()
+            if self._cat_pos is not None:
+                scores = np.ascontiguousarray(scores[:, :, self._cat_pos])
+            self.eval["scores"] = scores.reshape(self.eval["precision"].shape)
+        return self.eval["scores"]
+
+    def operating_points(self, iou_thr, recall, rng=("all", "all")):
+        """{category id: track score threshold} at which the category reaches
+        `recall` at `iou_thr` in the (area, time) range labelled `rng`, read
+        from eval["scores"] (score_at_recall() first)."""
+        if "scores" not in self.eval:
+            raise RuntimeError("Please run score_at_recall() first.")
+        P = self.params
+        aidx, tidx = P.area_rng_lbl.index(rng[0]), P.time_rng_lbl.index(rng[1])
+        cats = P.cat_ids if P.use_cats else [-1]
+        return operating_points(self.eval["scores"][..., aidx, tidx], P.iou_thrs,
+                                P.rec_thrs, cats, iou_thr, recall)
 
     def _summarize(self, summary_type, iou_thr=None, area_rng="all",
                    time_rng="all", freq_group_idx=None):
