@@ -322,7 +322,11 @@ static int before(int64_t a, int64_t b)
 {
     if (s_cat[a] != s_cat[b])
         return s_cat[a] < s_cat[b];
-    return s_score[a] > s_score[b]; /* -score ascending */
+    /* -score ascending, the way numpy's sorts compare doubles: a NaN is not
+     * before anything and everything else is before a NaN, so NaNs come last
+     * in input order (np.argsort(-score, kind="mergesort")) */
+    const double sa = s_score[a], sb = s_score[b];
+    return sa > sb || (sb != sb && sa == sa);
 }
 static void msort(int64_t *x, int64_t *tmp, int64_t n)
 {

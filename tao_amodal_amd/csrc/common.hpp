@@ -171,6 +171,20 @@ __device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t n)
     return x * q + (x < r ? x : r) + b / N_XCD;
 }
 
+// Sort key of a score: ascending key = the order of np.argsort(-score,
+// kind="mergesort"), for any double.  -0.0 counts as 0.0; every NaN, whatever
+// its sign or payload, gets one key above -inf's (0xfff0...), so NaNs come
+// last and the index that breaks ties keeps them in input order, as numpy
+// does.  The sorts (sort.hip) and the merge between ranks (exchange.hip)
+// must agree on it bit for bit.
+__device__ __forceinline__ uint64_t score_desc_key(double s)
+{
+    s = s + 0.0;  // -0.0 -> +0.0: argsort(-score) sees them as equal
+    const uint64_t u = (uint64_t)__double_as_longlong(s);
+    const uint64_t asc = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+    return s != s ? 0xfff8000000000000ull : ~asc;
+}
+
 __device__ __forceinline__ double readlane_f64(double v, int lane)
 {
     int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);

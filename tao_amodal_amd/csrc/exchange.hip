@@ -414,10 +414,8 @@ extern "C" int taoamd_exchange_unpack(int32_t n_cat, int32_t n_rng,
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t ex_desc_key(int64_t score_bits)
 {
-    double s = __longlong_as_double(score_bits) + 0.0;   // -0.0 -> +0.0
-    const uint64_t u = (uint64_t)__double_as_longlong(s);
-    const uint64_t asc = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-    return ~asc;                                          // ascending = score descending
+    // the sorts' key (common.hpp): ascending = score descending, NaN last
+    return score_desc_key(__longlong_as_double(score_bits));
 }
 
 // scores at their sorted place: the first message of the exchange

@@ -47,10 +47,7 @@ struct SortBufs {
 
 __device__ __forceinline__ uint64_t desc_key(double s)
 {
-    s = s + 0.0;  // -0.0 -> +0.0: argsort(-score) sees them as equal
-    uint64_t u = (uint64_t)__double_as_longlong(s);
-    uint64_t asc = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-    return ~asc;
+    return score_desc_key(s);   // common.hpp: any double, NaN last
 }
 
 __device__ __forceinline__ uint32_t digit_of(int pass, uint64_t key, int32_t idx,

@@ -847,7 +847,9 @@ def flatten_tao(gt: GTColumns, dt: DTColumns, max_dets=MAX_DETS,
     seg_max = np.maximum.reduceat(sc, t_off[:-1])
     trk_score[:] = sc[t_off[:-1]]
     required_average = False
-    for k in np.flatnonzero(seg_min != seg_max):
+    # (a track of ONE box has one score, a NaN too: NaN != NaN must not ask
+    # for the average there)
+    for k in np.flatnonzero((seg_min != seg_max) & (np.diff(t_off) > 1)):
         required_average = True
         trk_score[k] = np.mean(sc[t_off[k]:t_off[k + 1]])
     dt_trk_vid = dt.video_id[keep[first]]

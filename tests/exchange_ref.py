@@ -3,6 +3,9 @@ infrastructure: the gloo tests use it as the backend, the GPU tests compare
 the HIP kernels with it byte for byte)."""
 import numpy as np
 
+# the score columns the exchange tests run on besides their own: any double
+from scorepop import expected_order, score_population  # noqa: F401
+
 N_THR, N_REC = 10, 101
 REC_THRS = np.linspace(0.0, 1.00, int(np.round((1.00 - 0.0) / 0.01)) + 1,
                        endpoint=True)

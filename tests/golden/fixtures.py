@@ -22,6 +22,13 @@ F8  a down-scaled Config 2 with DECIMAL coordinates (16 videos x 300 frames
 F9  rule-dense cells (rule_cells): the greedy match's tie / ignore / threshold
     / sentinel rules in cells of 2 to 130 GTs, i.e. in every launch route of
     the match (group, single, big) on both levels
+F10 scores that are any double (two videos x 6 frames x 3 categories): logits
+    on both sides of zero, +-inf, +-0.0, +-5e-324, +-DBL_MAX and NaN (written
+    as the NaN / Infinity literals json.dump emits); a track whose mean is
+    finite, one whose mean is NaN (+inf and -inf), tracks of one NaN box; a
+    category whose best detection scores exactly 0.0 and one whose best scores
+    -1.0 (the markers of eval["scores"]).  No image is over 300 detections:
+    the order sorted() gives a list that holds NaNs is no rule to restate
 """
 import os
 import sys
@@ -515,8 +522,79 @@ def f9():
     return rule_cells(F9_SIZES, hidden_in=6, negative_ids=False)
 
 
+# --------------------------------------------------------------------------
+# F10: scores that are any double
+# --------------------------------------------------------------------------
+DBL_MAX = 1.7976931348623157e308
+
+
+def f10():
+    inf, nan = float("inf"), float("nan")
+    cats = [{"id": c, "name": "c%d" % c, "frequency": "fcr"[c - 1]} for c in (1, 2, 3)]
+    videos, images, tracks, anns, preds = [], [], [], [], []
+    for v in (1, 2):
+        videos.append({"id": v, "name": "v%d" % v, "neg_category_ids": [],
+                       "not_exhaustive_category_ids": []})
+        for f in range(6):
+            images.append({"id": 10 * v + f, "video_id": v, "frame_index": 30 * f,
+                           "neg_category_ids": [], "not_exhaustive_category_ids": []})
+        for c in (1, 2, 3):
+            # two GT tracks per (video, category): recall moves in steps
+            for g in range(2):
+                tid = 100 * v + 10 * c + g
+                tracks.append({"id": tid, "category_id": c, "video_id": v})
+                for f in range(6 - 2 * g):
+                    box = [200 * c + 400 * g, 50 + 5 * f, 60, 60]
+                    anns.append({"id": len(anns) + 1, "image_id": 10 * v + f,
+                                 "track_id": tid, "category_id": c, "bbox": box,
+                                 "area": box[2] * box[3], "visibility": 1.0,
+                                 "out_of_frame": False})
+    n_trk = [0]
+
+    def add_dt(v, c, frames, score, dx=0, g=0):
+        n_trk[0] += 1
+        for k, f in enumerate(frames):
+            preds.append({"image_id": 10 * v + f, "category_id": c,
+                          "bbox": [200 * c + 400 * g + dx, 50 + 5 * f, 60, 60],
+                          "score": score[k] if isinstance(score, list) else score,
+                          "track_id": n_trk[0], "video_id": v})
+
+    six = list(range(6))
+    # category 1: a track with differing scores (mean), one with +inf and -inf
+    # (mean NaN: last at the track level), one of a single NaN box
+    add_dt(1, 1, six, [2.5, -1.25, 0.5, 5e-324, -0.0, DBL_MAX])
+    add_dt(1, 1, six, [inf, -inf, 1.0, inf, -3.0, 0.0], dx=4)
+    add_dt(1, 1, [2], nan, dx=8)
+    add_dt(1, 1, six[:4], -DBL_MAX, g=1)
+    add_dt(2, 1, six, inf)
+    add_dt(2, 1, six, -1.25, dx=6)
+    add_dt(2, 1, [4], nan, dx=2)
+    add_dt(2, 1, six[:4], 2.5, g=1)
+    # category 2: the best detection has score exactly 0.0 (-0.0 ties with it,
+    # in file order), the rest lies below zero down to -inf
+    add_dt(1, 2, six, 0.0)
+    add_dt(1, 2, six, -0.0, dx=3)
+    add_dt(1, 2, six[:4], -5e-324, g=1)
+    add_dt(1, 2, six, -inf, dx=40)
+    add_dt(2, 2, six, -0.0, dx=1)
+    add_dt(2, 2, six[:4], 0.0, g=1)
+    add_dt(2, 2, six, -2.0, dx=5)
+    add_dt(2, 2, [0], nan, dx=9)
+    # category 3: the best detection has score exactly -1.0
+    add_dt(1, 3, six, -1.0)
+    add_dt(1, 3, six[:4], -1.5, g=1)
+    add_dt(1, 3, six, -DBL_MAX, dx=7)
+    add_dt(2, 3, six, -1.0, dx=2)
+    add_dt(2, 3, six[:4], -1.0, g=1)
+    add_dt(2, 3, six, [-1.0, -2.0, -1.0, -inf, -1.0, -1.0], dx=30)
+    add_dt(2, 3, [5], nan, dx=1)
+    gt = {"info": {"description": "scores that are any double"}, "images": images,
+          "videos": videos, "tracks": tracks, "annotations": anns, "categories": cats}
+    return gt, preds
+
+
 ALL = {"f1": f1, "f2": f2, "f3": f3, "f4": f4, "f5": f5, "f7": f7, "f8": f8,
-       "f9": f9}
+       "f9": f9, "f10": f10}
 # big fixtures: inputs stored gzipped, image level reduced to the integer
 # match counts + precision / recall + results + text (make_golden.py)
 LITE = {"f8"}

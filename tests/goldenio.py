@@ -16,6 +16,20 @@ ADVERSARIAL_FIXTURES = ["f7"]
 # frames, golden 3D IoUs = the reference's set-order sums.  Inputs gzipped, the
 # image level reduced to the integer match counts (fixtures.LITE)
 DECIMAL_SCALE_FIXTURES = ["f8"]
+# scores that are any double: logits, +-inf, +-0.0, subnormals, +-DBL_MAX, NaN
+# (integer boxes).  Its lists of scores hold NaN: compare them with
+# same_numbers(), not with ==
+SCORE_FIXTURES = ["f10"]
+
+
+def same_numbers(a, b):
+    """== on two sequences of numbers, a NaN equal to a NaN."""
+    a, b = list(a), list(b)
+    return len(a) == len(b) and all(x == y or (x != x and y != y) for x, y in zip(a, b))
+
+
+def same_number_dicts(a, b):
+    return a.keys() == b.keys() and same_numbers(a.values(), [b[k] for k in a])
 
 
 def path(name, fn):

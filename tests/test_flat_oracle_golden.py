@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 
 import orclib
-from goldenio import FIXTURES, INTEGER_FIXTURES, load_eval, load_inputs, load_json_gz, path
+from goldenio import FIXTURES, INTEGER_FIXTURES, SCORE_FIXTURES, load_eval, load_inputs, \
+    load_json_gz, path, same_number_dicts, same_numbers
 from tao_amodal_amd.columns import DTColumns, GTColumns
 from tao_amodal_amd import flatten as fl
 
@@ -30,7 +31,7 @@ def _check_side(f, out, want, unit_ids, sentinel, exact_iou=True):
         D, G = d1 - d0, g1 - g0
         r0 = w["ranges"][0]
         assert f.dt_id[d0:d1].tolist() == r0["dt_ids"], key
-        assert f.dt_score[d0:d1].tolist() == r0["dt_scores"], key
+        assert same_numbers(f.dt_score[d0:d1].tolist(), r0["dt_scores"]), key
         assert sorted(f.gt_id[g0:g1].tolist()) == sorted(r0["gt_ids"]), key
         wi = np.asarray(w["ious"], dtype=float)
         if D and G:
@@ -79,7 +80,7 @@ def _check_side(f, out, want, unit_ids, sentinel, exact_iou=True):
     assert have == {(int(k), int(r)) for k, r in zip(*np.nonzero(out["num_gt"]))}
 
 
-@pytest.mark.parametrize("name", FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES)
 def test_lvis_flatten_and_c_oracle(name):
     gtj, predj = load_inputs(name)
     want = load_json_gz(name, "lvis.json.gz")
@@ -92,7 +93,7 @@ def test_lvis_flatten_and_c_oracle(name):
     assert np.array_equal(out["recall"], r)
 
 
-@pytest.mark.parametrize("name", FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES)
 def test_tao_flatten_and_c_oracle(name):
     gtj, predj = load_inputs(name)
     want = load_json_gz(name, "tao.json.gz")
@@ -102,9 +103,10 @@ def test_tao_flatten_and_c_oracle(name):
     assert dt.track_id.tolist() == want["unique_track_ids"]
     f = fl.flatten_tao(GTColumns.from_json(gtj), dt)
     assert f.vid_ids.tolist() == want["vid_ids"] and f.cat_ids.tolist() == want["cat_ids"]
-    assert {str(k): v for k, v in f.track_scores.items()} == want["track_scores"]
+    assert same_number_dicts({str(k): v for k, v in f.track_scores.items()},
+                             want["track_scores"])
     out = orclib.run_flat(f)
-    exact = name in INTEGER_FIXTURES
+    exact = name in INTEGER_FIXTURES + SCORE_FIXTURES
     _check_side(f, out, want, f.vid_ids, -1, exact_iou=exact)
     p, r = load_eval(name)["tao"]
     assert np.array_equal(out["precision"].reshape(p.shape), p)

@@ -8,7 +8,7 @@ import contextlib
 import numpy as np
 import pytest
 
-from goldenio import FIXTURES, INTEGER_FIXTURES, load_eval, load_json_gz, path
+from goldenio import FIXTURES, INTEGER_FIXTURES, SCORE_FIXTURES, load_eval, load_json_gz, path
 from test_oracle_golden import _check_cells
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +23,7 @@ def _cli():
     return m
 
 
-@pytest.mark.parametrize("name", FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES)
 def test_cli_text_is_identical_to_the_reference(name, tmp_path):
     log = tmp_path / "out" / "eval.log"
     buf = io.StringIO()
@@ -201,12 +201,14 @@ def test_cli_serial_switch_gives_the_same_text(tmp_path, monkeypatch):
     assert got == open(path("f5", "cli_log.txt")).read()
 
 
-@pytest.mark.parametrize("name", FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES)
 def test_cli_text_with_the_prediction_file_read_on_the_device(name, tmp_path, monkeypatch):
     """The reference's text again with the device-side reader taking files of
     any size (csrc/json_ingest.hip; by default from 32 MB on): columns that
     stay on the device through both levels' table builds, or the host reader
-    where the device reader steps aside."""
+    where the device reader steps aside.  (f10: the objects whose score is a
+    NaN / Infinity literal go to the host reader and are patched in, and the
+    device table build then sorts those scores.)"""
     monkeypatch.setenv("TAOAMD_DEVICE_INGEST_MIN_BYTES", "0")
     log = tmp_path / "out" / "eval.log"
     buf = io.StringIO()

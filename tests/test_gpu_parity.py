@@ -7,7 +7,8 @@ import pytest
 import exchange_ref
 import orclib
 import wsguard
-from goldenio import FIXTURES, INTEGER_FIXTURES, load_eval, load_inputs, load_json_gz, path
+from goldenio import FIXTURES, INTEGER_FIXTURES, SCORE_FIXTURES, load_eval, load_inputs, \
+    load_json_gz, path
 from test_flat_oracle_golden import _check_side
 from tao_amodal_amd import flatten as fl
 from tao_amodal_amd.columns import DTColumns, GTColumns
@@ -39,7 +40,7 @@ def _compare_with_oracle(f, got, detail=True):
     assert np.array_equal(got["recall"], want["recall"])
 
 
-@pytest.mark.parametrize("name", FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES)
 def test_lvis_hip_matches_reference_golden(name):
     gtj, predj = load_inputs(name)
     want = load_json_gz(name, "lvis.json.gz")
@@ -52,7 +53,7 @@ def test_lvis_hip_matches_reference_golden(name):
     _compare_with_oracle(f, got)
 
 
-@pytest.mark.parametrize("name", FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES)
 def test_tao_hip_matches_reference_golden(name):
     gtj, predj = load_inputs(name)
     want = load_json_gz(name, "tao.json.gz")
@@ -60,7 +61,8 @@ def test_tao_hip_matches_reference_golden(name):
     dt.track_id, _ = fl.make_track_ids_unique(dt)
     f = fl.flatten_tao(GTColumns.from_json(gtj), dt)
     got = _engine().evaluate_flat(f, detail=True)
-    _check_side(f, got, want, f.vid_ids, -1, exact_iou=name in INTEGER_FIXTURES)
+    _check_side(f, got, want, f.vid_ids, -1,
+                exact_iou=name in INTEGER_FIXTURES + SCORE_FIXTURES)
     p, r = load_eval(name)["tao"]
     assert np.array_equal(got["precision"].reshape(p.shape), p)
     assert np.array_equal(got["recall"].reshape(r.shape), r)
@@ -520,14 +522,29 @@ def test_overlapped_streams_give_the_same_tensors():
 
 @pytest.mark.parametrize("world", [1, 2, 3, 8])
 def test_exchange_chunks_hip_vs_numpy_restatement(world):
+    _exchange_chunks(world)
+
+
+@pytest.mark.parametrize("population", ["logits", "specials", "nan"])
+@pytest.mark.parametrize("world", [1, 3, 8])
+def test_exchange_chunks_on_any_double(world, population):
+    _exchange_chunks(world, population)
+
+
+def _exchange_chunks(world, population=None):
     """taoamd_exchange_{sizes,pack,unpack} against tests/exchange_ref.py: the
     packed chunks byte for byte, the expanded tables against the plain
-    single-GPU finalize (no collective needed: every block is packed here)."""
+    single-GPU finalize (no collective needed: every block is packed here).
+    With a `population` the set's scores are any double (exchange_ref.
+    score_population): the tables the chunks carry come from that order."""
     import torch
     import exchange_ref
     from tao_amodal_amd import dist as tdist, engine
     be = tdist.HipBackend()
     gt, dt = synth(seed=31, V=6, F=20, C=53, dets_per_frame=40, n_present=9)
+    if population:
+        dt.score = exchange_ref.score_population(population, len(dt),
+                                                 np.random.default_rng(world))
     fl_ = fl.flatten_lvis(gt, dt)
     dt.track_id, _ = fl.make_track_ids_unique(dt)
     ft_ = fl.flatten_tao(gt, dt)
@@ -781,13 +798,26 @@ def test_cells_whose_detections_overlap_two_ground_truths(detail):
 
 @pytest.mark.parametrize("world,own", [(1, 0), (3, -1), (3, 1), (8, 7), (8, 0)])
 def test_exchange_positions_and_place_vs_numpy(world, own):
+    _exchange_positions_and_place(world, own)
+
+
+@pytest.mark.parametrize("population", ["logits", "specials", "nan"])
+@pytest.mark.parametrize("world,own", [(1, 0), (3, -1), (3, 1), (8, 7), (8, 0)])
+def test_exchange_positions_and_place_on_any_double(world, own, population):
+    _exchange_positions_and_place(world, own, population)
+
+
+def _exchange_positions_and_place(world, own, population=None):
     """taoamd_exchange_scores / _positions / _place (the by-video plan's owner
     side, round 5) against the numpy statement the gloo tests run with
     (tests/test_dist_gloo.py: stable -score sort of the sources' concatenation
     in rank order, L/eval.py:353-361): runs of equal scores across and inside
     sources, empty runs, an empty source, the rank's own rows read outside the
     wire buffer (own >= 0) or every source on the wire (own < 0), one and four
-    combo words."""
+    combo words.  With a `population` the scores are any double (exchange_ref.
+    score_population), drawn from a pool of twelve so that the runs of equal
+    keys stay: the key of the search between ranks must order them as numpy
+    does, every NaN last and a lower rank's NaN before a higher rank's."""
     import torch
     from test_dist_gloo import OracleBackend
     from tao_amodal_amd import dist as tdist
@@ -809,10 +839,15 @@ def test_exchange_positions_and_place_vs_numpy(world, own):
         # scores: few distinct values (ties across and inside sources), each
         # source's run descending
         scores = np.zeros(n)
+        pool = exchange_ref.score_population(population, 12, rng) if population else None
         for s in range(world):
             for kb in range(Kb):
                 a, b = src_base[s] + run_off[s, kb], src_base[s] + run_off[s, kb + 1]
-                scores[a:b] = -np.sort(-rng.integers(0, 6, b - a) / 5.0)
+                if population:
+                    run = pool[rng.integers(0, len(pool), b - a)]
+                    scores[a:b] = run[exchange_ref.expected_order(run)]
+                else:
+                    scores[a:b] = -np.sort(-rng.integers(0, 6, b - a) / 5.0)
         rows = rng.integers(-2 ** 62, 2 ** 62, (n, nw, 2))
         own_lo, own_hi = (int(src_base[own]), int(src_base[own + 1])) if own >= 0 else (0, 0)
         keep = np.ones(n, bool)
@@ -841,7 +876,8 @@ def test_exchange_positions_and_place_vs_numpy(world, own):
     # the scores at their sorted place
     n = 1000
     dst = torch.from_numpy(rng.permutation(n).astype(np.int32)).to("cuda:0")
-    sc = torch.from_numpy(rng.random(n)).to("cuda:0")
+    sc = torch.from_numpy(exchange_ref.score_population(population, n, rng) if population
+                          else rng.random(n)).to("cuda:0")
     out = torch.zeros(n, dtype=torch.int64, device="cuda:0")
     from tao_amodal_amd import _lib
     _lib.check(_lib.load().taoamd_exchange_scores(

@@ -3,7 +3,8 @@ import numpy as np
 import pytest
 
 from goldenio import (ADVERSARIAL_FIXTURES, DECIMAL_SCALE_FIXTURES, FIXTURES,
-                      INTEGER_FIXTURES, load_eval, load_inputs, load_json_gz)
+                      INTEGER_FIXTURES, SCORE_FIXTURES, load_eval, load_inputs, load_json_gz,
+                      same_number_dicts, same_numbers)
 from oracle import pyoracle
 
 
@@ -24,7 +25,7 @@ def _check_cells(got_cells, want_cells, exact_iou=True):
         assert len(g["ranges"]) == len(w["ranges"])
         for a, (gr, wr) in enumerate(zip(g["ranges"], w["ranges"])):
             for f in ("dt_ids", "gt_ids", "dt_scores"):
-                assert list(gr[f]) == list(wr[f]), (key, a, f)
+                assert same_numbers(gr[f], wr[f]), (key, a, f)
             for f in ("dt_matches", "gt_matches", "dt_ignore", "gt_ignore"):
                 assert np.array_equal(np.asarray(gr[f], dtype=float),
                                       np.asarray(wr[f], dtype=float)), (key, a, f)
@@ -47,7 +48,7 @@ def _check_results(got, want):
         assert float(gv) == wv, k
 
 
-@pytest.mark.parametrize("name", FIXTURES + ADVERSARIAL_FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + ADVERSARIAL_FIXTURES + SCORE_FIXTURES)
 def test_lvis_oracle_matches_reference(name):
     gt, pred = load_inputs(name)
     want = load_json_gz(name, "lvis.json.gz")
@@ -63,7 +64,7 @@ def test_lvis_oracle_matches_reference(name):
     assert got["freq_groups"] == want["freq_groups"]
 
 
-@pytest.mark.parametrize("name", FIXTURES + ADVERSARIAL_FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + ADVERSARIAL_FIXTURES + SCORE_FIXTURES)
 def test_tao_oracle_matches_reference(name):
     gt, pred = load_inputs(name)
     want = load_json_gz(name, "tao.json.gz")
@@ -72,7 +73,8 @@ def test_tao_oracle_matches_reference(name):
     assert [p["track_id"] for p in pred] == want["unique_track_ids"]
     got = pyoracle.tao_eval(gt, pred, frame_order="set")
     assert got["vid_ids"] == want["vid_ids"] and got["cat_ids"] == want["cat_ids"]
-    assert {str(k): v for k, v in got["track_scores"].items()} == want["track_scores"]
+    assert same_number_dicts({str(k): v for k, v in got["track_scores"].items()},
+                             want["track_scores"])
     _check_cells(got["cells"], want["cells"])
     p, r = load_eval(name)["tao"]
     assert np.array_equal(got["precision"], p)
