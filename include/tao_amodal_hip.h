@@ -846,6 +846,79 @@ int taoamd_score_at_recall(int64_t n_dt, int32_t n_cat, int32_t n_rng,
                            const int32_t *num_gt, double *scores, void *workspace, size_t workspace_bytes,
                            void *stream);
 
+/* ---- image-level error breakdown per range (csrc/error_types.hip) ------------------
+ * WHY a detection is no true positive, per visibility range and category.  No
+ * reference counterpart (pycocotools users reach for TIDE, Bolya et al., ECCV
+ * 2020); the definition is this library's.  Image level, boxes only.
+ *
+ * One call = one IoU threshold slot of the calling thread's iou_thrs (the
+ * foreground threshold tf = min(iou_thrs[slot], 1 - 1e-10), the clamp of the
+ * match), one background threshold bg_thr = tb with 0 <= tb < tf, and all
+ * n_rng <= TAOAMD_ERROR_TYPES_MAX_RNG ranges at once.  Rows are the rows of the
+ * use_cats = 1 cell table (what survived the max_dets cut and the federated
+ * filter).  For detection d (image u, category c) and range a:
+ *   E_a(u) = the ground truths of image u, of ANY category, whose gt_rng bit a
+ *            is clear;
+ *   s      = the maximum of bbIou(d, g) over g in E_a(u) of category c, 0 for
+ *            an empty set; its argmax = the LOWEST ground-truth row among equal
+ *            IoUs;
+ *   o      = the same maximum over the other categories.
+ * Exactly one type per (detection, range), the first rule that applies:
+ *   0 TP       match_gt[d][a * 10 + slot] >= 0 and that ground truth is
+ *              evaluated in a
+ *   1 IGNORED  matched to a ground truth ignored in a, or unmatched with
+ *              TAOAMD_DT_IGNORE_UNMATCHED
+ *   2 DUP      unmatched, s >= tf
+ *   3 LOC      unmatched, tb <= s < tf
+ *   4 CLS      unmatched, o >= tf
+ *   5 BOTH     unmatched, tb <= o < tf
+ *   6 BKG      otherwise
+ * (so with tb = 0 every unmatched, unignored detection is DUP or LOC).  An
+ * unmatched row with s >= tf always points at a ground truth another detection
+ * holds: the greedy match would otherwise have given the row a ground truth.
+ * Per (ground truth, range) with the gt_rng bit clear: `evaluated` counts it,
+ * `missed` counts it when no detection's match_gt names it at (a, slot),
+ * `missed_loc` counts a missed one that is the same-category argmax of at least
+ * one LOC detection of range a.
+ * The table follows match_gt, the in-cell index: a ground truth that carries
+ * TAOAMD_GT_ID_HIDDEN and holds a detection counts as TP / not missed here,
+ * whereas the sweep (the reference's dt_m == 0) sees that detection as
+ * unmatched.
+ *
+ *   dt_cat, dt_box, dt_flags   columns of the cell table, n_dt rows
+ *   dt_gt0      int32[n_dt]    first ground-truth row of the row's cell (match_gt
+ *                              counts from it)
+ *   match_gt    int32, row d at match_gt + d * match_stride (>= n_rng * 10
+ *               elements), identity order: what taoamd_match writes
+ *   gt_cat, gt_box, gt_rng     columns of the ground truths, n_gt rows
+ *   img_gt_off  int32[n_img + 1], img_gt int32[n_gt]: the ground-truth rows of
+ *               each image (the table is category-major: they are not contiguous);
+ *               img_dt_off, img_dt: the same for the detection rows
+ * Outputs (zeroed by the call): dt_counts int64[n_rng][n_cat][7],
+ * gt_counts int64[n_rng][n_cat][3] = {evaluated, missed, missed_loc}, and, if
+ * not NULL, dt_type uint8[n_dt][n_rng] in the table's row order.
+ * TAOAMD_ERR_ARG: slot outside [0, 10), bg_thr outside [0, tf), n_rng outside
+ * [1, 8]; TAOAMD_ERR_WORKSPACE: fewer bytes than
+ * taoamd_error_types_workspace(n_dt, n_gt, n_rng) (two byte tables
+ * [n_rng][n_gt] and the types [n_dt][n_rng] the counts are taken from when
+ * dt_type is NULL; any base address, contents need not be initialised).  Rows named by the CSR
+ * lists or by match_gt that lie outside the tables are skipped, never
+ * dereferenced. */
+#define TAOAMD_ERROR_TYPES_TILE 256    /* ground truths staged per step; lanes per image */
+#define TAOAMD_ERROR_TYPES_MAX_RNG 8
+size_t taoamd_error_types_workspace(int64_t n_dt, int64_t n_gt, int32_t n_rng);
+int taoamd_error_types(int64_t n_dt, int64_t n_gt, int32_t n_img, int32_t n_cat,
+                       int32_t n_rng, int32_t slot, double bg_thr,
+                       const int32_t *dt_cat, const double *dt_box,
+                       const uint8_t *dt_flags, const int32_t *dt_gt0,
+                       const int32_t *match_gt, int64_t match_stride,
+                       const int32_t *gt_cat, const double *gt_box,
+                       const uint32_t *gt_rng, const int32_t *img_gt_off,
+                       const int32_t *img_gt, const int32_t *img_dt_off,
+                       const int32_t *img_dt, int64_t *dt_counts, int64_t *gt_counts,
+                       uint8_t *dt_type, void *workspace, size_t workspace_bytes,
+                       void *stream);
+
 /* ---- multi-GPU result exchange (category-partitioned evaluation) -------------------
  * No reference counterpart (the reference is single-process); these carry the
  * tables of taoamd_accumulate_compact between ranks and end in the layout of

@@ -182,6 +182,8 @@ class DeviceProblem:
         self.n_dt = int(flat.cell_dt_off[-1])
         self.n_gt = int(flat.cell_gt_off[-1])
         self.n_pairs = int(flat.n_pairs)
+        # image / video of every cell (host): the error breakdown groups rows by it
+        self.cell_unit_host = flat.get("cell_unit")
         # tables a device-side build (flatten_dev.DeviceFlat) already holds in HBM
         on_dev = getattr(flat, "dev", {})
         d_cnt = np.diff(flat.cell_dt_off).astype(np.int64)
@@ -901,10 +903,11 @@ def set_order_iou(flat, pairs, mode=0):
     return out
 
 
-def stage_match(dp, ws, scatter=True, groups=None, singles=None):
+def stage_match(dp, ws, scatter=True, groups=None, singles=None, match_gt=None):
     """`groups` / `singles`: (device table, first, count) -- a slice of a
     launch plan instead of the problem's whole plan (the phases of the
-    multi-GPU exchange, dist.ShardedEval)."""
+    multi-GPU exchange, dist.ShardedEval).  `match_gt`: a table for the in-cell
+    match indices of this one call, where the workspace keeps none."""
     if dp.n_dt == 0:        # nothing was detected: every cell is GT-only
         return
     lib, t, s = _lib.load(), dp.t, _stream()
@@ -927,7 +930,8 @@ def stage_match(dp, ws, scatter=True, groups=None, singles=None):
         None if dp.kind == "lvis" else _ptr(ws.dt_rng),   # (image level: from the flags)
         _ptr(t["gt_flags"]), _ptr(t["dt_flags"]),
         _ptr(ws.dst) if scatter else None, 0, _ptr(ws.matched),
-        _ptr(ws.ignored), _ptr(ws.match_gt), _ptr(ws.ious_out),
+        _ptr(ws.ignored), _ptr(ws.match_gt if match_gt is None else match_gt),
+        _ptr(ws.ious_out),
         _ptr(t["dt_group"]), _ptr(t["dt_meta"]), g_ptr, n_g,
         s_ptr, n_s, s), "taoamd_match")
 
@@ -978,6 +982,81 @@ def stage_scores(dp, ws):
         dp.n_dt, dp.n_cat, dp.n_rng, _ptr(t["cat_off"]), order if ws.cell_order else None,
         _ptr(ws.matched), _ptr(ws.ignored), _ptr(t["dt_score"]), order, _ptr(ws.num_gt),
         _ptr(ws.scores), _ptr(ws.score_ws), ws.score_bytes, s), "taoamd_score_at_recall")
+
+
+def _rows_by_unit(unit, n_unit):
+    """CSR of the rows of a table by the unit (image) they belong to, rows of a
+    unit ascending: (off int32[n_unit + 1], rows int32[n])."""
+    off = torch.zeros(n_unit + 1, dtype=torch.int32, device=unit.device)
+    if unit.numel() == 0:
+        return off, torch.zeros(1, dtype=torch.int32, device=unit.device)
+    off[1:] = torch.cumsum(torch.bincount(unit, minlength=n_unit), 0)
+    return off, torch.argsort(unit, stable=True).to(torch.int32)
+
+
+def error_match_gt(dp, ws):
+    """The table stage_error_types reads the match indices from where the
+    workspace keeps none of its own: int32[n_dt, n_rng * 10], allocated on the
+    first call and kept with the workspace (240 bytes a row: 5.1 GB at 21.4 M
+    rows; `del ws.err_match_gt` gives it back).  A caller that runs the match
+    itself passes it as stage_match(match_gt=...) / run_guarded(match_gt=...)."""
+    if getattr(ws, "err_match_gt", None) is None:
+        ws.err_match_gt = torch.empty((max(dp.n_dt, 1), dp.n_rng * N_THR), dtype=torch.int32,
+                                      device=dp.device)
+    return ws.err_match_gt
+
+
+def stage_error_types(dp, ws, slot, tb, per_detection=False):
+    """Image-level error breakdown of the pass the workspace holds (after
+    stage_ranges .. stage_match): ws.err_dt_counts[n_rng, n_cat, 7],
+    ws.err_gt_counts[n_rng, n_cat, 3] and, with `per_detection`,
+    ws.err_dt_type[n_dt, n_rng] (taoamd_error_types; the definition is in
+    include/tao_amodal_hip.h) at IoU threshold slot `slot` of the calling
+    thread's thresholds and background threshold `tb`.  The per-image row lists
+    are built once per problem; the match indices come from the existing match
+    entry and stay on the device: the workspace's own table (detail mode), else
+    error_match_gt(), filled here by one more match with match_gt requested
+    unless the caller's match already wrote it.  Buffers are allocated on the
+    first call."""
+    if dp.kind != "lvis" or dp.mask_iou:
+        raise _lib.TaoAmdError("the error breakdown is the image level's, on boxes")
+    if dp.cell_unit_host is None:
+        raise _lib.TaoAmdError("the error breakdown needs the cells' images (flat.cell_unit)")
+    lib, t, s = _lib.load(), dp.t, _stream()
+    dev = dp.device
+    if getattr(dp, "err_tabs", None) is None:
+        cell_unit = torch.from_numpy(np.ascontiguousarray(dp.cell_unit_host, dtype=np.int64)
+                                     ).to(dev)
+        n_img = int(dp.cell_unit_host.max()) + 1 if dp.n_cells else 0
+        cells = torch.arange(dp.n_cells, dtype=torch.int64, device=dev)
+        gt_cell = torch.repeat_interleave(
+            cells, (t["cell_gt_off"][1:] - t["cell_gt_off"][:-1]).long())
+        dt_cell = t["dt_cell"][:dp.n_dt].long()
+        dp.err_tabs = (n_img,) + _rows_by_unit(cell_unit[gt_cell], n_img) \
+            + _rows_by_unit(cell_unit[dt_cell], n_img) \
+            + (t["dt_group"][:, 0].contiguous(),)
+    n_img, img_gt_off, img_gt, img_dt_off, img_dt, dt_gt0 = dp.err_tabs
+    if getattr(ws, "err_dt_counts", None) is None:
+        ws.err_bytes = lib.taoamd_error_types_workspace(dp.n_dt, dp.n_gt, dp.n_rng)
+        ws.err_ws = torch.empty(max(int(ws.err_bytes), 256), dtype=torch.uint8, device=dev)
+        ws.err_dt_counts = torch.empty((dp.n_rng, dp.n_cat, 7), dtype=torch.int64, device=dev)
+        ws.err_gt_counts = torch.empty((dp.n_rng, dp.n_cat, 3), dtype=torch.int64, device=dev)
+        ws.err_dt_type = None
+    match_gt = ws.match_gt
+    if match_gt is None:
+        if getattr(ws, "err_match_gt", None) is None and dp.n_dt:
+            stage_match(dp, ws, scatter=not ws.cell_order, match_gt=error_match_gt(dp, ws))
+        match_gt = getattr(ws, "err_match_gt", None)
+    if per_detection and ws.err_dt_type is None:
+        ws.err_dt_type = torch.empty((max(dp.n_dt, 1), dp.n_rng), dtype=torch.uint8, device=dev)
+    _lib.check(lib.taoamd_error_types(
+        dp.n_dt, dp.n_gt, n_img, dp.n_cat, dp.n_rng, int(slot), float(tb),
+        _ptr(t["dt_cat"]), _ptr(t["dt_box"]), _ptr(t["dt_flags"]), _ptr(dt_gt0),
+        _ptr(match_gt), dp.n_rng * N_THR, _ptr(t["gt_cat"]), _ptr(t["gt_box"]),
+        _ptr(ws.gt_rng), _ptr(img_gt_off), _ptr(img_gt), _ptr(img_dt_off), _ptr(img_dt),
+        _ptr(ws.err_dt_counts), _ptr(ws.err_gt_counts),
+        _ptr(ws.err_dt_type) if per_detection else None,
+        _ptr(ws.err_ws), ws.err_bytes, s), "taoamd_error_types")
 
 
 def stage_track_iou_guarded(dp, ws):
@@ -1219,7 +1298,7 @@ def time_stages(dpl, wsl, dpt, wst, reps=10):
     return out
 
 
-def run_guarded(dp, ws, flat=None, upto=None, read_count=True, head=True):
+def run_guarded(dp, ws, flat=None, upto=None, read_count=True, head=True, match_gt=None):
     """One evaluator pass; returns the number of pairs the frame-order guard
     recomputed (synchronises at the end to read it, unless read_count=False:
     guarded_pairs() gives it later).  `head=False`: a further pass over the
@@ -1237,7 +1316,10 @@ def run_guarded(dp, ws, flat=None, upto=None, read_count=True, head=True):
         stage_track_iou(dp, ws)
     stage_iou_guard(dp, ws)
     apply_iou_guard(dp, ws, flat)
-    stage_match(dp, ws)
+    if match_gt is None:
+        stage_match(dp, ws)
+    else:
+        stage_match(dp, ws, match_gt=match_gt)
     if upto != "match":
         stage_accumulate(dp, ws)
     if not read_count:

@@ -98,6 +98,7 @@ class GpuRun:
             torch.cuda.synchronize(self.device)
         self._detail = None
         self._head_done = False      # sort + IoU matrix of this problem are in the workspace
+        self._error_pass = False     # error_table() ran the pass evaluate() left out
         self.near_threshold_pairs = 0
         self.precision = self.recall = None
 
@@ -189,12 +190,14 @@ class GpuRun:
                     iou_3d_type=self.iou_3d_type)
         return self._detail
 
-    def thr_slots(self):
-        """Place of the caller's i-th IoU threshold among the kernels' combos."""
+    def thr_slots(self, views=True):
+        """Place of the caller's i-th IoU threshold among the kernels' combos
+        (`views`: for the per-cell views, which also want the caller's ranges
+        slot for slot)."""
         c = self.constants
         if c is None:
             return list(range(N_THR))
-        if not c.single:
+        if views and not c.single:
             self.detail()        # raises
         slot = np.empty(c.T, dtype=np.int64)
         slot[c.thr_blocks[0][0]] = np.arange(c.T)
@@ -236,6 +239,51 @@ class GpuRun:
             never = np.maximum.accumulate(unreached, axis=1)
             out[never & (self.recall[:, None] != -1)] = 0
         return out
+
+    def error_table(self, thr_index, bg_thr, per_detection=False):
+        """(dt_counts[n_rng, K, 7], gt_counts[n_rng, K, 3], dt_type[n_dt, n_rng]
+        or None) at the caller's `thr_index`-th IoU threshold, ranges in the
+        caller's order (engine.stage_error_types; the definition is in
+        include/tao_amodal_hip.h), from the pass the workspace holds after
+        evaluate()."""
+        c = self.constants
+        if self.flat.kind != "lvis":
+            raise NotImplementedError(
+                "error_types() at the track level: its IoU exists per (video, category) only")
+        if self.dp.mask_iou:
+            raise NotImplementedError("error_types() with iou_type='segm': boxes only")
+        if not self.flat.get("use_cats", True):
+            raise NotImplementedError(
+                "error_types() with use_cats = 0: one pooled category has no class confusion")
+        if c is not None and (len(c.thr_blocks) > 1 or len(c.rng_blocks) > 1):
+            raise NotImplementedError(
+                "error_types() is kept for up to %d IoU thresholds and one block of "
+                "ranges" % N_THR)
+        slot = self.thr_slots(views=False)[thr_index]
+        e = self.engine
+        with timed("kernels"), applied(c):
+            if c is not None and not c.single and not self._error_pass:
+                # one block of thresholds and of ranges, yet not the kernels'
+                # tables slot for slot: evaluate() left the pass to accumulate(),
+                # whose blocks repeat this very match
+                e.run_guarded(self.dp, self.ws, self.flat, upto="match", read_count=False,
+                              head=not self._head_done,
+                              match_gt=e.error_match_gt(self.dp, self.ws))
+                self._head_done = self._error_pass = True
+            e.stage_error_types(self.dp, self.ws, slot, bg_thr, per_detection)
+            self.torch.cuda.synchronize(self.device)
+        with timed("download"):
+            dt_counts = self.ws.err_dt_counts.cpu().numpy()
+            gt_counts = self.ws.err_gt_counts.cpu().numpy()
+            dt_type = self.ws.err_dt_type[:self.dp.n_dt].cpu().numpy() if per_detection \
+                else None
+        if c is not None:
+            # kernel range slot -> the caller's range
+            ks = [k for k, _ in sorted(c.rng_blocks[0][1], key=lambda ki: ki[1])]
+            dt_counts, gt_counts = dt_counts[ks], gt_counts[ks]
+            if dt_type is not None:
+                dt_type = np.ascontiguousarray(dt_type[:, ks])
+        return dt_counts, gt_counts, dt_type
 
     def pointer_tables(self):
         """What eval['dt_pointers'] is read from: the detections' ids and

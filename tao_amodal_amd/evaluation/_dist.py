@@ -418,6 +418,11 @@ class DistRun:
     def score_table(self):
         raise NotImplementedError("eval['scores'] in a multi-GPU run")
 
+    def error_table(self, thr_index, bg_thr, per_detection=False):
+        raise NotImplementedError(
+            "error_types() in a multi-GPU run: an image's ground truths of other "
+            "categories live on other ranks")
+
     def pointer_tables(self):
         if self._pointers is None:
             raise NotImplementedError(

@@ -96,6 +96,7 @@ class LVISEval:
         self.params.cat_ids = sorted(self.lvis_gt.get_cat_ids())
         self._run = None
         self._cat_pos = None
+        self._error_types = {}
 
     # ------------------------------------------------------------ stages
     def evaluate(self):
@@ -136,6 +137,7 @@ class LVISEval:
                                 subset=gt_cols is not self.lvis_gt.columns)
         else:
             self._run = GpuRun(flat, self.device, constants=constants)
+        self._error_types = {}
         self._run.evaluate()
         view = CellView(self._run, flat.img_ids, 0, "image_id", "visibility_rng",
                         self.params.visibility_rng)
@@ -245,6 +247,80 @@ class LVISEval:
         cats = P.cat_ids if P.use_cats else [-1]
         return operating_points(self.eval["scores"][..., aidx], P.iou_thrs, P.rec_thrs,
                                 cats, iou_thr, recall)
+
+    def error_types(self, iou_thr=0.5, bg_thr=0.1, per_detection=False):
+        """Why a detection is no true positive, per visibility range and
+        category, at the IoU threshold `iou_thr` (one of params.iou_thrs; the
+        foreground threshold tf = min(iou_thr, 1 - 1e-10)) and the background
+        threshold `bg_thr` (0 <= bg_thr < tf).  No counterpart in the
+        reference; the types follow TIDE (Bolya et al., ECCV 2020).  Callable
+        after evaluate(), computed on the device on request
+        (csrc/error_types.hip), cached per (iou_thr, bg_thr).
+
+        Rows are the detections that survived the max_dets cut and the
+        federated filter.  With s the largest box IoU of a detection with the
+        ground truths of ITS category in its image that the range evaluates
+        (0 if none) and o the same over the image's other categories, a
+        (detection, range) pair is the first of: TP (matched to an evaluated
+        ground truth), IGNORED (matched to an ignored one, or unmatched in a
+        not-exhaustive category), DUP (unmatched, s >= tf: the ground truth is
+        held by another detection), LOC (bg_thr <= s < tf), CLS (o >= tf), BOTH
+        (bg_thr <= o < tf), BKG.  Per evaluated ground truth: `evaluated`,
+        `missed` (no detection is matched to it), `missed_loc` (missed, and the
+        best same-category ground truth -- the first in table order among
+        equal IoUs -- of at least one LOC detection).
+
+        Returns {"types": the 7 names, "dt_counts": int64[n_rng, K, 7],
+        "gt_counts": int64[n_rng, K, 3], "rng_lbl": params.visibility_rng_lbl}
+        with the category axis in the order of params.cat_ids like
+        eval["precision"], and with per_detection=True "dt_type": (rows, types)
+        = the detections' rows in the prediction list and uint8[n, n_rng].
+
+        The table follows the match itself: a detection matched to a ground
+        truth whose id is 0 counts as TP here, whereas accumulate(), like the
+        reference (dt_m == 0), sees it as unmatched.  Not available: the track
+        level (its IoU exists per (video, category) only), iou_type="segm",
+        use_cats = 0, more than one block of edited constants, multi-GPU
+        runs."""
+        if self._run is None:
+            raise RuntimeError("Please run evaluate() first.")
+        P = self.params
+        at = np.where(iou_thr == np.asarray(P.iou_thrs))[0]
+        if len(at) == 0:
+            raise ValueError("iou_thr: {} is not one of params.iou_thrs".format(iou_thr))
+        tf = min(float(np.asarray(P.iou_thrs)[at[0]]), 1 - 1e-10)
+        if not 0 <= bg_thr < tf:
+            raise ValueError("bg_thr: {} is not in [0, {})".format(bg_thr, tf))
+        key = (int(at[0]), float(bg_thr))
+        hit = self._error_types.get(key)
+        if hit is None or (per_detection and "dt_type" not in hit):
+            dt_counts, gt_counts, dt_type = self._run.error_table(
+                key[0], key[1], per_detection)
+            if self._cat_pos is not None:
+                dt_counts = np.ascontiguousarray(dt_counts[:, self._cat_pos])
+                gt_counts = np.ascontiguousarray(gt_counts[:, self._cat_pos])
+            from ..._lib import ERROR_TYPES
+            hit = {"types": list(ERROR_TYPES), "dt_counts": dt_counts,
+                   "gt_counts": gt_counts, "rng_lbl": list(P.visibility_rng_lbl)}
+            if per_detection:
+                hit["dt_type"] = (np.asarray(self.flat.dt_row), dt_type)
+            self._error_types[key] = hit
+        return hit if per_detection else {k: v for k, v in hit.items() if k != "dt_type"}
+
+    def error_lines(self, iou_thr=0.5, bg_thr=0.1):
+        """error_types() as a small text table: a line per visibility range,
+        the seven types and the three ground-truth counts summed over the
+        categories.  Returned, not printed."""
+        e = self.error_types(iou_thr, bg_thr)
+        cols = e["types"] + ["GT", "missed", "missed_loc"]
+        rows = np.concatenate([e["dt_counts"].sum(1), e["gt_counts"].sum(1)], axis=1)
+        lbl = [e["rng_lbl"][a] if a < len(e["rng_lbl"]) else str(a) for a in range(len(rows))]
+        w = max([len(x) for x in lbl] + [10])
+        lines = [" error types @[ IoU={:0.2f} | bg={:0.2f} ]".format(iou_thr, bg_thr),
+                 " " + " " * w + "".join("{:>11s}".format(c) for c in cols)]
+        for name, r in zip(lbl, rows):
+            lines.append(" " + name.ljust(w) + "".join("{:>11d}".format(int(v)) for v in r))
+        return lines
 
     def _summarize(self, summary_type, iou_thr=None, visibility_rng="all",
                    freq_group_idx=None):
