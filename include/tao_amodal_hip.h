@@ -287,9 +287,14 @@ int taoamd_track_iou_single(int64_t n_dt, const int32_t *dt_group,
  * and then scatters the n_frames frames.  One call per track set (detections,
  * ground truth) into disjoint slot ranges of ONE table whose slot 0 is a far
  * box (reserve it: slot_first = 0 for the first set, its tracks based at 1).
- * `inexact` (optional, int32[1], zeroed by the caller) is set when some box has a
- * coordinate that is not an integer below 2^20 -- with none the per-frame
- * products and their sums are exact and taoamd_track_iou_near has nothing to do. */
+ * `inexact` (optional, int32[1], zeroed by the caller) collects two flags.
+ * Bit 0 is set when some box has a coordinate that is not an integer below
+ * 2^20 -- with none the per-frame products and their sums are exact and
+ * taoamd_track_iou_near has nothing to do.  Bit 1 is set when some box has an
+ * x, y, x + w or y + h that is not a finite number of magnitude below 1e300 (a
+ * NaN or an infinity sets it): the far box is an in-band sentinel, so
+ * taoamd_track_iou_planned is defined only for tables that leave bit 1 clear;
+ * a table that sets it goes to taoamd_track_iou, which takes any double. */
 int taoamd_track_pad(int64_t n_trk, int64_t n_frames, const int32_t *frame_off,
                      const int32_t *frame_pos, const double *frame_box,
                      const int32_t *meta, int64_t slot_first, int64_t n_slots,
@@ -863,6 +868,9 @@ int taoamd_score_at_recall(int64_t n_dt, int32_t n_cat, int32_t n_rng,
  *            an empty set; its argmax = the LOWEST ground-truth row among equal
  *            IoUs;
  *   o      = the same maximum over the other categories.
+ * A bbIou that is NaN (boxes may hold any double) is NO overlap: such a pair
+ * is left out of both maxima and can be no argmax -- a detection whose every
+ * overlap is NaN has s = o = 0 and no argmax.
  * Exactly one type per (detection, range), the first rule that applies:
  *   0 TP       match_gt[d][a * 10 + slot] >= 0 and that ground truth is
  *              evaluated in a

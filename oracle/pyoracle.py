@@ -24,6 +24,7 @@ representable (integer / dyadic coordinates, e.g. all synthetic sets).
 """
 import copy
 import itertools
+import math
 from collections import OrderedDict, defaultdict
 
 import numpy as np
@@ -46,18 +47,34 @@ TIME_LBL = ["all", "short", "medium", "long"]
 
 
 # --------------------------------------------------------------- arithmetic
+def c_fmin(a, b):
+    """C's fmin: the other operand when one is NaN; on numbers what Python's
+    min(a, b) gives, signed zeros included (b only if b < a)."""
+    return b if (b < a or a != a) else a
+
+
+def c_fmax(a, b):
+    """C's fmax, see c_fmin (b only if b > a)."""
+    return b if (b > a or a != a) else a
+
+
 def bb_iou(d, g):
-    """One entry of bbIou with iscrowd=0 (C/maskApi.c:109-120)."""
+    """One entry of bbIou with iscrowd=0 (C/maskApi.c:109-120): fmin / fmax,
+    and a NaN width or height passes ``w <= 0`` as it does in C."""
     da = d[2] * d[3]
     ga = g[2] * g[3]
-    w = min(d[2] + d[0], g[2] + g[0]) - max(d[0], g[0])
+    w = c_fmin(d[2] + d[0], g[2] + g[0]) - c_fmax(d[0], g[0])
     if w <= 0:
         return 0.0
-    h = min(d[3] + d[1], g[3] + g[1]) - max(d[1], g[1])
+    h = c_fmin(d[3] + d[1], g[3] + g[1]) - c_fmax(d[1], g[1])
     if h <= 0:
         return 0.0
     i = w * h
     u = da + ga - i
+    if u == 0:                  # C: 0 / 0 = NaN, x / +-0 = +-inf; no exception
+        if i == 0 or i != i:
+            return float("nan")
+        return math.copysign(float("inf"), i) * math.copysign(1.0, u)
     return i / u
 
 
@@ -79,8 +96,27 @@ def bb_intersect_union(d, g):
     return i, d[2] * d[3] + g[2] * g[3] - i
 
 
-def track_box_iou(dt_track, gt_track, frame_order, timeline):
-    """3D IoU of two {image_id: bbox} maps (T/eval.py:73-96)."""
+def bb_intersect_union_c(d, g):
+    """bb_intersect_union under the two rules of C that the kernels and the C
+    oracle follow where a coordinate is NaN: fmin / fmax return the other
+    operand (Python's max(nan, g) is nan), and a NaN width counts as 0
+    (``w > 0 ? w : 0``; Python's max(nan, 0) is nan).  On finite input the
+    same terms as bb_intersect_union but for the sign of a zero width
+    (max(-0.0, 0) is -0.0), which reaches no sum or ratio."""
+    w = c_fmin(d[0] + d[2], g[0] + g[2]) - c_fmax(d[0], g[0])
+    h = c_fmin(d[1] + d[3], g[1] + g[3]) - c_fmax(d[1], g[1])
+    w = w if w > 0 else 0.0
+    h = h if h > 0 else 0.0
+    i = w * h
+    return i, d[2] * d[3] + g[2] * g[3] - i
+
+
+def track_box_iou(dt_track, gt_track, frame_order, timeline, fired=None):
+    """3D IoU of two {image_id: bbox} maps (T/eval.py:73-96).  The reference
+    asserts ``i <= u``, which fails on ordinary decimal input ((x + w) - x > w
+    by rounding: a box against its own copy) and on NaN.  With ``fired`` (a
+    list) the assert does not raise: the failing (i, u) is appended to it and
+    the function goes on to ``i / u`` as the C oracle and the kernels do."""
     if frame_order == "set":
         image_ids = set(gt_track.keys()) | set(dt_track.keys())
     else:
@@ -99,7 +135,10 @@ def track_box_iou(dt_track, gt_track, frame_order, timeline):
             u += g[2] * g[3]
         elif d:
             u += d[2] * d[3]
-    assert i <= u
+    if fired is None:
+        assert i <= u
+    elif not i <= u:
+        fired.append((i, u))
     return i / u if u > 0 else 0
 
 
@@ -501,12 +540,13 @@ def lvis_lines(results):
 
 
 # ------------------------------------------------------------------- TaoEval
-def tao_eval(gt, preds, frame_order="set", iou_3d_type="3d_iou", use_cats=True):
+def tao_eval(gt, preds, frame_order="set", iou_3d_type="3d_iou", use_cats=True,
+             fired=None):
     """Track-level evaluation (T/tao.py:112-254, T/results.py:27-109,
     T/eval.py:178-276,459-584).  ``preds`` must already have unique track ids
     (the CLI calls make_track_ids_unique first).  ``use_cats=False`` restates
     the class-agnostic mode (T/eval.py:257-260,293-303): one cell per video,
-    no federated filter."""
+    no federated filter.  ``fired``: see track_box_iou."""
     gt = copy.deepcopy(gt)
     preds = copy.deepcopy(preds)
     merge = {m["id"]: c["id"] for c in gt["categories"] if "merged" in c
@@ -628,7 +668,7 @@ def tao_eval(gt, preds, frame_order="set", iou_3d_type="3d_iou", use_cats=True):
             for i, j in np.ndindex(ious.shape):
                 if iou_3d_type == "3d_iou":
                     ious[i, j] = track_box_iou(dmaps[i], gmaps[j], frame_order,
-                                               timeline)
+                                               timeline, fired)
                 elif iou_3d_type == "avg_iou":
                     ious[i, j] = track_avg_iou(dmaps[i], gmaps[j], frame_order,
                                                timeline)

@@ -87,6 +87,27 @@ void orc_bb_iou(const double *dt, const double *gt, size_t m, size_t n,
             o[g * m + d] = box_iou(dt + 4 * d, gt + 4 * g);
 }
 
+/* the same with the iscrowd column of bbIou (maskApi.c:109-120): the union
+ * of a crowd ground truth is the detection's area */
+void orc_bb_iou_crowd(const double *dt, const double *gt, size_t m, size_t n,
+                      const uint8_t *iscrowd, double *o)
+{
+    for (size_t g = 0; g < n; g++)
+        for (size_t d = 0; d < m; d++) {
+            const double *D = dt + 4 * d, *G = gt + 4 * g;
+            double v = 0;
+            double w = fmin(D[2] + D[0], G[2] + G[0]) - fmax(D[0], G[0]);
+            double h = fmin(D[3] + D[1], G[3] + G[1]) - fmax(D[1], G[1]);
+            if (!(w <= 0) && !(h <= 0)) {
+                double i = w * h;
+                double u = iscrowd && iscrowd[g] ? D[2] * D[3]
+                                                 : D[2] * D[3] + G[2] * G[3] - i;
+                v = i / u;
+            }
+            o[g * m + d] = v;
+        }
+}
+
 /* bit r of gt_rng[g]: GT g is ignored in range r; bit r of dt_rng[d]: an
  * unmatched detection d is ignored in range r */
 void orc_lvis_ranges(int64_t n_gt, const double *gt_vis,

@@ -498,7 +498,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                 v = vmem[k];
                 s_iou[wave][lane * GRP_GCAP + k] = v;
             }
-            if (!(v < tmin)) { ncand++; cand = k; vc = v; }
+            // (a NaN counts as two: once it is `best`, no later IoU is below
+            // it, so ANY later ground truth takes the match over, candidate or
+            // not -- the greedy does have a choice to make; sequential loop)
+            if (!(v < tmin)) { ncand += v != v ? 2 : 1; cand = k; vc = v; }
         }
     }
     if (!FUSED) {
@@ -507,7 +510,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     }
     // ---- closed form, lane = detection, for every cell in which no detection
     // has more than one CANDIDATE -- a GT whose IoU reaches the lowest
-    // threshold (a GT below it can never be chosen).  With at most one
+    // threshold (a GT below it can never be chosen, as long as no IoU of the
+    // detection is a NaN: see ncand above).  With at most one
     // candidate per detection the greedy has no choice to make: a detection
     // takes its candidate iff the IoU reaches the threshold and no earlier
     // *consuming* detection of the cell with the same candidate did (whether

@@ -285,16 +285,20 @@ PYSET_HD double set_order_iou(const int64_t *tl_id, const Frames &d, const Frame
         if (kd >= 0 && kg >= 0) {
             const double *D = d.box + 4 * (int64_t)kd, *G = g.box + 4 * (int64_t)kg;
             const double da = D[2] * D[3], ga = G[2] * G[3];
-            // (Python's max(a, b) is b only if b > a, min(a, b) is b only if b < a)
-            const double left = G[0] > D[0] ? G[0] : D[0];
+            // (Python's max(a, b) is b only if b > a, min(a, b) is b only if b < a:
+            // the same bits on numbers, signed zeros included.  Where one
+            // operand is a NaN the rule is C's, as in the kernels that add in
+            // timeline order: fmax / fmin give the other operand, and a NaN
+            // width counts as 0.)
+            const double left = (G[0] > D[0] || D[0] != D[0]) ? G[0] : D[0];
             const double r1 = D[0] + D[2], r2 = G[0] + G[2];
-            const double right = r2 < r1 ? r2 : r1;
-            const double top = G[1] > D[1] ? G[1] : D[1];
+            const double right = (r2 < r1 || r1 != r1) ? r2 : r1;
+            const double top = (G[1] > D[1] || D[1] != D[1]) ? G[1] : D[1];
             const double b1 = D[1] + D[3], b2 = G[1] + G[3];
-            const double bottom = b2 < b1 ? b2 : b1;
+            const double bottom = (b2 < b1 || b1 != b1) ? b2 : b1;
             double w = right - left, h = bottom - top;
-            w = 0.0 > w ? 0.0 : w;
-            h = 0.0 > h ? 0.0 : h;
+            w = (0.0 > w || w != w) ? 0.0 : w;
+            h = (0.0 > h || h != h) ? 0.0 : h;
             i_ = w * h;
             u_ = da + ga - i_;
             return true;

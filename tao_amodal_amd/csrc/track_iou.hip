@@ -219,6 +219,14 @@ __global__ __launch_bounds__(256) void track_iou_single_kernel(
 //           two far boxes give (0, 0), whose addition is exact (u, i >= +0).
 //           So the sequence of roundings equals the reference's walk over the
 //           union of the two tracks' frames in timeline order.
+// DOMAIN.  The far box is an in-band sentinel, so this kernel is only handed
+// tables whose every x, y, x + w, y + h is a finite number of magnitude below
+// TT_FAR: taoamd_track_pad raises bit 1 of its flag otherwise, and the caller
+// then takes the merge kernel, which has no sentinel (a real box at x ==
+// TT_FAR would be taken for an absent frame by the stager's frame mask: wrong
+// pair_frames, wrong avg_iou / imagenetvid).  Inside the domain min(x2, 1e300)
+// = x2 < 1e300 <= max(x1, 1e300), so w = max(negative, 0) = 0 whatever the
+// signs of w and h of the real box, and the terms above are exact.
 // Chunks in which no track of the task has a frame are skipped by the adder;
 // chunks that only hold GT frames add the areas alone.
 #define TT_P 8                   // timeline positions per chunk
@@ -600,7 +608,13 @@ __global__ void track_pad_kernel(int64_t n_frames, int64_t n_trk,
         const bool exact = b.x == rint(b.x) && b.y == rint(b.y) && b.z == rint(b.z) &&
                            b.w == rint(b.w) && fabs(b.x) < lim && fabs(b.y) < lim &&
                            fabs(b.z) < lim && fabs(b.w) < lim;
-        if (!exact && *inexact == 0) atomicOr(inexact, 1);
+        // bit 1: a corner that is not a finite number of magnitude below the far
+        // box's 1e300 (NaN fails the test too): such a table is not for the task
+        // kernel, whose far box stands for "no frame" only among smaller numbers
+        const bool near_ = fabs(b.x) < TT_FAR && fabs(b.y) < TT_FAR &&
+                           fabs(b.x + b.z) < TT_FAR && fabs(b.y + b.w) < TT_FAR;
+        const int32_t f = (exact ? 0 : 1) | (near_ ? 0 : 2);
+        if (f & ~*inexact) atomicOr(inexact, f);
     }
 }
 

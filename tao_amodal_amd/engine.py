@@ -324,9 +324,7 @@ class DeviceProblem:
     def _plan_track_iou(self, flat):
         """Padded frame table + launch plan of taoamd_track_iou_planned."""
         lib = _lib.load()
-        for k in ("tasks", "task_rows", "task_pairs", "task_out", "frames",
-                  "task_base", "trk_meta"):
-            self.t[k] = None
+        self._drop_plan()
         if self.device.type != "cuda":     # host-side plumbing tests: no kernels
             return
         if self.mask_iou:                  # taoamd_track_mask_iou: no plan
@@ -389,8 +387,7 @@ class DeviceProblem:
             n_pieces = 1 + int(task_pieces.sum())
             # (a task's stretch is addressed by 32-bit byte offsets)
             if n_pieces >= 2 ** 31 - 1 or int(task_pieces.max()) * 256 >= 2 ** 32:
-                for k in ("tasks", "task_rows", "task_pairs", "task_out", "trk_meta"):
-                    self.t[k] = None        # (the plan-less kernel takes over)
+                self._drop_plan()           # (the plan-less kernel takes over)
                 return
             self.t["task_base"] = torch.from_numpy(base.astype(np.int32)).to(dev)
             # (+ a margin behind the last piece: a stager lane whose row has no
@@ -405,7 +402,21 @@ class DeviceProblem:
         # integer boxes: frame sums are exact in any order, nothing to guard
         # (products < 2^40, tracks of at most 2^12 frames: every sum < 2^53)
         longest = int((meta[:, 1] - meta[:, 0]).max()) + 1 if len(meta) else 0
-        self.exact_terms = not bool(inexact.item()) and longest <= 4096
+        flags = int(inexact.item())
+        self.exact_terms = not (flags & 1) and longest <= 4096
+        # a corner at or beyond the far box's 1e300, or not finite: the task
+        # kernel's sentinel would not be out of band (the plan-less kernel
+        # takes over: it has none)
+        if flags & 2:
+            self._drop_plan()
+
+    PLAN_TABLES = ("tasks", "task_rows", "task_pairs", "task_out", "frames",
+                   "task_base", "trk_meta")
+
+    def _drop_plan(self):
+        """No launch plan: stage_track_iou takes the plan-less merge kernel."""
+        for k in self.PLAN_TABLES:
+            self.t[k] = None
 
     def guard_active(self):
         """Whether a pass runs the frame-order guard: the count-based
@@ -849,11 +860,28 @@ def guarded_pairs(dp, ws, check_sweep=True):
     return n
 
 
+def _fmax(a, b):
+    """Python's max(a, b) on numbers; where one is a NaN, the other (C's fmax:
+    the rule of the kernels on boxes that are any double)."""
+    return b if (b > a or a != a) else a
+
+
+def _fmin(a, b):
+    return b if (b < a or a != a) else a
+
+
+def _pos(w):
+    """Python's max(w, 0), and 0 for a NaN (C's ``w > 0 ? w : 0``)."""
+    return 0 if (0 > w or w != w) else w
+
+
 def set_order_iou(flat, pairs, mode=0):
     """3D IoU (mode 0) / average IoU (mode 1) of the listed pairs exactly as
     the reference computes them: {image id: box} maps in annotation order, the
     frames visited in the iteration order of
-    ``set(gt.keys()) | set(dt.keys())`` (T/eval.py:73-117)."""
+    ``set(gt.keys()) | set(dt.keys())`` (T/eval.py:73-117).  On a NaN
+    coordinate the per-frame terms follow C (_fmax, _fmin, _pos), as every
+    kernel does: the same bits as Python's max / min on everything else."""
     ioff = np.asarray(flat.cell_iou_off)
     d_off, g_off = np.asarray(flat.cell_dt_off), np.asarray(flat.cell_gt_off)
     tl_id, tl_start = np.asarray(flat.tl_image_id), np.asarray(flat.tl_vid_start)
@@ -886,8 +914,8 @@ def set_order_iou(flat, pairs, mode=0):
         for im in set(gmap.keys()) | set(dmap.keys()):
             g, d = gmap.get(im), dmap.get(im)
             if d and g:
-                w = max(min(d[0] + d[2], g[0] + g[2]) - max(d[0], g[0]), 0)
-                h = max(min(d[1] + d[3], g[1] + g[3]) - max(d[1], g[1]), 0)
+                w = _pos(_fmin(d[0] + d[2], g[0] + g[2]) - _fmax(d[0], g[0]))
+                h = _pos(_fmin(d[1] + d[3], g[1] + g[3]) - _fmax(d[1], g[1]))
                 i_ = w * h
                 u_ = d[2] * d[3] + g[2] * g[3] - i_
                 i += i_

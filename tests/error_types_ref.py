@@ -57,6 +57,7 @@ def error_types(f, match_gt, gt_rng, iou_thrs, slot, tb, n_rng=6):
         if len(G) == 0:
             continue
         iou = orclib.bb_iou(dt_box[D], gt_box[G])
+        iou = np.where(np.isnan(iou), -1.0, iou)   # a NaN overlap is no overlap
         same = dt_cat[D][:, None] == gt_cat[G][None, :]
         for a in range(n_rng):
             ev = ((gt_rng[G] >> np.uint32(a)) & 1) == 0

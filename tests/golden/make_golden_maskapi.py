@@ -4,6 +4,10 @@ mask functions), compiled from the reference source into oracle/_ref by
 
     bb_iou.npz       per case <case>_dt, <case>_gt and <case>_iou (bbIou,
                      iscrowd = 0, column-major as the reference returns it)
+    bb_iou_domain.npz  per population of tests/boxpop.py <kind>_dt [256, 4],
+                     <kind>_gt [96, 4] and <kind>_iou: bbIou on boxes that are
+                     any double (NaN sign and payload in the answers are the
+                     build machine's and no part of the contract)
     rle.json.gz      "poly": polygons on frames with the reference's
                      rleFrPoly / rleToString / rleFrString / rleToBbox /
                      rleArea answers; "merge": mask lists with the union and
@@ -23,6 +27,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
+import boxpop  # noqa: E402
 import orclib  # noqa: E402
 from oracle import rle  # noqa: E402
 
@@ -104,6 +109,12 @@ def main():
         arrays[name + "_dt"], arrays[name + "_gt"] = dt, gt
         arrays[name + "_iou"] = orclib.ref_bb_iou(dt, gt)
     np.savez_compressed(os.path.join(OUT, "bb_iou.npz"), **arrays)
+    arrays = {}
+    for kind in boxpop.KINDS:
+        dt, gt = boxpop.golden_boxes(kind)
+        arrays[kind + "_dt"], arrays[kind + "_gt"] = dt, gt
+        arrays[kind + "_iou"] = orclib.ref_bb_iou(dt, gt)
+    np.savez_compressed(os.path.join(OUT, "bb_iou_domain.npz"), **arrays)
     with gzip.open(os.path.join(OUT, "rle.json.gz"), "wt") as f:
         json.dump(dict(poly=poly_cases(), merge=merge_cases()), f)
     print("wrote", OUT)

@@ -72,21 +72,26 @@ def thresholds():
     return a, b
 
 
-def bb_iou(dt, gt):
+def bb_iou(dt, gt, iscrowd=None):
     dt, gt = _c(dt, np.float64).reshape(-1, 4), _c(gt, np.float64).reshape(-1, 4)
     m, n = len(dt), len(gt)
     o = np.zeros(m * n)
-    lib().orc_bb_iou(_p(dt), _p(gt), C.c_size_t(m), C.c_size_t(n), _p(o))
+    if iscrowd is None:
+        lib().orc_bb_iou(_p(dt), _p(gt), C.c_size_t(m), C.c_size_t(n), _p(o))
+    else:
+        crowd = _c(iscrowd, np.uint8)
+        assert len(crowd) == n
+        lib().orc_bb_iou_crowd(_p(dt), _p(gt), C.c_size_t(m), C.c_size_t(n), _p(crowd), _p(o))
     return o.reshape((m, n), order="F")
 
 
-def ref_bb_iou(dt, gt):
-    """The reference's own compiled bbIou (oracle/_ref), iscrowd = 0."""
+def ref_bb_iou(dt, gt, iscrowd=None):
+    """The reference's own compiled bbIou (oracle/_ref), iscrowd = 0 by default."""
     r = C.CDLL(REF_SO)
     dt, gt = _c(dt, np.float64).reshape(-1, 4), _c(gt, np.float64).reshape(-1, 4)
     m, n = len(dt), len(gt)
     o = np.zeros(m * n)
-    crowd = np.zeros(max(n, 1), dtype=np.uint8)
+    crowd = np.zeros(max(n, 1), dtype=np.uint8) if iscrowd is None else _c(iscrowd, np.uint8)
     r.bbIou(_p(dt), _p(gt), C.c_ulong(m), C.c_ulong(n), _p(crowd), _p(o))
     return o.reshape((m, n), order="F")
 

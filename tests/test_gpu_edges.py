@@ -123,3 +123,61 @@ def test_reference_doctest_boxes_through_the_kernels():
     D.track_id, _ = flatten.make_track_ids_unique(D)
     got = engine.evaluate_flat(flatten.flatten_tao(G, D), detail=True)
     assert np.array_equal(got["iou"], want)
+
+
+def _box_population_inputs(kind):
+    """A small synthetic pair with a population of tests/boxpop.py implanted,
+    as the JSON objects the class API and the Python oracle take."""
+    import boxpop
+    from tao_amodal_amd.synth import synth
+    gt, dt = synth(seed=41, V=3, F=6, C=6, dets_per_frame=8, gt_tracks_per_video=4,
+                   n_present=2, n_neg=1)
+    gtj, predj = gt.to_json(), dt.to_json()
+    rng = np.random.default_rng([41, boxpop.KINDS.index(kind)])
+    g_rows, d_rows = boxpop.implant(gt, dt, kind, rng, gt_share=0.1, dt_share=0.2)
+    assert [a["id"] for a in gtj["annotations"]] == gt.ann_id.tolist()
+    for k in g_rows:
+        gtj["annotations"][k]["bbox"] = gt.ann_bbox[k].tolist()
+    for k in d_rows:
+        predj[k]["bbox"] = dt.bbox[k].tolist()
+    return gtj, predj
+
+
+@pytest.mark.parametrize("kind", ["nonfinite", "flipped"])
+def test_box_populations_through_the_class_api(kind, monkeypatch):
+    """Boxes with NaN / +-inf / -0.0 / 5e-324 coordinates, and boxes with w < 0
+    and h < 0, through LVISEval and TaoEval against the Python oracle.  Image
+    level: pyoracle.bb_iou follows C's fmin / fmax, as the reference's compiled
+    bbIou does.  Track level: the reference's ``assert i <= u`` reports
+    instead of raising, and on the non-finite population the statement takes
+    the two rules of C that are the contract there (pyoracle.
+    bb_intersect_union_c; DESIGN.md, "Box coordinates: the domain")."""
+    from tao_amodal_amd.evaluation.lvis_amodal import LVIS, LVISEval, LVISResults
+    from tao_amodal_amd.evaluation.tao_amodal import Tao, TaoEval, TaoResults
+    gt, pred = _box_population_inputs(kind)
+    lg = LVIS(copy.deepcopy(gt))
+    le = LVISEval(lg, LVISResults(lg, copy.deepcopy(pred)), "bbox")
+    le.run()
+    want = pyoracle.lvis_eval(gt, pred)
+    assert np.array_equal(le.eval["precision"], want["precision"])
+    assert np.array_equal(le.eval["recall"], want["recall"])
+    assert le.result_lines() == want["printed"]
+    assert (want["precision"] > 0).any()
+    if kind == "nonfinite":
+        n_nan = sum(int(np.isnan(np.asarray(c["ious"], dtype=np.float64)).sum())
+                    for c in want["cells"].values())
+        assert n_nan > 0
+        monkeypatch.setattr(pyoracle, "bb_intersect_union", pyoracle.bb_intersect_union_c)
+    p2 = copy.deepcopy(pred)
+    pyoracle.make_track_ids_unique(p2)
+    tg = Tao(copy.deepcopy(gt))
+    te = TaoEval(tg, TaoResults(tg, copy.deepcopy(p2)))
+    te.run()
+    fired = []
+    wt = pyoracle.tao_eval(gt, p2, frame_order="timeline", fired=fired)
+    assert np.array_equal(te.eval["precision"], wt["precision"])
+    assert np.array_equal(te.eval["recall"], wt["recall"])
+    assert te.result_lines() == wt["printed"]
+    assert (wt["precision"] > 0).any()
+    # the reference's assert: silent on boxes no rectangle meets, fired by NaN
+    assert (len(fired) > 0) == (kind == "nonfinite"), len(fired)
