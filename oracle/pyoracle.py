@@ -304,7 +304,7 @@ def masked_mean(s):
 
 
 # ------------------------------------------------------------------ LVISEval
-def lvis_eval(gt, preds, use_cats=True, iou_type="bbox"):
+def lvis_eval(gt, preds, use_cats=True, iou_type="bbox", max_dets=MAX_DETS):
     """Image-level evaluation.  gt: parsed annotation dict; preds: list of
     dicts (a private deep copy is taken).  L/eval.py:59-145, L/lvis.py:38-97,
     L/results.py:10-71.  ``use_cats=False`` restates params.use_cats = 0
@@ -324,7 +324,7 @@ def lvis_eval(gt, preds, use_cats=True, iou_type="bbox"):
     cat_ids = sorted(cats)
     cat_set = set(cat_ids)
 
-    preds = limit_dets_per_image(preds)
+    preds = limit_dets_per_image(preds, max_dets)
     if "bbox" in preds[0]:                       # L/results.py:42-52
         for k, p in enumerate(preds):
             x1, y1, w_, h_ = p["bbox"]
@@ -541,7 +541,7 @@ def lvis_lines(results):
 
 # ------------------------------------------------------------------- TaoEval
 def tao_eval(gt, preds, frame_order="set", iou_3d_type="3d_iou", use_cats=True,
-             fired=None):
+             fired=None, max_dets=MAX_DETS):
     """Track-level evaluation (T/tao.py:112-254, T/results.py:27-109,
     T/eval.py:178-276,459-584).  ``preds`` must already have unique track ids
     (the CLI calls make_track_ids_unique first).  ``use_cats=False`` restates
@@ -574,7 +574,7 @@ def tao_eval(gt, preds, frame_order="set", iou_3d_type="3d_iou", use_cats=True,
     for p in preds:
         assert seen.setdefault(p["track_id"], p["video_id"]) == \
             p["video_id"], "Track id appears in more than one video"
-    preds = limit_dets_per_image(preds)
+    preds = limit_dets_per_image(preds, max_dets)
     dt_tracks = OrderedDict()
     for k, p in enumerate(preds):
         t = dt_tracks.setdefault(p["track_id"], {

@@ -436,9 +436,11 @@ def flatten_lvis(gt: GTColumns, dt: DTColumns, max_dets=MAX_DETS,
         raise AssertionError("Results do not correspond to current LVIS set.")
     # area = w * h of the box (L/results.py:51); results that come as masks
     # only bring the mask's area instead (L/results.py:56, DTColumns.area)
-    d_area = (dt.bbox[:, 2] * dt.bbox[:, 3])[keep] \
-        if getattr(dt, "area", None) is None else \
-        np.asarray(dt.area, dtype=np.float64)[keep]
+    # (w * h may overflow to inf, which the area filter then drops: no warning)
+    with np.errstate(over="ignore"):
+        d_area = (dt.bbox[:, 2] * dt.bbox[:, 3])[keep] \
+            if getattr(dt, "area", None) is None else \
+            np.asarray(dt.area, dtype=np.float64)[keep]
 
     # ---- detection selection + federated filter
     d_cat = _lookup(cat_ids, d_catid)
@@ -834,9 +836,11 @@ def flatten_tao(gt: GTColumns, dt: DTColumns, max_dets=MAX_DETS,
         raise AssertionError("Results do not correspond to current Tao set.")
     # area = w * h of the box (L/results.py:51); results that come as masks
     # only bring the mask's area instead (L/results.py:56, DTColumns.area)
-    d_area = (dt.bbox[:, 2] * dt.bbox[:, 3])[keep] \
-        if getattr(dt, "area", None) is None else \
-        np.asarray(dt.area, dtype=np.float64)[keep]
+    # (w * h may overflow to inf, which the area filter then drops: no warning)
+    with np.errstate(over="ignore"):
+        d_area = (dt.bbox[:, 2] * dt.bbox[:, 3])[keep] \
+            if getattr(dt, "area", None) is None else \
+            np.asarray(dt.area, dtype=np.float64)[keep]
     # track score over *all* kept boxes of the track (T/results.py:88-98)
     trk_score = np.empty(len(u))
     by_trk = np.argsort(inv, kind="stable")

@@ -29,6 +29,11 @@ F10 scores that are any double (two videos x 6 frames x 3 categories): logits
     category whose best detection scores exactly 0.0 and one whose best scores
     -1.0 (the markers of eval["scores"]).  No image is over 300 detections:
     the order sorted() gives a list that holds NaNs is no rule to restate
+F11 prediction-side rules (tests/predrules.py, every motif once): several
+    boxes of a track on one image, boxes that vote in the track score and count
+    for nothing else, equal track scores ordered by the visiting order of the
+    images, track ids 0, 2^31 and 2^40.  Built for max_dets 8 and evaluated by
+    the CLI at 300; make_golden_predrules.py records the class API at 3 and 8
 """
 import os
 import sys
@@ -36,6 +41,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", ".."))
+sys.path.insert(1, os.path.join(os.path.dirname(__file__), ".."))
 from tao_amodal_amd.synth import synth  # noqa: E402
 
 
@@ -593,8 +599,14 @@ def f10():
     return gt, preds
 
 
+def f11():
+    import predrules
+    s = predrules.sized(max_dets=8, wide=True)
+    return s.gt, s.preds
+
+
 ALL = {"f1": f1, "f2": f2, "f3": f3, "f4": f4, "f5": f5, "f7": f7, "f8": f8,
-       "f9": f9, "f10": f10}
+       "f9": f9, "f10": f10, "f11": f11}
 # big fixtures: inputs stored gzipped, image level reduced to the integer
 # match counts + precision / recall + results + text (make_golden.py)
 LITE = {"f8"}

@@ -20,6 +20,11 @@ DECIMAL_SCALE_FIXTURES = ["f8"]
 # (integer boxes).  Its lists of scores hold NaN: compare them with
 # same_numbers(), not with ==
 SCORE_FIXTURES = ["f10"]
+# prediction-side rules of the table build (tests/predrules.py): duplicate
+# boxes of a track on one image, boxes that only vote, ties in visiting order,
+# wide track ids.  predrules.npz / .json.gz next to it: the reference's class
+# API on the same motifs under max_dets 3 and 8 (make_golden_predrules.py)
+PRED_RULE_FIXTURES = ["f11"]
 
 
 def same_numbers(a, b):

@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 
 import orclib
-from goldenio import FIXTURES, INTEGER_FIXTURES, SCORE_FIXTURES, load_eval, load_inputs, \
+from goldenio import FIXTURES, INTEGER_FIXTURES, PRED_RULE_FIXTURES, SCORE_FIXTURES, \
+    load_eval, load_inputs, \
     load_json_gz, path, same_number_dicts, same_numbers
 from tao_amodal_amd.columns import DTColumns, GTColumns
 from tao_amodal_amd import flatten as fl
@@ -80,7 +81,7 @@ def _check_side(f, out, want, unit_ids, sentinel, exact_iou=True):
     assert have == {(int(k), int(r)) for k, r in zip(*np.nonzero(out["num_gt"]))}
 
 
-@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES + PRED_RULE_FIXTURES)
 def test_lvis_flatten_and_c_oracle(name):
     gtj, predj = load_inputs(name)
     want = load_json_gz(name, "lvis.json.gz")
@@ -93,7 +94,7 @@ def test_lvis_flatten_and_c_oracle(name):
     assert np.array_equal(out["recall"], r)
 
 
-@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES + PRED_RULE_FIXTURES)
 def test_tao_flatten_and_c_oracle(name):
     gtj, predj = load_inputs(name)
     want = load_json_gz(name, "tao.json.gz")
@@ -106,7 +107,7 @@ def test_tao_flatten_and_c_oracle(name):
     assert same_number_dicts({str(k): v for k, v in f.track_scores.items()},
                              want["track_scores"])
     out = orclib.run_flat(f)
-    exact = name in INTEGER_FIXTURES + SCORE_FIXTURES
+    exact = name in INTEGER_FIXTURES + SCORE_FIXTURES + PRED_RULE_FIXTURES
     _check_side(f, out, want, f.vid_ids, -1, exact_iou=exact)
     p, r = load_eval(name)["tao"]
     assert np.array_equal(out["precision"].reshape(p.shape), p)

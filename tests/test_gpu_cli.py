@@ -8,7 +8,8 @@ import contextlib
 import numpy as np
 import pytest
 
-from goldenio import FIXTURES, INTEGER_FIXTURES, SCORE_FIXTURES, load_eval, load_json_gz, path
+from goldenio import FIXTURES, INTEGER_FIXTURES, PRED_RULE_FIXTURES, SCORE_FIXTURES, \
+    load_eval, load_json_gz, path
 from test_oracle_golden import _check_cells
 
 pytestmark = pytest.mark.gpu
@@ -23,7 +24,7 @@ def _cli():
     return m
 
 
-@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES + PRED_RULE_FIXTURES)
 def test_cli_text_is_identical_to_the_reference(name, tmp_path):
     log = tmp_path / "out" / "eval.log"
     buf = io.StringIO()
@@ -67,7 +68,7 @@ def test_class_api_state_matches_reference(name):
     assert ev.eval["dt_pointers"][0][0] == {} or (0, 0) in ptr
 
 
-@pytest.mark.parametrize("name", ["f1", "f2", "f9"])
+@pytest.mark.parametrize("name", ["f1", "f2", "f9"] + PRED_RULE_FIXTURES)
 def test_tao_class_api_state_matches_reference(name):
     import json
     from tao_amodal_amd import flatten
@@ -90,7 +91,7 @@ def test_tao_class_api_state_matches_reference(name):
             if es[0] is None:
                 continue
             cells[vid, cat] = {"ious": ev.ious[vid, cat], "ranges": es}
-    _check_cells(cells, want["cells"], exact_iou=name in INTEGER_FIXTURES)
+    _check_cells(cells, want["cells"], exact_iou=name in INTEGER_FIXTURES + PRED_RULE_FIXTURES)
     for p_ in want["dt_pointers"]:
         k, a, t = p_["idx"]
         g = ev.eval["dt_pointers"][k][a][t]
@@ -201,7 +202,7 @@ def test_cli_serial_switch_gives_the_same_text(tmp_path, monkeypatch):
     assert got == open(path("f5", "cli_log.txt")).read()
 
 
-@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES + PRED_RULE_FIXTURES)
 def test_cli_text_with_the_prediction_file_read_on_the_device(name, tmp_path, monkeypatch):
     """The reference's text again with the device-side reader taking files of
     any size (csrc/json_ingest.hip; by default from 32 MB on): columns that

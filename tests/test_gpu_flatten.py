@@ -7,7 +7,7 @@ import pytest
 
 import orclib
 import scorepop
-from goldenio import FIXTURES, SCORE_FIXTURES, load_inputs, same_number_dicts
+from goldenio import FIXTURES, PRED_RULE_FIXTURES, SCORE_FIXTURES, load_inputs, same_number_dicts
 from tao_amodal_amd import flatten as fl
 from tao_amodal_amd.columns import DTColumns, GTColumns
 from tao_amodal_amd.synth import synth
@@ -45,7 +45,7 @@ def _lvis_both(gt, dt, max_dets=300):
     assert np.array_equal(res["recall"], ref["recall"])
 
 
-@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES + PRED_RULE_FIXTURES)
 def test_lvis_device_tables_equal_the_numpy_tables_on_the_fixtures(name):
     gtj, predj = load_inputs(name)
     _lvis_both(GTColumns.from_json(gtj), DTColumns.from_json(predj))
@@ -95,7 +95,7 @@ def _tao_both(gt, dt, max_dets=300):
     assert np.array_equal(res["recall"], ref["recall"])
 
 
-@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES + PRED_RULE_FIXTURES)
 def test_tao_device_tables_equal_the_numpy_tables_on_the_fixtures(name):
     gtj, predj = load_inputs(name)
     _tao_both(GTColumns.from_json(gtj), DTColumns.from_json(predj))

@@ -8,7 +8,8 @@ import exchange_ref
 import orclib
 import scorepop
 import wsguard
-from goldenio import FIXTURES, INTEGER_FIXTURES, SCORE_FIXTURES, load_eval, load_inputs, \
+from goldenio import FIXTURES, INTEGER_FIXTURES, PRED_RULE_FIXTURES, SCORE_FIXTURES, \
+    load_eval, load_inputs, \
     load_json_gz, path
 from test_flat_oracle_golden import _check_side
 from tao_amodal_amd import flatten as fl
@@ -47,7 +48,7 @@ def _compare_with_oracle(f, got, detail=True, equal_nan=False):
     assert np.array_equal(got["recall"], want["recall"])
 
 
-@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES + PRED_RULE_FIXTURES)
 def test_lvis_hip_matches_reference_golden(name):
     gtj, predj = load_inputs(name)
     want = load_json_gz(name, "lvis.json.gz")
@@ -60,7 +61,7 @@ def test_lvis_hip_matches_reference_golden(name):
     _compare_with_oracle(f, got)
 
 
-@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + SCORE_FIXTURES + PRED_RULE_FIXTURES)
 def test_tao_hip_matches_reference_golden(name):
     gtj, predj = load_inputs(name)
     want = load_json_gz(name, "tao.json.gz")
@@ -69,7 +70,8 @@ def test_tao_hip_matches_reference_golden(name):
     f = fl.flatten_tao(GTColumns.from_json(gtj), dt)
     got = _engine().evaluate_flat(f, detail=True)
     _check_side(f, got, want, f.vid_ids, -1,
-                exact_iou=name in INTEGER_FIXTURES + SCORE_FIXTURES)
+                exact_iou=name in INTEGER_FIXTURES + SCORE_FIXTURES
+                + PRED_RULE_FIXTURES)
     p, r = load_eval(name)["tao"]
     assert np.array_equal(got["precision"].reshape(p.shape), p)
     assert np.array_equal(got["recall"].reshape(r.shape), r)

@@ -3,7 +3,8 @@ import numpy as np
 import pytest
 
 from goldenio import (ADVERSARIAL_FIXTURES, DECIMAL_SCALE_FIXTURES, FIXTURES,
-                      INTEGER_FIXTURES, SCORE_FIXTURES, load_eval, load_inputs, load_json_gz,
+                      INTEGER_FIXTURES, PRED_RULE_FIXTURES, SCORE_FIXTURES, load_eval,
+                      load_inputs, load_json_gz,
                       same_number_dicts, same_numbers)
 from oracle import pyoracle
 
@@ -48,7 +49,8 @@ def _check_results(got, want):
         assert float(gv) == wv, k
 
 
-@pytest.mark.parametrize("name", FIXTURES + ADVERSARIAL_FIXTURES + SCORE_FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + ADVERSARIAL_FIXTURES + SCORE_FIXTURES
+                         + PRED_RULE_FIXTURES)
 def test_lvis_oracle_matches_reference(name):
     gt, pred = load_inputs(name)
     want = load_json_gz(name, "lvis.json.gz")
@@ -64,7 +66,8 @@ def test_lvis_oracle_matches_reference(name):
     assert got["freq_groups"] == want["freq_groups"]
 
 
-@pytest.mark.parametrize("name", FIXTURES + ADVERSARIAL_FIXTURES + SCORE_FIXTURES)
+@pytest.mark.parametrize("name", FIXTURES + ADVERSARIAL_FIXTURES + SCORE_FIXTURES
+                         + PRED_RULE_FIXTURES)
 def test_tao_oracle_matches_reference(name):
     gt, pred = load_inputs(name)
     want = load_json_gz(name, "tao.json.gz")
