@@ -927,6 +927,100 @@ int taoamd_error_types(int64_t n_dt, int64_t n_gt, int32_t n_img, int32_t n_cat,
                        uint8_t *dt_type, void *workspace, size_t workspace_bytes,
                        void *stream);
 
+/* ---- track-level error breakdown per range (csrc/track_error_types.hip) ------------
+ * WHY a detection track is no true positive, per (area, time) range and
+ * category: the section above, rule for rule, on the track tables.  The
+ * definition is this library's.  Track level, boxes, the 3d_iou metric (mode 0
+ * of taoamd_track_iou) only.
+ *
+ * One call = one IoU threshold slot (tf = min(iou_thrs[slot], 1 - 1e-10)), one
+ * background threshold bg_thr = tb with 0 <= tb < tf, and all n_rng <=
+ * TAOAMD_TAO_RNG ranges at once (the reference constants give 20, slot = area
+ * index * 4 + time index as taoamd_tao_ranges writes them; the last area slot
+ * is "highly-and-partially-occluded").  Rows are the detection tracks of the
+ * use_cats = 1 track table (after the max_dets cut and the federated filter);
+ * ground truths are the ground-truth tracks.  For detection track d (video v,
+ * category c) and range a:
+ *   E_a(v) = the ground-truth tracks of video v, of ANY category, whose gt_rng
+ *            bit a is clear;
+ *   s      = the maximum over g in E_a(v) of category c of the pass's own IoU,
+ *            iou[cell_iou_off[cell] + d_local * G + g_local] -- the matrix the
+ *            match read, the frame-order guard's patches included -- 0 for an
+ *            empty set; its argmax = the LOWEST ground-truth row among equal
+ *            IoUs.  Taken from that matrix, an unmatched row with s >= tf
+ *            always points at a ground truth another detection holds;
+ *   o      = the same maximum over g in E_a(v) of the other categories, of the
+ *            IoU the plan-less taoamd_track_iou gives the pair: i and u added
+ *            over the union of the two tracks' frames in ascending timeline
+ *            order (a frame both have adds i_ and u_, a frame only one has
+ *            adds that box's w * h to u), u > 0 ? i / u : 0.  No frame-order
+ *            guard here: there is no reference counterpart whose set order
+ *            could matter.
+ * An IoU that is NaN (boxes may hold any double) is NO overlap, as above.
+ * Exactly one type per (detection track, range), the first rule that applies:
+ *   0 TP       match_gt[d][a * 10 + slot] >= 0 and that ground truth is
+ *              evaluated in a
+ *   1 IGNORED  matched to a ground truth ignored in a, or unmatched with bit a
+ *              of dt_rng[d] set (the image level tests the flag alone; dt_rng
+ *              holds the not-exhaustive flag AND the area / length windows)
+ *   2 DUP      unmatched, s >= tf
+ *   3 LOC      unmatched, tb <= s < tf
+ *   4 CLS      unmatched, o >= tf
+ *   5 BOTH     unmatched, tb <= o < tf
+ *   6 BKG      otherwise
+ * Per (ground-truth track, range) with the gt_rng bit clear: `evaluated`,
+ * `missed` (no detection's match_gt names it at (a, slot)), `missed_loc` (a
+ * missed one that is the same-category argmax of at least one LOC detection of
+ * range a).  The table follows match_gt, the in-cell index: a ground truth that
+ * carries TAOAMD_GT_ID_HIDDEN and holds a detection counts as TP / not missed
+ * here, whereas the sweep (the reference's dt_m == 0) sees that detection as
+ * unmatched.
+ *
+ *   dt_cat, dt_rng   columns of the track table / of taoamd_tao_ranges, n_dt rows
+ *   dt_group    int32[n_dt][4] {first ground-truth row of the row's cell (match_gt
+ *               counts from it), ground truths of the cell G, the row's place in
+ *               its cell d_local, the cell}
+ *   cell_iou_off int64[n_cells + 1], iou double[n_iou]: the pass's IoU matrix
+ *   match_gt    int32, row d at match_gt + d * match_stride (>= n_rng * 10
+ *               elements), identity order: what taoamd_match writes
+ *   gt_cat, gt_rng   columns of the ground-truth tracks, n_gt rows
+ *   *_frame_off, *_frame_pos, *_frame_box: the tracks' CSR frame lists of
+ *               taoamd_track_iou (positions strictly ascending within a track)
+ *   vid_gt_off  int32[n_vid + 1], vid_gt int32[n_gt]: the ground-truth rows of
+ *               each video (the table is category-major: they are not
+ *               contiguous); vid_dt_off, vid_dt: the same for the detection rows
+ * Outputs (zeroed by the call): dt_counts int64[n_rng][n_cat][7], gt_counts
+ * int64[n_rng][n_cat][3] = {evaluated, missed, missed_loc}, and, if not NULL,
+ * dt_type uint8[n_dt][n_rng] in the table's row order and dt_over
+ * uint32[n_dt][2], the cross-category result alone: bit a of word 0 = o >= tf
+ * in range a, bit a of word 1 = o >= tb in range a (with tb = 0 every bit below
+ * n_rng: the empty maximum is 0).  No (detection track x ground-truth track)
+ * matrix is stored: a pair's IoU is folded into the two masks when it is known.
+ * TAOAMD_ERR_ARG: slot outside [0, 10), bg_thr outside [0, tf), n_rng outside
+ * [1, TAOAMD_TAO_RNG]; TAOAMD_ERR_WORKSPACE: fewer bytes than
+ * taoamd_track_error_types_workspace(n_dt, n_gt, n_rng) (the two masks per row
+ * and two byte tables [n_rng][n_gt]; any base address, contents need not be
+ * initialised).  Rows named by the CSR lists, by dt_group or by match_gt that
+ * lie outside the tables are skipped, never dereferenced: such a ground truth
+ * is in no E_a, such a match counts as none, a detection row no video lists
+ * has o = 0. */
+#define TAOAMD_TRACK_ERROR_TYPES_TILE 16    /* ground-truth tracks staged per step */
+size_t taoamd_track_error_types_workspace(int64_t n_dt, int64_t n_gt, int32_t n_rng);
+int taoamd_track_error_types(int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou,
+                             int32_t n_vid, int32_t n_cat, int32_t n_rng, int32_t slot,
+                             double bg_thr, const int32_t *dt_cat, const uint32_t *dt_rng,
+                             const int32_t *dt_group, const int64_t *cell_iou_off,
+                             const double *iou, const int32_t *match_gt, int64_t match_stride,
+                             const int32_t *gt_cat, const uint32_t *gt_rng,
+                             const int32_t *dt_frame_off, const int32_t *dt_frame_pos,
+                             const double *dt_frame_box, const int32_t *gt_frame_off,
+                             const int32_t *gt_frame_pos, const double *gt_frame_box,
+                             const int32_t *vid_gt_off, const int32_t *vid_gt,
+                             const int32_t *vid_dt_off, const int32_t *vid_dt,
+                             int64_t *dt_counts, int64_t *gt_counts, uint8_t *dt_type,
+                             uint32_t *dt_over, void *workspace, size_t workspace_bytes,
+                             void *stream);
+
 /* ---- multi-GPU result exchange (category-partitioned evaluation) -------------------
  * No reference counterpart (the reference is single-process); these carry the
  * tables of taoamd_accumulate_compact between ranks and end in the layout of

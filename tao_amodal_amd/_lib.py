@@ -20,6 +20,7 @@ LVIS_RNG, TAO_RNG = 6, 20
 MAX_GT_PER_CELL = 3072
 SEGMENT_TILE = 2816
 ERROR_TYPES_TILE = 256
+TRACK_ERROR_TYPES_TILE = 16
 ERROR_TYPES = ("TP", "IGNORED", "DUP", "LOC", "CLS", "BOTH", "BKG")
 
 _vp, _i64, _i32, _sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
@@ -183,6 +184,11 @@ SIGNATURES = {
     "taoamd_error_types": (C.c_int, [_i64, _i64, _i32, _i32, _i32, _i32, C.c_double,
                                      _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "taoamd_track_error_types_workspace": (_sz, [_i64, _i64, _i32]),
+    "taoamd_track_error_types": (C.c_int, [_i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
+                                           C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1087,6 +1087,63 @@ def stage_error_types(dp, ws, slot, tb, per_detection=False):
         _ptr(ws.err_ws), ws.err_bytes, s), "taoamd_error_types")
 
 
+def stage_track_error_types(dp, ws, slot, tb, per_detection=False):
+    """Track-level error breakdown of the pass the workspace holds (after
+    stage_ranges .. stage_match): ws.err_dt_counts[n_rng, n_cat, 7],
+    ws.err_gt_counts[n_rng, n_cat, 3] and, with `per_detection`,
+    ws.err_dt_type[n_dt, n_rng] (taoamd_track_error_types; the definition is in
+    include/tao_amodal_hip.h) at IoU threshold slot `slot` of the calling
+    thread's thresholds and background threshold `tb`.  The same-category IoUs
+    are ws.iou of the pass, the frame-order guard's patches included; the
+    cross-category ones are computed here and never stored.  The per-video row
+    lists are built once per problem; the match indices come from the
+    workspace's own table (detail mode), else from error_match_gt() (800 bytes
+    a row), filled here by one more match unless the caller's match already
+    wrote it.  Buffers are allocated on the first call."""
+    if dp.kind != "tao" or dp.mask_iou:
+        raise _lib.TaoAmdError("the track-level error breakdown is the track level's, on boxes")
+    if dp.iou_mode != 0:
+        raise _lib.TaoAmdError("the track-level error breakdown is defined for the 3d_iou metric")
+    if dp.cell_unit_host is None:
+        raise _lib.TaoAmdError("the error breakdown needs the cells' videos (flat.cell_unit)")
+    lib, t, s = _lib.load(), dp.t, _stream()
+    dev = dp.device
+    if getattr(dp, "err_tabs", None) is None:
+        cell_unit = torch.from_numpy(np.ascontiguousarray(dp.cell_unit_host, dtype=np.int64)
+                                     ).to(dev)
+        n_vid = int(dp.cell_unit_host.max()) + 1 if dp.n_cells else 0
+        cells = torch.arange(dp.n_cells, dtype=torch.int64, device=dev)
+        gt_cell = torch.repeat_interleave(
+            cells, (t["cell_gt_off"][1:] - t["cell_gt_off"][:-1]).long())
+        dt_cell = t["dt_cell"][:dp.n_dt].long()
+        dp.err_tabs = (n_vid,) + _rows_by_unit(cell_unit[gt_cell], n_vid) \
+            + _rows_by_unit(cell_unit[dt_cell], n_vid)
+    n_vid, vid_gt_off, vid_gt, vid_dt_off, vid_dt = dp.err_tabs
+    if getattr(ws, "err_dt_counts", None) is None:
+        ws.err_bytes = lib.taoamd_track_error_types_workspace(dp.n_dt, dp.n_gt, dp.n_rng)
+        ws.err_ws = torch.empty(max(int(ws.err_bytes), 256), dtype=torch.uint8, device=dev)
+        ws.err_dt_counts = torch.empty((dp.n_rng, dp.n_cat, 7), dtype=torch.int64, device=dev)
+        ws.err_gt_counts = torch.empty((dp.n_rng, dp.n_cat, 3), dtype=torch.int64, device=dev)
+        ws.err_dt_type = None
+    match_gt = ws.match_gt
+    if match_gt is None:
+        if getattr(ws, "err_match_gt", None) is None and dp.n_dt:
+            stage_match(dp, ws, scatter=not ws.cell_order, match_gt=error_match_gt(dp, ws))
+        match_gt = getattr(ws, "err_match_gt", None)
+    if per_detection and ws.err_dt_type is None:
+        ws.err_dt_type = torch.empty((max(dp.n_dt, 1), dp.n_rng), dtype=torch.uint8, device=dev)
+    _lib.check(lib.taoamd_track_error_types(
+        dp.n_dt, dp.n_gt, dp.n_cells, dp.n_iou, n_vid, dp.n_cat, dp.n_rng, int(slot), float(tb),
+        _ptr(t["dt_cat"]), _ptr(ws.dt_rng), _ptr(t["dt_group"]), _ptr(t["cell_iou_off"]),
+        _ptr(ws.iou), _ptr(match_gt), dp.n_rng * N_THR, _ptr(t["gt_cat"]), _ptr(ws.gt_rng),
+        _ptr(t["dt_frame_off"]), _ptr(t["dt_frame_pos"]), _ptr(t["dt_frame_box"]),
+        _ptr(t["gt_frame_off"]), _ptr(t["gt_frame_pos"]), _ptr(t["gt_frame_box"]),
+        _ptr(vid_gt_off), _ptr(vid_gt), _ptr(vid_dt_off), _ptr(vid_dt),
+        _ptr(ws.err_dt_counts), _ptr(ws.err_gt_counts),
+        _ptr(ws.err_dt_type) if per_detection else None, None,
+        _ptr(ws.err_ws), ws.err_bytes, s), "taoamd_track_error_types")
+
+
 def stage_track_iou_guarded(dp, ws):
     stage_track_iou(dp, ws)
     stage_iou_guard(dp, ws)

@@ -243,13 +243,15 @@ class GpuRun:
     def error_table(self, thr_index, bg_thr, per_detection=False):
         """(dt_counts[n_rng, K, 7], gt_counts[n_rng, K, 3], dt_type[n_dt, n_rng]
         or None) at the caller's `thr_index`-th IoU threshold, ranges in the
-        caller's order (engine.stage_error_types; the definition is in
-        include/tao_amodal_hip.h), from the pass the workspace holds after
+        caller's order (engine.stage_error_types at the image level,
+        engine.stage_track_error_types at the track level; the definitions are
+        in include/tao_amodal_hip.h), from the pass the workspace holds after
         evaluate()."""
         c = self.constants
-        if self.flat.kind != "lvis":
+        track = self.flat.kind == "tao"
+        if track and self.iou_3d_type != "3d_iou":
             raise NotImplementedError(
-                "error_types() at the track level: its IoU exists per (video, category) only")
+                "error_types() with iou_3d_type=%r: defined for '3d_iou'" % self.iou_3d_type)
         if self.dp.mask_iou:
             raise NotImplementedError("error_types() with iou_type='segm': boxes only")
         if not self.flat.get("use_cats", True):
@@ -270,7 +272,8 @@ class GpuRun:
                               head=not self._head_done,
                               match_gt=e.error_match_gt(self.dp, self.ws))
                 self._head_done = self._error_pass = True
-            e.stage_error_types(self.dp, self.ws, slot, bg_thr, per_detection)
+            stage = e.stage_track_error_types if track else e.stage_error_types
+            stage(self.dp, self.ws, slot, bg_thr, per_detection)
             self.torch.cuda.synchronize(self.device)
         with timed("download"):
             dt_counts = self.ws.err_dt_counts.cpu().numpy()

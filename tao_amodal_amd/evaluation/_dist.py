@@ -420,8 +420,8 @@ class DistRun:
 
     def error_table(self, thr_index, bg_thr, per_detection=False):
         raise NotImplementedError(
-            "error_types() in a multi-GPU run: an image's ground truths of other "
-            "categories live on other ranks")
+            "error_types() in a multi-GPU run: an image's (a video's) ground truths of "
+            "other categories live on other ranks")
 
     def pointer_tables(self):
         if self._pointers is None:

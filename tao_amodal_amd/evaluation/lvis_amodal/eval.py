@@ -278,10 +278,9 @@ class LVISEval:
 
         The table follows the match itself: a detection matched to a ground
         truth whose id is 0 counts as TP here, whereas accumulate(), like the
-        reference (dt_m == 0), sees it as unmatched.  Not available: the track
-        level (its IoU exists per (video, category) only), iou_type="segm",
-        use_cats = 0, more than one block of edited constants, multi-GPU
-        runs."""
+        reference (dt_m == 0), sees it as unmatched.  Not available:
+        iou_type="segm", use_cats = 0, more than one block of edited constants,
+        multi-GPU runs.  The track level has its own, TaoEval.error_types()."""
         if self._run is None:
             raise RuntimeError("Please run evaluate() first.")
         P = self.params

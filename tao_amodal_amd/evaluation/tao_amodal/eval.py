@@ -110,6 +110,7 @@ class TaoEval:
         self.flat = self.tao_dt.flat
         self._run = None
         self._cat_pos = None
+        self._error_types = {}
 
     # ------------------------------------------------------------ stages
     def evaluate(self, show_progress=False):
@@ -163,6 +164,7 @@ class TaoEval:
         else:
             self._run = GpuRun(flat, self.device, self.params.iou_3d_type,
                                constants=constants)
+        self._error_types = {}
         self._run.evaluate()
         P = self.params
         rngs = [(a, t) for a in P.area_rng for t in P.time_rng]
@@ -277,6 +279,89 @@ class TaoEval:
         cats = P.cat_ids if P.use_cats else [-1]
         return operating_points(self.eval["scores"][..., aidx, tidx], P.iou_thrs,
                                 P.rec_thrs, cats, iou_thr, recall)
+
+    def error_types(self, iou_thr=0.5, bg_thr=0.1, per_detection=False):
+        """Why a detection track is no true positive, per (area, time) range
+        and category, at the IoU threshold `iou_thr` (one of params.iou_thrs;
+        the foreground threshold tf = min(iou_thr, 1 - 1e-10)) and the
+        background threshold `bg_thr` (0 <= bg_thr < tf): LVISEval.error_types()
+        rule for rule on tracks and their 3D IoU.  No counterpart in the
+        reference.  Callable after evaluate(), computed on the device on request
+        (csrc/track_error_types.hip), cached per (iou_thr, bg_thr).
+
+        Rows are the detection tracks that survived the max_dets cut and the
+        federated filter.  With s the largest 3D IoU of a track with the
+        ground-truth tracks of ITS category in its video that the range
+        evaluates (0 if none; taken from the IoU matrix the match read) and o
+        the same over the video's other categories, a (track, range) pair is
+        the first of: TP (matched to an evaluated ground truth), IGNORED
+        (matched to an ignored one, or unmatched and itself outside the range:
+        a not-exhaustive category, or an area / length outside the range's
+        windows), DUP (unmatched, s >= tf: the ground truth is held by another
+        track), LOC (bg_thr <= s < tf), CLS (o >= tf), BOTH (bg_thr <= o < tf),
+        BKG.  Per evaluated ground-truth track: `evaluated`, `missed` (no
+        detection track is matched to it), `missed_loc` (missed, and the best
+        same-category ground truth -- the first in table order among equal
+        IoUs -- of at least one LOC track).
+
+        Returns {"types": the 7 names, "dt_counts": int64[n_rng, K, 7],
+        "gt_counts": int64[n_rng, K, 3], "rng_lbl": the (area label, time
+        label) of every range} with n_rng = areas x durations in the order of
+        eval["precision"]'s last two axes flattened, the category axis in the
+        order of params.cat_ids, and with per_detection=True "dt_type": (ids,
+        types) = the rows' track ids and uint8[n, n_rng].
+
+        The table follows the match itself: a track matched to a ground truth
+        whose id is the "unmatched" sentinel counts as TP here, whereas
+        accumulate(), like the reference, sees it as unmatched.  Not available:
+        iou_type="segm", use_cats = 0, an iou_3d_type other than "3d_iou", more
+        than one block of edited constants, multi-GPU runs."""
+        if self._run is None:
+            raise RuntimeError("Please run evaluate() first.")
+        P = self.params
+        at = np.where(iou_thr == np.asarray(P.iou_thrs))[0]
+        if len(at) == 0:
+            raise ValueError("iou_thr: {} is not one of params.iou_thrs".format(iou_thr))
+        tf = min(float(np.asarray(P.iou_thrs)[at[0]]), 1 - 1e-10)
+        if not 0 <= bg_thr < tf:
+            raise ValueError("bg_thr: {} is not in [0, {})".format(bg_thr, tf))
+        key = (int(at[0]), float(bg_thr))
+        hit = self._error_types.get(key)
+        if hit is None or (per_detection and "dt_type" not in hit):
+            dt_counts, gt_counts, dt_type = self._run.error_table(
+                key[0], key[1], per_detection)
+            if self._cat_pos is not None:
+                dt_counts = np.ascontiguousarray(dt_counts[:, self._cat_pos])
+                gt_counts = np.ascontiguousarray(gt_counts[:, self._cat_pos])
+            from ..._lib import ERROR_TYPES
+
+            def lbl(names, i):
+                return names[i] if i < len(names) else str(i)
+            hit = {"types": list(ERROR_TYPES), "dt_counts": dt_counts,
+                   "gt_counts": gt_counts,
+                   "rng_lbl": [(lbl(P.area_rng_lbl, a), lbl(P.time_rng_lbl, t))
+                               for a in range(len(P.area_rng))
+                               for t in range(len(P.time_rng))]}
+            if per_detection:
+                hit["dt_type"] = (np.asarray(self._run.flat.dt_id), dt_type)
+            self._error_types[key] = hit
+        return hit if per_detection else {k: v for k, v in hit.items() if k != "dt_type"}
+
+    def error_lines(self, iou_thr=0.5, bg_thr=0.1):
+        """error_types() as a small text table: a line per (area, time) range,
+        the seven types and the three ground-truth counts summed over the
+        categories.  Returned, not printed."""
+        e = self.error_types(iou_thr, bg_thr)
+        cols = e["types"] + ["GT", "missed", "missed_loc"]
+        rows = np.concatenate([e["dt_counts"].sum(1), e["gt_counts"].sum(1)], axis=1)
+        lbl = ["{}/{}".format(*e["rng_lbl"][a]) if a < len(e["rng_lbl"]) else str(a)
+               for a in range(len(rows))]
+        w = max([len(x) for x in lbl] + [10])
+        lines = [" track error types @[ IoU={:0.2f} | bg={:0.2f} ]".format(iou_thr, bg_thr),
+                 " " + " " * w + "".join("{:>11s}".format(c) for c in cols)]
+        for name, r in zip(lbl, rows):
+            lines.append(" " + name.ljust(w) + "".join("{:>11d}".format(int(v)) for v in r))
+        return lines
 
     def _summarize(self, summary_type, iou_thr=None, area_rng="all",
                    time_rng="all", freq_group_idx=None):

@@ -1,8 +1,9 @@
 #!/usr/bin/env python
-"""Measurement of the image-level error breakdown (taoamd_error_types) on the
-synthetic configurations of bench.py, with HIP events:
+"""Measurement of the error breakdowns (taoamd_error_types,
+taoamd_track_error_types) on the synthetic configurations of bench.py, with HIP
+events:
 
-    python tools/time_error_types.py [--config 3s] [--reps 20] [--warmup 3]
+    python tools/time_error_types.py [--level image|track] [--config 3s] [--reps 20] [--warmup 3]
 
 Times, on the image level's tables of that configuration, each alone on an idle
 stream: the fused match as a benchmark step runs it (the yardstick), the
@@ -10,7 +11,11 @@ detail-mode match that produces match_gt (existing code the breakdown depends
 on), and the breakdown itself with and without the per-detection table; lists
 the breakdown's kernels and the pair counts that bound it (an image's
 detections x ALL its ground truths against the match's same-category pairs).
-Prints one JSON line."""
+--level track times, on the track table of the configuration: stage_track_iou of
+a benchmark step (the same-category pairs), the plan-less taoamd_track_iou on
+the cells pooled per video (every pair of a video, the cross-category ones done
+naively), the match that produces match_gt, and the breakdown; lists its kernels
+and the (pair, shared frame) counts.  Prints one JSON line."""
 import argparse
 import json
 import os
@@ -24,8 +29,113 @@ sys.path.insert(0, ROOT)
 CONFIGS = {"2": (200, 300, 50), "3s": (2000, 300, 50), "5s": (10000, 1, 1000)}
 
 
+def timed_calls(fn, warmup, reps):
+    import torch
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return {"min_ms": round(min(out), 4), "median_ms": round(float(np.median(out)), 4),
+            "max_ms": round(max(out), 4)}
+
+
+def pooled_cells(dp, lists):
+    """The track table's frame lists regrouped so that a video is ONE cell: what
+    the plan-less taoamd_track_iou needs to compute every (detection track,
+    ground-truth track) pair of a video.  On the device."""
+    import torch
+    _, vid_gt_off, vid_gt, vid_dt_off, vid_dt = lists
+    t = dp.t
+    out = {}
+    for side, rows, n in (("dt", vid_dt, dp.n_dt), ("gt", vid_gt, dp.n_gt)):
+        rows = rows[:n].long()
+        off = t[side + "_frame_off"].long()
+        cnt = (off[1:] - off[:-1])[rows]
+        new_off = torch.zeros(n + 1, dtype=torch.int64, device=rows.device)
+        new_off[1:] = torch.cumsum(cnt, 0)
+        take = torch.repeat_interleave(off[rows] - new_off[:-1], cnt) \
+            + torch.arange(int(new_off[-1]), device=rows.device)
+        out[side + "_frame_off"] = new_off.to(torch.int32)
+        out[side + "_frame_pos"] = t[side + "_frame_pos"][take].contiguous()
+        out[side + "_frame_box"] = t[side + "_frame_box"][take].contiguous()
+    d_cnt = (vid_dt_off[1:] - vid_dt_off[:-1]).long()
+    g_cnt = (vid_gt_off[1:] - vid_gt_off[:-1]).long()
+    iou_off = torch.zeros(len(d_cnt) + 1, dtype=torch.int64, device=d_cnt.device)
+    iou_off[1:] = torch.cumsum(d_cnt * g_cnt, 0)
+    out.update(cell_dt_off=vid_dt_off, cell_gt_off=vid_gt_off, cell_iou_off=iou_off,
+               n_cells=len(d_cnt), n_pairs=int(iou_off[-1]))
+    return out
+
+
+def track_level(a, gt, dt, dev, V):
+    import torch
+    from tao_amodal_amd import _lib, engine, flatten, flatten_dev
+    dt.track_id, _ = flatten.make_track_ids_unique(dt)
+    fl = flatten_dev.flatten_tao(gt, dt, device=dev)
+    dp = engine.DeviceProblem(fl, dev)
+    ws = engine.Workspace(dp)
+    engine.run_guarded(dp, ws, fl, upto="match", read_count=False)
+    torch.cuda.synchronize()
+    lib = _lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def timed(fn):
+        return timed_calls(fn, a.warmup, a.reps)
+    res = {"level": "track", "config": a.config, "videos": V, "rows": dp.n_dt,
+           "ground_truths": dp.n_gt, "categories": dp.n_cat, "cells": dp.n_cells,
+           "same_category_pairs": dp.n_iou,
+           "same_category_pair_frames": int(ws.pair_frames.item()),
+           "dt_frames": int(dp.t["dt_frame_pos"].numel()),
+           "gt_frames": int(dp.t["gt_frame_pos"].numel())}
+    res["track_iou_step"] = timed(lambda: engine.stage_track_iou(dp, ws))
+    res["match_fused"] = timed(lambda: engine.stage_match(dp, ws))
+    # the first call builds the per-video lists and runs the match for match_gt
+    engine.stage_track_error_types(dp, ws, 0, a.bg_thr)
+    torch.cuda.synchronize()
+    res["match_with_match_gt"] = timed(
+        lambda: engine.stage_match(dp, ws, match_gt=ws.err_match_gt))
+    res["track_error_types"] = timed(
+        lambda: engine.stage_track_error_types(dp, ws, 0, a.bg_thr))
+    res["track_error_types_per_detection"] = timed(
+        lambda: engine.stage_track_error_types(dp, ws, 0, a.bg_thr, per_detection=True))
+    _lib.kernel_timing(True)
+    for _ in range(a.reps):
+        engine.stage_track_error_types(dp, ws, 0, a.bg_thr)
+    res["kernels_ms"] = {k: round(ms / n, 4) for k, (ms, n) in _lib.kernel_timings().items()}
+    _lib.kernel_timing(False)
+    res["dt_counts_by_type_range0"] = ws.err_dt_counts[0].sum(0).tolist()
+    res["gt_counts_range0"] = ws.err_gt_counts[0].sum(0).tolist()
+    # the second yardstick: every pair of a video through the plan-less kernel
+    p = pooled_cells(dp, dp.err_tabs)
+    res["video_pairs"] = p["n_pairs"]
+    res["cross_category_pairs"] = p["n_pairs"] - dp.n_iou
+    iou = torch.empty(max(p["n_pairs"], 1), dtype=torch.float64, device=dev)
+    frames = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def naive():
+        _lib.check(lib.taoamd_track_iou(
+            p["n_cells"], p["cell_dt_off"].data_ptr(), p["cell_gt_off"].data_ptr(),
+            p["cell_iou_off"].data_ptr(), p["n_pairs"], p["dt_frame_off"].data_ptr(),
+            p["dt_frame_pos"].data_ptr(), p["dt_frame_box"].data_ptr(),
+            p["gt_frame_off"].data_ptr(), p["gt_frame_pos"].data_ptr(),
+            p["gt_frame_box"].data_ptr(), 0, iou.data_ptr(), frames.data_ptr(), stream),
+            "taoamd_track_iou")
+    res["track_iou_planless_video_pooled"] = timed(naive)
+    res["video_pair_frames"] = int(frames.item())
+    res["cross_category_pair_frames"] = res["video_pair_frames"] - res["same_category_pair_frames"]
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--level", choices=("image", "track"), default="image")
     ap.add_argument("--config", choices=sorted(CONFIGS), default="3s")
     ap.add_argument("--videos", type=int, default=None)
     ap.add_argument("--cats", type=int, default=1203)
@@ -41,6 +151,8 @@ def main():
     V = a.videos or V
     dev = torch.device("cuda", 0)
     gt, dt = synth(seed=a.seed, V=V, F=F, C=a.cats, dets_per_frame=D)
+    if a.level == "track":
+        return track_level(a, gt, dt, dev, V)
     fl = flatten_dev.flatten_lvis(gt, dt, device=dev)
     dp = engine.DeviceProblem(fl, dev)
     ws = engine.Workspace(dp)
@@ -48,19 +160,7 @@ def main():
     torch.cuda.synchronize()
 
     def timed(fn):
-        for _ in range(a.warmup):
-            fn()
-        torch.cuda.synchronize()
-        out = []
-        for _ in range(a.reps):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            fn()
-            e1.record()
-            e1.synchronize()
-            out.append(e0.elapsed_time(e1))
-        return {"min_ms": round(min(out), 4), "median_ms": round(float(np.median(out)), 4),
-                "max_ms": round(max(out), 4)}
+        return timed_calls(fn, a.warmup, a.reps)
 
     res = {"config": a.config, "videos": V, "rows": dp.n_dt, "ground_truths": dp.n_gt,
            "categories": dp.n_cat, "cells": dp.n_cells, "same_category_pairs": dp.n_iou}
