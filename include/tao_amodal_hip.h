@@ -443,6 +443,32 @@ int taoamd_match(int64_t n_cells, const int32_t *cell_dt_off,
                  const int32_t *groups, int32_t n_groups, const int32_t *singles,
                  int32_t n_singles, void *stream);
 
+/* Compact rows (image level: box IoU computed by the kernel, one combo word of
+ * at most six ranges, launch plan with dt_meta, rows in cell order).  Where no
+ * detection of a cell overlaps two ground truths by the lowest threshold, a row
+ * is a function of 18 bits and the match stores those instead of the pair:
+ *   compact[d] : bits 0-9   the thresholds the detection is matched at
+ *                bits 10-15 the matched ground truth's range mask
+ *                bit 16     the detection is ignored when unmatched
+ *                bit 17     the matched ground truth's id is hidden
+ *                bit 31     escape: the cell went through the sequential greedy
+ *                           and the full pair lies at rows[2 * d], as
+ *                           taoamd_match stores it
+ * rows: uint64[n_dt][2], 16-byte aligned.  taoamd_expand_rows writes the pair of
+ * every row that is not escaped (afterwards `rows` holds what taoamd_match would
+ * have stored); taoamd_accumulate_by_order_compact sweeps the compact form.
+ * TAOAMD_ERR_ARG for a problem outside this shape. */
+int taoamd_match_compact(int64_t n_cells, const int32_t *cell_dt_off,
+                         const int32_t *cell_gt_off, int32_t max_gt_per_cell,
+                         const double *dt_box, const double *gt_box, int32_t n_rng,
+                         const uint32_t *gt_rng, const uint8_t *gt_flags,
+                         const uint8_t *dt_flags, uint64_t *rows, uint32_t *compact,
+                         const int32_t *dt_group, const uint32_t *dt_meta,
+                         const int32_t *groups, int32_t n_groups, const int32_t *singles,
+                         int32_t n_singles, void *stream);
+int taoamd_expand_rows(int64_t n_dt, int32_t n_rng, const uint32_t *compact,
+                       uint64_t *rows, void *stream);
+
 /* ---- cell-table build, detection side (csrc/flatten.hip) ----------------------
  * The per-box half of what the reference does with dicts in L/results.py:20-84,
  * L/lvis.py:90-96, L/eval.py:59-110 (and the T/ counterparts): the host keeps
@@ -817,6 +843,18 @@ int taoamd_accumulate_by_order_chunked(int64_t n_dt, int32_t n_cat, int32_t n_rn
                                const int32_t *num_gt, int32_t max_segment,
                                double *precision, double *recall, void *workspace,
                                size_t workspace_bytes, void *stream);
+/* ... through the compact rows of taoamd_match_compact: the one-pass sweep
+ * gathers the 4-byte words through order[] and fetches a 16-byte pair from
+ * `rows` only where a word is escaped.  prepared != 0: on a prepared workspace.
+ * TAOAMD_ERR_ARG where the pass would not take the one-pass sweep
+ * (taoamd_accumulate_plan_kind 2 or 3) -- taoamd_expand_rows and
+ * taoamd_accumulate_by_order* serve there. */
+int taoamd_accumulate_by_order_compact(int64_t n_dt, int32_t n_cat, int32_t n_rng,
+                               const int32_t *cat_off, const int32_t *order,
+                               const uint32_t *compact, const uint64_t *rows,
+                               const int32_t *num_gt, int32_t max_segment,
+                               double *precision, double *recall, void *workspace,
+                               size_t workspace_bytes, int32_t prepared, void *stream);
 
 /* ---- score at each recall threshold ----------------------------------------------
  * pycocotools' eval["scores"] (cocoeval.py accumulate: ss[ri] = dtScoresSorted[pi]):

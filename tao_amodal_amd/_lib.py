@@ -125,6 +125,9 @@ SIGNATURES = {
     "taoamd_match": (C.c_int, [_i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32,
                                _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp]),
+    "taoamd_match_compact": (C.c_int, [_i64, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp]),
+    "taoamd_expand_rows": (C.c_int, [_i64, _i32, _vp, _vp, _vp]),
     "taoamd_gather_rows": (C.c_int, [_i64, _i32, _vp, _vp, _i64, _vp, _vp,
                                      _vp, _vp]),
     "taoamd_compact_elems": (_sz, [_i32, _i32]),
@@ -177,6 +180,9 @@ SIGNATURES = {
                                              _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
     "taoamd_accumulate_by_order_chunked": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp,
                                              _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "taoamd_accumulate_by_order_compact": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp,
+                                                     _vp, _i32, _vp, _vp, _vp, _sz, _i32,
+                                                     _vp]),
     "taoamd_score_at_recall_workspace": (_sz, [_i64, _i32, _i32]),
     "taoamd_score_at_recall": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                          _vp, _vp, _vp, _sz, _vp]),

@@ -72,6 +72,7 @@ struct AccArgs {
     const uint64_t *matched;
     const uint64_t *ignored;
     const int32_t *order;    // optional: sorted position -> row of matched / ignored
+    const uint32_t *compact; // optional (gathered one-pass sweep): 4-byte rows, taoamd_match_compact
     const int32_t *num_gt;
     int32_t *cat_chunk_off;  // [n_cat + 1]
     const int32_t *chunk_tab;  // [chunk] category of the chunk; null: searched per wavefront
@@ -284,12 +285,134 @@ __device__ __forceinline__ void load_chunk(const AccArgs &a, int64_t start, int 
 // category's rows in cell order are one contiguous piece as well (the cells are
 // category-major), so the gathers of a category's super-chunks, which the XCD
 // order puts behind one L2, stay inside that piece.
-template <int ACC_BLK_N, bool GATHER = false>
+//
+// GATHER == 2, compact rows (taoamd_match_compact): sorted place p holds the
+// 4-byte word compact[order[p]] -- 32 rows to a 128-byte line where the 16-byte
+// rows are 8 -- and a word with its top bit set says "the full row, at the same
+// index of the row table" (a detection the sequential greedy matched).  A word
+// w expands without a multiply: R = its ten threshold bits repeated six times
+// (shift-or), and three masks that depend on bits 10-17 alone (the candidate's
+// range mask g, u = ignored when unmatched, h = candidate hidden) from a table
+// in LDS, filled once per workgroup:
+//     A = h && u ? ALL : S(g) * 0x3ff     ignored where R is set
+//     B = u ? ALL : 0                     ignored where R is not
+//     ignored = R & A | ~R & B,  matched = h ? 0 : R & ALL
+// so that  TP = matched & ~ignored = R & T  with T = (h ? 0 : ALL) & ~A  and
+// valid = ~ignored = bitselect(R, ~A, ~B): the table holds the pair (T, ~A), one
+// 16-byte LDS read a row, and ~B = ~u | ~ALL comes from bit 16 and two SGPRs.
+#define CROW_ESCAPE 0x80000000u
+#define CROW_KEYS 256            // bits 10-17 of a word
+
+__device__ __forceinline__ uint64_t crow_all(int32_t n_rng)
+{
+    constexpr uint64_t S_ALL = 1ull | 1ull << 10 | 1ull << 20 | 1ull << 30 |
+                               1ull << 40 | 1ull << 50;
+    constexpr uint64_t C9 = 1ull | 1ull << 9 | 1ull << 18 | 1ull << 27 |
+                            1ull << 36 | 1ull << 45;
+    return ((((uint64_t)(0xffffffffu >> (32 - n_rng))) * C9) & S_ALL) * 0x3ffull;
+}
+
+__device__ __forceinline__ void crow_table(ulonglong2 *tab, int32_t n_rng)
+{
+    constexpr uint64_t S_ALL = 1ull | 1ull << 10 | 1ull << 20 | 1ull << 30 |
+                               1ull << 40 | 1ull << 50;
+    constexpr uint64_t C9 = 1ull | 1ull << 9 | 1ull << 18 | 1ull << 27 |
+                            1ull << 36 | 1ull << 45;
+    const uint32_t rmask = 0xffffffffu >> (32 - n_rng);
+    const uint64_t all = crow_all(n_rng);
+    for (int key = threadIdx.x; key < CROW_KEYS; key += blockDim.x) {
+        const uint32_t g = (uint32_t)key & 63u & rmask;
+        const bool u = (key >> 6) & 1, h = (key >> 7) & 1;
+        const uint64_t A = h && u ? all : (((uint64_t)g * C9) & S_ALL) * 0x3ffull;
+        ulonglong2 e;
+        e.x = (h ? 0ull : all) & ~A;
+        e.y = ~A;
+        tab[key] = e;
+    }
+}
+
+__device__ __forceinline__ void crow_expand(uint32_t w, const ulonglong2 *tab, uint32_t nall_lo,
+                                            uint32_t nall_hi, uint64_t &tpw, uint64_t &vw)
+{
+    const uint32_t m10 = w & 0x3ffu;
+    uint32_t lo = m10 | m10 << 10;
+    lo |= lo << 20;
+    const uint32_t hi = m10 >> 2 | m10 << 8 | m10 << 18;
+    const ulonglong2 e = tab[(w >> 10) & (CROW_KEYS - 1)];
+    const uint64_t T = e.x, nA = e.y;
+    const uint32_t nu = ~(uint32_t)((int32_t)(w << 15) >> 31);      // ~0 unless bit 16 is set
+    const uint32_t t_lo = lo & (uint32_t)T, t_hi = hi & (uint32_t)(T >> 32);
+    const uint32_t v_lo = (lo & (uint32_t)nA) | (~lo & (nu | nall_lo));
+    const uint32_t v_hi = (hi & (uint32_t)(nA >> 32)) | (~hi & (nu | nall_hi));
+    tpw = (uint64_t)t_hi << 32 | t_lo;
+    vw = (uint64_t)v_hi << 32 | v_lo;
+}
+
+// The words of a chunk: the places (coalesced), the workgroup's table while they
+// travel, then all the 4-byte gathers in one batch.  The sweep expands a block's
+// words where it transposes them (crow_rows): eight registers a chunk are
+// carried there, not the thirty-two of the expanded rows.
+template <int ACC_BLK_N>
+__device__ __forceinline__ void load_chunk_compact(const AccArgs &a, int64_t start, int len,
+                                                   int lane, uint32_t (&w)[ACC_BLK_N],
+                                                   ulonglong2 *tab)
+{
+    // (one combo word, 16-byte pairs: the entry point saw to it)
+    const bool full = len == ACC_BLK_N * WAVE;                     // (uniform)
+    const int32_t *__restrict__ ob = a.order + start;
+    uint32_t at[ACC_BLK_N];
+    if (full) {
+#pragma unroll
+        for (int blk = 0; blk < ACC_BLK_N; blk++) at[blk] = (uint32_t)ob[blk * WAVE + lane];
+    } else {
+        // a category's last chunk: a lane past its rows re-reads the first
+#pragma unroll
+        for (int blk = 0; blk < ACC_BLK_N; blk++) {
+            const int i = blk * WAVE + lane;
+            at[blk] = len > 0 ? (uint32_t)ob[i < len ? i : 0] : 0u;
+        }
+    }
+    // (every wavefront of the workgroup comes through here: the barrier is uniform)
+    crow_table(tab, a.n_rng);
+    __syncthreads();
+    if (full || len > 0) {
+#pragma unroll
+        for (int blk = 0; blk < ACC_BLK_N; blk++) w[blk] = a.compact[at[blk]];
+    } else {
+#pragma unroll
+        for (int blk = 0; blk < ACC_BLK_N; blk++) w[blk] = 0;
+    }
+}
+
+// TP and valid word of my row of block `blk` from its compact word; an escaped
+// row (rare: the place is read again rather than kept) from the row table.
+template <int ACC_BLK_N>
+__device__ __forceinline__ void crow_rows(const AccArgs &a, int64_t start, int len, int lane,
+                                          int blk, uint32_t w, const ulonglong2 *tab,
+                                          uint32_t nall_lo, uint32_t nall_hi,
+                                          uint64_t &tpw, uint64_t &vw)
+{
+    const bool full = len == ACC_BLK_N * WAVE;                     // (uniform)
+    crow_expand(w, tab, nall_lo, nall_hi, tpw, vw);
+    if (__ballot(w & CROW_ESCAPE) != 0) {
+        if (w & CROW_ESCAPE) {
+            const int i = blk * WAVE + lane;
+            const uint32_t r = (uint32_t)a.order[start + (full || i < len ? i : 0)];
+            const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(
+                reinterpret_cast<const char *>(a.matched) + (uint64_t)r * 16u);
+            tpw = v.x & ~v.y;
+            vw = ~v.y;
+        }
+    }
+    if (!full && blk * WAVE + lane >= len) { tpw = 0; vw = 0; }
+}
+
+template <int ACC_BLK_N, int GATHER = 0>
 __device__ __forceinline__ void load_chunk_tv(const AccArgs &a, int64_t start, int word, int len,
                                               int lane, uint64_t (&tpw)[ACC_BLK_N],
                                               uint64_t (&vw)[ACC_BLK_N])
 {
-    if (GATHER && a.wide && len == ACC_BLK_N * WAVE) {
+    if (GATHER == 1 && a.wide && len == ACC_BLK_N * WAVE) {
         const int32_t *__restrict__ ob = a.order + start;              // (uniform)
         uint32_t at[ACC_BLK_N];
 #pragma unroll
@@ -1103,7 +1226,8 @@ __global__ void acc_cj_kernel(AccArgs a, RecThr rec)
 // half the wavefronts, half the per-wavefront set-up, still 64 VGPRs)
 // GATHER: rows in cell order, fetched through a.order (load_chunk_tv); a kernel
 // of its own, so that the streaming form keeps its code and its registers
-template <int SW, int MODE, bool GATHER = false, int NB = SWEEP_NB>
+// (GATHER == 2: through the compact rows -- load_chunk_compact, crow_rows)
+template <int SW, int MODE, int GATHER = 0, int NB = SWEEP_NB>
 __global__ __launch_bounds__(SW * WAVE) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void acc_sweep_kernel(AccArgs a, RecThr rec)
 {
@@ -1113,6 +1237,7 @@ void acc_sweep_kernel(AccArgs a, RecThr rec)
     __shared__ int32_t s_cj[EMIT_RMAX][N_REC];
     __shared__ uint16_t s_jr[SW][WAVE];          // thresholds a chunk emitted: jlo | jhi << 8
     __shared__ int32_t s_done;
+    __shared__ ulonglong2 s_crow[GATHER == 2 ? CROW_KEYS : 1];
     const int lane = lane_id();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (threadIdx.x == 0) s_done = 0;
@@ -1144,7 +1269,16 @@ void acc_sweep_kernel(AccArgs a, RecThr rec)
     const bool swept = k >= a.k_begin && k < a.k_end;       // (uniform)
     // ---- rows of my chunk: every load ahead of anything else
     uint64_t tpw[NB], vw[NB];
-    load_chunk_tv<NB, GATHER>(a, start, word, len, lane, tpw, vw);
+    uint32_t cw[NB];
+    uint32_t nall_lo = 0, nall_hi = 0;
+    if (GATHER == 2) {
+        load_chunk_compact<NB>(a, start, len, lane, cw, s_crow);
+        const uint64_t nall = ~crow_all(a.n_rng);                      // (uniform)
+        nall_lo = (uint32_t)nall;
+        nall_hi = (uint32_t)(nall >> 32);
+    } else {
+        load_chunk_tv<NB, GATHER>(a, start, word, len, lane, tpw, vw);
+    }
     const int r_lo = (word * WAVE) / N_THR;
     const int r_hi = min(a.n_rng - 1, (word * WAVE + WAVE - 1) / N_THR);
     if (MODE != 2) {
@@ -1158,9 +1292,15 @@ void acc_sweep_kernel(AccArgs a, RecThr rec)
     uint64_t T[NB], TF[NB];
     uint32_t tp_own = 0, n_own = 0;
 #pragma unroll
-    for (int blk = 0; blk < NB; blk++) {
+    for (int b_ = 0; b_ < NB; b_++) {
+        // (compact rows: last block first, the order the walk below uses them in --
+        // the block that is walked last is not carried through all the others)
+        const int blk = GATHER == 2 ? NB - 1 - b_ : b_;
         uint64_t t_ = 0, v_ = 0;
         if (blk * WAVE < len) {
+            if (GATHER == 2)
+                crow_rows<NB>(a, start, len, lane, blk, cw[blk], s_crow, nall_lo, nall_hi,
+                              tpw[blk], vw[blk]);
 #if defined(SW_ABLATE) && (SW_ABLATE & 2)     // (timing experiment: no transposes)
             t_ = tpw[blk];
             v_ = vw[blk];
@@ -1333,9 +1473,12 @@ void acc_sweep_kernel(AccArgs a, RecThr rec)
         const uint64_t v = s_max[w][lane];
         if (pr_better((uint32_t)(v >> 32), (uint32_t)v, later)) later = v;
     }
-    a.sc_max[so] = live ? later : PR_ZERO;
+    // (compact rows, one combo word: worked out again here, not carried in two
+    // registers through the look-back and the walk)
+    const int64_t so_end = GATHER == 2 ? (int64_t)sc * WAVE + lane : so;
+    a.sc_max[so_end] = live ? later : PR_ZERO;
     // thresholds reached up to the end of this SC (its last wavefront's)
-    a.sc_jhi[so] = (uint8_t)(live ? s_jr[SW - 1][lane] >> 8 : 0);
+    a.sc_jhi[so_end] = (uint8_t)(live ? s_jr[SW - 1][lane] >> 8 : 0);
 }
 
 // The envelope of the later SCs folded into val: one wavefront per (category,
@@ -1641,7 +1784,8 @@ static int accumulate_compact(int64_t n_dt, int32_t n_cat, int32_t n_rng,
                               const int32_t *num_gt, int32_t k_begin, int32_t k_end,
                               int32_t max_segment, double *val, double *rec,
                               void *workspace, size_t workspace_bytes, void *stream,
-                              int phase = ACC_ALL, int force_mode = SWEEP_AUTO)
+                              int phase = ACC_ALL, int force_mode = SWEEP_AUTO,
+                              const uint32_t *compact = nullptr)
 {
     if (n_cat <= 0 || n_rng < 1 || n_rng > 32) return TAOAMD_ERR_ARG;
     if (k_begin < 0 || k_end > n_cat || k_begin > k_end) return TAOAMD_ERR_ARG;
@@ -1656,6 +1800,7 @@ static int accumulate_compact(int64_t n_dt, int32_t n_cat, int32_t n_rng,
     a.chunk_tab = nullptr;
     a.n_dt = n_dt; a.n_cat = n_cat; a.n_rng = n_rng;
     a.cat_off = cat_off; a.matched = matched; a.ignored = ignored; a.order = order;
+    a.compact = compact;
     a.paired = matched != nullptr && ignored == matched + 1;
     a.wide = a.paired && ((uintptr_t)matched & 15) == 0;
     a.num_gt = num_gt; a.val = (uint64_t *)val; a.rec = rec;
@@ -1690,6 +1835,7 @@ static int accumulate_compact(int64_t n_dt, int32_t n_cat, int32_t n_rng,
     a.fused_rows = 0;
     a.fused_lo = -1;
     if (all_fused && phase == ACC_PLAN) return TAOAMD_OK;     // no chunk table
+    if (all_fused && compact != nullptr) return TAOAMD_ERR_ARG;
     if (all_fused) {
         const unsigned grid = (unsigned)(k_end - k_begin);
         int32_t lo = -1;
@@ -1717,6 +1863,9 @@ static int accumulate_compact(int64_t n_dt, int32_t n_cat, int32_t n_rng,
     a.inline_scans = max_segment > 0 && max_segment <= ACC_INLINE_CHUNKS * ACC_CH;
     const size_t nc = (size_t)a.n_chunks_max, nw = (size_t)a.n_words;
     const int mode = force_mode != SWEEP_AUTO ? force_mode : sweep_mode(n_dt);
+    // compact rows: the gathered one-pass sweep of one combo word alone reads them
+    if (compact != nullptr && (mode == SWEEP_CHUNKED || !order || !a.wide || a.n_words != 1 || n_rng > 6))
+        return TAOAMD_ERR_ARG;
     if (mode != SWEEP_CHUNKED) {
         a.sc_rows = SWEEP_SW * SWEEP_NB * WAVE;
         a.inline_scans = 0;
@@ -1756,13 +1905,18 @@ static int accumulate_compact(int64_t n_dt, int32_t n_cat, int32_t n_rng,
             uint32_t g = ++g_sc_gen;
             a.sc_gen = (g & 0x3fffffffu) ? (g & 0x3fffffffu) : (++g_sc_gen & 0x3fffffffu);
             a.sc_error = t.header;
-            if (a.order)
-                TAO_TIMED("acc_sweep_kernel", s, (acc_sweep_kernel<SWEEP_SW, 0, true><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
+            if (a.compact)
+                TAO_TIMED("acc_sweep_kernel", s, (acc_sweep_kernel<SWEEP_SW, 0, 2><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
+            else if (a.order)
+                TAO_TIMED("acc_sweep_kernel", s, (acc_sweep_kernel<SWEEP_SW, 0, 1><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
             else
                 TAO_TIMED("acc_sweep_kernel", s, (acc_sweep_kernel<SWEEP_SW, 0><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
+        } else if (a.compact) {
+            TAO_TIMED("acc_sccount_kernel", s, (acc_sweep_kernel<SWEEP_SW, 2, 2><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
+            TAO_TIMED("acc_sweep_kernel", s, (acc_sweep_kernel<SWEEP_SW, 1, 2><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
         } else if (a.order) {
-            TAO_TIMED("acc_sccount_kernel", s, (acc_sweep_kernel<SWEEP_SW, 2, true><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
-            TAO_TIMED("acc_sweep_kernel", s, (acc_sweep_kernel<SWEEP_SW, 1, true><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
+            TAO_TIMED("acc_sccount_kernel", s, (acc_sweep_kernel<SWEEP_SW, 2, 1><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
+            TAO_TIMED("acc_sweep_kernel", s, (acc_sweep_kernel<SWEEP_SW, 1, 1><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
         } else {
             TAO_TIMED("acc_sccount_kernel", s, (acc_sweep_kernel<SWEEP_SW, 2><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
             TAO_TIMED("acc_sweep_kernel", s, (acc_sweep_kernel<SWEEP_SW, 1><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
@@ -1843,7 +1997,7 @@ static int accumulate_all(int64_t n_dt, int32_t n_cat, int32_t n_rng,
                           const int32_t *num_gt, int32_t max_segment,
                           double *precision, double *recall, void *workspace,
                           size_t workspace_bytes, void *stream, int phase = ACC_ALL,
-                          int force_mode = SWEEP_AUTO)
+                          int force_mode = SWEEP_AUTO, const uint32_t *compact = nullptr)
 {
     if (n_cat <= 0 || n_rng < 1 || n_rng > 32) return TAOAMD_ERR_ARG;
     if (!workspace) return TAOAMD_ERR_ARG;
@@ -1853,7 +2007,7 @@ static int accumulate_all(int64_t n_dt, int32_t n_cat, int32_t n_rng,
     if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
     int st = accumulate_compact(n_dt, n_cat, n_rng, cat_off, order, matched, ignored,
                                 num_gt, 0, n_cat, max_segment, val, rec, workspace,
-                                workspace_bytes, stream, phase, force_mode);
+                                workspace_bytes, stream, phase, force_mode, compact);
     if (st != TAOAMD_OK || phase == ACC_PLAN) return st;
     return taoamd_finalize(n_cat, n_rng, num_gt, val, rec, precision, recall, stream);
 }
@@ -1936,6 +2090,27 @@ extern "C" int taoamd_accumulate_by_order_prepared(int64_t n_dt, int32_t n_cat, 
     return accumulate_all(n_dt, n_cat, n_rng, cat_off, order, matched, ignored,
                           num_gt, max_segment, precision, recall, workspace,
                           workspace_bytes, stream, ACC_SWEEP);
+}
+
+// ... through the compact rows of taoamd_match_compact (one combo word, the
+// one-pass sweep: TAOAMD_ERR_ARG where the pass would take another kernel).
+// `rows`: the table of 16-byte pairs that holds the escaped rows.  prepared != 0:
+// on a prepared workspace.
+extern "C" int taoamd_accumulate_by_order_compact(int64_t n_dt, int32_t n_cat, int32_t n_rng,
+                                                  const int32_t *cat_off,
+                                                  const int32_t *order,
+                                                  const uint32_t *compact,
+                                                  const uint64_t *rows,
+                                                  const int32_t *num_gt, int32_t max_segment,
+                                                  double *precision, double *recall,
+                                                  void *workspace, size_t workspace_bytes,
+                                                  int32_t prepared, void *stream)
+{
+    if (!order || !compact || !rows) return TAOAMD_ERR_ARG;
+    return accumulate_all(n_dt, n_cat, n_rng, cat_off, order, rows, rows + 1,
+                          num_gt, max_segment, precision, recall, workspace,
+                          workspace_bytes, stream, prepared ? ACC_SWEEP : ACC_ALL,
+                          SWEEP_AUTO, compact);
 }
 
 // ... and from the chunked kernels whatever the sweep mode: the second sweep of

@@ -204,7 +204,15 @@ struct MatchArgs {
     const int32_t *singles;   // [n_singles] cells handled one per wavefront
     int32_t n_groups, n_singles;
     int32_t xcd;              // blocks renumbered per XCD (xcd_block)
+    uint32_t *compact;        // optional [n_dt]: 4-byte rows (taoamd_match_compact)
 };
+
+// The 4-byte row of the closed-form path (COMPACT): a row is a function of
+// the ten threshold bits m10 (bits 0-9), the candidate's range mask (10-15),
+// "ignored when unmatched" (16) and "the candidate is hidden" (17).  A row the
+// sequential greedy produced is not: its word is TAOAMD_ROW_ESCAPE and the full
+// 16-byte row lies at the same index of the row table.
+#define TAOAMD_ROW_ESCAPE 0x80000000u
 
 // range mask of detection d: the caller's table, or -- image level, where the
 // mask is "every range iff the detection is ignored when unmatched"
@@ -337,6 +345,7 @@ __global__ __launch_bounds__(256) void match_kernel(MatchArgs a, IouThr thr)
         }
         if (lane < nd) {
             store_row(a, t_row, word, my_m, my_i);
+            if (a.compact != nullptr) a.compact[t_row] = TAOAMD_ROW_ESCAPE;
         }
     }
 }
@@ -362,9 +371,13 @@ __global__ __launch_bounds__(256) void match_kernel(MatchArgs a, IouThr thr)
 // cache line per store --; false: rows stay in cell order, a run's rows are ONE
 // contiguous piece written by a whole wavefront, dst[] is not read and the match
 // does not depend on the sort (the sweep gathers them through order[]).
-template <bool FUSED, bool FAST = false, bool SCATTER = true>
+// COMPACT (FAST && !SCATTER only): a detection of the closed-form path stores
+// its 4-byte word into a.compact[d] and no row; one of the sequential loop
+// stores the escape word there and its full row as ever.
+template <bool FUSED, bool FAST = false, bool SCATTER = true, bool COMPACT = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void match_group_kernel(MatchArgs a, IouThr thr)
 {
+    static_assert(!COMPACT || (FAST && !SCATTER), "compact rows: the fast cell-order instance");
     __shared__ double4 s_gt[4][WAVE];
     // IoU tile of the run: only where the IoUs come from memory.  The fused
     // kernel keeps a detection's candidate in registers and, in the rare cell
@@ -522,6 +535,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     // run at once; only cells where some detection overlaps two GTs by the
     // lowest threshold or more go through the sequential loop below.
     uint64_t my_m = 0, my_i = 0;
+    uint32_t my_c = TAOAMD_ROW_ESCAPE;
     // lanes [ca, ce) hold the detections of my cell
     const uint64_t starts = __ballot(lane < nD && dloc == 0);
     const int ca = lane - dloc;
@@ -605,7 +619,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             const uint64_t sg = ((uint64_t)(mygrng & rmask) * C9) & S_ALL;
             const uint64_t sd = ((uint64_t)((uint32_t)t_rng & rmask) * C9) & S_ALL;
             const uint32_t X = myghid ? all10 : (~m10 & all10);
-            if (simple) {
+            if (COMPACT) {
+                // (the same operands: the sweep and taoamd_expand_rows work the
+                // two products out from them)
+                if (simple)
+                    my_c = m10 | (mygrng & rmask) << 10 |
+                           (((uint32_t)t_rng & rmask) ? 1u << 16 : 0u) |
+                           (myghid ? 1u << 17 : 0u);
+            } else if (simple) {
                 my_m = myghid ? 0ull : (uint64_t)m10 * sall;
                 my_i = (uint64_t)m10 * sg | (uint64_t)X * sd;
             }
@@ -634,7 +655,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     // are narrowed to the cell's <= GRP_GCAP GTs so the inner loop is 32-bit.
     const uint64_t todo = __ballot(lane < nD && !simple);
     if (todo == 0) {                  // (wave-uniform: the common case)
-        if (lane < nD) store_row(a, t_row, word, my_m, my_i);
+        if (COMPACT) {
+            if (lane < nD) a.compact[t_row] = my_c;
+        } else if (lane < nD) {
+            store_row(a, t_row, word, my_m, my_i);
+        }
         return;
     }
     const int combo = word * WAVE + lane;
@@ -692,7 +717,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         if (a.match_gt != nullptr && active)
             a.match_gt[(int64_t)(d0 + i) * n_combo + combo] = m;
     }
-    if (lane < nD) {
+    if (COMPACT) {
+        // simple lanes keep their word, the loop's lanes (my_c untouched: the
+        // escape) store their full row beside it
+        if (lane < nD) a.compact[t_row] = my_c;
+        if ((todo >> lane) & 1ull) store_row(a, t_row, word, my_m, my_i);
+    } else if (lane < nD) {
         store_row(a, t_row, word, my_m, my_i);
     }
 }
@@ -766,6 +796,7 @@ __global__ __launch_bounds__(64) void match_big_kernel(MatchArgs a, IouThr thr,
         if (lane == 0) {
             const int64_t rowi = a.dst != nullptr ? a.dst[d] : d;
             store_row(a, rowi, word, mw, iw);
+            if (a.compact != nullptr) a.compact[rowi] = TAOAMD_ROW_ESCAPE;
         }
         if (a.match_gt != nullptr && active)
             a.match_gt[(int64_t)d * n_combo + combo] = m;
@@ -912,21 +943,21 @@ extern "C" int taoamd_match_plan_host(int64_t n_cells, const int32_t *cell_dt_of
     return TAOAMD_OK;
 }
 
-extern "C" int taoamd_match(int64_t n_cells, const int32_t *cell_dt_off,
-                            const int32_t *cell_gt_off,
-                            const int64_t *cell_iou_off,
-                            int32_t max_gt_per_cell, const double *dt_box,
-                            const double *gt_box, const double *iou,
-                            int32_t n_rng, const uint32_t *gt_rng,
-                            const uint32_t *dt_rng, const uint8_t *gt_flags,
-                            const uint8_t *dt_flags, const int32_t *dst,
-                            int64_t out_stride, uint64_t *matched,
-                            uint64_t *ignored, int32_t *match_gt,
-                            double *ious_out, const int32_t *dt_group,
-                            const uint32_t *dt_meta,
-                            const int32_t *groups, int32_t n_groups,
-                            const int32_t *singles, int32_t n_singles,
-                            void *stream)
+static int match_launch(int64_t n_cells, const int32_t *cell_dt_off,
+                        const int32_t *cell_gt_off,
+                        const int64_t *cell_iou_off,
+                        int32_t max_gt_per_cell, const double *dt_box,
+                        const double *gt_box, const double *iou,
+                        int32_t n_rng, const uint32_t *gt_rng,
+                        const uint32_t *dt_rng, const uint8_t *gt_flags,
+                        const uint8_t *dt_flags, const int32_t *dst,
+                        int64_t out_stride, uint64_t *matched,
+                        uint64_t *ignored, int32_t *match_gt,
+                        double *ious_out, const int32_t *dt_group,
+                        const uint32_t *dt_meta,
+                        const int32_t *groups, int32_t n_groups,
+                        const int32_t *singles, int32_t n_singles,
+                        uint32_t *compact, void *stream)
 {
     if (n_cells == 0) return TAOAMD_OK;
     if (n_rng < 1 || n_rng > 32) return TAOAMD_ERR_ARG;
@@ -954,6 +985,12 @@ extern "C" int taoamd_match(int64_t n_cells, const int32_t *cell_dt_off,
     a.singles = planned ? singles : nullptr; a.n_singles = planned ? n_singles : 0;
     static const int xcd_env = getenv("TAOAMD_XCD") ? atoi(getenv("TAOAMD_XCD")) : 1;
     a.xcd = xcd_env;
+    a.compact = compact;
+    // compact rows: the fast cell-order instance on dense 16-byte pairs, nothing else
+    if (compact != nullptr &&
+        !(planned && fused && a.dt_meta && !a.dt_rng && !a.ious_out && !a.match_gt &&
+          a.n_words == 1 && n_rng <= 6 && !a.dst && a.wide && a.out_stride == 2))
+        return TAOAMD_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (planned && n_groups > 0) {
         const unsigned gb = (unsigned)(((int64_t)n_groups * a.n_words + 3) / 4);
@@ -961,6 +998,7 @@ extern "C" int taoamd_match(int64_t n_cells, const int32_t *cell_dt_off,
         const bool fast = fused && a.dt_meta && !a.dt_rng && !a.ious_out && !a.match_gt &&
                           a.n_words == 1 && n_rng <= 6;
         if (fast && a.dst) TAO_TIMED("match_group_kernel", s, (match_group_kernel<true, true><<<gb, 256, 0, s>>>(a, match_thr())));
+        else if (fast && compact) TAO_TIMED("match_group_kernel", s, (match_group_kernel<true, true, false, true><<<gb, 256, 0, s>>>(a, match_thr())));
         else if (fast) TAO_TIMED("match_group_kernel", s, (match_group_kernel<true, true, false><<<gb, 256, 0, s>>>(a, match_thr())));
         else if (fused) TAO_TIMED("match_group_kernel", s, match_group_kernel<true><<<gb, 256, 0, s>>>(a, match_thr()));
         else TAO_TIMED("match_group_kernel", s, match_group_kernel<false><<<gb, 256, 0, s>>>(a, match_thr()));
@@ -980,6 +1018,86 @@ extern "C" int taoamd_match(int64_t n_cells, const int32_t *cell_dt_off,
                 TAO_TIMED("match_big_kernel", s, match_big_kernel<false><<<(unsigned)items, 64, lds, s>>>(a, match_thr(), cap));
         }
     }
+    TAO_LAUNCH_CHECK();
+    return TAOAMD_OK;
+}
+
+extern "C" int taoamd_match(int64_t n_cells, const int32_t *cell_dt_off,
+                            const int32_t *cell_gt_off,
+                            const int64_t *cell_iou_off,
+                            int32_t max_gt_per_cell, const double *dt_box,
+                            const double *gt_box, const double *iou,
+                            int32_t n_rng, const uint32_t *gt_rng,
+                            const uint32_t *dt_rng, const uint8_t *gt_flags,
+                            const uint8_t *dt_flags, const int32_t *dst,
+                            int64_t out_stride, uint64_t *matched,
+                            uint64_t *ignored, int32_t *match_gt,
+                            double *ious_out, const int32_t *dt_group,
+                            const uint32_t *dt_meta,
+                            const int32_t *groups, int32_t n_groups,
+                            const int32_t *singles, int32_t n_singles,
+                            void *stream)
+{
+    return match_launch(n_cells, cell_dt_off, cell_gt_off, cell_iou_off, max_gt_per_cell,
+                        dt_box, gt_box, iou, n_rng, gt_rng, dt_rng, gt_flags, dt_flags, dst,
+                        out_stride, matched, ignored, match_gt, ious_out, dt_group, dt_meta,
+                        groups, n_groups, singles, n_singles, nullptr, stream);
+}
+
+extern "C" int taoamd_match_compact(int64_t n_cells, const int32_t *cell_dt_off,
+                                    const int32_t *cell_gt_off, int32_t max_gt_per_cell,
+                                    const double *dt_box, const double *gt_box,
+                                    int32_t n_rng, const uint32_t *gt_rng,
+                                    const uint8_t *gt_flags, const uint8_t *dt_flags,
+                                    uint64_t *rows, uint32_t *compact,
+                                    const int32_t *dt_group, const uint32_t *dt_meta,
+                                    const int32_t *groups, int32_t n_groups,
+                                    const int32_t *singles, int32_t n_singles,
+                                    void *stream)
+{
+    if (!compact || !rows || !dt_box) return TAOAMD_ERR_ARG;
+    return match_launch(n_cells, cell_dt_off, cell_gt_off, nullptr, max_gt_per_cell,
+                        dt_box, gt_box, nullptr, n_rng, gt_rng, nullptr, gt_flags, dt_flags,
+                        nullptr, 0, rows, rows + 1, nullptr, nullptr, dt_group, dt_meta,
+                        groups, n_groups, singles, n_singles, compact, stream);
+}
+
+// ------------------------------------------------------- compact -> full rows
+// The rows of a compact pass as the 16-byte pairs every other reader takes
+// (escaped rows are in place already).  The products of match_group_kernel's
+// fast word, from the same operands.
+__global__ __launch_bounds__(256) void expand_rows_kernel(int64_t n, uint32_t rmask,
+                                                          const uint32_t *__restrict__ compact,
+                                                          ulonglong2 *__restrict__ rows)
+{
+    constexpr uint64_t S_ALL = 1ull | 1ull << 10 | 1ull << 20 | 1ull << 30 |
+                               1ull << 40 | 1ull << 50;
+    constexpr uint64_t C9 = 1ull | 1ull << 9 | 1ull << 18 | 1ull << 27 |
+                            1ull << 36 | 1ull << 45;
+    const uint64_t sall = ((uint64_t)rmask * C9) & S_ALL;
+    for (int64_t d = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; d < n;
+         d += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t w = compact[d];
+        if (w & TAOAMD_ROW_ESCAPE) continue;
+        const uint32_t m10 = w & 0x3ffu, g = (w >> 10) & rmask;
+        const bool un = (w >> 16) & 1u, hid = (w >> 17) & 1u;
+        const uint64_t sg = ((uint64_t)g * C9) & S_ALL;
+        const uint32_t X = hid ? 0x3ffu : (~m10 & 0x3ffu);
+        ulonglong2 v;
+        v.x = hid ? 0ull : (uint64_t)m10 * sall;
+        v.y = (uint64_t)m10 * sg | (un ? (uint64_t)X * sall : 0ull);
+        rows[d] = v;
+    }
+}
+
+extern "C" int taoamd_expand_rows(int64_t n_dt, int32_t n_rng, const uint32_t *compact,
+                                  uint64_t *rows, void *stream)
+{
+    if (n_dt == 0) return TAOAMD_OK;
+    if (n_rng < 1 || n_rng > 6 || !compact || !rows || ((uintptr_t)rows & 15)) return TAOAMD_ERR_ARG;
+    const unsigned blocks = (unsigned)((n_dt + 255) / 256 < 8192 ? (n_dt + 255) / 256 : 8192);
+    TAO_TIMED("expand_rows_kernel", (hipStream_t)stream, expand_rows_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(
+        n_dt, 0xffffffffu >> (32 - n_rng), compact, reinterpret_cast<ulonglong2 *>(rows)));
     TAO_LAUNCH_CHECK();
     return TAOAMD_OK;
 }

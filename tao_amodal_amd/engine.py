@@ -498,9 +498,19 @@ class Workspace:
         # rows of (matched, ignored) pairs, one pair per 64 combos: the match
         # stores a pair with one 16-byte store and the sweep loads it with one
         # load (the C ABI sees two tables, the second one word behind the first)
-        self.rows = torch.empty((max(dp.n_dt, 1), dp.n_words, 2),
-                                dtype=torch.int64, device=dev)
-        self.matched, self.ignored = self.rows[..., 0], self.rows[..., 1]
+        # (rows / matched / ignored are read through the properties below: a
+        # compact pass leaves most rows as 4-byte words)
+        self._rows = torch.empty((max(dp.n_dt, 1), dp.n_words, 2),
+                                 dtype=torch.int64, device=dev)
+        self._matched, self._ignored = self._rows[..., 0], self._rows[..., 1]
+        # gathered form: one 4-byte word per detection, in cell order, where the
+        # row is a function of 18 bits (taoamd_match_compact); rows_pending: the
+        # last match stored that form and `rows` has not been expanded from it
+        self.compact_buf = torch.empty(max(dp.n_dt, 1), dtype=torch.int32, device=dev) \
+            if self.gather else None
+        self.rows_pending = False
+        self.rows_expanded = 0            # expansions so far (taoamd_expand_rows)
+        self._dp = dp
         self.acc_bytes = lib.taoamd_accumulate_workspace(dp.n_dt, dp.n_cat,
                                                          dp.n_rng)
         self.acc_ws = buf(self.acc_bytes)
@@ -568,6 +578,26 @@ def _order_of(ws):
 
 
 Workspace.order = property(_order_of)
+
+
+def expand_rows(ws):
+    """The full (matched, ignored) rows of the last pass: after a compact pass
+    (stage_match on a gathering workspace) they are expanded from the 4-byte
+    words on the current stream, once, until the next such pass."""
+    if ws.rows_pending:
+        dp = ws._dp
+        with torch.cuda.device(dp.device):
+            _lib.check(_lib.load().taoamd_expand_rows(
+                dp.n_dt, dp.n_rng, _ptr(ws.compact_buf), _ptr(ws._rows), _stream()),
+                "taoamd_expand_rows")
+        ws.rows_pending = False
+        ws.rows_expanded += 1
+    return ws
+
+
+Workspace.rows = property(lambda ws: expand_rows(ws)._rows)
+Workspace.matched = property(lambda ws: expand_rows(ws)._matched)
+Workspace.ignored = property(lambda ws: expand_rows(ws)._ignored)
 
 
 def stage_ranges(dp, ws):
@@ -949,6 +979,20 @@ def stage_match(dp, ws, scatter=True, groups=None, singles=None, match_gt=None):
     fused = dp.kind == "lvis" and not dp.mask_iou
     if groups is None:
         ws.cell_order = not scatter
+    # the compact form exactly where the workspace gathers: the whole plan, rows
+    # in cell order, no per-detection tables asked for
+    if (ws.gather and not scatter and groups is None and match_gt is None
+            and ws.match_gt is None and ws.ious_out is None):
+        _lib.check(lib.taoamd_match_compact(
+            dp.n_cells, _ptr(t["cell_dt_off"]), _ptr(t["cell_gt_off"]), dp.max_g,
+            _ptr(t["dt_box"]), _ptr(t["gt_box"]), dp.n_rng, _ptr(ws.gt_rng),
+            _ptr(t["gt_flags"]), _ptr(t["dt_flags"]), _ptr(ws._rows), _ptr(ws.compact_buf),
+            _ptr(t["dt_group"]), _ptr(t["dt_meta"]), g_ptr, n_g, s_ptr, n_s, s),
+            "taoamd_match_compact")
+        ws.rows_pending = True
+        return
+    if groups is None:
+        ws.rows_pending = False       # (every row is stored in full)
     _lib.check(lib.taoamd_match(
         dp.n_cells, _ptr(t["cell_dt_off"]), _ptr(t["cell_gt_off"]),
         _ptr(t["cell_iou_off"]), dp.max_g,
@@ -968,7 +1012,16 @@ def stage_accumulate_by_order(dp, ws):
     """The sweep over rows the match left in cell order (stage_match(scatter=
     False)): gathered through the sort's order[] by the first sweep."""
     lib, t, s = _lib.load(), dp.t, _stream()
-    fn = lib.taoamd_accumulate_by_order_prepared if ws.acc_prepared == _plan_key(dp) \
+    key = _plan_key(dp)
+    if ws.rows_pending and key[1] in (2, 3):
+        # (the one-pass sweep reads the 4-byte words; `rows` stays unexpanded)
+        _lib.check(lib.taoamd_accumulate_by_order_compact(
+            dp.n_dt, dp.n_cat, dp.n_rng, _ptr(t["cat_off"]), _ptr(ws.order),
+            _ptr(ws.compact_buf), _ptr(ws._rows), _ptr(ws.num_gt), dp.acc_hint,
+            _ptr(ws.precision), _ptr(ws.recall), _ptr(ws.acc_ws), ws.acc_bytes,
+            int(ws.acc_prepared == key), s), "taoamd_accumulate_by_order_compact")
+        return
+    fn = lib.taoamd_accumulate_by_order_prepared if ws.acc_prepared == key \
         else lib.taoamd_accumulate_by_order
     _lib.check(fn(
         dp.n_dt, dp.n_cat, dp.n_rng, _ptr(t["cat_off"]), _ptr(ws.order),
