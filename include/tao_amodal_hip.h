@@ -249,6 +249,15 @@ int taoamd_track_mask_iou(int64_t n_cells, const int32_t *cell_dt_off,
  *   task_base  int32[n_tasks]  a task's first piece
  * A task stages its tracks' frames in LDS chunk by chunk of the timeline and
  * adds the per-frame terms in ascending timeline order, one lane per pair.
+ *   zero_out   int64[n_zero]  the zero list of taoamd_track_iou_plan_spans_host:
+ *              places in `iou` that receive +0.0 (pairs without a common
+ *              timeline position, which that plan keeps out of the tasks).
+ *              They are stored by workgroups of the same launch, behind the
+ *              tasks', in every call: a pass defines every entry of `iou` that
+ *              the tasks and the zero list name, whatever the buffer held.
+ *              n_zero = 0, zero_out = NULL: the tasks alone (the plan of
+ *              taoamd_track_iou_plan_host, whose tasks hold every pair).
+ *              n_tasks = 0 with n_zero > 0 stores the zeros alone.
  * Both forms give bit-identical results. */
 int taoamd_track_iou(int64_t n_cells, const int32_t *cell_dt_off,
                      const int32_t *cell_gt_off, const int64_t *cell_iou_off,
@@ -262,6 +271,7 @@ int taoamd_track_iou_planned(int64_t n_tasks, const int32_t *tasks,
                              const int64_t *task_out, const double *frames,
                              const int32_t *task_base, const int32_t *trk_meta,
                              int32_t mode, double *iou, int64_t *pair_frames,
+                             int64_t n_zero, const int64_t *zero_out,
                              void *stream);
 
 /* The same IoUs when EVERY detection and ground-truth track has exactly one
@@ -381,13 +391,36 @@ int taoamd_pyset_union_order_host(int64_t n_a, const int64_t *a, int64_t n_b,
  * tasks_host == NULL to get sizes[0..2] = tasks, task_rows entries, task_pairs
  * entries; then with buffers of 4 * sizes[0], sizes[1], sizes[2] int32 and
  * sizes[2] int64.  Every (detection track, GT track) pair of every cell lands
- * in exactly one task.  Synchronous, host only. */
+ * in exactly one task, whatever the two tracks' spans.  Synchronous, host only.
+ *
+ * taoamd_track_iou_plan_spans_host is the span-aware plan, packed by the same
+ * rules (cells by descending end of timeline, a cell's detections by first
+ * position, GT blocks of at most 31, tasks of <= 64 pairs and <= 32 rows, rows
+ * by first position).  A ZERO PAIR -- both tracks have a frame (first <= last)
+ * and last_d < first_g or last_g < first_d: no common position, so its result
+ * is +0.0 in every mode -- lands in no task: its place in `iou` goes to
+ * zero_out (ascending), for taoamd_track_iou_planned's (n_zero, zero_out).
+ * Spans that touch (last_d == first_g) share a position and stay in a task, and
+ * so does every pair with a track without frames (the reference's 0 / 0).  A
+ * detection track whose pairs are all zero pairs is a row of no task; a GT
+ * track is a row of a task only if one of that task's pairs uses it.  Every
+ * pair is exactly once in task_out or zero_out.  sizes has FOUR entries here:
+ * sizes[3] = the zero list's length (zero_out_host: sizes[3] int64, filled
+ * whenever it is not NULL).  On an input without zero pairs the four task
+ * arrays equal taoamd_track_iou_plan_host's. */
 int taoamd_track_iou_plan_host(int64_t n_cells, const int32_t *cell_dt_off_host,
                                const int32_t *cell_gt_off_host,
                                const int64_t *cell_iou_off_host,
                                const int32_t *trk_meta_host, int64_t *sizes,
                                int32_t *tasks_host, int32_t *task_rows_host,
                                int32_t *task_pairs_host, int64_t *task_out_host);
+int taoamd_track_iou_plan_spans_host(int64_t n_cells, const int32_t *cell_dt_off_host,
+                                     const int32_t *cell_gt_off_host,
+                                     const int64_t *cell_iou_off_host,
+                                     const int32_t *trk_meta_host, int64_t *sizes,
+                                     int32_t *tasks_host, int32_t *task_rows_host,
+                                     int32_t *task_pairs_host, int64_t *task_out_host,
+                                     int64_t *zero_out_host);
 
 /* ---- greedy assignment --------------------------------------------------------
  * If dt_box/gt_box are non-NULL the IoU matrix of each cell is computed on the

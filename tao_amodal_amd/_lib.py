@@ -59,7 +59,7 @@ SIGNATURES = {
     "taoamd_track_iou_single": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
                                           _vp, _vp, _vp]),
     "taoamd_track_iou_planned": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                           _i32, _vp, _vp, _vp]),
+                                           _i32, _vp, _vp, _i64, _vp, _vp]),
     "taoamd_track_stream": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "taoamd_json_pred_workspace": (_sz, [_sz]),
     "taoamd_json_pred_open": (_vp, [C.c_char_p, _vp, _sz, _vp, C.c_char_p, _sz, _vp]),
@@ -82,6 +82,8 @@ SIGNATURES = {
     "taoamd_pyset_union_order_host": (C.c_int, [_i64, _vp, _i64, _vp, _vp, _vp]),
     "taoamd_track_iou_plan_host": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp,
                                              _vp, _vp, _vp, _vp]),
+    "taoamd_track_iou_plan_spans_host": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp,
+                                                   _vp, _vp, _vp, _vp, _vp]),
     "taoamd_flat_map": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "taoamd_flat_count_bad": (C.c_int, [_i64, _vp, _vp, _vp, _vp]),

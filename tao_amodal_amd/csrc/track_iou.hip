@@ -3,7 +3,9 @@
 //   track_iou_task_kernel  the planned path: one wavefront per task (<= 32
 //                          tracks, <= 64 track pairs), frames staged in LDS
 //                          chunk by chunk of the timeline from the padded frame
-//                          table, lane = pair adds the per-frame terms in order
+//                          table, lane = pair adds the per-frame terms in order;
+//                          workgroups behind the tasks store +0.0 for the pairs
+//                          the span-aware plan kept out (no common position)
 //   track_pad_*            CSR frame lists -> padded frame table
 //   track_iou_kernel       plan-less fallback: lane per pair, two-pointer merge
 //
@@ -237,6 +239,7 @@ __global__ __launch_bounds__(256) void track_iou_single_kernel(
 #define TT_SLOTS (TT_ROUNDS * TT_GROUPS)
 #define TT_FAR 1e300
 #define TT_SETS 2                // chunks between a load and its use (even)
+#define TT_ZERO_PER 8            // zero-list entries per thread of a trailing workgroup
 
 // v_max_f64 / v_min_f64 as such: fmax() / fmin() make the compiler canonicalise
 // every operand it cannot prove free of signalling NaNs (one extra v_max_f64
@@ -390,11 +393,23 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(MODE == 2 ?
     const int32_t *__restrict__ task_pairs, const int64_t *__restrict__ task_out,
     const double4 *__restrict__ frames, const int32_t *__restrict__ task_base,
     const int4 *__restrict__ trk_meta,
-    double *__restrict__ iou, unsigned long long *__restrict__ pair_frames)
+    double *__restrict__ iou, unsigned long long *__restrict__ pair_frames,
+    int32_t n_tasks, int64_t n_zero, const int64_t *__restrict__ zero_out)
 {
     __shared__ __align__(16) double rows[2][TT_ROWS * TT_RS];
     __shared__ int4 meta[TT_SLOTS];
     __shared__ int32_t span[2];               // first chunk start, last position
+
+    // The workgroups behind the tasks write the zero list: the pairs the
+    // span-aware plan kept out of the tasks (no common position: +0.0 in every
+    // mode), so that every pass defines every entry of `iou`.
+    if ((int32_t)blockIdx.x >= n_tasks) {
+        const int64_t stride = (int64_t)(gridDim.x - n_tasks) * blockDim.x;
+        for (int64_t k = (int64_t)(blockIdx.x - n_tasks) * blockDim.x + threadIdx.x;
+             k < n_zero; k += stride)
+            iou[zero_out[k]] = 0.0;
+        return;
+    }
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;        // 0, 1: stagers; 2: adder
@@ -809,29 +824,38 @@ extern "C" int taoamd_track_iou_planned(int64_t n_tasks, const int32_t *tasks,
                                         const int32_t *task_base,
                                         const int32_t *trk_meta, int32_t mode,
                                         double *iou, int64_t *pair_frames,
+                                        int64_t n_zero, const int64_t *zero_out,
                                         void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
-    if (mode < 0 || mode > 2 || n_tasks < 0) return TAOAMD_ERR_ARG;
+    if (mode < 0 || mode > 2 || n_tasks < 0 || n_tasks > INT32_MAX - 4096 || n_zero < 0 ||
+        (n_zero > 0 && !zero_out))
+        return TAOAMD_ERR_ARG;
     if (pair_frames) TAO_HIP(hipMemsetAsync(pair_frames, 0, 8, s));
-    if (n_tasks == 0) return TAOAMD_OK;
-    if (!tasks || !task_rows || !task_pairs || !task_out || !frames || !task_base ||
-        !trk_meta || !iou)
+    if (n_tasks == 0 && n_zero == 0) return TAOAMD_OK;
+    if (!iou || (n_tasks > 0 && (!tasks || !task_rows || !task_pairs || !task_out || !frames ||
+                                 !task_base || !trk_meta)))
         return TAOAMD_ERR_ARG;
     unsigned long long *pf = (unsigned long long *)pair_frames;
+    // trailing workgroups for the zero list: TT_ZERO_PER stores a thread, 4096 at the most
+    const unsigned zero_wgs = (unsigned)std::min<int64_t>(
+        (n_zero + 192 * TT_ZERO_PER - 1) / (192 * TT_ZERO_PER), 4096);
+    const unsigned grid = (unsigned)n_tasks + zero_wgs;
     // (TAOAMD_TT_LDS_PAD: unused dynamic LDS per task, i.e. fewer tasks per CU --
     // a schedule experiment: room for the other level's workgroups beside this kernel)
     static const unsigned lds_pad = getenv("TAOAMD_TT_LDS_PAD") ? (unsigned)atoi(getenv("TAOAMD_TT_LDS_PAD")) : 0u;
 #define TT_LAUNCH(M)                                                           \
     TAO_TIMED("track_iou_task_kernel", s,                                      \
-              track_iou_task_kernel<M><<<(unsigned)n_tasks, 192, lds_pad, s>>>( \
+              track_iou_task_kernel<M><<<grid, 192, lds_pad, s>>>(             \
                   (const int4 *)tasks, task_rows, task_pairs, task_out,        \
-                  (const double4 *)frames, task_base, (const int4 *)trk_meta, iou, pf))
+                  (const double4 *)frames, task_base, (const int4 *)trk_meta, iou, pf, \
+                  (int32_t)n_tasks, n_zero, zero_out))
     if (mode == 0 && pf == nullptr)
         TAO_TIMED("track_iou_task_kernel", s,
-                  (track_iou_task_kernel<0, false><<<(unsigned)n_tasks, 192, lds_pad, s>>>(
+                  (track_iou_task_kernel<0, false><<<grid, 192, lds_pad, s>>>(
                       (const int4 *)tasks, task_rows, task_pairs, task_out,
-                      (const double4 *)frames, task_base, (const int4 *)trk_meta, iou, pf)));
+                      (const double4 *)frames, task_base, (const int4 *)trk_meta, iou, pf,
+                      (int32_t)n_tasks, n_zero, zero_out)));
     else if (mode == 0) TT_LAUNCH(0);
     else if (mode == 1) TT_LAUNCH(1);
     else TT_LAUNCH(2);
@@ -1002,14 +1026,26 @@ extern "C" int taoamd_pyset_union_order_host(int64_t n_a, const int64_t *a, int6
 // longest start first, and the cells that share a task have similar spans);
 // the detection tracks of a cell by first position.  A task is filled track
 // by track: a detection track brings one pair per GT track of its cell's GT
-// block (< TT_ROWS tracks), the block's rows are added when the task does not
-// hold them yet; a task is closed when the next track would exceed 64 pairs or
-// TT_ROWS rows -- so a big cell spills into the next task and the tail of one
-// cell shares a wavefront with the head of the next.
-extern "C" int taoamd_track_iou_plan_host(
-    int64_t n_cells, const int32_t *cell_dt_off, const int32_t *cell_gt_off,
-    const int64_t *cell_iou_off, const int32_t *trk_meta, int64_t *sizes,
-    int32_t *tasks, int32_t *task_rows, int32_t *task_pairs, int64_t *task_out)
+// block (< TT_ROWS tracks) that the plan keeps, a GT track's row is added when
+// the task does not hold it yet; a task is closed when the next track would
+// exceed 64 pairs or TT_ROWS rows -- so a big cell spills into the next task
+// and the tail of one cell shares a wavefront with the head of the next.
+//
+// SPANS (taoamd_track_iou_plan_spans_host): a pair of two tracks that both have
+// a frame and whose spans first .. last do not intersect has no common frame;
+// every per-frame intersection is +0, so the result is +0.0 in every mode
+// (mode 0: 0 / u, or the u > 0 test's 0.0; modes 1, 2: a sum of zeros over a
+// count >= 1).  Such a pair goes to the zero list instead of a task, a
+// detection track that keeps no pair is no row, and a GT track is a row only of
+// tasks that hold one of its kept pairs.  Without SPANS every pair is kept and
+// the first detection track of a block brings all the block's rows: the plan
+// of taoamd_track_iou_plan_host, which the span-aware plan therefore equals on
+// an input without such pairs.
+static int tt_plan(bool spans, int64_t n_cells, const int32_t *cell_dt_off,
+                   const int32_t *cell_gt_off, const int64_t *cell_iou_off,
+                   const int32_t *trk_meta, int64_t *sizes, int32_t *tasks,
+                   int32_t *task_rows, int32_t *task_pairs, int64_t *task_out,
+                   int64_t *zero_out)
 {
     if (n_cells < 0 || !cell_dt_off || !cell_gt_off || !cell_iou_off ||
         !trk_meta || !sizes)
@@ -1019,6 +1055,12 @@ extern "C" int taoamd_track_iou_plan_host(
     const int64_t n_dt = cell_dt_off[n_cells];
     auto first_of = [&](int64_t t) { return trk_meta[4 * t]; };
     auto last_of = [&](int64_t t) { return trk_meta[4 * t + 1]; };
+    // the zero rule: both tracks have a frame, the spans share no position
+    auto zero_pair = [&](int64_t d, int64_t g) {
+        if (!spans) return false;
+        const int32_t fd = first_of(d), ld = last_of(d), fg = first_of(g), lg = last_of(g);
+        return fd <= ld && fg <= lg && (ld < fg || lg < fd);
+    };
     std::vector<int64_t> order;
     std::vector<int32_t> cell_hi(n_cells, -1);
     for (int64_t c = 0; c < n_cells; c++) {
@@ -1032,6 +1074,20 @@ extern "C" int taoamd_track_iou_plan_host(
         cell_hi[c] = hi;
         order.push_back(c);
     }
+    // the zero list in ascending place (cells, detections, GTs as `iou` has them)
+    int64_t nz = 0;
+    if (spans)
+        for (int64_t c = 0; c < n_cells; c++) {
+            if (cell_hi[c] < 0) continue;         // (no pair, or no frame at all)
+            const int32_t d0 = cell_dt_off[c], D = cell_dt_off[c + 1] - d0;
+            const int32_t g0 = cell_gt_off[c], G = cell_gt_off[c + 1] - g0;
+            for (int32_t d = 0; d < D; d++)
+                for (int32_t g = 0; g < G; g++)
+                    if (zero_pair(d0 + d, n_dt + g0 + g)) {
+                        if (zero_out) zero_out[nz] = cell_iou_off[c] + (int64_t)d * G + g;
+                        nz++;
+                    }
+        }
     std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
         return cell_hi[a] > cell_hi[b];
     });
@@ -1081,26 +1137,43 @@ extern "C" int taoamd_track_iou_plan_host(
         for (int32_t gb = 0; gb < gblocks; gb++) {
             const int32_t ga = (int32_t)((int64_t)gb * G / gblocks);
             const int32_t ng = (int32_t)((int64_t)(gb + 1) * G / gblocks) - ga;
-            int32_t grow0 = -1;          // the block's first row in the open task
+            int32_t grow[TT_ROWS];       // the block's GT tracks' rows in the open task, or -1
+            std::fill(grow, grow + ng, -1);
             for (int32_t k = 0; k < D; k++) {
                 const int32_t d = dts[k];
-                if (n_pairs + ng > 64 || n_rows + (grow0 < 0 ? ng : 0) + 1 > TT_ROWS) {
+                int32_t keep[TT_ROWS], nk = 0, fresh = 0;     // kept GTs; those without a row yet
+                for (int32_t g = 0; g < ng; g++)
+                    if (!zero_pair(d0 + d, n_dt + g0 + ga + g)) {
+                        keep[nk++] = g;
+                        fresh += grow[g] < 0;
+                    }
+                if (nk == 0) continue;       // (every pair of the track is on the zero list)
+                // (the track may be a row of the open task already: by its pairs
+                // with an earlier block, where blocks are thin enough to share a task)
+                int32_t drow = -1;
+                for (int32_t r = 0; gb > 0 && r < n_rows; r++)
+                    if (rows[r] == d0 + d) drow = r;
+                if (n_pairs + nk > 64 || n_rows + fresh + (drow < 0) > TT_ROWS) {
                     close();
-                    grow0 = -1;
+                    std::fill(grow, grow + ng, -1);
+                    fresh = nk;
+                    drow = -1;
                 }
-                if (grow0 < 0) {
-                    grow0 = n_rows;
-                    for (int32_t g = 0; g < ng; g++)
-                        rows[n_rows++] = (int32_t)(n_dt + g0 + ga + g);
+                for (int32_t j = 0; j < nk; j++)
+                    if (grow[keep[j]] < 0) {
+                        grow[keep[j]] = n_rows;
+                        rows[n_rows++] = (int32_t)(n_dt + g0 + ga + keep[j]);
+                    }
+                if (drow < 0) {
+                    drow = n_rows;
+                    rows[n_rows++] = d0 + d;
                 }
-                rows[n_rows] = d0 + d;
-                for (int32_t g = 0; g < ng; g++) {
-                    pair_d[n_pairs] = n_rows;
-                    pair_g[n_pairs] = grow0 + g;
-                    pair_out[n_pairs] = cell_iou_off[c] + (int64_t)d * G + ga + g;
+                for (int32_t j = 0; j < nk; j++) {
+                    pair_d[n_pairs] = drow;
+                    pair_g[n_pairs] = grow[keep[j]];
+                    pair_out[n_pairs] = cell_iou_off[c] + (int64_t)d * G + ga + keep[j];
                     n_pairs++;
                 }
-                n_rows++;
             }
         }
     }
@@ -1109,5 +1182,25 @@ extern "C" int taoamd_track_iou_plan_host(
     sizes[0] = nt;
     sizes[1] = nr;
     sizes[2] = np;
+    if (spans) sizes[3] = nz;
     return TAOAMD_OK;
+}
+
+extern "C" int taoamd_track_iou_plan_host(
+    int64_t n_cells, const int32_t *cell_dt_off, const int32_t *cell_gt_off,
+    const int64_t *cell_iou_off, const int32_t *trk_meta, int64_t *sizes,
+    int32_t *tasks, int32_t *task_rows, int32_t *task_pairs, int64_t *task_out)
+{
+    return tt_plan(false, n_cells, cell_dt_off, cell_gt_off, cell_iou_off, trk_meta, sizes,
+                   tasks, task_rows, task_pairs, task_out, nullptr);
+}
+
+extern "C" int taoamd_track_iou_plan_spans_host(
+    int64_t n_cells, const int32_t *cell_dt_off, const int32_t *cell_gt_off,
+    const int64_t *cell_iou_off, const int32_t *trk_meta, int64_t *sizes,
+    int32_t *tasks, int32_t *task_rows, int32_t *task_pairs, int64_t *task_out,
+    int64_t *zero_out)
+{
+    return tt_plan(true, n_cells, cell_dt_off, cell_gt_off, cell_iou_off, trk_meta, sizes,
+                   tasks, task_rows, task_pairs, task_out, zero_out);
 }

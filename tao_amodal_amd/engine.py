@@ -136,30 +136,43 @@ def track_meta(flat):
     return np.concatenate(metas), sides, n_slots
 
 
-def track_iou_plan(flat, meta):
-    """Launch plan of taoamd_track_iou_planned (one wavefront per task: up to
-    32 tracks, up to 64 track pairs).  Returns tasks[n, 4], task_rows,
-    task_pairs (int32) and task_out (int64)."""
-    import ctypes as C
+def _track_iou_plan(flat, meta, spans):
+    """The two-call protocol of the plan functions: sizes, then the tables."""
     lib = _lib.load()
+    name = "taoamd_track_iou_plan_spans_host" if spans else "taoamd_track_iou_plan_host"
     d_off = np.ascontiguousarray(flat.cell_dt_off, dtype=np.int32)
     g_off = np.ascontiguousarray(flat.cell_gt_off, dtype=np.int32)
     i_off = np.ascontiguousarray(flat.cell_iou_off, dtype=np.int64)
     meta = np.ascontiguousarray(meta, dtype=np.int32)
-    sizes = np.zeros(3, dtype=np.int64)
+    sizes = np.zeros(4 if spans else 3, dtype=np.int64)
     args = (len(d_off) - 1, d_off.ctypes.data, g_off.ctypes.data,
             i_off.ctypes.data, meta.ctypes.data, sizes.ctypes.data)
-    _lib.check(lib.taoamd_track_iou_plan_host(*args, None, None, None, None),
-               "taoamd_track_iou_plan_host")
-    tasks = np.zeros((int(sizes[0]), 4), dtype=np.int32)
-    rows = np.zeros(int(sizes[1]), dtype=np.int32)
-    pairs = np.zeros(int(sizes[2]), dtype=np.int32)
-    out = np.zeros(int(sizes[2]), dtype=np.int64)
-    if sizes[0]:
-        _lib.check(lib.taoamd_track_iou_plan_host(
-            *args, tasks.ctypes.data, rows.ctypes.data, pairs.ctypes.data,
-            out.ctypes.data), "taoamd_track_iou_plan_host")
-    return tasks, rows, pairs, out
+    _lib.check(getattr(lib, name)(*args, *([None] * (5 if spans else 4))), name)
+    tabs = [np.zeros((int(sizes[0]), 4), dtype=np.int32),
+            np.zeros(int(sizes[1]), dtype=np.int32),
+            np.zeros(int(sizes[2]), dtype=np.int32),
+            np.zeros(int(sizes[2]), dtype=np.int64)]
+    if spans:
+        tabs.append(np.zeros(int(sizes[3]), dtype=np.int64))
+    if sizes[0] or (spans and sizes[3]):
+        _lib.check(getattr(lib, name)(*args, *(t.ctypes.data for t in tabs)), name)
+    return tuple(tabs)
+
+
+def track_iou_plan(flat, meta):
+    """Launch plan of taoamd_track_iou_planned with every pair in a task (one
+    wavefront per task: up to 32 tracks, up to 64 track pairs).  Returns
+    tasks[n, 4], task_rows, task_pairs (int32) and task_out (int64)."""
+    return _track_iou_plan(flat, meta, False)
+
+
+def track_iou_plan_spans(flat, meta):
+    """The span-aware launch plan (taoamd_track_iou_plan_spans_host), the one
+    the engine uses: pairs of two tracks whose spans first .. last share no
+    position are +0.0 in every mode and go to a zero list instead of a task.
+    Returns tasks[n, 4], task_rows, task_pairs (int32), task_out and zero_out
+    (int64)."""
+    return _track_iou_plan(flat, meta, True)
 
 
 class DeviceProblem:
@@ -348,7 +361,7 @@ class DeviceProblem:
         if self.single_frame:
             self.exact_terms = True
             return
-        tasks, rows, pairs, out = track_iou_plan(flat, meta)
+        tasks, rows, pairs, out, zero = track_iou_plan_spans(flat, meta)
         self.n_tasks = len(tasks)
         if self.n_tasks == 0:
             return
@@ -357,6 +370,7 @@ class DeviceProblem:
         self.t["task_rows"] = torch.from_numpy(rows).to(dev)
         self.t["task_pairs"] = torch.from_numpy(pairs).to(dev)
         self.t["task_out"] = torch.from_numpy(out).to(dev)
+        self.t["zero_out"] = torch.from_numpy(zero).to(dev)
         self.t["trk_meta"] = torch.from_numpy(
             np.ascontiguousarray(meta, dtype=np.int32)).to(dev)
         padded = torch.empty((n_slots, 4), dtype=torch.float64, device=dev)
@@ -411,7 +425,7 @@ class DeviceProblem:
             self._drop_plan()
 
     PLAN_TABLES = ("tasks", "task_rows", "task_pairs", "task_out", "frames",
-                   "task_base", "trk_meta")
+                   "task_base", "trk_meta", "zero_out")
 
     def _drop_plan(self):
         """No launch plan: stage_track_iou takes the plan-less merge kernel."""
@@ -745,7 +759,8 @@ def stage_track_iou(dp, ws):
             dp.n_tasks, _ptr(t["tasks"]), _ptr(t["task_rows"]),
             _ptr(t["task_pairs"]), _ptr(t["task_out"]), _ptr(t["frames"]),
             _ptr(t["task_base"]), _ptr(t["trk_meta"]), dp.iou_mode, _ptr(ws.iou),
-            None if counted else _ptr(ws.pair_frames), s), "taoamd_track_iou_planned")
+            None if counted else _ptr(ws.pair_frames), int(t["zero_out"].numel()),
+            _ptr(t["zero_out"]), s), "taoamd_track_iou_planned")
         ws.pairs_counted = True
         return
     _lib.check(lib.taoamd_track_iou(
