@@ -998,6 +998,97 @@ int taoamd_error_types(int64_t n_dt, int64_t n_gt, int32_t n_img, int32_t n_cat,
                        uint8_t *dt_type, void *workspace, size_t workspace_bytes,
                        void *stream);
 
+/* taoamd_error_types with the links a fix would hand every detection: the same
+ * pass, outputs and workspace (taoamd_error_types_workspace), plus, per
+ * (detection d, range a),
+ *   link_same   int32[n_dt][n_rng]  the argmax row of s (-1: none), the rule above
+ *   link_other  int32[n_dt][n_rng]  the argmax row of o under the same rule: the
+ *               LOWEST ground-truth row among equal IoUs, a NaN IoU no overlap
+ * for every row, whatever its type (a row no image lists: -1), and
+ *   held        uint8[n_rng][n_gt]  1 where some detection's match_gt names the
+ *               ground truth at (a, slot): the complement of `missed`.
+ * All three are required (TAOAMD_ERR_ARG otherwise) and zeroed / filled by the call. */
+int taoamd_error_types_links(int64_t n_dt, int64_t n_gt, int32_t n_img, int32_t n_cat,
+                             int32_t n_rng, int32_t slot, double bg_thr,
+                             const int32_t *dt_cat, const double *dt_box,
+                             const uint8_t *dt_flags, const int32_t *dt_gt0,
+                             const int32_t *match_gt, int64_t match_stride,
+                             const int32_t *gt_cat, const double *gt_box,
+                             const uint32_t *gt_rng, const int32_t *img_gt_off,
+                             const int32_t *img_gt, const int32_t *img_dt_off,
+                             const int32_t *img_dt, int64_t *dt_counts, int64_t *gt_counts,
+                             uint8_t *dt_type, int32_t *link_same, int32_t *link_other,
+                             uint8_t *held, void *workspace, size_t workspace_bytes,
+                             void *stream);
+
+/* ---- error impact: the AP each error type costs (csrc/error_impact.hip) ------------
+ * TIDE's dAP on the tables of an error breakdown: the precision the evaluation
+ * would reach if every error of one type were fixed.  The definition is this
+ * library's.  Level-agnostic: the call reads type bytes, links, scores and the
+ * sort's order[], neither boxes nor images.
+ *
+ * Context: one error_types call (one slot, tf, tb, all n_rng ranges) and its
+ * terms.  link_same / link_other / held as above.
+ * Base list of (category c, range a): the rows order[cat_off[c] .. cat_off[c + 1])
+ * -- sweep order: stable descending score, NaN scores last --; a row of type TP
+ * is a true positive, types DUP to BKG are false positives, IGNORED rows and
+ * any byte >= 7 are dropped; num_gt = evaluated.  Precision at the calling
+ * thread's rec_thrs (ascending) by the arithmetic of taoamd_accumulate for one
+ * threshold (reference lvis_amodal/eval.py:370-417): pr = tp / (fp + tp +
+ * np.spacing(1)), the envelope from the right, searchsorted(rc, rec_thrs,
+ * "left"), 0 from the first threshold never reached, -1 for the whole
+ * category where num_gt == 0.
+ * Nine variants, each a fix applied to the base alone, in this order:
+ *   0 BASE
+ *   1 CLS   a CLS row leaves its category's list.  Where its link_other g is
+ *           not held, the WINNER among the CLS rows of range a linking g (of
+ *           any category) joins the list of g's category as a true positive,
+ *           after every row of that list whose score is >= its own, at the very
+ *           end if its score is a NaN.  Adopted rows are all true positives, so
+ *           their order among themselves cannot change a precision value.
+ *   2 LOC   a LOC row whose link_same is held leaves; among the LOC rows of
+ *           range a that link the same missed ground truth the WINNER becomes a
+ *           true positive at its own place, the others leave.  (A LOC row
+ *           without a link -- tb = 0, no ground truth of its category -- stays a
+ *           false positive.)
+ *   3 BOTH, 4 DUP, 5 BKG   the rows of that type leave
+ *   6 MISS  num_gt' = evaluated - the missed ground truths that no LOC row
+ *           links by link_same and no CLS row links by link_other in range a;
+ *           the rows are BASE's
+ *   7 FP    every row of types DUP to BKG leaves
+ *   8 FN    num_gt' = evaluated - missed; the rows are BASE's
+ * WINNER: the greatest score; equal scores (-0.0 == 0.0) go to the lowest table
+ * row; a NaN score loses to every number, between two NaNs the lower row wins.
+ * A (category, range) whose num_gt' is 0 is -1 like num_gt == 0.
+ * The table follows match_gt like the breakdown: where a ground truth carries
+ * TAOAMD_GT_ID_HIDDEN and holds a detection, BASE differs from the sweep of
+ * taoamd_accumulate; everywhere else BASE is bit-identical to its precision at
+ * the slot.
+ *
+ *   cat_off  int32[n_cat + 1], order int32[n_dt]: the sort's tables
+ *   score    double[n_dt], dt_cat int32[n_dt], dt_type uint8[n_dt][n_rng]: by table row
+ *   gt_cat   int32[n_gt], gt_rng uint32[n_gt]
+ * Outputs: precision double[9][101][n_cat][n_rng], num_gt int32[9][n_cat][n_rng]
+ * (num_gt' of every variant).  Rows, links and categories outside the tables
+ * are skipped, never dereferenced (a CLS row with such a link leaves its list
+ * and nothing is adopted; an entry of order[] outside the table is a row of no
+ * list, and the place of an adopted row, found by bisection, is then undefined).  TAOAMD_ERR_ARG: n_rng outside [1, 8], n_cat <= 0,
+ * sizes outside [0, 2^31), a missing table; TAOAMD_ERR_WORKSPACE: fewer bytes
+ * than taoamd_error_impact_workspace(n_dt, n_gt, n_cat, n_rng) (the winners, 12
+ * bytes per (table, range, ground truth); the adopted rows per insertion slot,
+ * 4 bytes per (range, row); any base address, contents need not be
+ * initialised). */
+#define TAOAMD_ERROR_IMPACT_FIXES 9
+#define TAOAMD_ERROR_IMPACT_CHUNK 256  /* insertion slots + rows of a category per sweep step */
+size_t taoamd_error_impact_workspace(int64_t n_dt, int64_t n_gt, int32_t n_cat, int32_t n_rng);
+int taoamd_error_impact(int64_t n_dt, int64_t n_gt, int32_t n_cat, int32_t n_rng,
+                        const int32_t *cat_off, const int32_t *order, const double *score,
+                        const int32_t *dt_cat, const uint8_t *dt_type,
+                        const int32_t *link_same, const int32_t *link_other,
+                        const int32_t *gt_cat, const uint32_t *gt_rng, const uint8_t *held,
+                        double *precision, int32_t *num_gt, void *workspace,
+                        size_t workspace_bytes, void *stream);
+
 /* ---- track-level error breakdown per range (csrc/track_error_types.hip) ------------
  * WHY a detection track is no true positive, per (area, time) range and
  * category: the section above, rule for rule, on the track tables.  The

@@ -22,6 +22,8 @@ SEGMENT_TILE = 2816
 ERROR_TYPES_TILE = 256
 TRACK_ERROR_TYPES_TILE = 16
 ERROR_TYPES = ("TP", "IGNORED", "DUP", "LOC", "CLS", "BOTH", "BKG")
+ERROR_IMPACT_CHUNK = 256
+ERROR_FIXES = ("BASE", "CLS", "LOC", "BOTH", "DUP", "BKG", "MISS", "FP", "FN")
 
 _vp, _i64, _i32, _sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
 
@@ -192,6 +194,13 @@ SIGNATURES = {
     "taoamd_error_types": (C.c_int, [_i64, _i64, _i32, _i32, _i32, _i32, C.c_double,
                                      _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "taoamd_error_types_links": (C.c_int, [_i64, _i64, _i32, _i32, _i32, _i32, C.c_double,
+                                           _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _sz, _vp]),
+    "taoamd_error_impact_workspace": (_sz, [_i64, _i64, _i32, _i32]),
+    "taoamd_error_impact": (C.c_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "taoamd_track_error_types_workspace": (_sz, [_i64, _i64, _i32]),
     "taoamd_track_error_types": (C.c_int, [_i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
                                            C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _i64,

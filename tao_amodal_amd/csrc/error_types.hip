@@ -36,6 +36,9 @@
 //   err_tally_kernel  lane = ground truth: the three counts per (range,
 //                     category) from the two byte tables the pair kernel marks
 // Counts are integers, marks are stores of 1: nothing depends on an order.
+// taoamd_error_types_links is the same pass with the pair kernel's LINKS form:
+// it also keeps the argmax of o and stores both argmaxes per (detection, range)
+// and the held marks in the caller's tables, for error_impact.hip.
 #include "common.hpp"
 #include "workspace.hpp"
 
@@ -67,6 +70,7 @@ struct ErrArgs {
     uint8_t *types;                  // [n_dt][n_rng]: the caller's dt_type, else the workspace's
     uint8_t *ws_types;
     uint8_t *gt_hit, *gt_loc;        // [n_rng][n_gt]
+    int32_t *link_same, *link_other; // [n_dt][n_rng], taoamd_error_types_links only
 };
 
 // One add per distinct key among the wavefront's live lanes: the leader of the
@@ -83,6 +87,9 @@ __device__ __forceinline__ void err_count(unsigned long long *base, bool live, i
     }
 }
 
+// LINKS: the argmax of o under the rule of s, and both argmaxes stored per
+// (detection, range) -- what a fix would hand the detection (error_impact.hip)
+template <bool LINKS>
 __global__ __launch_bounds__(ERR_TILE) void err_pair_kernel(ErrArgs a)
 {
     __shared__ double4 s_box[ERR_TILE];
@@ -119,8 +126,13 @@ __global__ __launch_bounds__(ERR_TILE) void err_pair_kernel(ErrArgs a)
         }
         double s[ERR_RMAX], o[ERR_RMAX];
         int32_t arg[ERR_RMAX];
+        int32_t arg_o[LINKS ? ERR_RMAX : 1];
 #pragma unroll
         for (int r = 0; r < ERR_RMAX; r++) { s[r] = 0.0; o[r] = 0.0; arg[r] = -1; }
+        if (LINKS) {
+#pragma unroll
+            for (int r = 0; r < ERR_RMAX; r++) arg_o[LINKS ? r : 0] = -1;
+        }
 
         for (int64_t g0 = g_lo; g0 < g_hi; g0 += ERR_TILE) {
             const int ng = (int)min((int64_t)ERR_TILE, g_hi - g0);
@@ -149,7 +161,13 @@ __global__ __launch_bounds__(ERR_TILE) void err_pair_kernel(ErrArgs a)
                     const bool in = (open >> r) & 1u;
                     const bool up_s = in && same &&
                         (v > s[r] || (v == s[r] && (uint32_t)M.z < (uint32_t)arg[r]));
-                    const bool up_o = in && !same && v > o[r];
+                    bool up_o = in && !same && v > o[r];
+                    if (LINKS) {
+                        const int q = LINKS ? r : 0;
+                        up_o = up_o || (in && !same && v == o[r] &&
+                                        (uint32_t)M.z < (uint32_t)arg_o[q]);
+                        arg_o[q] = up_o ? M.z : arg_o[q];
+                    }
                     s[r] = up_s ? v : s[r];
                     arg[r] = up_s ? M.z : arg[r];
                     o[r] = up_o ? v : o[r];
@@ -179,6 +197,10 @@ __global__ __launch_bounds__(ERR_TILE) void err_pair_kernel(ErrArgs a)
                 ty = ERR_BOTH;
             }
             if (valid) a.types[d * a.n_rng + r] = (uint8_t)ty;
+            if (LINKS && valid) {
+                a.link_same[d * a.n_rng + r] = arg[r];
+                a.link_other[d * a.n_rng + r] = arg_o[LINKS ? r : 0];
+            }
         }
     }
 }
@@ -234,18 +256,20 @@ extern "C" size_t taoamd_error_types_workspace(int64_t n_dt, int64_t n_gt, int32
     return measure([&](Carve &c) { err_layout(c, n_dt, n_gt, n_rng, a); });
 }
 
-extern "C" int taoamd_error_types(int64_t n_dt, int64_t n_gt, int32_t n_img, int32_t n_cat,
-                                  int32_t n_rng, int32_t slot, double bg_thr,
-                                  const int32_t *dt_cat, const double *dt_box,
-                                  const uint8_t *dt_flags, const int32_t *dt_gt0,
-                                  const int32_t *match_gt, int64_t match_stride,
-                                  const int32_t *gt_cat, const double *gt_box,
-                                  const uint32_t *gt_rng, const int32_t *img_gt_off,
-                                  const int32_t *img_gt, const int32_t *img_dt_off,
-                                  const int32_t *img_dt, int64_t *dt_counts,
-                                  int64_t *gt_counts, uint8_t *dt_type, void *workspace,
-                                  size_t workspace_bytes, void *stream)
+static int err_run(int64_t n_dt, int64_t n_gt, int32_t n_img, int32_t n_cat,
+                   int32_t n_rng, int32_t slot, double bg_thr,
+                   const int32_t *dt_cat, const double *dt_box,
+                   const uint8_t *dt_flags, const int32_t *dt_gt0,
+                   const int32_t *match_gt, int64_t match_stride,
+                   const int32_t *gt_cat, const double *gt_box,
+                   const uint32_t *gt_rng, const int32_t *img_gt_off,
+                   const int32_t *img_gt, const int32_t *img_dt_off,
+                   const int32_t *img_dt, int64_t *dt_counts,
+                   int64_t *gt_counts, uint8_t *dt_type, int32_t *link_same,
+                   int32_t *link_other, uint8_t *held, void *workspace,
+                   size_t workspace_bytes, void *stream)
 {
+    const bool links = link_same != nullptr;
     if (n_dt < 0 || n_dt > 0x7fffffff || n_gt < 0 || n_gt > 0x7fffffff || n_img < 0 ||
         n_cat <= 0 || n_rng < 1 || n_rng > ERR_RMAX || slot < 0 || slot >= N_THR)
         return TAOAMD_ERR_ARG;
@@ -272,6 +296,8 @@ extern "C" int taoamd_error_types(int64_t n_dt, int64_t n_gt, int32_t n_img, int
     a.dt_counts = (unsigned long long *)dt_counts;
     a.gt_counts = (unsigned long long *)gt_counts;
     a.types = dt_type ? dt_type : a.ws_types;
+    a.link_same = link_same; a.link_other = link_other;
+    if (links) a.gt_hit = held;      // the marks of the pair kernel, in the caller's table
     const size_t cells = (size_t)n_rng * n_cat;
     TAO_HIP(hipMemsetAsync(dt_counts, 0, cells * ERR_NTYPE * sizeof(int64_t), s));
     TAO_HIP(hipMemsetAsync(gt_counts, 0, cells * ERR_NGT * sizeof(int64_t), s));
@@ -279,9 +305,19 @@ extern "C" int taoamd_error_types(int64_t n_dt, int64_t n_gt, int32_t n_img, int
         TAO_HIP(hipMemsetAsync(a.gt_hit, 0, (size_t)n_gt * n_rng, s));
         TAO_HIP(hipMemsetAsync(a.gt_loc, 0, (size_t)n_gt * n_rng, s));
     }
-    if (n_dt > 0 && n_img > 0)
-        TAO_TIMED("err_pair_kernel", s,
-                  err_pair_kernel<<<(unsigned)n_img, ERR_TILE, 0, s>>>(a));
+    if (links && n_dt > 0) {
+        // (a row no image lists links nothing)
+        TAO_HIP(hipMemsetAsync(link_same, 0xff, (size_t)n_dt * n_rng * sizeof(int32_t), s));
+        TAO_HIP(hipMemsetAsync(link_other, 0xff, (size_t)n_dt * n_rng * sizeof(int32_t), s));
+    }
+    if (n_dt > 0 && n_img > 0) {
+        if (links)
+            TAO_TIMED("err_pair_links_kernel", s,
+                      err_pair_kernel<true><<<(unsigned)n_img, ERR_TILE, 0, s>>>(a));
+        else
+            TAO_TIMED("err_pair_kernel", s,
+                      err_pair_kernel<false><<<(unsigned)n_img, ERR_TILE, 0, s>>>(a));
+    }
     if (n_dt > 0)
         TAO_TIMED("err_count_kernel", s,
                   err_count_kernel<<<(unsigned)((n_dt + 255) / 256), 256, 0, s>>>(a));
@@ -290,4 +326,45 @@ extern "C" int taoamd_error_types(int64_t n_dt, int64_t n_gt, int32_t n_img, int
                   err_tally_kernel<<<(unsigned)((n_gt + 255) / 256), 256, 0, s>>>(a));
     TAO_LAUNCH_CHECK();
     return TAOAMD_OK;
+}
+
+extern "C" int taoamd_error_types(int64_t n_dt, int64_t n_gt, int32_t n_img, int32_t n_cat,
+                                  int32_t n_rng, int32_t slot, double bg_thr,
+                                  const int32_t *dt_cat, const double *dt_box,
+                                  const uint8_t *dt_flags, const int32_t *dt_gt0,
+                                  const int32_t *match_gt, int64_t match_stride,
+                                  const int32_t *gt_cat, const double *gt_box,
+                                  const uint32_t *gt_rng, const int32_t *img_gt_off,
+                                  const int32_t *img_gt, const int32_t *img_dt_off,
+                                  const int32_t *img_dt, int64_t *dt_counts,
+                                  int64_t *gt_counts, uint8_t *dt_type, void *workspace,
+                                  size_t workspace_bytes, void *stream)
+{
+    return err_run(n_dt, n_gt, n_img, n_cat, n_rng, slot, bg_thr, dt_cat, dt_box, dt_flags,
+                   dt_gt0, match_gt, match_stride, gt_cat, gt_box, gt_rng, img_gt_off, img_gt,
+                   img_dt_off, img_dt, dt_counts, gt_counts, dt_type, nullptr, nullptr, nullptr,
+                   workspace, workspace_bytes, stream);
+}
+
+// The same pass with the links of every (detection, range) and the held marks
+// stored for taoamd_error_impact; counts and types are those of
+// taoamd_error_types, the workspace is its workspace.
+extern "C" int taoamd_error_types_links(int64_t n_dt, int64_t n_gt, int32_t n_img,
+                                        int32_t n_cat, int32_t n_rng, int32_t slot,
+                                        double bg_thr, const int32_t *dt_cat,
+                                        const double *dt_box, const uint8_t *dt_flags,
+                                        const int32_t *dt_gt0, const int32_t *match_gt,
+                                        int64_t match_stride, const int32_t *gt_cat,
+                                        const double *gt_box, const uint32_t *gt_rng,
+                                        const int32_t *img_gt_off, const int32_t *img_gt,
+                                        const int32_t *img_dt_off, const int32_t *img_dt,
+                                        int64_t *dt_counts, int64_t *gt_counts, uint8_t *dt_type,
+                                        int32_t *link_same, int32_t *link_other, uint8_t *held,
+                                        void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!link_same || !link_other || !held) return TAOAMD_ERR_ARG;
+    return err_run(n_dt, n_gt, n_img, n_cat, n_rng, slot, bg_thr, dt_cat, dt_box, dt_flags,
+                   dt_gt0, match_gt, match_stride, gt_cat, gt_box, gt_rng, img_gt_off, img_gt,
+                   img_dt_off, img_dt, dt_counts, gt_counts, dt_type, link_same, link_other, held,
+                   workspace, workspace_bytes, stream);
 }

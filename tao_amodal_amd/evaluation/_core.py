@@ -247,6 +247,34 @@ class GpuRun:
         engine.stage_track_error_types at the track level; the definitions are
         in include/tao_amodal_hip.h), from the pass the workspace holds after
         evaluate()."""
+        track = self.flat.kind == "tao"
+        c, slot = self._error_pass_at(thr_index)
+        e = self.engine
+        with timed("kernels"), applied(c):
+            stage = e.stage_track_error_types if track else e.stage_error_types
+            stage(self.dp, self.ws, slot, bg_thr, per_detection)
+            self.torch.cuda.synchronize(self.device)
+        with timed("download"):
+            dt_counts = self.ws.err_dt_counts.cpu().numpy()
+            gt_counts = self.ws.err_gt_counts.cpu().numpy()
+            dt_type = self.ws.err_dt_type[:self.dp.n_dt].cpu().numpy() if per_detection \
+                else None
+        if c is not None:
+            # kernel range slot -> the caller's range
+            ks = self._range_slots(c)
+            dt_counts, gt_counts = dt_counts[ks], gt_counts[ks]
+            if dt_type is not None:
+                dt_type = np.ascontiguousarray(dt_type[:, ks])
+        return dt_counts, gt_counts, dt_type
+
+    @staticmethod
+    def _range_slots(c):
+        return [k for k, _ in sorted(c.rng_blocks[0][1], key=lambda ki: ki[1])]
+
+    def _error_pass_at(self, thr_index):
+        """What error_table() and impact_table() share: the refusals, the
+        kernels' slot of the caller's threshold, and the match pass where
+        evaluate() left it out.  Returns (constants, slot)."""
         c = self.constants
         track = self.flat.kind == "tao"
         if track and self.iou_3d_type != "3d_iou":
@@ -272,21 +300,39 @@ class GpuRun:
                               head=not self._head_done,
                               match_gt=e.error_match_gt(self.dp, self.ws))
                 self._head_done = self._error_pass = True
-            stage = e.stage_track_error_types if track else e.stage_error_types
-            stage(self.dp, self.ws, slot, bg_thr, per_detection)
+        return c, slot
+
+    def impact_table(self, thr_index, bg_thr):
+        """(precision[9, R, K, n_rng], num_gt[9, K, n_rng]) of the nine fixes at
+        the caller's `thr_index`-th IoU threshold: recall thresholds and ranges
+        in the caller's order (engine.stage_error_impact; the definition is in
+        include/tao_amodal_hip.h), from the pass the workspace holds after
+        evaluate().  Refuses what error_table() refuses, in its words."""
+        if self.flat.kind == "tao":
+            raise NotImplementedError("error_impact() is the image level's")
+        c = self.constants
+        if c is not None and len(c.thr_blocks) == 1 and len(c.rng_blocks) == 1 \
+                and len(c.rec_blocks) > 1:
+            raise NotImplementedError(
+                "error_impact() is kept for up to %d recall thresholds" % N_REC)
+        c, slot = self._error_pass_at(thr_index)
+        with timed("kernels"), applied(c):
+            self.engine.stage_error_impact(self.dp, self.ws, slot, bg_thr)
             self.torch.cuda.synchronize(self.device)
         with timed("download"):
-            dt_counts = self.ws.err_dt_counts.cpu().numpy()
-            gt_counts = self.ws.err_gt_counts.cpu().numpy()
-            dt_type = self.ws.err_dt_type[:self.dp.n_dt].cpu().numpy() if per_detection \
-                else None
-        if c is not None:
-            # kernel range slot -> the caller's range
-            ks = [k for k, _ in sorted(c.rng_blocks[0][1], key=lambda ki: ki[1])]
-            dt_counts, gt_counts = dt_counts[ks], gt_counts[ks]
-            if dt_type is not None:
-                dt_type = np.ascontiguousarray(dt_type[:, ks])
-        return dt_counts, gt_counts, dt_type
+            p = self.ws.imp_precision.cpu().numpy()
+            num_gt = self.ws.imp_num_gt.cpu().numpy().astype(np.int64)
+        if c is None:
+            return p, num_gt
+        ks = self._range_slots(c)
+        r_idx = c.rec_blocks[0][0]
+        out = np.empty((p.shape[0], c.R) + p.shape[2:3] + (len(ks),))
+        out[:, r_idx] = p[:, :c.R][..., ks]
+        if not c.rec_sorted:
+            # the reference fills a row IN THE CALLER'S ORDER and stops at the
+            # first threshold the category never reaches (see accumulate)
+            out[np.maximum.accumulate(out == 0, axis=1)] = 0
+        return out, num_gt[..., ks]
 
     def pointer_tables(self):
         """What eval['dt_pointers'] is read from: the detections' ids and

@@ -423,6 +423,9 @@ class DistRun:
             "error_types() in a multi-GPU run: an image's (a video's) ground truths of "
             "other categories live on other ranks")
 
+    def impact_table(self, thr_index, bg_thr):
+        return self.error_table(thr_index, bg_thr)         # raises
+
     def pointer_tables(self):
         if self._pointers is None:
             raise NotImplementedError(

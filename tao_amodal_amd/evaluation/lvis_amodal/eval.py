@@ -97,6 +97,7 @@ class LVISEval:
         self._run = None
         self._cat_pos = None
         self._error_types = {}
+        self._error_impact = {}
 
     # ------------------------------------------------------------ stages
     def evaluate(self):
@@ -138,6 +139,7 @@ class LVISEval:
         else:
             self._run = GpuRun(flat, self.device, constants=constants)
         self._error_types = {}
+        self._error_impact = {}
         self._run.evaluate()
         view = CellView(self._run, flat.img_ids, 0, "image_id", "visibility_rng",
                         self.params.visibility_rng)
@@ -319,6 +321,70 @@ class LVISEval:
                  " " + " " * w + "".join("{:>11s}".format(c) for c in cols)]
         for name, r in zip(lbl, rows):
             lines.append(" " + name.ljust(w) + "".join("{:>11d}".format(int(v)) for v in r))
+        return lines
+
+    def error_impact(self, iou_thr=0.5, bg_thr=0.1):
+        """The AP each error type costs, per visibility range: TIDE's dAP (Bolya
+        et al., ECCV 2020) on the table of error_types(iou_thr, bg_thr).  For
+        each of nine variants of the evaluation -- BASE and one fix each, a fix
+        applied to BASE alone -- the precision table at `iou_thr` is computed
+        once more on the device (csrc/error_impact.hip), with accumulate()'s
+        arithmetic.  Callable after evaluate(), cached per (iou_thr, bg_thr).
+
+        The fixes: CLS (a CLS row leaves its category; where the ground truth
+        of another category it overlaps best is missed, the best-scored CLS row
+        linking it joins that category as a true positive at its score), LOC
+        (per missed ground truth the best-scored LOC row that overlaps it best
+        becomes a true positive, the other LOC rows leave), BOTH, DUP, BKG
+        (the rows of the type leave), MISS (the missed ground truths that no
+        LOC or CLS row links are taken out of num_gt), FP (every false positive
+        leaves), FN (every missed ground truth is taken out of num_gt).  The
+        exact rules are in include/tao_amodal_hip.h, section "error impact".
+
+        Returns {"fixes": the nine names, "precision": float64[9, R, K, n_rng]
+        (-1: nothing to evaluate, like eval["precision"]), "ap": float64[9,
+        n_rng] = the mean of the precisions > -1 of each [R, K] slab, "dap":
+        float64[8, n_rng] = ap[1:] - ap[0], "rng_lbl": params.visibility_rng_lbl},
+        the category axis in the order of params.cat_ids.  ap[0] is what
+        summarize() reports as AP at `iou_thr`, except where a ground truth
+        whose id is 0 holds a detection (see error_types()).  Not available
+        where error_types() is not."""
+        if self._run is None:
+            raise RuntimeError("Please run evaluate() first.")
+        P = self.params
+        at = np.where(iou_thr == np.asarray(P.iou_thrs))[0]
+        if len(at) == 0:
+            raise ValueError("iou_thr: {} is not one of params.iou_thrs".format(iou_thr))
+        tf = min(float(np.asarray(P.iou_thrs)[at[0]]), 1 - 1e-10)
+        if not 0 <= bg_thr < tf:
+            raise ValueError("bg_thr: {} is not in [0, {})".format(bg_thr, tf))
+        key = (int(at[0]), float(bg_thr))
+        hit = self._error_impact.get(key)
+        if hit is None:
+            precision, _ = self._run.impact_table(key[0], key[1])
+            if self._cat_pos is not None:
+                precision = np.ascontiguousarray(precision[:, :, self._cat_pos])
+            from ..._lib import ERROR_FIXES
+            ap = np.array([[masked_mean(precision[v, :, :, a])
+                            for a in range(precision.shape[3])]
+                           for v in range(precision.shape[0])], dtype=np.float64)
+            hit = {"fixes": list(ERROR_FIXES), "precision": precision, "ap": ap,
+                   "dap": ap[1:] - ap[0], "rng_lbl": list(P.visibility_rng_lbl)}
+            self._error_impact[key] = hit
+        return dict(hit)
+
+    def impact_lines(self, iou_thr=0.5, bg_thr=0.1):
+        """error_impact() as a small text table: a line per visibility range,
+        AP and the dAP of the eight fixes.  Returned, not printed."""
+        e = self.error_impact(iou_thr, bg_thr)
+        cols = ["AP"] + ["d" + name for name in e["fixes"][1:]]
+        rows = np.concatenate([e["ap"][:1], e["dap"]]).T
+        lbl = [e["rng_lbl"][a] if a < len(e["rng_lbl"]) else str(a) for a in range(len(rows))]
+        w = max([len(x) for x in lbl] + [10])
+        lines = [" error impact @[ IoU={:0.2f} | bg={:0.2f} ]".format(iou_thr, bg_thr),
+                 " " + " " * w + "".join("{:>9s}".format(c) for c in cols)]
+        for name, r in zip(lbl, rows):
+            lines.append(" " + name.ljust(w) + "".join("{:>9.4f}".format(float(v)) for v in r))
         return lines
 
     def _summarize(self, summary_type, iou_thr=None, visibility_rng="all",

@@ -4,6 +4,7 @@ taoamd_track_error_types) on the synthetic configurations of bench.py, with HIP
 events:
 
     python tools/time_error_types.py [--level image|track] [--config 3s] [--reps 20] [--warmup 3]
+                                     [--impact]
 
 Times, on the image level's tables of that configuration, each alone on an idle
 stream: the fused match as a benchmark step runs it (the yardstick), the
@@ -15,7 +16,11 @@ detections x ALL its ground truths against the match's same-category pairs).
 a benchmark step (the same-category pairs), the plan-less taoamd_track_iou on
 the cells pooled per video (every pair of a video, the cross-category ones done
 naively), the match that produces match_gt, and the breakdown; lists its kernels
-and the (pair, shared frame) counts.  Prints one JSON line."""
+and the (pair, shared frame) counts.  --impact (image level) adds the error
+impact: the breakdown with its links (taoamd_error_types_links), the links pass
+followed by the sweep of the nine variants (engine.stage_error_impact), the
+kernels of both, and AP and dAP over all categories in range 0.  Prints one
+JSON line."""
 import argparse
 import json
 import os
@@ -143,6 +148,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--bg-thr", type=float, default=0.1)
+    ap.add_argument("--impact", action="store_true")
     a = ap.parse_args()
     import torch
     from tao_amodal_amd import _lib, engine, flatten_dev
@@ -187,6 +193,28 @@ def main():
     _lib.kernel_timing(False)
     res["dt_counts_by_type_range0"] = ws.err_dt_counts[0].sum(0).tolist()
     res["gt_counts_range0"] = ws.err_gt_counts[0].sum(0).tolist()
+    if a.impact:
+        # the first call allocates the link tables and the sweep's workspace
+        engine.stage_error_impact(dp, ws, 0, a.bg_thr)
+        torch.cuda.synchronize()
+        res["error_types_links"] = timed(
+            lambda: engine._error_types_pass(dp, ws, 0, a.bg_thr, True, links=True))
+        res["error_impact_links_and_sweep"] = timed(
+            lambda: engine.stage_error_impact(dp, ws, 0, a.bg_thr))
+        _lib.kernel_timing(True)
+        for _ in range(a.reps):
+            engine.stage_error_impact(dp, ws, 0, a.bg_thr)
+        res["impact_kernels_ms"] = {k: round(ms / n, 4)
+                                    for k, (ms, n) in _lib.kernel_timings().items()}
+        _lib.kernel_timing(False)
+        res["impact_sweep_kernels_ms"] = round(sum(
+            v for k, v in res["impact_kernels_ms"].items() if k.startswith("imp_")), 4)
+        res["impact_workspace_bytes"] = int(ws.imp_bytes)
+        p = ws.imp_precision[..., 0].cpu().numpy()
+        ap_ = [float(v[v > -1].mean()) if (v > -1).any() else -1.0 for v in p]
+        res["fixes"] = list(_lib.ERROR_FIXES)
+        res["ap_range0"] = [round(v, 6) for v in ap_]
+        res["dap_range0"] = [round(v - ap_[0], 6) for v in ap_[1:]]
     print(json.dumps(res))
 
 
