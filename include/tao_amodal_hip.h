@@ -1089,6 +1089,26 @@ int taoamd_error_impact(int64_t n_dt, int64_t n_gt, int32_t n_cat, int32_t n_rng
                         double *precision, int32_t *num_gt, void *workspace,
                         size_t workspace_bytes, void *stream);
 
+/* taoamd_error_impact on the tables of the track level
+ * (taoamd_track_error_types_links, below): the definition above word for word,
+ * with n_rng in [1, TAOAMD_TAO_RNG].  What differs lies in the tables, not in
+ * the sweep: the rows are detection tracks, s is taken from the pass's IoU
+ * matrix and o from the plan-less 3D IoU, and IGNORED comes by dt_rng.
+ * TAOAMD_ERR_ARG: n_rng outside [1, TAOAMD_TAO_RNG], else as above;
+ * TAOAMD_ERR_WORKSPACE: fewer bytes than taoamd_track_error_impact_workspace(n_dt,
+ * n_gt, n_cat, n_rng), the same function of its sizes.  taoamd_error_impact
+ * keeps its limit of 8 ranges. */
+size_t taoamd_track_error_impact_workspace(int64_t n_dt, int64_t n_gt, int32_t n_cat,
+                                           int32_t n_rng);
+int taoamd_track_error_impact(int64_t n_dt, int64_t n_gt, int32_t n_cat, int32_t n_rng,
+                              const int32_t *cat_off, const int32_t *order,
+                              const double *score, const int32_t *dt_cat,
+                              const uint8_t *dt_type, const int32_t *link_same,
+                              const int32_t *link_other, const int32_t *gt_cat,
+                              const uint32_t *gt_rng, const uint8_t *held, double *precision,
+                              int32_t *num_gt, void *workspace, size_t workspace_bytes,
+                              void *stream);
+
 /* ---- track-level error breakdown per range (csrc/track_error_types.hip) ------------
  * WHY a detection track is no true positive, per (area, time) range and
  * category: the section above, rule for rule, on the track tables.  The
@@ -1182,6 +1202,36 @@ int taoamd_track_error_types(int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_
                              int64_t *dt_counts, int64_t *gt_counts, uint8_t *dt_type,
                              uint32_t *dt_over, void *workspace, size_t workspace_bytes,
                              void *stream);
+
+/* taoamd_track_error_types with the links a fix would hand every detection
+ * track: the same pass, inputs, outputs and workspace
+ * (taoamd_track_error_types_workspace), plus, per (detection track d, range a),
+ *   link_same   int32[n_dt][n_rng]  the ground-truth TABLE row of the argmax of s
+ *               (the first row of d's cell + the in-cell argmax; -1: none)
+ *   link_other  int32[n_dt][n_rng]  the argmax row of o under the rule of s: the
+ *               LOWEST ground-truth row among equal IoUs -- by row number,
+ *               whatever order vid_gt lists the rows in --, a NaN IoU no overlap,
+ *               a pair of IoU 0 the argmax where nothing better exists
+ * for every row, whatever its type (a row no video lists: link_other -1), and
+ *   held        uint8[n_rng][n_gt]  1 where some detection track's match_gt names
+ *               the ground truth at (a, slot): the complement of `missed`.
+ * All three are required (TAOAMD_ERR_ARG otherwise) and zeroed / filled by the
+ * call; they are the tables taoamd_track_error_impact reads. */
+int taoamd_track_error_types_links(int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou,
+                                   int32_t n_vid, int32_t n_cat, int32_t n_rng, int32_t slot,
+                                   double bg_thr, const int32_t *dt_cat, const uint32_t *dt_rng,
+                                   const int32_t *dt_group, const int64_t *cell_iou_off,
+                                   const double *iou, const int32_t *match_gt,
+                                   int64_t match_stride, const int32_t *gt_cat,
+                                   const uint32_t *gt_rng, const int32_t *dt_frame_off,
+                                   const int32_t *dt_frame_pos, const double *dt_frame_box,
+                                   const int32_t *gt_frame_off, const int32_t *gt_frame_pos,
+                                   const double *gt_frame_box, const int32_t *vid_gt_off,
+                                   const int32_t *vid_gt, const int32_t *vid_dt_off,
+                                   const int32_t *vid_dt, int64_t *dt_counts,
+                                   int64_t *gt_counts, uint8_t *dt_type, uint32_t *dt_over,
+                                   int32_t *link_same, int32_t *link_other, uint8_t *held,
+                                   void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- multi-GPU result exchange (category-partitioned evaluation) -------------------
  * No reference counterpart (the reference is single-process); these carry the

@@ -206,6 +206,14 @@ SIGNATURES = {
                                            C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "taoamd_track_error_types_links": (C.c_int, [_i64, _i64, _i64, _i64, _i32, _i32, _i32,
+                                                 _i32, C.c_double, _vp, _vp, _vp, _vp, _vp,
+                                                 _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                 _vp, _vp, _vp, _vp, _sz, _vp]),
+    "taoamd_track_error_impact_workspace": (_sz, [_i64, _i64, _i32, _i32]),
+    "taoamd_track_error_impact": (C.c_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -43,7 +43,7 @@ using namespace taoamd;
 #define IMP_CHUNK TAOAMD_ERROR_IMPACT_CHUNK
 #define IMP_NVAR TAOAMD_ERROR_IMPACT_FIXES
 #define IMP_NLIST 7            // distinct row lists: MISS and FN sweep BASE's
-#define IMP_RMAX 8
+#define IMP_RMAX 8             // ranges of the image level; the track level has TAOAMD_TAO_RNG
 
 enum { T_TP = 0, T_IGNORED, T_DUP, T_LOC, T_CLS, T_BOTH, T_BKG };
 enum { V_BASE = 0, V_CLS, V_LOC, V_BOTH, V_DUP, V_BKG, V_MISS, V_FP, V_FN };
@@ -161,6 +161,7 @@ __device__ __forceinline__ void imp_count(uint32_t *base, bool live, int32_t key
     }
 }
 
+template <int RMAX>
 __global__ __launch_bounds__(256) void imp_gt_kernel(ImpArgs a)
 {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -170,7 +171,7 @@ __global__ __launch_bounds__(256) void imp_gt_kernel(ImpArgs a)
     const uint32_t rng = ok ? a.gt_rng[g] : 0xffffffffu;
     const int64_t plane = (int64_t)a.n_cat * a.n_rng;
 #pragma unroll
-    for (int r = 0; r < IMP_RMAX; r++) {
+    for (int r = 0; r < RMAX; r++) {
         if (r >= a.n_rng) continue;                            // (uniform)
         const bool ev = ok && !((rng >> r) & 1u);
         const int64_t at = (int64_t)r * a.n_gt + g;
@@ -330,30 +331,41 @@ static void imp_layout(Carve &c, int64_t n_dt, int64_t n_gt, int32_t n_cat, int3
     a.cnt = c.take<uint32_t>((size_t)3 * n_cat * n_rng);
 }
 
-static bool imp_sizes_ok(int64_t n_dt, int64_t n_gt, int32_t n_cat, int32_t n_rng)
+static bool imp_sizes_ok(int64_t n_dt, int64_t n_gt, int32_t n_cat, int32_t n_rng, int32_t cap)
 {
     return n_dt >= 0 && n_dt <= 0x7fffffff && n_gt >= 0 && n_gt <= 0x7fffffff && n_cat > 0 &&
-           n_rng >= 1 && n_rng <= IMP_RMAX;
+           n_rng >= 1 && n_rng <= cap;
+}
+
+static size_t imp_workspace(int64_t n_dt, int64_t n_gt, int32_t n_cat, int32_t n_rng, int32_t cap)
+{
+    if (!imp_sizes_ok(n_dt, n_gt, n_cat, n_rng, cap)) return 0;
+    ImpArgs a;
+    return measure([&](Carve &c) { imp_layout(c, n_dt, n_gt, n_cat, n_rng, a); });
 }
 
 extern "C" size_t taoamd_error_impact_workspace(int64_t n_dt, int64_t n_gt, int32_t n_cat,
                                                 int32_t n_rng)
 {
-    if (!imp_sizes_ok(n_dt, n_gt, n_cat, n_rng)) return 0;
-    ImpArgs a;
-    return measure([&](Carve &c) { imp_layout(c, n_dt, n_gt, n_cat, n_rng, a); });
+    return imp_workspace(n_dt, n_gt, n_cat, n_rng, IMP_RMAX);
 }
 
-extern "C" int taoamd_error_impact(int64_t n_dt, int64_t n_gt, int32_t n_cat, int32_t n_rng,
-                                   const int32_t *cat_off, const int32_t *order,
-                                   const double *score, const int32_t *dt_cat,
-                                   const uint8_t *dt_type, const int32_t *link_same,
-                                   const int32_t *link_other, const int32_t *gt_cat,
-                                   const uint32_t *gt_rng, const uint8_t *held,
-                                   double *precision, int32_t *num_gt, void *workspace,
-                                   size_t workspace_bytes, void *stream)
+extern "C" size_t taoamd_track_error_impact_workspace(int64_t n_dt, int64_t n_gt, int32_t n_cat,
+                                                      int32_t n_rng)
 {
-    if (!imp_sizes_ok(n_dt, n_gt, n_cat, n_rng)) return TAOAMD_ERR_ARG;
+    return imp_workspace(n_dt, n_gt, n_cat, n_rng, TAOAMD_TAO_RNG);
+}
+
+// cap: the most ranges the entry point takes (IMP_RMAX or TAOAMD_TAO_RNG); only
+// imp_gt_kernel's unrolled loop is sized by it, every other kernel indexes by n_rng
+static int imp_run(int32_t cap, int64_t n_dt, int64_t n_gt, int32_t n_cat, int32_t n_rng,
+                   const int32_t *cat_off, const int32_t *order, const double *score,
+                   const int32_t *dt_cat, const uint8_t *dt_type, const int32_t *link_same,
+                   const int32_t *link_other, const int32_t *gt_cat, const uint32_t *gt_rng,
+                   const uint8_t *held, double *precision, int32_t *num_gt, void *workspace,
+                   size_t workspace_bytes, void *stream)
+{
+    if (!imp_sizes_ok(n_dt, n_gt, n_cat, n_rng, cap)) return TAOAMD_ERR_ARG;
     if (!cat_off || !precision || !num_gt || !workspace) return TAOAMD_ERR_ARG;
     if (n_dt > 0 && (!order || !score || !dt_cat || !dt_type || !link_same || !link_other))
         return TAOAMD_ERR_ARG;
@@ -381,11 +393,46 @@ extern "C" int taoamd_error_impact(int64_t n_dt, int64_t n_gt, int32_t n_cat, in
         TAO_TIMED("imp_win_kernel", s, imp_win_kernel<<<row_blocks, 256, 0, s>>>(a));
         TAO_TIMED("imp_adopt_kernel", s, imp_adopt_kernel<<<row_blocks, 256, 0, s>>>(a));
     }
-    if (n_gt > 0)
-        TAO_TIMED("imp_gt_kernel", s,
-                  imp_gt_kernel<<<(unsigned)((n_gt + 255) / 256), 256, 0, s>>>(a));
+    if (n_gt > 0) {
+        const unsigned gt_blocks = (unsigned)((n_gt + 255) / 256);
+        if (cap <= IMP_RMAX)
+            TAO_TIMED("imp_gt_kernel", s, imp_gt_kernel<IMP_RMAX><<<gt_blocks, 256, 0, s>>>(a));
+        else
+            TAO_TIMED("imp_gt_kernel", s,
+                      imp_gt_kernel<TAOAMD_TAO_RNG><<<gt_blocks, 256, 0, s>>>(a));
+    }
     TAO_TIMED("imp_sweep_kernel", s,
               imp_sweep_kernel<<<(unsigned)((int64_t)n_cat * n_rng), IMP_CHUNK, 0, s>>>(a, rec_thr()));
     TAO_LAUNCH_CHECK();
     return TAOAMD_OK;
+}
+
+extern "C" int taoamd_error_impact(int64_t n_dt, int64_t n_gt, int32_t n_cat, int32_t n_rng,
+                                   const int32_t *cat_off, const int32_t *order,
+                                   const double *score, const int32_t *dt_cat,
+                                   const uint8_t *dt_type, const int32_t *link_same,
+                                   const int32_t *link_other, const int32_t *gt_cat,
+                                   const uint32_t *gt_rng, const uint8_t *held,
+                                   double *precision, int32_t *num_gt, void *workspace,
+                                   size_t workspace_bytes, void *stream)
+{
+    return imp_run(IMP_RMAX, n_dt, n_gt, n_cat, n_rng, cat_off, order, score, dt_cat, dt_type,
+                   link_same, link_other, gt_cat, gt_rng, held, precision, num_gt, workspace,
+                   workspace_bytes, stream);
+}
+
+// The same sweep on the tables of the track level (taoamd_track_error_types_links):
+// up to TAOAMD_TAO_RNG ranges.
+extern "C" int taoamd_track_error_impact(int64_t n_dt, int64_t n_gt, int32_t n_cat, int32_t n_rng,
+                                         const int32_t *cat_off, const int32_t *order,
+                                         const double *score, const int32_t *dt_cat,
+                                         const uint8_t *dt_type, const int32_t *link_same,
+                                         const int32_t *link_other, const int32_t *gt_cat,
+                                         const uint32_t *gt_rng, const uint8_t *held,
+                                         double *precision, int32_t *num_gt, void *workspace,
+                                         size_t workspace_bytes, void *stream)
+{
+    return imp_run(TAOAMD_TAO_RNG, n_dt, n_gt, n_cat, n_rng, cat_off, order, score, dt_cat,
+                   dt_type, link_same, link_other, gt_cat, gt_rng, held, precision, num_gt,
+                   workspace, workspace_bytes, stream);
 }

@@ -36,6 +36,11 @@
 // The additions of a pair come in the plan-less kernel's order (ascending
 // position over the union of the two tracks' frames) and the file is compiled
 // with the same -ffp-contract=off: the IoUs equal taoamd_track_iou's bit for bit.
+// taoamd_track_error_types_links is the same pass with the LINKS form of the
+// pair and class kernels: the pair kernel also keeps the argmax of o per range
+// (lane-major LDS columns, folded once a tile where the masks are), the class
+// kernel stores the argmax of s it has anyway, and the ground-truth marks land
+// in the caller's table, for taoamd_track_error_impact (error_impact.hip).
 #include "common.hpp"
 #include "workspace.hpp"
 
@@ -76,6 +81,7 @@ struct TrkErrArgs {
     uint32_t *dt_over;               // [n_dt][2] or null
     uint32_t *over;                  // [n_dt][2]: what the pair kernel found
     uint8_t *gt_hit, *gt_loc;        // [n_rng][n_gt]
+    int32_t *link_same, *link_other; // [n_dt][n_rng], taoamd_track_error_types_links only
 };
 
 // One add per distinct key among the wavefront's live lanes (as err_count of
@@ -118,7 +124,16 @@ struct OwnTrack {
     }
 };
 
-__global__ __launch_bounds__(TE_LANES) void trk_err_pair_kernel(TrkErrArgs a)
+// LINKS: the argmax of o per range under the rule of s (the greatest IoU, the
+// lowest table row among equal ones, a NaN is no overlap), kept in one LDS
+// column per lane: [r][tid] is the lane's own word, read and written by no
+// other lane, so the columns need no barrier and their banks never conflict.
+// 72 520 B of LDS a workgroup leave two workgroups a CU, the two wavefronts a
+// SIMD of the plain form; LINKS asks for them, since the allocator left alone
+// takes 256 VGPRs + 28 AGPRs, one wavefront.  The plain form asks for nothing:
+// it stays the kernel it was (219 VGPRs).
+template <bool LINKS>
+__global__ __launch_bounds__(TE_LANES, LINKS ? 2 : 1) void trk_err_pair_kernel(TrkErrArgs a)
 {
     // a ground-truth frame parked as (x1, y1, x2 = x + w, y2 = y + h, area = w * h)
     __shared__ double s_fr[2][TE_G][TE_P][5];
@@ -126,6 +141,10 @@ __global__ __launch_bounds__(TE_LANES) void trk_err_pair_kernel(TrkErrArgs a)
     __shared__ int32_t s_cat[TE_G], s_cur[TE_G], s_end[TE_G], s_first[TE_G], s_last[TE_G];
     __shared__ uint32_t s_open[TE_G];        // ranges that evaluate the track
     __shared__ int32_t s_span[2];            // first, last position of the round's detection tracks
+    // LINKS: o of (range, lane), its table row (-1: none); the tile's table rows
+    __shared__ double s_best[LINKS ? TE_RMAX : 1][LINKS ? TE_LANES : 1];
+    __shared__ int32_t s_arg[LINKS ? TE_RMAX : 1][LINKS ? TE_LANES : 1];
+    __shared__ int32_t s_row[LINKS ? TE_G : 1];
 
     const int v = blockIdx.x;
     const int tid = threadIdx.x;
@@ -162,6 +181,9 @@ __global__ __launch_bounds__(TE_LANES) void trk_err_pair_kernel(TrkErrArgs a)
             atomicMax(&s_span[1], a.dfpos[fe - 1]);
         }
         uint32_t hi = 0, lo = 0;
+        if constexpr (LINKS) {
+            for (int r = 0; r < a.n_rng; r++) { s_best[r][tid] = 0.0; s_arg[r][tid] = -1; }
+        }
 
         for (int64_t g0 = g_lo; g0 < g_hi; g0 += TE_G) {
             const int ng = (int)min((int64_t)TE_G, g_hi - g0);
@@ -175,6 +197,7 @@ __global__ __launch_bounds__(TE_LANES) void trk_err_pair_kernel(TrkErrArgs a)
                 if (open) { s = a.gfoff[row]; e = a.gfoff[row + 1]; }
                 s_cat[tid] = ok ? a.gt_cat[row] : -1;
                 s_open[tid] = open;
+                if constexpr (LINKS) s_row[tid] = row;
                 s_cur[tid] = s;
                 s_end[tid] = e;
                 s_first[tid] = e > s ? a.gfpos[s] : INT32_MAX;
@@ -191,7 +214,9 @@ __global__ __launch_bounds__(TE_LANES) void trk_err_pair_kernel(TrkErrArgs a)
             }
             mine = mine && need;
             // (uniform) nothing of this tile is evaluated for any lane, or no frame anywhere
-            if (!__syncthreads_or(mine) || p_hi < p_lo) continue;
+            // (LINKS: pairs without a frame have IoU 0, and an IoU of 0 can be the argmax)
+            if (!__syncthreads_or(mine) || (!LINKS && p_hi < p_lo)) continue;
+            const bool frames = p_hi >= p_lo;
             const bool wave_mine = __ballot(mine) != 0;
 
             double si[TE_G], su[TE_G];
@@ -227,9 +252,9 @@ __global__ __launch_bounds__(TE_LANES) void trk_err_pair_kernel(TrkErrArgs a)
                 }
             };
 
-            const int32_t c_lo = p_lo >> 3, c_hi = p_hi >> 3;
+            const int32_t c_lo = p_lo >> 3, c_hi = !LINKS || frames ? p_hi >> 3 : c_lo - 1;
             static_assert(TE_P == 8, "chunk of a position = position >> 3");
-            stage(c_lo * TE_P, 0);
+            if (!LINKS || frames) stage(c_lo * TE_P, 0);
             for (int32_t c = c_lo; c <= c_hi; c++) {
                 const int b = (c - c_lo) & 1;
                 const int32_t p0 = c * TE_P;
@@ -276,15 +301,39 @@ __global__ __launch_bounds__(TE_LANES) void trk_err_pair_kernel(TrkErrArgs a)
                 // (a NaN IoU compares false: no overlap)
                 hi |= iou >= a.tf ? open : 0u;
                 lo |= iou >= a.tb ? open : 0u;
+                if constexpr (LINKS) {
+                    // the ranges that evaluate the track, one LDS read-compare-write each
+                    const bool take = open != 0;
+                    if (__ballot(take) == 0) continue;         // (uniform)
+                    const int32_t row = s_row[g];
+                    uint32_t left = __builtin_amdgcn_readfirstlane(s_open[g]);
+                    while (left) {
+                        const int r = __builtin_ctz(left);
+                        left &= left - 1;
+                        if (take) {
+                            const double b = s_best[r][tid];
+                            // (row numbers decide a tie, not the order of the video's list)
+                            if (iou > b || (iou == b && (uint32_t)row < (uint32_t)s_arg[r][tid])) {
+                                s_best[r][tid] = iou;
+                                s_arg[r][tid] = row;
+                            }
+                        }
+                    }
+                }
             }
         }
         if (valid) {
             a.over[2 * d] = hi;
             a.over[2 * d + 1] = lo;
+            if constexpr (LINKS) {
+                for (int r = 0; r < a.n_rng; r++) a.link_other[d * a.n_rng + r] = s_arg[r][tid];
+            }
         }
     }
 }
 
+// LINKS: the argmax of s, as a table row, stored per (detection track, range)
+template <bool LINKS>
 __global__ __launch_bounds__(256) void trk_err_class_kernel(TrkErrArgs a)
 {
     const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -351,6 +400,9 @@ __global__ __launch_bounds__(256) void trk_err_class_kernel(TrkErrArgs a)
             ty = TE_BOTH;
         }
         if (valid && a.dt_type) a.dt_type[d * a.n_rng + r] = (uint8_t)ty;
+        if constexpr (LINKS) {
+            if (valid) a.link_same[d * a.n_rng + r] = arg[r] >= 0 ? gt0 + arg[r] : -1;
+        }
         trk_err_count(a.dt_counts + (int64_t)r * a.n_cat * TE_NTYPE, ok, cat * TE_NTYPE + ty);
     }
 }
@@ -388,7 +440,7 @@ extern "C" size_t taoamd_track_error_types_workspace(int64_t n_dt, int64_t n_gt,
     return measure([&](Carve &c) { trk_err_layout(c, n_dt, n_gt, n_rng, a); });
 }
 
-extern "C" int taoamd_track_error_types(
+static int trk_err_run(
     int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou, int32_t n_vid, int32_t n_cat,
     int32_t n_rng, int32_t slot, double bg_thr, const int32_t *dt_cat, const uint32_t *dt_rng,
     const int32_t *dt_group, const int64_t *cell_iou_off, const double *iou,
@@ -397,8 +449,10 @@ extern "C" int taoamd_track_error_types(
     const int32_t *gt_frame_off, const int32_t *gt_frame_pos, const double *gt_frame_box,
     const int32_t *vid_gt_off, const int32_t *vid_gt, const int32_t *vid_dt_off,
     const int32_t *vid_dt, int64_t *dt_counts, int64_t *gt_counts, uint8_t *dt_type,
-    uint32_t *dt_over, void *workspace, size_t workspace_bytes, void *stream)
+    uint32_t *dt_over, int32_t *link_same, int32_t *link_other, uint8_t *held, void *workspace,
+    size_t workspace_bytes, void *stream)
 {
+    const bool links = link_same != nullptr;
     if (n_dt < 0 || n_dt > 0x7fffffff || n_gt < 0 || n_gt > 0x7fffffff || n_cells < 0 ||
         n_iou < 0 || n_vid < 0 || n_cat <= 0 || n_rng < 1 || n_rng > TE_RMAX || slot < 0 ||
         slot >= N_THR)
@@ -432,6 +486,8 @@ extern "C" int taoamd_track_error_types(
     a.dt_counts = (unsigned long long *)dt_counts;
     a.gt_counts = (unsigned long long *)gt_counts;
     a.dt_type = dt_type; a.dt_over = dt_over;
+    a.link_same = link_same; a.link_other = link_other;
+    if (links) a.gt_hit = held;      // the marks of the class kernel, in the caller's table
     const size_t cells = (size_t)n_rng * n_cat;
     TAO_HIP(hipMemsetAsync(dt_counts, 0, cells * TE_NTYPE * sizeof(int64_t), s));
     TAO_HIP(hipMemsetAsync(gt_counts, 0, cells * TE_NGT * sizeof(int64_t), s));
@@ -442,15 +498,71 @@ extern "C" int taoamd_track_error_types(
     if (n_dt > 0) {
         // (a row no video lists, or whose video has nothing to compare it with: no overlap)
         TAO_HIP(hipMemsetAsync(a.over, 0, (size_t)n_dt * 2 * sizeof(uint32_t), s));
-        if (n_vid > 0 && n_gt > 0)
-            TAO_TIMED("trk_err_pair_kernel", s,
-                      trk_err_pair_kernel<<<(unsigned)n_vid, TE_LANES, 0, s>>>(a));
-        TAO_TIMED("trk_err_class_kernel", s,
-                  trk_err_class_kernel<<<(unsigned)((n_dt + 255) / 256), 256, 0, s>>>(a));
+        // (and links no ground truth of another category; every link_same is written
+        // by the class kernel)
+        if (links)
+            TAO_HIP(hipMemsetAsync(link_other, 0xff, (size_t)n_dt * n_rng * sizeof(int32_t), s));
+        const unsigned row_blocks = (unsigned)((n_dt + 255) / 256);
+        if (links) {
+            if (n_vid > 0 && n_gt > 0)
+                TAO_TIMED("trk_err_pair_links_kernel", s,
+                          trk_err_pair_kernel<true><<<(unsigned)n_vid, TE_LANES, 0, s>>>(a));
+            TAO_TIMED("trk_err_class_links_kernel", s,
+                      trk_err_class_kernel<true><<<row_blocks, 256, 0, s>>>(a));
+        } else {
+            if (n_vid > 0 && n_gt > 0)
+                TAO_TIMED("trk_err_pair_kernel", s,
+                          trk_err_pair_kernel<false><<<(unsigned)n_vid, TE_LANES, 0, s>>>(a));
+            TAO_TIMED("trk_err_class_kernel", s,
+                      trk_err_class_kernel<false><<<row_blocks, 256, 0, s>>>(a));
+        }
     }
     if (n_gt > 0)
         TAO_TIMED("trk_err_tally_kernel", s,
                   trk_err_tally_kernel<<<(unsigned)((n_gt + 255) / 256), 256, 0, s>>>(a));
     TAO_LAUNCH_CHECK();
     return TAOAMD_OK;
+}
+
+extern "C" int taoamd_track_error_types(
+    int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou, int32_t n_vid, int32_t n_cat,
+    int32_t n_rng, int32_t slot, double bg_thr, const int32_t *dt_cat, const uint32_t *dt_rng,
+    const int32_t *dt_group, const int64_t *cell_iou_off, const double *iou,
+    const int32_t *match_gt, int64_t match_stride, const int32_t *gt_cat, const uint32_t *gt_rng,
+    const int32_t *dt_frame_off, const int32_t *dt_frame_pos, const double *dt_frame_box,
+    const int32_t *gt_frame_off, const int32_t *gt_frame_pos, const double *gt_frame_box,
+    const int32_t *vid_gt_off, const int32_t *vid_gt, const int32_t *vid_dt_off,
+    const int32_t *vid_dt, int64_t *dt_counts, int64_t *gt_counts, uint8_t *dt_type,
+    uint32_t *dt_over, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return trk_err_run(n_dt, n_gt, n_cells, n_iou, n_vid, n_cat, n_rng, slot, bg_thr, dt_cat,
+                       dt_rng, dt_group, cell_iou_off, iou, match_gt, match_stride, gt_cat, gt_rng,
+                       dt_frame_off, dt_frame_pos, dt_frame_box, gt_frame_off, gt_frame_pos,
+                       gt_frame_box, vid_gt_off, vid_gt, vid_dt_off, vid_dt, dt_counts, gt_counts,
+                       dt_type, dt_over, nullptr, nullptr, nullptr, workspace, workspace_bytes,
+                       stream);
+}
+
+// The same pass with the links of every (detection track, range) and the held
+// marks stored for taoamd_track_error_impact; counts, types and masks are those
+// of taoamd_track_error_types, the workspace is its workspace.
+extern "C" int taoamd_track_error_types_links(
+    int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou, int32_t n_vid, int32_t n_cat,
+    int32_t n_rng, int32_t slot, double bg_thr, const int32_t *dt_cat, const uint32_t *dt_rng,
+    const int32_t *dt_group, const int64_t *cell_iou_off, const double *iou,
+    const int32_t *match_gt, int64_t match_stride, const int32_t *gt_cat, const uint32_t *gt_rng,
+    const int32_t *dt_frame_off, const int32_t *dt_frame_pos, const double *dt_frame_box,
+    const int32_t *gt_frame_off, const int32_t *gt_frame_pos, const double *gt_frame_box,
+    const int32_t *vid_gt_off, const int32_t *vid_gt, const int32_t *vid_dt_off,
+    const int32_t *vid_dt, int64_t *dt_counts, int64_t *gt_counts, uint8_t *dt_type,
+    uint32_t *dt_over, int32_t *link_same, int32_t *link_other, uint8_t *held, void *workspace,
+    size_t workspace_bytes, void *stream)
+{
+    if (!link_same || !link_other || !held) return TAOAMD_ERR_ARG;
+    return trk_err_run(n_dt, n_gt, n_cells, n_iou, n_vid, n_cat, n_rng, slot, bg_thr, dt_cat,
+                       dt_rng, dt_group, cell_iou_off, iou, match_gt, match_stride, gt_cat, gt_rng,
+                       dt_frame_off, dt_frame_pos, dt_frame_box, gt_frame_off, gt_frame_pos,
+                       gt_frame_box, vid_gt_off, vid_gt, vid_dt_off, vid_dt, dt_counts, gt_counts,
+                       dt_type, dt_over, link_same, link_other, held, workspace, workspace_bytes,
+                       stream);
 }

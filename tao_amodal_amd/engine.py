@@ -1216,6 +1216,12 @@ def stage_track_error_types(dp, ws, slot, tb, per_detection=False):
     workspace's own table (detail mode), else from error_match_gt() (800 bytes
     a row), filled here by one more match unless the caller's match already
     wrote it.  Buffers are allocated on the first call."""
+    _track_error_types_pass(dp, ws, slot, tb, per_detection, links=False)
+
+
+def _track_error_types_pass(dp, ws, slot, tb, per_detection, links):
+    """stage_track_error_types; `links`: through taoamd_track_error_types_links,
+    which also fills ws.err_link_same, ws.err_link_other and ws.err_held."""
     if dp.kind != "tao" or dp.mask_iou:
         raise _lib.TaoAmdError("the track-level error breakdown is the track level's, on boxes")
     if dp.iou_mode != 0:
@@ -1248,16 +1254,59 @@ def stage_track_error_types(dp, ws, slot, tb, per_detection=False):
         match_gt = getattr(ws, "err_match_gt", None)
     if per_detection and ws.err_dt_type is None:
         ws.err_dt_type = torch.empty((max(dp.n_dt, 1), dp.n_rng), dtype=torch.uint8, device=dev)
-    _lib.check(lib.taoamd_track_error_types(
-        dp.n_dt, dp.n_gt, dp.n_cells, dp.n_iou, n_vid, dp.n_cat, dp.n_rng, int(slot), float(tb),
-        _ptr(t["dt_cat"]), _ptr(ws.dt_rng), _ptr(t["dt_group"]), _ptr(t["cell_iou_off"]),
-        _ptr(ws.iou), _ptr(match_gt), dp.n_rng * N_THR, _ptr(t["gt_cat"]), _ptr(ws.gt_rng),
-        _ptr(t["dt_frame_off"]), _ptr(t["dt_frame_pos"]), _ptr(t["dt_frame_box"]),
-        _ptr(t["gt_frame_off"]), _ptr(t["gt_frame_pos"]), _ptr(t["gt_frame_box"]),
-        _ptr(vid_gt_off), _ptr(vid_gt), _ptr(vid_dt_off), _ptr(vid_dt),
-        _ptr(ws.err_dt_counts), _ptr(ws.err_gt_counts),
-        _ptr(ws.err_dt_type) if per_detection else None, None,
-        _ptr(ws.err_ws), ws.err_bytes, s), "taoamd_track_error_types")
+    head = (dp.n_dt, dp.n_gt, dp.n_cells, dp.n_iou, n_vid, dp.n_cat, dp.n_rng, int(slot),
+            float(tb), _ptr(t["dt_cat"]), _ptr(ws.dt_rng), _ptr(t["dt_group"]),
+            _ptr(t["cell_iou_off"]), _ptr(ws.iou), _ptr(match_gt), dp.n_rng * N_THR, _ptr(t["gt_cat"]), _ptr(ws.gt_rng),
+            _ptr(t["dt_frame_off"]), _ptr(t["dt_frame_pos"]), _ptr(t["dt_frame_box"]),
+            _ptr(t["gt_frame_off"]), _ptr(t["gt_frame_pos"]), _ptr(t["gt_frame_box"]),
+            _ptr(vid_gt_off), _ptr(vid_gt), _ptr(vid_dt_off), _ptr(vid_dt),
+            _ptr(ws.err_dt_counts), _ptr(ws.err_gt_counts),
+            _ptr(ws.err_dt_type) if per_detection else None, None)
+    if links:
+        _lib.check(lib.taoamd_track_error_types_links(
+            *head, _ptr(ws.err_link_same), _ptr(ws.err_link_other), _ptr(ws.err_held),
+            _ptr(ws.err_ws), ws.err_bytes, s), "taoamd_track_error_types_links")
+    else:
+        _lib.check(lib.taoamd_track_error_types(*head, _ptr(ws.err_ws), ws.err_bytes, s),
+                   "taoamd_track_error_types")
+
+
+def stage_track_error_impact(dp, ws, slot, tb):
+    """The Track-AP each error type costs, of the pass the workspace holds
+    (after stage_ranges .. stage_match and the sort): the track-level breakdown
+    once more with its links (taoamd_track_error_types_links: ws.err_link_same,
+    ws.err_link_other int32[n_dt, n_rng], ws.err_held uint8[n_rng, n_gt], the
+    types in ws.err_dt_type), then the sweep of the nine variants
+    (taoamd_track_error_impact; the definition is in include/tao_amodal_hip.h):
+    ws.imp_precision[9, 101, n_cat, n_rng] under the calling thread's recall
+    thresholds and ws.imp_num_gt[9, n_cat, n_rng].  Buffers are allocated on the
+    first call and kept with the workspace: the two link tables are 8 bytes per
+    (track, range) together -- 58 MB at 361 577 tracks and 20 ranges --, the
+    sweep's own workspace another 4 (`del ws.err_link_same, ws.err_link_other,
+    ws.imp_ws` gives them back)."""
+    lib, dev = _lib.load(), dp.device
+    if getattr(ws, "err_link_same", None) is None:
+        shape = (max(dp.n_dt, 1), dp.n_rng)
+        ws.err_link_same = torch.empty(shape, dtype=torch.int32, device=dev)
+        ws.err_link_other = torch.empty(shape, dtype=torch.int32, device=dev)
+        ws.err_held = torch.empty((dp.n_rng, max(dp.n_gt, 1)), dtype=torch.uint8, device=dev)
+    _track_error_types_pass(dp, ws, slot, tb, per_detection=True, links=True)
+    if getattr(ws, "imp_ws", None) is None:
+        ws.imp_bytes = lib.taoamd_track_error_impact_workspace(dp.n_dt, dp.n_gt, dp.n_cat,
+                                                               dp.n_rng)
+        ws.imp_ws = torch.empty(max(int(ws.imp_bytes), 256), dtype=torch.uint8, device=dev)
+        ws.imp_precision = torch.empty((len(_lib.ERROR_FIXES), N_REC, dp.n_cat, dp.n_rng),
+                                       dtype=torch.float64, device=dev)
+        ws.imp_num_gt = torch.empty((len(_lib.ERROR_FIXES), dp.n_cat, dp.n_rng),
+                                    dtype=torch.int32, device=dev)
+    t = dp.t
+    ws.imp_order = ws.order          # (derived on demand: alive while the pass runs)
+    _lib.check(lib.taoamd_track_error_impact(
+        dp.n_dt, dp.n_gt, dp.n_cat, dp.n_rng, _ptr(t["cat_off"]), _ptr(ws.imp_order),
+        _ptr(t["dt_score"]), _ptr(t["dt_cat"]), _ptr(ws.err_dt_type), _ptr(ws.err_link_same),
+        _ptr(ws.err_link_other), _ptr(t["gt_cat"]), _ptr(ws.gt_rng), _ptr(ws.err_held),
+        _ptr(ws.imp_precision), _ptr(ws.imp_num_gt), _ptr(ws.imp_ws), ws.imp_bytes, _stream()),
+        "taoamd_track_error_impact")
 
 
 def stage_track_iou_guarded(dp, ws):

@@ -305,11 +305,11 @@ class GpuRun:
     def impact_table(self, thr_index, bg_thr):
         """(precision[9, R, K, n_rng], num_gt[9, K, n_rng]) of the nine fixes at
         the caller's `thr_index`-th IoU threshold: recall thresholds and ranges
-        in the caller's order (engine.stage_error_impact; the definition is in
-        include/tao_amodal_hip.h), from the pass the workspace holds after
+        in the caller's order (engine.stage_error_impact at the image level,
+        engine.stage_track_error_impact at the track level; the definition is
+        in include/tao_amodal_hip.h), from the pass the workspace holds after
         evaluate().  Refuses what error_table() refuses, in its words."""
-        if self.flat.kind == "tao":
-            raise NotImplementedError("error_impact() is the image level's")
+        track = self.flat.kind == "tao"
         c = self.constants
         if c is not None and len(c.thr_blocks) == 1 and len(c.rng_blocks) == 1 \
                 and len(c.rec_blocks) > 1:
@@ -317,7 +317,9 @@ class GpuRun:
                 "error_impact() is kept for up to %d recall thresholds" % N_REC)
         c, slot = self._error_pass_at(thr_index)
         with timed("kernels"), applied(c):
-            self.engine.stage_error_impact(self.dp, self.ws, slot, bg_thr)
+            e = self.engine
+            stage = e.stage_track_error_impact if track else e.stage_error_impact
+            stage(self.dp, self.ws, slot, bg_thr)
             self.torch.cuda.synchronize(self.device)
         with timed("download"):
             p = self.ws.imp_precision.cpu().numpy()

@@ -111,6 +111,7 @@ class TaoEval:
         self._run = None
         self._cat_pos = None
         self._error_types = {}
+        self._error_impact = {}
 
     # ------------------------------------------------------------ stages
     def evaluate(self, show_progress=False):
@@ -165,6 +166,7 @@ class TaoEval:
             self._run = GpuRun(flat, self.device, self.params.iou_3d_type,
                                constants=constants)
         self._error_types = {}
+        self._error_impact = {}
         self._run.evaluate()
         P = self.params
         rngs = [(a, t) for a in P.area_rng for t in P.time_rng]
@@ -361,6 +363,79 @@ class TaoEval:
                  " " + " " * w + "".join("{:>11s}".format(c) for c in cols)]
         for name, r in zip(lbl, rows):
             lines.append(" " + name.ljust(w) + "".join("{:>11d}".format(int(v)) for v in r))
+        return lines
+
+    def error_impact(self, iou_thr=0.5, bg_thr=0.1):
+        """The Track-AP each error type costs, per (area, time) range: TIDE's
+        dAP (Bolya et al., ECCV 2020) on the table of error_types(iou_thr,
+        bg_thr), LVISEval.error_impact() rule for rule on tracks.  For each of
+        nine variants of the evaluation -- BASE and one fix each, a fix applied
+        to BASE alone -- the precision table at `iou_thr` is computed once more
+        on the device (csrc/track_error_types.hip for the links, csrc/
+        error_impact.hip for the sweep), with accumulate()'s arithmetic.
+        Callable after evaluate(), cached per (iou_thr, bg_thr).
+
+        The fixes are LVISEval.error_impact()'s: CLS, LOC, BOTH, DUP, BKG, MISS,
+        FP, FN; a CLS track is handed the ground-truth track of another
+        category whose plan-less 3D IoU with it is greatest among those the
+        range evaluates, a LOC track the best one of its own category by the
+        IoU matrix the match read.  The exact rules are in
+        include/tao_amodal_hip.h, section "error impact".
+
+        Returns {"fixes": the nine names, "precision": float64[9, R, K, n_rng]
+        (-1: nothing to evaluate, like eval["precision"]), "ap": float64[9,
+        n_rng] = the mean of the precisions > -1 of each [R, K] slab, "dap":
+        float64[8, n_rng] = ap[1:] - ap[0], "rng_lbl": the (area label, time
+        label) of every range} with n_rng = areas x durations in the order of
+        eval["precision"]'s last two axes flattened and the category axis in
+        the order of params.cat_ids.  ap[0] is what summarize() reports as AP at
+        `iou_thr`, except where a ground-truth track whose id is the
+        "unmatched" sentinel holds a detection track (see error_types()).  Not
+        available where error_types() is not, nor with more than 101 recall
+        thresholds."""
+        if self._run is None:
+            raise RuntimeError("Please run evaluate() first.")
+        P = self.params
+        at = np.where(iou_thr == np.asarray(P.iou_thrs))[0]
+        if len(at) == 0:
+            raise ValueError("iou_thr: {} is not one of params.iou_thrs".format(iou_thr))
+        tf = min(float(np.asarray(P.iou_thrs)[at[0]]), 1 - 1e-10)
+        if not 0 <= bg_thr < tf:
+            raise ValueError("bg_thr: {} is not in [0, {})".format(bg_thr, tf))
+        key = (int(at[0]), float(bg_thr))
+        hit = self._error_impact.get(key)
+        if hit is None:
+            precision, _ = self._run.impact_table(key[0], key[1])
+            if self._cat_pos is not None:
+                precision = np.ascontiguousarray(precision[:, :, self._cat_pos])
+            from ..._lib import ERROR_FIXES
+            ap = np.array([[masked_mean(precision[v, :, :, a])
+                            for a in range(precision.shape[3])]
+                           for v in range(precision.shape[0])], dtype=np.float64)
+
+            def lbl(names, i):
+                return names[i] if i < len(names) else str(i)
+            hit = {"fixes": list(ERROR_FIXES), "precision": precision, "ap": ap,
+                   "dap": ap[1:] - ap[0],
+                   "rng_lbl": [(lbl(P.area_rng_lbl, a), lbl(P.time_rng_lbl, t))
+                               for a in range(len(P.area_rng))
+                               for t in range(len(P.time_rng))]}
+            self._error_impact[key] = hit
+        return dict(hit)
+
+    def impact_lines(self, iou_thr=0.5, bg_thr=0.1):
+        """error_impact() as a small text table: a line per (area, time) range,
+        AP and the dAP of the eight fixes.  Returned, not printed."""
+        e = self.error_impact(iou_thr, bg_thr)
+        cols = ["AP"] + ["d" + name for name in e["fixes"][1:]]
+        rows = np.concatenate([e["ap"][:1], e["dap"]]).T
+        lbl = ["{}/{}".format(*e["rng_lbl"][a]) if a < len(e["rng_lbl"]) else str(a)
+               for a in range(len(rows))]
+        w = max([len(x) for x in lbl] + [10])
+        lines = [" track error impact @[ IoU={:0.2f} | bg={:0.2f} ]".format(iou_thr, bg_thr),
+                 " " + " " * w + "".join("{:>9s}".format(c) for c in cols)]
+        for name, r in zip(lbl, rows):
+            lines.append(" " + name.ljust(w) + "".join("{:>9.4f}".format(float(v)) for v in r))
         return lines
 
     def _summarize(self, summary_type, iou_thr=None, area_rng="all",

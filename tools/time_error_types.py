@@ -16,11 +16,12 @@ detections x ALL its ground truths against the match's same-category pairs).
 a benchmark step (the same-category pairs), the plan-less taoamd_track_iou on
 the cells pooled per video (every pair of a video, the cross-category ones done
 naively), the match that produces match_gt, and the breakdown; lists its kernels
-and the (pair, shared frame) counts.  --impact (image level) adds the error
-impact: the breakdown with its links (taoamd_error_types_links), the links pass
-followed by the sweep of the nine variants (engine.stage_error_impact), the
-kernels of both, and AP and dAP over all categories in range 0.  Prints one
-JSON line."""
+and the (pair, shared frame) counts.  --impact adds the error impact: the
+breakdown with its links (taoamd_error_types_links; --level track:
+taoamd_track_error_types_links), the links pass followed by the sweep of the
+nine variants (engine.stage_error_impact / engine.stage_track_error_impact),
+the kernels of both, and AP and dAP over all categories in range 0.  Prints
+one JSON line."""
 import argparse
 import json
 import os
@@ -135,6 +136,29 @@ def track_level(a, gt, dt, dev, V):
     res["track_iou_planless_video_pooled"] = timed(naive)
     res["video_pair_frames"] = int(frames.item())
     res["cross_category_pair_frames"] = res["video_pair_frames"] - res["same_category_pair_frames"]
+    if a.impact:
+        # the first call allocates the link tables and the sweep's workspace
+        engine.stage_track_error_impact(dp, ws, 0, a.bg_thr)
+        torch.cuda.synchronize()
+        res["track_error_types_links"] = timed(
+            lambda: engine._track_error_types_pass(dp, ws, 0, a.bg_thr, True, links=True))
+        res["track_error_impact_links_and_sweep"] = timed(
+            lambda: engine.stage_track_error_impact(dp, ws, 0, a.bg_thr))
+        _lib.kernel_timing(True)
+        for _ in range(a.reps):
+            engine.stage_track_error_impact(dp, ws, 0, a.bg_thr)
+        res["impact_kernels_ms"] = {k: round(ms / n, 4)
+                                    for k, (ms, n) in _lib.kernel_timings().items()}
+        _lib.kernel_timing(False)
+        res["impact_sweep_kernels_ms"] = round(sum(
+            v for k, v in res["impact_kernels_ms"].items() if k.startswith("imp_")), 4)
+        res["impact_workspace_bytes"] = int(ws.imp_bytes)
+        res["link_table_bytes"] = int(ws.err_link_same.numel() + ws.err_link_other.numel()) * 4
+        p = ws.imp_precision[..., 0].cpu().numpy()
+        ap_ = [float(v[v > -1].mean()) if (v > -1).any() else -1.0 for v in p]
+        res["fixes"] = list(_lib.ERROR_FIXES)
+        res["ap_range0"] = [round(v, 6) for v in ap_]
+        res["dap_range0"] = [round(v - ap_[0], 6) for v in ap_[1:]]
     print(json.dumps(res))
 
 
