@@ -172,7 +172,13 @@ int taoamd_tao_ranges(int64_t n_gt, const double *gt_area,
  * produces them; row i belongs to detection / ground truth i of the cell
  * tables (n_dt / n_gt rows, dt_total / gt_total runs in all).  0 where the
  * tight boxes do not overlap, -1 where the frames differ, else |d & g| / |d | g|
- * (an empty intersection over a union of 1).  Workspace:
+ * (an empty intersection over a union of 1), both counted as rleIou's loop
+ * counts them: up to the frame's end, or up to the pixel at which both masks
+ * finish a run and continue with an empty one, or at which the two current
+ * runs have 2^32 pixels left between them -- the reference stops there.  Run
+ * lengths of a mask add up to its height * width, less than 2^32.  The two masks of a pair with one
+ * frame size must add up to the same total: on unequal totals the reference's
+ * loop never returns, and the value here is unspecified.  Workspace:
  * taoamd_rle_iou_workspace(n_dt, dt_total, n_gt, gt_total) bytes (per-run
  * prefix sums, rebuilt by every call). */
 size_t taoamd_rle_iou_workspace(int64_t n_dt, int64_t dt_total, int64_t n_gt,
@@ -196,7 +202,8 @@ int taoamd_rle_iou(int64_t n_cells, const int32_t *cell_dt_off,
  * lists *_off / *_runs and frame size *_hw[k] = (height, width), as
  * taoamd_rle_copy produces them; no tight box: see the kernel).  Per shared
  * position t: i_t = |d_t & g_t|, u_t = |d_t | g_t|, both 0 when the frame sizes
- * differ.  mode 0 = 3d_iou: sum i_t / (sum u_t + the pixels of the frames only
+ * differ, both counted up to the pixel where rleMerge's loop stops (as for
+ * taoamd_rle_iou, same domain).  mode 0 = 3d_iou: sum i_t / (sum u_t + the pixels of the frames only
  * one track has), integers summed exactly, 0 when the denominator is 0;
  * 1 = avg_iou: the ratios i_t / u_t (0 where u_t = 0) added in ascending
  * timeline order, over |F_d u F_g|; 2 = imagenetvid: #{t : i_t > u_t / 2} over

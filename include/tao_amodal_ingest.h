@@ -179,7 +179,10 @@ int taoamd_host_all_in_sorted(int64_t n_keys, const int64_t *keys, int64_t n,
  *                 what ann["segmentation"]["counts"] holds after _to_mask;
  *                 returns its length, writes at most cap-1 characters + NUL.
  * add_* return the index of the new mask, or -1 for arguments no mask can be
- * made of (no part, a part without a vertex, a frame of 2^32 pixels or more).
+ * made of (no part, a part without a vertex, a frame of 2^32 pixels or more;
+ * for add_counts / add_string run lengths that add up to 2^32 or more, or a
+ * height or width beyond int32: the device's 32-bit prefix sums cannot hold
+ * them).  Empty runs are kept as they come.
  * A batch is not thread safe; different batches are independent. */
 void *taoamd_rle_new(void);
 void taoamd_rle_free(void *handle);

@@ -121,7 +121,10 @@ class _Runs:
 
 
 def merge(masks, intersect=False):
-    """Union (or intersection) of masks, folded left to right -- rleMerge."""
+    """Union (or intersection) of masks, folded left to right -- rleMerge.
+    Like rleIou's, its loop ends when the pixels left in the two current runs
+    add up to 0 as C uints: at the frame's end, and before it where both
+    cursors have just taken an empty run or hold 2^32 pixels between them."""
     if len(masks) == 0:
         return {"h": 0, "w": 0, "counts": []}
     h, w = masks[0]["h"], masks[0]["w"]
@@ -138,7 +141,7 @@ def merge(masks, intersect=False):
             run += n
             a.take(n)
             b.take(n)
-            rest = a.left + b.left
+            rest = (a.left + b.left) & 0xFFFFFFFF     # the sum of two C uints
             nv = (a.v & b.v) if intersect else (a.v | b.v)
             if nv != v or rest == 0:
                 out.append(run)
@@ -236,7 +239,8 @@ def bb_overlap(db, gb):
 def iou_pair(d, g, db=None, gb=None):
     """IoU of two masks, iscrowd = 0 -- the body of rleIou: 0 when the tight
     boxes do not overlap, -1 when the frames differ, else |d & g| / |d | g|
-    with an empty intersection reported over a union of 1."""
+    with an empty intersection reported over a union of 1.  Both are counted up
+    to the pixel at which the loop stops (see merge)."""
     db = to_bbox(d) if db is None else db
     gb = to_bbox(g) if gb is None else gb
     if not bb_overlap(db, gb):
@@ -253,7 +257,7 @@ def iou_pair(d, g, db=None, gb=None):
                 inter += n
         a.take(n)
         b.take(n)
-        if a.left + b.left == 0:
+        if (a.left + b.left) & 0xFFFFFFFF == 0:     # the sum of two C uints
             break
     if inter == 0:
         union = 1

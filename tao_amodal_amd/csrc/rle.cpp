@@ -232,6 +232,17 @@ std::string to_text(const uint32_t *c, int64_t n)
     return s;
 }
 
+// What the device's 32-bit prefix sums and (height, width) columns can hold:
+// run lengths that add up to less than 2^32, sizes within int32.  (The
+// reference walks longer lists run by run; here they are refused.)
+bool holds(const Mask &m)
+{
+    if (m.h > INT32_MAX || m.w > INT32_MAX) return false;
+    uint64_t sum = 0;
+    for (uint32_t r : m.runs) sum += r;
+    return sum < (1ull << 32);
+}
+
 }  // namespace
 
 extern "C" {
@@ -306,6 +317,7 @@ int64_t taoamd_rle_add_counts(void *handle, const uint32_t *counts, int64_t m,
     k.h = height;
     k.w = width;
     k.runs.assign(counts, counts + m);
+    if (!holds(k)) return -1;
     b->push(k);
     return b->count() - 1;
 }
@@ -315,7 +327,9 @@ int64_t taoamd_rle_add_string(void *handle, const char *text, int64_t height,
 {
     Batch *b = (Batch *)handle;
     if (!text || height < 0 || width < 0) return -1;
-    b->push(from_text(text, height, width));
+    const Mask k = from_text(text, height, width);
+    if (!holds(k)) return -1;
+    b->push(k);
     return b->count() - 1;
 }
 

@@ -25,6 +25,11 @@
 // are read through the caches.  Integer adds / compares on data read once: no
 // use for the matrix cores; measured bound by instruction issue and LDS
 // latency, not by HBM.
+//
+// The sum counts every pixel; the reference's loop can stop before the frame's
+// end (coincident empty runs, 2^32 pixels left in two runs).  Those pairs are
+// walked with two cursors over the raw run lengths, as the reference does
+// (rle_walk.hpp: rle_stops_early, rle_two_cursors).
 #include "rle_walk.hpp"
 
 using namespace taoamd;
@@ -37,6 +42,7 @@ struct RleArgs {
     const int64_t *dt_off, *gt_off;           // CSR of the run lists
     const int32_t *dt_hw, *gt_hw;             // (height, width) per mask
     const double *dt_bb, *gt_bb;              // tight box (x, y, w, h) per mask
+    const uint32_t *dt_runs, *gt_runs;        // the run lengths themselves
     const uint32_t *dt_end;                   // E per run of the detections
     const uint2 *gt_pre;                      // (E, P) per run of the ground truths
     const uint32_t *dt_ones, *gt_ones;        // ones per mask
@@ -70,6 +76,7 @@ __device__ __forceinline__ void rle_cell(const RleArgs &a, int32_t d0, int32_t D
         const int64_t ab = a.dt_off[d];
         const uint32_t ka = (uint32_t)(a.dt_off[d + 1] - ab);
         const uint32_t ones_a = a.dt_ones[d];
+        const bool big = rle_big_frame(hd, wd);
         // the detection's run boundaries, RLE_RPT * 64 at a time; a list that
         // fits one piece (the usual case) is loaded once for all its pairs.
         // A lane owns RLE_RPT CONSECUTIVE boundaries i = piece base + lane*RPT
@@ -105,6 +112,10 @@ __device__ __forceinline__ void rle_cell(const RleArgs &a, int32_t d0, int32_t D
                 const uint32_t kb = (uint32_t)(a.gt_off[g + 1] - bb);
                 const uint2 *__restrict__ tab = gt_tab + (bb - gt_tab_base);
                 const uint32_t ones_b = a.gt_ones[g];
+                // (the flag is asked for here and looked at behind the walk,
+                // whose reads hide its latency: in front of the walk, one more
+                // dependent LDS read per pair cost 9 % of the kernel)
+                const uint32_t b_flag = kb ? tab[0].y : 0u;
                 uint32_t acc = 0;
                 for (uint32_t piece = 0; piece < n_pieces; piece++) {
                     if (n_pieces > 1) load_piece(piece);
@@ -112,8 +123,14 @@ __device__ __forceinline__ void rle_cell(const RleArgs &a, int32_t d0, int32_t D
                 }
 #pragma unroll
                 for (int s = WAVE / 2; s > 0; s >>= 1) acc += __shfl_xor(acc, s, WAVE);
-                const uint32_t inter = acc;
-                const uint32_t uni = inter == 0 ? 1u : ones_a + ones_b - inter;
+                uint32_t inter = acc;
+                uint32_t uni = ones_a + ones_b - inter;
+                // the rare pair on which the reference stops early: its own walk
+                // instead (the sum above read nothing out of bounds on it)
+                if (__builtin_expect(big || b_flag != 0, 0) && ka && kb &&
+                    rle_stops_early(lane, a.dt_runs + ab, ka, a.gt_runs + bb, kb, b_flag))
+                    rle_two_cursors(a.dt_runs + ab, ka, a.gt_runs + bb, kb, inter, uni);
+                if (inter == 0) uni = 1u;
                 if (lane == 0) out[(int64_t)dd * G + gg] = (double)inter / (double)uni;
             }
         }
@@ -176,6 +193,7 @@ extern "C" int taoamd_rle_iou(int64_t n_cells, const int32_t *cell_dt_off,
     a.cell_dt_off = cell_dt_off; a.cell_gt_off = cell_gt_off;
     a.cell_iou_off = cell_iou_off;
     a.dt_off = dt_off; a.gt_off = gt_off;
+    a.dt_runs = dt_runs; a.gt_runs = gt_runs;
     a.dt_hw = dt_hw; a.gt_hw = gt_hw; a.dt_bb = dt_bb; a.gt_bb = gt_bb;
     a.iou = iou;
     TAO_TIMED("rle_iou_kernel", s, rle_iou_kernel<<<dim3((unsigned)n_cells), RLE_THREADS, 0, s>>>(a));

@@ -7,7 +7,10 @@
 //
 // A track maps timeline positions to masks.  For a shared position t of the
 // detection track d and the GT track g, i_t = |d_t & g_t| and u_t = |d_t | g_t|
-// (pycocotools merge / area: both 0 when the two frame sizes differ).  Then
+// as the areas of pycocotools' merge give them: both 0 when the two frame sizes
+// differ, and both counted only up to the pixel at which rleMerge's loop stops
+// (the frame's end, or earlier on coincident empty runs / 2^32 pixels left in
+// two runs: rle_walk.hpp).  Then
 //   3d_iou:      sum_shared i_t / (sum_shared u_t + pixels of d's frames g lacks
 //                + pixels of g's frames d lacks), integers summed exactly;
 //   avg_iou:     (sum over shared t, ascending, of i_t / u_t) / |F_d u F_g|;
@@ -20,7 +23,10 @@
 // i_t: the frame sizes and the masks' column spans settle many of them (u_t =
 // 0, or i_t = 0), the rest walk the runs as in rle_iou.hip (a lane owns RLE_RPT
 // consecutive run boundaries of the detection's mask and merges them against
-// the ground truth's (E, P) prefix table: rle_walk.hpp).  Every lane ends a
+// the ground truth's (E, P) prefix table: rle_walk.hpp); a pair on which the
+// reference's loop may stop early is then walked with its two cursors, also
+// where a shortcut has settled it (they assume that every pixel counts).
+// Every lane ends a
 // frame with the same i_t, so the per-pair sums are wavefront-uniform and the
 // ratios of avg_iou are added in timeline order -- no item list, no second
 // pass and no workspace beyond the per-mask prefix sums.
@@ -38,6 +44,7 @@ struct TrackMaskArgs {
     const int32_t *dt_frame_off, *dt_frame_pos, *gt_frame_off, *gt_frame_pos;
     const int64_t *dt_off, *gt_off;           // CSR of the run lists, one mask per frame
     const int32_t *dt_hw, *gt_hw;             // (height, width) per mask
+    const uint32_t *dt_runs, *gt_runs;        // the run lengths themselves
     const uint32_t *dt_end;                   // E per run of the detections' masks
     const uint2 *gt_pre;                      // (E, P) per run of the GT masks
     const uint32_t *dt_ones, *gt_ones;        // ones per mask
@@ -153,6 +160,23 @@ __global__ __launch_bounds__(TMI_THREADS) void track_mask_iou_kernel(TrackMaskAr
                     if (h > 0 && ones_a != 0 && ones_b != 0 && columns_meet(a, fa, fb, (uint32_t)h))
                         inter = mask_inter(a, lane, fa, fb);
                     uni = (uint64_t)ones_a + ones_b - inter;
+                    // the rare pair on which the reference stops early takes
+                    // its two cursors instead, whatever the shortcuts said (they
+                    // assume that every pixel counts)
+                    const int64_t bb = a.gt_off[fb];
+                    const uint32_t kb = (uint32_t)(a.gt_off[fb + 1] - bb);
+                    const uint32_t b_flag = kb ? a.gt_pre[bb].y : 0u;
+                    const bool rare = b_flag != 0 || rle_big_frame(h, a.dt_hw[2 * fa + 1]);
+                    if (__builtin_expect(rare, 0) && kb) {
+                        const int64_t ab = a.dt_off[fa];
+                        const uint32_t ka = (uint32_t)(a.dt_off[fa + 1] - ab);
+                        if (ka && rle_stops_early(lane, a.dt_runs + ab, ka, a.gt_runs + bb, kb,
+                                                  b_flag)) {
+                            uint32_t u32;
+                            rle_two_cursors(a.dt_runs + ab, ka, a.gt_runs + bb, kb, inter, u32);
+                            uni = u32;
+                        }
+                    }
                 }
                 shared++;
                 I += inter;
@@ -224,6 +248,7 @@ extern "C" int taoamd_track_mask_iou(
     a.dt_frame_off = dt_frame_off; a.dt_frame_pos = dt_frame_pos;
     a.gt_frame_off = gt_frame_off; a.gt_frame_pos = gt_frame_pos;
     a.dt_off = dt_off; a.gt_off = gt_off;
+    a.dt_runs = dt_runs; a.gt_runs = gt_runs;
     a.dt_hw = dt_hw; a.gt_hw = gt_hw;
     a.mode = mode;
     a.iou = iou;

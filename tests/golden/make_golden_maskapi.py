@@ -12,6 +12,10 @@ mask functions), compiled from the reference source into oracle/_ref by
                      rleFrPoly / rleToString / rleFrString / rleToBbox /
                      rleArea answers; "merge": mask lists with the union and
                      intersection of rleMerge and the rleIou matrix
+    rle_domain.npz   per pair kind of tests/rlepop.py <kind>_iou (rleIou of
+                     each pair), <kind>_inter and <kind>_union (rleArea of
+                     rleMerge's intersection and union); answers only, the
+                     masks come from the population's seeds
 
 The inputs are the seeded cases the tests ran against the live library; the
 masks handed to merge / IoU are rasterised by oracle/rle.py (what the tests
@@ -28,6 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(HERE))
 import boxpop  # noqa: E402
+import rlepop  # noqa: E402
 import orclib  # noqa: E402
 from oracle import rle  # noqa: E402
 
@@ -99,6 +104,18 @@ def merge_cases():
     return out
 
 
+def domain_cases():
+    arrays = {}
+    for kind in rlepop.PAIR_KINDS:
+        pairs = rlepop.pairs_of(kind)[0]
+        arrays[kind + "_iou"] = np.array([orclib.ref_rle_iou([d], [g])[0, 0] for d, g in pairs])
+        for name, cut in (("_inter", True), ("_union", False)):
+            arrays[kind + name] = np.array(
+                [orclib.ref_rle_area(orclib.ref_rle_merge([d, g], cut)) for d, g in pairs],
+                dtype=np.int64)
+    return arrays
+
+
 def main():
     if not os.path.exists(orclib.REF_SO):
         sys.exit("oracle/_ref not built: run __graft_entry__.build() where "
@@ -115,6 +132,7 @@ def main():
         arrays[kind + "_dt"], arrays[kind + "_gt"] = dt, gt
         arrays[kind + "_iou"] = orclib.ref_bb_iou(dt, gt)
     np.savez_compressed(os.path.join(OUT, "bb_iou_domain.npz"), **arrays)
+    np.savez_compressed(os.path.join(OUT, "rle_domain.npz"), **domain_cases())
     with gzip.open(os.path.join(OUT, "rle.json.gz"), "wt") as f:
         json.dump(dict(poly=poly_cases(), merge=merge_cases()), f)
     print("wrote", OUT)

@@ -112,7 +112,9 @@ def test_rle_iou_kernel_long_run_lists():
 def test_rle_iou_kernel_cells_beyond_the_lds_table_and_empty_runs():
     """40 ground truths of ~300 runs each do not fit the 6144-run LDS table
     (the kernel then reads the prefix sums through the caches); run lists with
-    empty runs inside (legal in an uncompressed RLE) count the same pixels."""
+    empty runs inside (legal in an uncompressed RLE), here on the ground
+    truths' side only: no pair has a common stop (tests/rlepop.py: stop_pixel),
+    so the same pixels count."""
     rng = np.random.default_rng(11)
     h, w = 300, 400
     db, gb = MaskBatch(), MaskBatch()

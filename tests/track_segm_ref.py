@@ -6,7 +6,10 @@ frPyObjects semantics); the three formulas are written out literally.
 A track is a dict {timeline position: mask}, a mask an oracle dict
 {"h", "w", "counts"}.  For a shared position t, i_t = area(merge([d_t, g_t],
 intersect=True)) and u_t = area(merge([d_t, g_t])) -- both 0 when the frame
-sizes differ, because merge then returns an empty mask.
+sizes differ, because merge then returns an empty mask, and both counted only
+up to the pixel at which rleMerge's loop stops: the frame's end, or before it
+where both masks finish a run and go on with an empty one, or where the two
+current runs have 2^32 pixels left between them (tests/rlepop.py: stop_pixel).
 """
 import numpy as np
 
