@@ -1311,15 +1311,25 @@ __device__ __forceinline__ void ss_split_chunk(const SsArgs &a, const SsChunk &c
 // chunk's 1000-2000 samples in 16-32 registers per lane was 0.09 ms of pure
 // latency at the head of the step's critical chain (1300 wavefronts on 1024
 // SIMDs, nothing to hide behind).  Here the four wavefronts of a workgroup each
-// sort a quarter of the samples (every fourth one: four runs of the same
-// distribution; 8 registers per lane, a fifth of the network), park their
-// sorted runs in LDS, and an element's rank among all samples is its place in
-// its own run plus, by binary search, the elements of the other three runs
-// below it -- the packed words are distinct (they end in the sample's position
-// in the chunk), so there are no ties to break.
+// sort a quarter of the samples (every fourth block of 64: four runs of the
+// same distribution; 8 registers per lane, a fifth of the network), and an
+// element's rank among all samples is its place in its own run plus, by binary
+// search, the elements of the other three runs below it -- the packed words are
+// distinct (they end in the sample's position in the chunk), so there are no
+// ties to break.
+//
+// Round 10: the runs are parked one at a time.  In round k wavefront k writes
+// its sorted run to the ONE shared buffer, the three others search it and add
+// to their ranks: 4 KB of LDS and 57 VGPRs where all four runs at once, three
+// sets of searches in flight, took 16 KB and 144 -- beside the track level's
+// 3D IoU a CU has 9.6 KB free (seven tasks of 22 024 B) and a SIMD about 110
+// VGPRs, and a workgroup that does not fit there waits until the tasks have
+// drained (459 us inside the step for 40 us of work; now 101).  The ranks are
+// sums over the same three runs as before, so every splitter is the one the
+// all-at-once form chose.
 template <int R>
 __device__ __forceinline__ void ss_split_chunk4(const SsArgs &a, const SsChunk &c, int lane,
-                                                int wave, uint64_t (*runs)[WAVE * 8])
+                                                int wave, uint64_t *run)
 {
     const int32_t S = ss_over(c.n), B = c.n_buckets, m = S * B;
     const int32_t stride = c.n / m;
@@ -1381,12 +1391,11 @@ __device__ __forceinline__ void ss_split_chunk4(const SsArgs &a, const SsChunk &
                      : __longlong_as_double((long long)SS_PAD);
     }
     ss_bitonic_packed<R>(p, lane);
-#pragma unroll
-    for (int r = 0; r < R; r++) runs[wave][lane * R + r] = (uint64_t)__double_as_longlong(p[r]);
-    // (slots past R * 64 of a run are never read: every search is bounded by R * 64)
-    __syncthreads();
-    // ranks of my R elements: the searches of all of them step together
-    // (fixed depth log2(R * 64): R x 3 independent LDS reads per step)
+    // ranks of my R elements, one parked run a round (`wave` is uniform: the
+    // barriers are met by whole wavefronts).  The searches step together four
+    // elements at a time (fixed depth log2(R * 64), four independent LDS reads
+    // per step): all eight of R = 8 at once took the kernel from 57 to 66
+    // VGPRs, past the 64 that leave it a place beside the 3D IoU's wavefronts.
     int32_t rank[R];
     uint64_t v[R];
 #pragma unroll
@@ -1395,19 +1404,31 @@ __device__ __forceinline__ void ss_split_chunk4(const SsArgs &a, const SsChunk &
         rank[r] = lane * R + r;
     }
 #pragma unroll
-    for (int o = 1; o < 4; o++) {
-        const uint64_t *__restrict__ run = runs[(wave + o) & 3];
-        int32_t lo[R];
+    for (int k = 0; k < 4; k++) {
+        if (wave == k) {
+            // (slots past R * 64 are never read: every search is bounded by R * 64)
 #pragma unroll
-        for (int r = 0; r < R; r++) lo[r] = 0;
-#pragma unroll
-        for (int half = R * WAVE / 2; half > 0; half >>= 1) {
-#pragma unroll
-            for (int r = 0; r < R; r++)            // (lo + half - 1 < R * 64 always)
-                lo[r] += run[lo[r] + half - 1] < v[r] ? half : 0;
+            for (int r = 0; r < R; r++) run[lane * R + r] = v[r];
         }
+        __syncthreads();
+        if (wave != k) {
+            constexpr int G = R < 4 ? R : 4;
 #pragma unroll
-        for (int r = 0; r < R; r++) rank[r] += lo[r] + (run[lo[r]] < v[r] ? 1 : 0);
+            for (int r0 = 0; r0 < R; r0 += G) {
+                int32_t lo[G];
+#pragma unroll
+                for (int g = 0; g < G; g++) lo[g] = 0;
+#pragma unroll
+                for (int half = R * WAVE / 2; half > 0; half >>= 1) {
+#pragma unroll
+                    for (int g = 0; g < G; g++)    // (lo + half - 1 < R * 64 always)
+                        lo[g] += run[lo[g] + half - 1] < v[r0 + g] ? half : 0;
+                }
+#pragma unroll
+                for (int g = 0; g < G; g++) rank[r0 + g] += lo[g] + (run[lo[g]] < v[r0 + g] ? 1 : 0);
+            }
+        }
+        if (k < 3) __syncthreads();                // the next run overwrites this one
     }
     // splitter b = the sample of rank b * S - 1: its full key from the scores
     // (all of a lane's candidate loads in flight together, as above)
@@ -1433,15 +1454,15 @@ __device__ __forceinline__ void ss_split_chunk4(const SsArgs &a, const SsChunk &
 
 __global__ __launch_bounds__(256) void ss_split4_kernel(SsArgs a, int32_t n_split)
 {
-    __shared__ uint64_t runs[4][WAVE * 8];
+    __shared__ uint64_t run[WAVE * 8];             // the run of one wavefront at a time: 4 KB
     const int lane = lane_id();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const SsChunk c = a.chunks[a.split_list[blockIdx.x]];
     const int32_t m = ss_over(c.n) * c.n_buckets;  // <= 2048 samples, <= 512 a wavefront
-    if (m <= 256) ss_split_chunk4<1>(a, c, lane, wave, runs);
-    else if (m <= 512) ss_split_chunk4<2>(a, c, lane, wave, runs);
-    else if (m <= 1024) ss_split_chunk4<4>(a, c, lane, wave, runs);
-    else ss_split_chunk4<8>(a, c, lane, wave, runs);
+    if (m <= 256) ss_split_chunk4<1>(a, c, lane, wave, run);
+    else if (m <= 512) ss_split_chunk4<2>(a, c, lane, wave, run);
+    else if (m <= 1024) ss_split_chunk4<4>(a, c, lane, wave, run);
+    else ss_split_chunk4<8>(a, c, lane, wave, run);
 }
 
 __global__ __launch_bounds__(256) void ss_split_kernel(SsArgs a, int32_t n_split)
