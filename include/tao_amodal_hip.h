@@ -1240,6 +1240,90 @@ int taoamd_track_error_types_links(int64_t n_dt, int64_t n_gt, int64_t n_cells, 
                                    int32_t *link_same, int32_t *link_other, uint8_t *held,
                                    void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- track-level association: per-frame followers (csrc/track_association.hip) -----
+ * WHICH detection track follows a ground-truth track, frame by frame: coverage,
+ * ID switches, fragmentation, mostly-tracked / mostly-lost, and coverage by
+ * visibility.  The reference has no counterpart; the definition is this
+ * library's.  Track level, boxes.  The pass reads the track tables alone: no
+ * IoU matrix, no match, none of the evaluation constants.
+ *
+ * Rows are those of the use_cats = 1 track table (after the max_dets cut and the
+ * federated filter).  Ground-truth track g lies in one cell (video, category);
+ * its CANDIDATES are the detection tracks of that cell, whatever their dt_flags.
+ * g has the frames k = 0 .. L - 1 at timeline positions p_k (strictly
+ * ascending) with box b_k and visibility vis_k.
+ *   f(d, g, k)  for a candidate d that has a frame at p_k: box_iou(d's box there,
+ *               b_k) -- this library's restatement of the reference's bbIou, not
+ *               crowd, the detection first, compiled with -ffp-contract=off: the
+ *               bits of taoamd_bb_iou.  Boxes may be any double; a NaN is no
+ *               overlap.
+ *   best_k(g)   the candidate of the greatest f(d, g, k) >= frame_thr; among
+ *               equal values the LOWEST table row (the best-scored track: a
+ *               cell's rows are in descending score); -1 if there is none.
+ *               Frame k is COVERED iff best_k >= 0.
+ *   frame_thr   any double in (0, 1], an argument of its own (not one of the IoU
+ *               thresholds of taoamd_set_thresholds).
+ *   follow[cell_iou_off[cell] + d_local * G + g_local]  the number of frames of g
+ *               on which d is best: the layout of the pass's IoU matrix.
+ * Per ground-truth track, gt_assoc int32[n_gt][7]:
+ *   0 frames          L
+ *   1 covered         the covered frames
+ *   2 ids             the candidates d with follow > 0
+ *   3 switches        over the covered frames in ascending position, uncovered
+ *                     ones skipped: those whose best differs from that of the
+ *                     covered frame before
+ *   4 fragments       the covered k with k = 0 or k - 1 uncovered; neighbours in
+ *                     the track's OWN frame list, not in timeline positions: a
+ *                     ground truth annotated with holes is not penalised
+ *   5 primary         the table row of the d of the greatest follow > 0, the
+ *                     lowest row among equal counts; -1 if covered = 0
+ *   6 primary_frames  that count
+ * Per category, cat_counts int64[n_cat][8], over the ground-truth tracks whose
+ * gt_flags lacks TAOAMD_GT_IGNORE: tracks, frames, covered, ids, switches,
+ * fragments, mostly_tracked (5 * covered >= 4 * frames), mostly_lost
+ * (5 * covered < frames).
+ * By visibility, vis_counts int64[n_vis][n_cat][3] = {frames, covered, followed
+ * by the track's primary} over the same tracks: n_vis <= 8 closed windows
+ * vis_rng double[n_vis][2] (device); a frame counts in EVERY window with lo <=
+ * vis_k <= hi (they overlap, as the image level's do), a NaN visibility in none.
+ * n_vis = 0 with vis_rng, gt_frame_vis and vis_counts NULL is allowed.
+ * Per frame: best int32[n_gt_frames] = the in-cell index of best_k or -1, and,
+ * if not NULL, best_iou double[n_gt_frames] = its overlap, 0.0 where uncovered.
+ *
+ *   cell_dt_off, cell_gt_off, cell_iou_off   the cell tables (n_cells + 1 entries)
+ *   gt_cat, gt_flags   columns of the ground-truth tracks, n_gt rows
+ *   *_frame_off, *_frame_pos, *_frame_box: the tracks' CSR frame lists of
+ *               taoamd_track_iou, n_dt_frames / n_gt_frames frames in all
+ *   gt_frame_vis double[n_gt_frames]: the visibility of every ground-truth frame
+ * Every output is zeroed / filled by the call; all but best_iou are integers and
+ * best_iou is one box_iou value, so every output is exact and the same from run
+ * to run: the follow counts and the count tables are integer adds, whose sum
+ * does not depend on the order of arrival; no float is ever added.
+ * TAOAMD_ERR_ARG: frame_thr outside (0, 1] (a NaN included), n_vis outside
+ * [0, 8], a size below 0; TAOAMD_ERR_WORKSPACE: fewer bytes than
+ * taoamd_track_association_workspace(n_dt, n_gt, n_gt_frames) (a descriptor per
+ * detection track, the cell of every ground-truth row, the track of every
+ * ground-truth frame, a track's counts per window; any base address, contents
+ * need not be initialised).  Both
+ * are answered before the first device call.  Rows and frames named by the CSR
+ * tables that lie outside the tables are skipped, never dereferenced: a ground-
+ * truth row no cell lists has no candidates, a frame no track lists no follower. */
+#define TAOAMD_TRACK_ASSOCIATION_TILE 64    /* ground-truth frames a workgroup takes */
+#define TAOAMD_TRACK_ASSOCIATION_VIS 8      /* visibility windows, at most */
+size_t taoamd_track_association_workspace(int64_t n_dt, int64_t n_gt, int64_t n_gt_frames);
+int taoamd_track_association(int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou,
+                             int64_t n_dt_frames, int64_t n_gt_frames, int32_t n_cat,
+                             int32_t n_vis, double frame_thr, const int32_t *cell_dt_off,
+                             const int32_t *cell_gt_off, const int64_t *cell_iou_off,
+                             const int32_t *gt_cat, const uint8_t *gt_flags,
+                             const int32_t *dt_frame_off, const int32_t *dt_frame_pos,
+                             const double *dt_frame_box, const int32_t *gt_frame_off,
+                             const int32_t *gt_frame_pos, const double *gt_frame_box,
+                             const double *gt_frame_vis, const double *vis_rng,
+                             int32_t *follow, int32_t *gt_assoc, int64_t *cat_counts,
+                             int64_t *vis_counts, int32_t *best, double *best_iou,
+                             void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- multi-GPU result exchange (category-partitioned evaluation) -------------------
  * No reference counterpart (the reference is single-process); these carry the
  * tables of taoamd_accumulate_compact between ranks and end in the layout of

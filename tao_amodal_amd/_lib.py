@@ -24,6 +24,13 @@ TRACK_ERROR_TYPES_TILE = 16
 ERROR_TYPES = ("TP", "IGNORED", "DUP", "LOC", "CLS", "BOTH", "BKG")
 ERROR_IMPACT_CHUNK = 256
 ERROR_FIXES = ("BASE", "CLS", "LOC", "BOTH", "DUP", "BKG", "MISS", "FP", "FN")
+TRACK_ASSOCIATION_TILE = 64
+TRACK_ASSOCIATION_VIS = 8
+ASSOC_TRACK_COLUMNS = ("frames", "covered", "ids", "switches", "fragments", "primary",
+                       "primary_frames")
+ASSOC_CAT_COLUMNS = ("tracks", "frames", "covered", "ids", "switches", "fragments",
+                     "mostly_tracked", "mostly_lost")
+ASSOC_VIS_COLUMNS = ("frames", "covered", "primary")
 
 _vp, _i64, _i32, _sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
 
@@ -214,6 +221,9 @@ SIGNATURES = {
     "taoamd_track_error_impact_workspace": (_sz, [_i64, _i64, _i32, _i32]),
     "taoamd_track_error_impact": (C.c_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "taoamd_track_association_workspace": (_sz, [_i64, _i64, _i64]),
+    "taoamd_track_association": (C.c_int, [_i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32,
+                                           C.c_double] + [_vp] * 20 + [_sz, _vp]),
 }
 
 _lib = None

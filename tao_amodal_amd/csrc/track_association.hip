@@ -1,0 +1,464 @@
+// Track-level association (gfx950): WHICH detection track follows a ground-
+// truth track, frame by frame.  The reference has no such table; the definition
+// is this library's, stated in include/tao_amodal_hip.h and DESIGN.md section 8.
+//
+// Rows are those of the use_cats = 1 track table.  Ground-truth track g lies in
+// one cell (video, category); its candidates are the detection tracks of that
+// cell.  For frame k of g at timeline position p_k, f(d, g, k) = box_iou(d's box
+// at p_k, g's box) where d has a frame at p_k, and best_k(g) = the candidate of
+// the greatest f >= frame_thr, the lowest row among equal values, -1 if none.
+//
+//   assoc_dt_meta_kernel  lane = detection track: {first frame, end, first and
+//                         last position} of its frame list, clamped to the tables
+//   assoc_cell_kernel     lane = cell: the cell of every ground-truth row
+//   assoc_frame_kernel    wavefront = ground-truth track: the track of every frame
+//   assoc_pair_kernel     THE HOT ONE.  lane = ground-truth frame, the whole table
+//                         as one flat list: a lane holds its frame's box and
+//                         position in registers and walks the cell's detection
+//                         tracks in ascending row, so a strict `>` keeps the lowest
+//                         row and the (max, row) state never leaves the lane -- no
+//                         LDS, no barrier, no cross-lane step, no rounds: a cell of
+//                         any size is the same loop.  A candidate's frame at p_k is
+//                         found in its position list (strictly ascending integers)
+//                         between the two indices the track's first and last
+//                         position allow: a track without holes is ONE probe, else
+//                         a binary search between them.  Lanes of a wavefront are
+//                         consecutive frames, as a rule of one track: the
+//                         candidate's descriptor is one address for all of them,
+//                         the probes touch neighbouring entries.
+//   assoc_walk_kernel     wavefront = ground-truth track, lane = frame of a chunk of
+//                         64: best[] is read coalesced; covered, fragments and
+//                         switches are popcounts of ballots (the covered frame
+//                         before a lane's is the highest covered lane below it, or
+//                         the carry of the chunk before); the follow counts are one
+//                         INTEGER add per distinct follower of a chunk into the
+//                         track's own column -- order-free, nothing is decided by
+//                         arrival
+//   assoc_column_kernel   wavefront = ground-truth track, behind a kernel boundary:
+//                         ids and the primary from the finished column (lanes
+//                         stride it; the greatest (count, ~index) of the wavefront),
+//                         then the frames once more for the visibility windows,
+//                         which need the primary
+//   assoc_tally_kernel    lane = ground-truth track: its row into the two count
+//                         tables, integer adds, one per (wavefront, category,
+//                         column)
+// (A lane per track that walks its own frames, the first form of the three, took
+// 0.63 ms at 20 000 tracks of 150 frames: 300 wavefronts, every load 64 cache
+// lines, two dependent walks.  See DESIGN.md section 8.)
+// box_iou is common.hpp's, compiled with -ffp-contract=off like every other use:
+// the bits of taoamd_bb_iou.  Everything else is an integer.
+#include "common.hpp"
+#include "workspace.hpp"
+
+using namespace taoamd;
+
+#define TA_TILE TAOAMD_TRACK_ASSOCIATION_TILE   // ground-truth frames per workgroup of the pair kernel
+#define TA_VMAX TAOAMD_TRACK_ASSOCIATION_VIS    // visibility windows
+#define TA_NASSOC 7
+#define TA_NCAT 8
+#define TA_NVIS 3
+
+static_assert(TA_TILE % WAVE == 0, "whole wavefronts");
+
+struct AssocArgs {
+    int64_t n_dt, n_gt, n_cells, n_iou, n_dt_frames, n_gt_frames;
+    int32_t n_cat, n_vis;
+    double thr;
+    const int32_t *cell_dt_off, *cell_gt_off;
+    const int64_t *cell_iou_off;
+    const int32_t *gt_cat;
+    const uint8_t *gt_flags;
+    const int32_t *dfoff, *dfpos;
+    const double4 *dfbox;
+    const int32_t *gfoff, *gfpos;
+    const double4 *gfbox;
+    const double *gfvis, *vis_rng;
+    int32_t *follow;                 // [n_iou], the layout of the IoU matrix
+    int32_t *gt_assoc;               // [n_gt][7]
+    unsigned long long *cat_counts;  // [n_cat][8]
+    unsigned long long *vis_counts;  // [n_vis][n_cat][3]
+    int32_t *best;                   // [n_gt_frames]
+    double *best_iou;                // [n_gt_frames] or null
+    int4 *dt_meta;                   // [n_dt] {first frame, end, first position, last position}
+    int32_t *gt_cell;                // [n_gt], -1: in no cell
+    int32_t *frame_gt;               // [n_gt_frames], -1: of no track
+    int32_t *trk_vis;                // [n_gt][8][3]: a track's counts per visibility window
+};
+
+__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi)
+{
+    return v < lo ? lo : (v > hi ? hi : v);
+}
+
+__global__ __launch_bounds__(256) void assoc_dt_meta_kernel(AssocArgs a)
+{
+    const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= a.n_dt) return;
+    // (offsets clamped to the table: a bad CSR reads wrong frames, never past an end)
+    const int64_t fs = clamp64(a.dfoff[d], 0, a.n_dt_frames);
+    const int64_t fe = clamp64(a.dfoff[d + 1], fs, a.n_dt_frames);
+    int4 m = make_int4((int32_t)fs, (int32_t)fe, 0, -1);
+    if (fe > fs) {
+        m.z = a.dfpos[fs];
+        m.w = a.dfpos[fe - 1];
+    }
+    a.dt_meta[d] = m;
+}
+
+__global__ __launch_bounds__(256) void assoc_cell_kernel(AssocArgs a)
+{
+    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= a.n_cells) return;
+    const int64_t g0 = clamp64(a.cell_gt_off[c], 0, a.n_gt);
+    const int64_t g1 = clamp64(a.cell_gt_off[c + 1], g0, a.n_gt);
+    for (int64_t g = g0; g < g1; g++) a.gt_cell[g] = (int32_t)c;
+}
+
+__global__ __launch_bounds__(256) void assoc_frame_kernel(AssocArgs a)
+{
+    const int64_t g = (int64_t)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
+    if (g >= a.n_gt) return;
+    const int64_t s = clamp64(a.gfoff[g], 0, a.n_gt_frames);
+    const int64_t e = clamp64(a.gfoff[g + 1], s, a.n_gt_frames);
+    for (int64_t k = s + lane_id(); k < e; k += WAVE) a.frame_gt[k] = (int32_t)g;
+}
+
+__global__ __launch_bounds__(TA_TILE) void assoc_pair_kernel(AssocArgs a)
+{
+    const int64_t k = (int64_t)blockIdx.x * TA_TILE + threadIdx.x;
+    if (k >= a.n_gt_frames) return;
+    const int32_t g = a.frame_gt[k];
+    const int32_t cell = g >= 0 ? a.gt_cell[g] : -1;
+    int64_t d0 = 0, d1 = 0;
+    if (cell >= 0) {
+        d0 = clamp64(a.cell_dt_off[cell], 0, a.n_dt);
+        d1 = clamp64(a.cell_dt_off[cell + 1], d0, a.n_dt);
+    }
+    int32_t arg = -1;
+    double top = 0.0;
+    if (d1 > d0) {
+        const int64_t p = a.gfpos[k];
+        const double4 G = a.gfbox[k];
+        for (int64_t d = d0; d < d1; d++) {
+            const int4 m = a.dt_meta[d];
+            if (p < m.z || p > m.w) continue;          // (a track without frames: z > w)
+            // positions ascend strictly: the frame at p, if any, lies no further from
+            // the list's first entry than p from its position, nor from its last
+            int64_t lo = max((int64_t)m.x, (int64_t)m.y - 1 - ((int64_t)m.w - p));
+            int64_t hi = min((int64_t)m.y - 1, (int64_t)m.x + (p - (int64_t)m.z));
+            while (lo < hi) {
+                const int64_t mid = (lo + hi) >> 1;
+                if (a.dfpos[mid] < p) lo = mid + 1; else hi = mid;
+            }
+            if (a.dfpos[lo] != p) continue;
+            const double4 D = a.dfbox[lo];
+            const double v = box_iou(D.x, D.y, D.z, D.w, G.x, G.y, G.z, G.w);
+            // (ascending rows: an equal overlap never replaces the follower; a NaN compares
+            // false; frame_thr > 0 = the empty maximum)
+            if (v >= a.thr && v > top) {
+                top = v;
+                arg = (int32_t)(d - d0);
+            }
+        }
+    }
+    a.best[k] = arg;
+    if (a.best_iou) a.best_iou[k] = top;
+}
+
+__device__ __forceinline__ long long wave_sum(long long v)
+{
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// base[key * N + c] += the sum of v[c] over the wavefront's live lanes of that
+// key: one add per (distinct key, column with a sum), by the key's first lane
+// (trk_err_count of track_error_types.hip with amounts instead of ones).
+template <int N>
+__device__ __forceinline__ void assoc_add(unsigned long long *base, bool live, int32_t key,
+                                          const int32_t (&v)[N])
+{
+    uint64_t left = __ballot(live);
+    while (left) {
+        const int lead = __builtin_ctzll(left);
+        const int32_t k = __builtin_amdgcn_readlane(key, lead);
+        const bool mine = live && key == k;
+        const uint64_t same = __ballot(mine);
+#pragma unroll
+        for (int c = 0; c < N; c++) {
+            const long long s = wave_sum(mine ? (long long)v[c] : 0ll);
+            if (lane_id() == lead && s != 0)
+                atomicAdd(base + (int64_t)k * N + c, (unsigned long long)s);
+        }
+        left &= ~same;
+    }
+}
+
+// A wavefront's ground-truth track: its frames [s, e), its candidates [d0, d0 + D)
+// and its column of `follow` (entry d at col + d * G), clamped to the tables.
+struct OwnColumn {
+    int64_t s, e, d0, D, G, col;
+    __device__ __forceinline__ void init(const AssocArgs &a, int64_t g)
+    {
+        s = clamp64(a.gfoff[g], 0, a.n_gt_frames);
+        e = clamp64(a.gfoff[g + 1], s, a.n_gt_frames);
+        d0 = D = G = col = 0;
+        const int32_t cell = a.gt_cell[g];
+        if (cell >= 0) {
+            d0 = clamp64(a.cell_dt_off[cell], 0, a.n_dt);
+            D = clamp64(a.cell_dt_off[cell + 1], d0, a.n_dt) - d0;
+            const int64_t g0 = a.cell_gt_off[cell];
+            G = (int64_t)a.cell_gt_off[cell + 1] - g0;
+            col = a.cell_iou_off[cell] + (g - g0);
+        }
+    }
+    // where the count of in-cell index d lies, -1: nowhere
+    __device__ __forceinline__ int64_t at(const AssocArgs &a, int64_t d) const
+    {
+        const int64_t i = col + d * G;
+        return d < D && i >= 0 && i < a.n_iou ? i : -1;
+    }
+};
+
+// wavefront = ground-truth track, lane = frame of a chunk of 64: one coalesced read
+// of best[] a chunk; covered, fragments and switches are popcounts of ballots (the
+// covered frame before a lane's = the highest covered lane below it, or the carry
+// of the chunk before), the follow counts one integer add per distinct follower of
+// the chunk.  Everything counted is the same in every lane.
+__global__ __launch_bounds__(256) void assoc_walk_kernel(AssocArgs a)
+{
+    const int64_t g = (int64_t)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
+    if (g >= a.n_gt) return;                 // (whole wavefronts)
+    const int lane = lane_id();
+    OwnColumn o;
+    o.init(a, g);
+    int32_t covered = 0, switches = 0, fragments = 0;
+    int32_t last = -1;                       // the follower of the last covered frame so far
+    bool gap = true;                         // the frame before the chunk is uncovered (or there is none)
+    for (int64_t base = o.s; base < o.e; base += WAVE) {
+        const int64_t k = base + lane;
+        const int32_t b = k < o.e ? a.best[k] : -1;
+        const bool cov = b >= 0;
+        const uint64_t m = __ballot(cov);
+        if (m == 0) { gap = true; continue; }           // (uniform)
+        covered += __popcll(m);
+        const bool open = lane == 0 ? gap : !((m >> ((lane + WAVE - 1) & (WAVE - 1))) & 1ull);
+        fragments += __popcll(__ballot(cov && open));
+        const uint64_t below = m & ((1ull << lane) - 1ull);
+        int32_t before = __shfl(b, below ? 63 - __builtin_clzll(below) : 0);
+        before = below ? before : last;
+        switches += __popcll(__ballot(cov && before >= 0 && before != b));
+        uint64_t left = m;
+        while (left) {
+            const int lead = __builtin_ctzll(left);
+            const int32_t d = __builtin_amdgcn_readlane(b, lead);
+            const uint64_t same = __ballot(b == d);
+            const int64_t at = o.at(a, d);
+            if (lane == lead && at >= 0) atomicAdd(a.follow + at, (int32_t)__popcll(same));
+            left &= ~same;
+        }
+        last = __builtin_amdgcn_readlane(b, 63 - __builtin_clzll(m));
+        gap = !((m >> (WAVE - 1)) & 1ull);
+    }
+    if (lane == 0) {
+        int32_t *out = a.gt_assoc + g * TA_NASSOC;
+        out[0] = (int32_t)(o.e - o.s);
+        out[1] = covered;
+        out[3] = switches;
+        out[4] = fragments;
+    }
+}
+
+__device__ __forceinline__ unsigned long long wave_max(unsigned long long v)
+{
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) {
+        const unsigned long long w = __shfl_xor(v, o);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+
+// wavefront = ground-truth track, behind the walk (a kernel boundary: the column
+// is complete).  Lanes stride the column: ids, and the primary as the greatest
+// (count, ~index); then the frames once more, coalesced, for the visibility
+// windows, which need the primary: the track's [window][3] counts go to trk_vis.
+__global__ __launch_bounds__(256) void assoc_column_kernel(AssocArgs a)
+{
+    const int64_t g = (int64_t)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
+    if (g >= a.n_gt) return;                 // (whole wavefronts)
+    const int lane = lane_id();
+    OwnColumn o;
+    o.init(a, g);
+    int32_t ids = 0;
+    unsigned long long top = 0;              // count << 32 | ~index: the greatest count, the lowest index
+    for (int64_t d = lane; d < o.D; d += WAVE) {
+        const int64_t at = o.at(a, d);
+        const int32_t c = at >= 0 ? a.follow[at] : 0;
+        const unsigned long long key = ((unsigned long long)(uint32_t)c << 32) | (uint32_t)~(uint32_t)d;
+        ids += c > 0;
+        top = c > 0 && key > top ? key : top;
+    }
+    ids = (int32_t)wave_sum(ids);
+    top = wave_max(top);
+    const int32_t prim = top ? (int32_t)~(uint32_t)top : -1;
+    int32_t cnt[TA_VMAX][TA_NVIS];
+#pragma unroll
+    for (int w = 0; w < TA_VMAX; w++) cnt[w][0] = cnt[w][1] = cnt[w][2] = 0;
+    if (a.n_vis > 0)                         // (uniform)
+        for (int64_t base = o.s; base < o.e; base += WAVE) {
+            const int64_t k = base + lane;
+            const bool live = k < o.e;
+            const int32_t b = live ? a.best[k] : -1;
+            const double vis = live ? a.gfvis[k] : 0.0;
+#pragma unroll
+            for (int w = 0; w < TA_VMAX; w++) {
+                if (w >= a.n_vis) continue;  // (uniform)
+                // (closed windows; a NaN visibility compares false: in no window)
+                const bool in = live && a.vis_rng[2 * w] <= vis && vis <= a.vis_rng[2 * w + 1];
+                cnt[w][0] += __popcll(__ballot(in));
+                cnt[w][1] += __popcll(__ballot(in && b >= 0));
+                cnt[w][2] += __popcll(__ballot(in && b >= 0 && b == prim));
+            }
+        }
+    if (lane == 0) {
+        int32_t *out = a.gt_assoc + g * TA_NASSOC;
+        out[2] = ids;
+        out[5] = prim >= 0 ? (int32_t)(o.d0 + prim) : -1;
+        out[6] = (int32_t)(top >> 32);
+        int32_t *v = a.trk_vis + g * (TA_VMAX * TA_NVIS);
+#pragma unroll
+        for (int w = 0; w < TA_VMAX; w++) {
+            v[w * TA_NVIS] = cnt[w][0];
+            v[w * TA_NVIS + 1] = cnt[w][1];
+            v[w * TA_NVIS + 2] = cnt[w][2];
+        }
+    }
+}
+
+// lane = ground-truth track: its row of gt_assoc and of trk_vis into the two count
+// tables, one integer add per (wavefront, category, column)
+__global__ __launch_bounds__(256) void assoc_tally_kernel(AssocArgs a)
+{
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool valid = g < a.n_gt;
+    const int32_t cat = valid ? a.gt_cat[g] : 0;
+    const bool ok = valid && !(a.gt_flags[g] & TAOAMD_GT_IGNORE) && cat >= 0 && cat < a.n_cat;
+    int32_t frames = 0, covered = 0, ids = 0, switches = 0, fragments = 0;
+    if (ok) {
+        const int32_t *in = a.gt_assoc + g * TA_NASSOC;
+        frames = in[0]; covered = in[1]; ids = in[2]; switches = in[3]; fragments = in[4];
+    }
+    const int32_t row[TA_NCAT] = {1, frames, covered, ids, switches, fragments,
+                                  5 * (int64_t)covered >= 4 * (int64_t)frames,
+                                  5 * (int64_t)covered < (int64_t)frames};
+    assoc_add<TA_NCAT>(a.cat_counts, ok, cat, row);
+#pragma unroll
+    for (int w = 0; w < TA_VMAX; w++) {
+        if (w >= a.n_vis) continue;          // (uniform)
+        int32_t cnt[TA_NVIS] = {0, 0, 0};
+        if (ok) {
+            const int32_t *v = a.trk_vis + g * (TA_VMAX * TA_NVIS) + w * TA_NVIS;
+            cnt[0] = v[0]; cnt[1] = v[1]; cnt[2] = v[2];
+        }
+        assoc_add<TA_NVIS>(a.vis_counts + (int64_t)w * a.n_cat * TA_NVIS, ok, cat, cnt);
+    }
+}
+
+// The tables of the pass, in buffer order: a function of (n_dt, n_gt, n_gt_frames)
+static void assoc_layout(Carve &c, int64_t n_dt, int64_t n_gt, int64_t n_gt_frames, AssocArgs &a)
+{
+    a.dt_meta = c.take<int4>((size_t)n_dt);
+    a.gt_cell = c.take<int32_t>((size_t)n_gt);
+    a.frame_gt = c.take<int32_t>((size_t)n_gt_frames);
+    a.trk_vis = c.take<int32_t>((size_t)n_gt * TA_VMAX * TA_NVIS);
+}
+
+extern "C" size_t taoamd_track_association_workspace(int64_t n_dt, int64_t n_gt,
+                                                     int64_t n_gt_frames)
+{
+    if (n_dt < 0 || n_dt > 0x7fffffff || n_gt < 0 || n_gt > 0x7fffffff || n_gt_frames < 0 ||
+        n_gt_frames > 0x7fffffff)
+        return 0;
+    AssocArgs a;
+    return measure([&](Carve &c) { assoc_layout(c, n_dt, n_gt, n_gt_frames, a); });
+}
+
+extern "C" int taoamd_track_association(
+    int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou, int64_t n_dt_frames,
+    int64_t n_gt_frames, int32_t n_cat, int32_t n_vis, double frame_thr,
+    const int32_t *cell_dt_off, const int32_t *cell_gt_off, const int64_t *cell_iou_off,
+    const int32_t *gt_cat, const uint8_t *gt_flags, const int32_t *dt_frame_off,
+    const int32_t *dt_frame_pos, const double *dt_frame_box, const int32_t *gt_frame_off,
+    const int32_t *gt_frame_pos, const double *gt_frame_box, const double *gt_frame_vis,
+    const double *vis_rng, int32_t *follow, int32_t *gt_assoc, int64_t *cat_counts,
+    int64_t *vis_counts, int32_t *best, double *best_iou, void *workspace,
+    size_t workspace_bytes, void *stream)
+{
+    if (n_dt < 0 || n_dt > 0x7fffffff || n_gt < 0 || n_gt > 0x7fffffff || n_cells < 0 ||
+        n_cells > 0x7fffffff || n_iou < 0 || n_dt_frames < 0 || n_dt_frames > 0x7fffffff ||
+        n_gt_frames < 0 || n_gt_frames > 0x7fffffff || n_cat <= 0 || n_vis < 0 || n_vis > TA_VMAX)
+        return TAOAMD_ERR_ARG;
+    // (a NaN compares false both times)
+    if (!(frame_thr > 0) || !(frame_thr <= 1)) return TAOAMD_ERR_ARG;
+    if (!cat_counts || !workspace) return TAOAMD_ERR_ARG;
+    if (n_vis > 0 && (!vis_rng || !vis_counts || (n_gt_frames > 0 && !gt_frame_vis)))
+        return TAOAMD_ERR_ARG;
+    if (n_cells > 0 && (!cell_dt_off || !cell_gt_off || !cell_iou_off)) return TAOAMD_ERR_ARG;
+    if (n_dt > 0 && !dt_frame_off) return TAOAMD_ERR_ARG;
+    if (n_dt_frames > 0 && (!dt_frame_pos || !dt_frame_box)) return TAOAMD_ERR_ARG;
+    if (n_gt > 0 && (!gt_cat || !gt_flags || !gt_frame_off || !gt_assoc)) return TAOAMD_ERR_ARG;
+    if (n_gt_frames > 0 && (!gt_frame_pos || !gt_frame_box || !best)) return TAOAMD_ERR_ARG;
+    if (n_iou > 0 && !follow) return TAOAMD_ERR_ARG;
+    Carve c(workspace);
+    AssocArgs a;
+    assoc_layout(c, n_dt, n_gt, n_gt_frames, a);
+    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    a.n_dt = n_dt; a.n_gt = n_gt; a.n_cells = n_cells; a.n_iou = n_iou;
+    a.n_dt_frames = n_dt_frames; a.n_gt_frames = n_gt_frames;
+    a.n_cat = n_cat; a.n_vis = n_vis; a.thr = frame_thr;
+    a.cell_dt_off = cell_dt_off; a.cell_gt_off = cell_gt_off; a.cell_iou_off = cell_iou_off;
+    a.gt_cat = gt_cat; a.gt_flags = gt_flags;
+    a.dfoff = dt_frame_off; a.dfpos = dt_frame_pos;
+    a.dfbox = reinterpret_cast<const double4 *>(dt_frame_box);
+    a.gfoff = gt_frame_off; a.gfpos = gt_frame_pos;
+    a.gfbox = reinterpret_cast<const double4 *>(gt_frame_box);
+    a.gfvis = gt_frame_vis; a.vis_rng = vis_rng;
+    a.follow = follow; a.gt_assoc = gt_assoc;
+    a.cat_counts = (unsigned long long *)cat_counts;
+    a.vis_counts = (unsigned long long *)vis_counts;
+    a.best = best; a.best_iou = best_iou;
+    TAO_HIP(hipMemsetAsync(cat_counts, 0, (size_t)n_cat * TA_NCAT * sizeof(int64_t), s));
+    if (n_vis > 0)
+        TAO_HIP(hipMemsetAsync(vis_counts, 0, (size_t)n_vis * n_cat * TA_NVIS * sizeof(int64_t), s));
+    if (n_iou > 0) TAO_HIP(hipMemsetAsync(follow, 0, (size_t)n_iou * sizeof(int32_t), s));
+    if (n_gt == 0) return TAOAMD_OK;
+    // (a ground-truth row no cell lists has no candidates, a frame no track lists no follower)
+    TAO_HIP(hipMemsetAsync(a.gt_cell, 0xff, (size_t)n_gt * sizeof(int32_t), s));
+    if (n_gt_frames > 0)
+        TAO_HIP(hipMemsetAsync(a.frame_gt, 0xff, (size_t)n_gt_frames * sizeof(int32_t), s));
+    if (n_dt > 0)
+        TAO_TIMED("assoc_dt_meta_kernel", s,
+                  assoc_dt_meta_kernel<<<(unsigned)((n_dt + 255) / 256), 256, 0, s>>>(a));
+    if (n_cells > 0)
+        TAO_TIMED("assoc_cell_kernel", s,
+                  assoc_cell_kernel<<<(unsigned)((n_cells + 255) / 256), 256, 0, s>>>(a));
+    if (n_gt_frames > 0) {
+        TAO_TIMED("assoc_frame_kernel", s,
+                  assoc_frame_kernel<<<(unsigned)((n_gt + 256 / WAVE - 1) / (256 / WAVE)), 256, 0,
+                                       s>>>(a));
+        TAO_TIMED("assoc_pair_kernel", s,
+                  assoc_pair_kernel<<<(unsigned)((n_gt_frames + TA_TILE - 1) / TA_TILE), TA_TILE,
+                                      0, s>>>(a));
+    }
+    const int per = 256 / WAVE;
+    const unsigned track_blocks = (unsigned)((n_gt + per - 1) / per);
+    TAO_TIMED("assoc_walk_kernel", s, assoc_walk_kernel<<<track_blocks, 256, 0, s>>>(a));
+    TAO_TIMED("assoc_column_kernel", s, assoc_column_kernel<<<track_blocks, 256, 0, s>>>(a));
+    TAO_TIMED("assoc_tally_kernel", s,
+              assoc_tally_kernel<<<(unsigned)((n_gt + 255) / 256), 256, 0, s>>>(a));
+    TAO_LAUNCH_CHECK();
+    return TAOAMD_OK;
+}

@@ -1309,6 +1309,72 @@ def stage_track_error_impact(dp, ws, slot, tb):
         "taoamd_track_error_impact")
 
 
+def set_frame_visibility(dp, vis):
+    """The visibility of every ground-truth frame of a track-level problem
+    (float64[n_gt_frames], the annotations' `visibility` in the order of
+    gt_frame_*): what stage_track_association's windows read.  Uploaded once."""
+    vis = np.ascontiguousarray(vis, dtype=np.float64)
+    if len(vis) != int(dp.t["gt_frame_pos"].numel()):
+        raise _lib.TaoAmdError("%d visibilities for %d ground-truth frames"
+                               % (len(vis), int(dp.t["gt_frame_pos"].numel())))
+    dp.t["gt_frame_vis"] = torch.from_numpy(vis if len(vis) else np.zeros(1)).to(dp.device)
+
+
+def stage_track_association(dp, ws, frame_thr, vis_rng):
+    """Per-frame followers of the ground-truth tracks (taoamd_track_association;
+    the definition is in include/tao_amodal_hip.h): ws.assoc_follow[n_iou] in the
+    layout of the IoU matrix, ws.assoc_gt[n_gt, 7], ws.assoc_cat_counts[n_cat, 8],
+    ws.assoc_vis_counts[n_vis, n_cat, 3] (None without windows), ws.assoc_best
+    [n_gt_frames] and ws.assoc_best_iou[n_gt_frames], at the per-frame threshold
+    `frame_thr` in (0, 1] and the closed visibility windows `vis_rng` (up to 8
+    {lo, hi} pairs; they need set_frame_visibility).  On request only.  Reads the
+    track tables alone -- never ws.iou, never the match --, so it depends on
+    neither the metric, the thresholds nor the ranges.  Buffers are allocated on
+    the first call and kept with the workspace."""
+    if dp.kind != "tao" or dp.mask_iou:
+        raise _lib.TaoAmdError("the track association is the track level's, on boxes")
+    lib, t, dev = _lib.load(), dp.t, dp.device
+    vis_rng = np.ascontiguousarray(vis_rng if vis_rng is not None else [],
+                                   dtype=np.float64).reshape(-1, 2)
+    n_vis = len(vis_rng)
+    if n_vis > _lib.TRACK_ASSOCIATION_VIS:
+        raise _lib.TaoAmdError("%d visibility windows; the kernels take up to %d"
+                               % (n_vis, _lib.TRACK_ASSOCIATION_VIS))
+    if n_vis and t.get("gt_frame_vis") is None:
+        raise _lib.TaoAmdError("visibility windows need the frames' visibility "
+                               "(engine.set_frame_visibility)")
+    n_df, n_gf = int(t["dt_frame_pos"].numel()), int(t["gt_frame_pos"].numel())
+    if getattr(ws, "assoc_gt", None) is None:
+        ws.assoc_bytes = lib.taoamd_track_association_workspace(dp.n_dt, dp.n_gt, n_gf)
+        ws.assoc_ws = torch.empty(max(int(ws.assoc_bytes), 256), dtype=torch.uint8, device=dev)
+        ws.assoc_follow = torch.empty(max(dp.n_iou, 1), dtype=torch.int32, device=dev)
+        ws.assoc_gt = torch.empty((max(dp.n_gt, 1), len(_lib.ASSOC_TRACK_COLUMNS)),
+                                  dtype=torch.int32, device=dev)
+        ws.assoc_cat_counts = torch.empty((dp.n_cat, len(_lib.ASSOC_CAT_COLUMNS)),
+                                          dtype=torch.int64, device=dev)
+        ws.assoc_best = torch.empty(max(n_gf, 1), dtype=torch.int32, device=dev)
+        ws.assoc_best_iou = torch.empty(max(n_gf, 1), dtype=torch.float64, device=dev)
+        ws.assoc_vis_counts = None
+    if n_vis and (ws.assoc_vis_counts is None or ws.assoc_vis_counts.shape[0] != n_vis):
+        ws.assoc_vis_counts = torch.empty((n_vis, dp.n_cat, len(_lib.ASSOC_VIS_COLUMNS)),
+                                          dtype=torch.int64, device=dev)
+    if not n_vis:
+        ws.assoc_vis_counts = None
+    rng_t = torch.from_numpy(vis_rng).to(dev) if n_vis else None
+    _lib.check(lib.taoamd_track_association(
+        dp.n_dt, dp.n_gt, dp.n_cells, dp.n_iou, n_df, n_gf, dp.n_cat, n_vis, float(frame_thr),
+        _ptr(t["cell_dt_off"]), _ptr(t["cell_gt_off"]), _ptr(t["cell_iou_off"]),
+        _ptr(t["gt_cat"]), _ptr(t["gt_flags"]),
+        _ptr(t["dt_frame_off"]), _ptr(t["dt_frame_pos"]), _ptr(t["dt_frame_box"]),
+        _ptr(t["gt_frame_off"]), _ptr(t["gt_frame_pos"]), _ptr(t["gt_frame_box"]),
+        _ptr(t["gt_frame_vis"]) if n_vis else None, _ptr(rng_t),
+        _ptr(ws.assoc_follow), _ptr(ws.assoc_gt), _ptr(ws.assoc_cat_counts),
+        _ptr(ws.assoc_vis_counts), _ptr(ws.assoc_best), _ptr(ws.assoc_best_iou),
+        _ptr(ws.assoc_ws), ws.assoc_bytes, _stream()), "taoamd_track_association")
+    # (the windows' upload is read by the kernels of this stream: alive until they ran)
+    ws.assoc_vis_rng = rng_t
+
+
 def stage_track_iou_guarded(dp, ws):
     stage_track_iou(dp, ws)
     stage_iou_guard(dp, ws)

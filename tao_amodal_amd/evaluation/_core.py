@@ -336,6 +336,42 @@ class GpuRun:
             out[np.maximum.accumulate(out == 0, axis=1)] = 0
         return out, num_gt[..., ks]
 
+    def association_table(self, frame_thr, vis_rng, ann_vis):
+        """The per-frame followers of the ground-truth tracks
+        (engine.stage_track_association; the definition is in
+        include/tao_amodal_hip.h) at the per-frame threshold `frame_thr` and the
+        visibility windows `vis_rng`: dict(gt_assoc int32[n_gt, 7] with the
+        primary as a table row, cat_counts int64[K, 8], vis_counts int64[n_vis,
+        K, 3], best int32[n_gt_frames] as in-cell indices, best_iou).  `ann_vis`:
+        the `visibility` column of the ground-truth annotations the tables were
+        built from; the frames' own is gathered and uploaded on the first call.
+        Reads the track tables alone: no constants, no match, no IoU matrix."""
+        if self.flat.kind != "tao":
+            raise NotImplementedError("association() is the track level's")
+        if self.dp.mask_iou:
+            raise NotImplementedError("association() with iou_type='segm': boxes only")
+        if not self.flat.get("use_cats", True):
+            raise NotImplementedError(
+                "association() with use_cats = 0: the candidates of a ground-truth track "
+                "are the detection tracks of its category")
+        e, dp, ws = self.engine, self.dp, self.ws
+        if dp.t.get("gt_frame_vis") is None:
+            with timed("upload+plan"):
+                rows = self.flat.gt_frame_box.index
+                e.set_frame_visibility(dp, np.asarray(ann_vis, dtype=np.float64)[rows])
+        with timed("kernels"):
+            e.stage_track_association(dp, ws, frame_thr, vis_rng)
+            self.torch.cuda.synchronize(self.device)
+        with timed("download"):
+            n_gt, n_gf = dp.n_gt, int(dp.t["gt_frame_pos"].numel())
+            n_vis = len(vis_rng)
+            return {"gt_assoc": ws.assoc_gt[:n_gt].cpu().numpy(),
+                    "cat_counts": ws.assoc_cat_counts.cpu().numpy(),
+                    "vis_counts": ws.assoc_vis_counts.cpu().numpy() if n_vis else
+                    np.zeros((0, dp.n_cat, 3), dtype=np.int64),
+                    "best": ws.assoc_best[:n_gf].cpu().numpy(),
+                    "best_iou": ws.assoc_best_iou[:n_gf].cpu().numpy()}
+
     def pointer_tables(self):
         """What eval['dt_pointers'] is read from: the detections' ids and
         (matched, ignored) words in the sweep's order (category-major, stable

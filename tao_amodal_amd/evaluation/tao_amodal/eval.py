@@ -112,6 +112,8 @@ class TaoEval:
         self._cat_pos = None
         self._error_types = {}
         self._error_impact = {}
+        self._association = {}
+        self._gt_columns = None
 
     # ------------------------------------------------------------ stages
     def evaluate(self, show_progress=False):
@@ -167,6 +169,8 @@ class TaoEval:
                                constants=constants)
         self._error_types = {}
         self._error_impact = {}
+        self._association = {}
+        self._gt_columns = gt_cols      # the annotation rows the tables' frames name
         self._run.evaluate()
         P = self.params
         rngs = [(a, t) for a in P.area_rng for t in P.time_rng]
@@ -422,6 +426,122 @@ class TaoEval:
                                for t in range(len(P.time_rng))]}
             self._error_impact[key] = hit
         return dict(hit)
+
+    def association(self, frame_thr=0.5, vis_rng=None, vis_lbl=None, per_track=False,
+                    per_frame=False):
+        """Which detection track follows a ground-truth track, frame by frame:
+        coverage, ID switches, fragmentation, mostly-tracked / mostly-lost, and
+        coverage split by the frames' visibility -- what error_types() cannot
+        say about a LOC or missed ground-truth track (never found, handed from
+        id to id, or lost when it became occluded).  No counterpart in the
+        reference.  Callable after evaluate(), computed on the device on request
+        (csrc/track_association.hip), cached per argument set.
+
+        Rows are the tracks that survived the max_dets cut and the federated
+        filter.  The candidates of a ground-truth track are the detection tracks
+        of its video and category, whatever their flags.  On a frame of the
+        ground truth, the best follower is the candidate with a box in that
+        frame whose box IoU (pycocotools' bbIou, not crowd) with the ground
+        truth's is greatest and at least `frame_thr`, a double in (0, 1] -- the
+        best-scored one among equal IoUs; the frame is covered if there is one.
+        Per ground-truth track: `frames`, `covered`, `ids` (distinct followers),
+        `switches` (covered frames whose follower differs from that of the
+        covered frame before), `fragments` (covered stretches of the track's own
+        frame list), `primary` (the track that follows most frames, the
+        best-scored among equal counts) and `primary_frames`.  Per category,
+        over the ground-truth tracks that are not ignored: `tracks`, the sums of
+        `frames`, `covered`, `ids`, `switches`, `fragments`, and `mostly_tracked`
+        (covered >= 80 % of the frames), `mostly_lost` (< 20 %).  Per closed
+        visibility window [lo, hi] (up to 8, they may overlap; default: the
+        image level's all, highly-occluded, partially-occluded, highly-visible,
+        highly-and-partially-occluded) and category: `frames`, `covered` and
+        frames followed by the track's `primary`; a NaN visibility is in none.
+
+        Returns {"columns": {"tracks": ..., "cat_counts": ..., "vis_counts":
+        ...} (the column names), "cat_counts": int64[K, 8], "vis_counts":
+        int64[n_vis, K, 3], "vis_rng", "vis_lbl", "frame_thr"} with the category
+        axis in the order of params.cat_ids; with per_track=True "tracks":
+        (ground-truth track ids, int64[n_gt, 7], `primary` as the detection
+        track's id, -1 for none); with per_frame=True "frames": (frame_off
+        int64[n_gt + 1], image ids, the best detection track's id per frame or
+        -1, best_iou -- 0.0 where uncovered), frames of track i at frame_off[i]
+        .. frame_off[i + 1].  It reads the track tables alone: the result does
+        not depend on iou_3d_type, params.iou_thrs or the ranges.  Not available:
+        iou_type="segm", use_cats = 0, multi-GPU runs."""
+        if self._run is None:
+            raise RuntimeError("Please run evaluate() first.")
+        frame_thr = float(frame_thr)
+        if not 0 < frame_thr <= 1:
+            raise ValueError("frame_thr: {} is not in (0, 1]".format(frame_thr))
+        if vis_rng is None:
+            from ..lvis_amodal.eval import Params as LvisParams
+            lp = LvisParams(self.params.iou_type)
+            vis_rng = lp.visibility_rng[:5]
+            if vis_lbl is None:
+                vis_lbl = lp.visibility_rng_lbl[:5]
+        rng = np.asarray(vis_rng, dtype=np.float64).reshape(-1, 2)
+        if len(rng) > 8:
+            raise ValueError("vis_rng: up to 8 visibility windows")
+        if vis_lbl is None:
+            vis_lbl = ["[{:g}, {:g}]".format(lo, hi) for lo, hi in rng.tolist()]
+        vis_lbl = [str(x) for x in vis_lbl]
+        if len(vis_lbl) != len(rng):
+            raise ValueError("vis_lbl: {} labels for {} windows".format(len(vis_lbl), len(rng)))
+        key = (frame_thr, rng.tobytes(), tuple(vis_lbl))
+        hit = self._association.get(key)
+        if hit is None:
+            from ..._lib import ASSOC_CAT_COLUMNS, ASSOC_TRACK_COLUMNS, ASSOC_VIS_COLUMNS
+            t = self._run.association_table(frame_thr, rng, self._gt_columns.ann_vis)
+            flat = self._run.flat
+            cat_counts, vis_counts = t["cat_counts"], t["vis_counts"]
+            if self._cat_pos is not None:
+                cat_counts = np.ascontiguousarray(cat_counts[self._cat_pos])
+                vis_counts = np.ascontiguousarray(vis_counts[:, self._cat_pos])
+            dt_id = np.asarray(flat.dt_id, dtype=np.int64)
+            tracks = t["gt_assoc"].astype(np.int64)
+            prim = tracks[:, 5]
+            tracks[:, 5] = np.where(prim >= 0, dt_id[np.maximum(prim, 0)], -1) if len(dt_id) \
+                else -1
+            # frames: the image at (video, timeline position), the follower's id
+            foff = np.asarray(flat.gt_frame_off, dtype=np.int64)
+            g_of = np.repeat(np.arange(len(foff) - 1), np.diff(foff))
+            cell = np.asarray(flat.gt_cell, dtype=np.int64)[g_of]
+            vid = np.asarray(flat.cell_unit, dtype=np.int64)[cell]
+            img = np.asarray(flat.tl_image_id)[np.asarray(flat.tl_vid_start, dtype=np.int64)[vid]
+                                               + np.asarray(flat.gt_frame_pos, dtype=np.int64)]
+            best = t["best"].astype(np.int64)
+            row = np.asarray(flat.cell_dt_off, dtype=np.int64)[cell] + best
+            best_id = np.where(best >= 0, dt_id[np.where(best >= 0, row, 0)], -1) \
+                if len(dt_id) else np.full(len(best), -1, dtype=np.int64)
+            hit = {"columns": {"tracks": list(ASSOC_TRACK_COLUMNS),
+                               "cat_counts": list(ASSOC_CAT_COLUMNS),
+                               "vis_counts": list(ASSOC_VIS_COLUMNS)},
+                   "cat_counts": cat_counts, "vis_counts": vis_counts,
+                   "vis_rng": rng.tolist(), "vis_lbl": list(vis_lbl), "frame_thr": frame_thr,
+                   "tracks": (np.asarray(flat.gt_id), tracks),
+                   "frames": (foff, np.asarray(img), best_id, t["best_iou"])}
+            self._association[key] = hit
+        drop = [k for k, on in (("tracks", per_track), ("frames", per_frame)) if not on]
+        return {k: v for k, v in hit.items() if k not in drop}
+
+    def association_lines(self, frame_thr=0.5, vis_rng=None, vis_lbl=None):
+        """association() as a small text table: the totals over the categories,
+        then a line per visibility window with its frames, the covered ones and
+        those the primary follower covers, in per cent.  Returned, not printed."""
+        a = self.association(frame_thr, vis_rng, vis_lbl)
+        tot = a["cat_counts"].sum(0)
+        cols = a["columns"]["cat_counts"]
+
+        def pct(n, d):
+            return "{:>9.2f}".format(100.0 * float(n) / float(d)) if d else "{:>9s}".format("-")
+        w = max([len(x) for x in a["vis_lbl"]] + [10])
+        lines = [" track association @[ frame IoU={:0.2f} ]".format(a["frame_thr"]),
+                 " " + "  ".join("{}={}".format(c, int(v)) for c, v in zip(cols, tot))
+                 + "  coverage={}".format(pct(tot[2], tot[1]).strip())]
+        for name, v in zip(a["vis_lbl"], a["vis_counts"].sum(1)):
+            lines.append(" " + name.ljust(w) + "{:>11d}".format(int(v[0]))
+                         + pct(v[1], v[0]) + pct(v[2], v[0]))
+        return lines
 
     def impact_lines(self, iou_thr=0.5, bg_thr=0.1):
         """error_impact() as a small text table: a line per (area, time) range,

@@ -4,7 +4,7 @@ taoamd_track_error_types) on the synthetic configurations of bench.py, with HIP
 events:
 
     python tools/time_error_types.py [--level image|track] [--config 3s] [--reps 20] [--warmup 3]
-                                     [--impact]
+                                     [--impact] [--association]
 
 Times, on the image level's tables of that configuration, each alone on an idle
 stream: the fused match as a benchmark step runs it (the yardstick), the
@@ -20,8 +20,10 @@ and the (pair, shared frame) counts.  --impact adds the error impact: the
 breakdown with its links (taoamd_error_types_links; --level track:
 taoamd_track_error_types_links), the links pass followed by the sweep of the
 nine variants (engine.stage_error_impact / engine.stage_track_error_impact),
-the kernels of both, and AP and dAP over all categories in range 0.  Prints
-one JSON line."""
+the kernels of both, and AP and dAP over all categories in range 0.  --level
+track --association times, instead of the breakdown, the per-frame followers
+(engine.stage_track_association) and the plan-less taoamd_track_iou over the
+same cells in the same process.  Prints one JSON line."""
 import argparse
 import json
 import os
@@ -101,6 +103,8 @@ def track_level(a, gt, dt, dev, V):
            "dt_frames": int(dp.t["dt_frame_pos"].numel()),
            "gt_frames": int(dp.t["gt_frame_pos"].numel())}
     res["track_iou_step"] = timed(lambda: engine.stage_track_iou(dp, ws))
+    if a.association:
+        return association(a, res, gt, fl, dp, ws, timed)
     res["match_fused"] = timed(lambda: engine.stage_match(dp, ws))
     # the first call builds the per-video lists and runs the match for match_gt
     engine.stage_track_error_types(dp, ws, 0, a.bg_thr)
@@ -162,6 +166,56 @@ def track_level(a, gt, dt, dev, V):
     print(json.dumps(res))
 
 
+def association(a, res, gt, fl, dp, ws, timed):
+    """--level track --association: the per-frame followers
+    (engine.stage_track_association) at frame_thr 0.5 with the five default
+    visibility windows and without windows, its kernels, and -- in the same
+    process -- the plan-less taoamd_track_iou over the SAME cells: the same
+    (detection track, ground-truth track) pairs and the same shared frames."""
+    import torch
+    from tao_amodal_amd import _lib, engine
+    lib = _lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    windows = [[0, 1.0], [0, 0.1], [0.1, 0.8], [0.8, 1.0], [0, 0.8]]
+    engine.set_frame_visibility(dp, np.asarray(gt.ann_vis)[fl.gt_frame_box.index])
+    # the first call allocates the buffers
+    engine.stage_track_association(dp, ws, 0.5, windows)
+    torch.cuda.synchronize()
+    res["track_association"] = timed(lambda: engine.stage_track_association(dp, ws, 0.5, windows))
+    res["track_association_no_windows"] = timed(
+        lambda: engine.stage_track_association(dp, ws, 0.5, []))
+    _lib.kernel_timing(True)
+    for _ in range(a.reps):
+        engine.stage_track_association(dp, ws, 0.5, windows)
+    res["kernels_ms"] = {k: round(ms / n, 4) for k, (ms, n) in _lib.kernel_timings().items()}
+    _lib.kernel_timing(False)
+    res["association_workspace_bytes"] = int(ws.assoc_bytes)
+    tot = ws.assoc_cat_counts.sum(0).tolist()
+    res["cat_counts_total"] = dict(zip(_lib.ASSOC_CAT_COLUMNS, tot))
+    res["vis_counts_total"] = ws.assoc_vis_counts.sum(1).tolist()
+    t = dp.t
+    iou = torch.empty(max(dp.n_iou, 1), dtype=torch.float64, device=dp.device)
+    frames = torch.zeros(1, dtype=torch.int64, device=dp.device)
+
+    def naive():
+        _lib.check(lib.taoamd_track_iou(
+            dp.n_cells, t["cell_dt_off"].data_ptr(), t["cell_gt_off"].data_ptr(),
+            t["cell_iou_off"].data_ptr(), dp.n_iou, t["dt_frame_off"].data_ptr(),
+            t["dt_frame_pos"].data_ptr(), t["dt_frame_box"].data_ptr(),
+            t["gt_frame_off"].data_ptr(), t["gt_frame_pos"].data_ptr(),
+            t["gt_frame_box"].data_ptr(), 0, iou.data_ptr(), frames.data_ptr(), stream),
+            "taoamd_track_iou")
+    res["track_iou_planless_same_cells"] = timed(naive)
+    res["planless_pair_frames"] = int(frames.item())
+    _lib.kernel_timing(True)
+    for _ in range(a.reps):
+        naive()
+    res["planless_kernels_ms"] = {k: round(ms / n, 4)
+                                  for k, (ms, n) in _lib.kernel_timings().items()}
+    _lib.kernel_timing(False)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--level", choices=("image", "track"), default="image")
@@ -173,7 +227,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--bg-thr", type=float, default=0.1)
     ap.add_argument("--impact", action="store_true")
+    ap.add_argument("--association", action="store_true")
     a = ap.parse_args()
+    if a.association and a.level != "track":
+        ap.error("--association is the track level's: --level track")
     import torch
     from tao_amodal_amd import _lib, engine, flatten_dev
     from tao_amodal_amd.synth import synth
