@@ -127,7 +127,8 @@ struct Cursor {
             if (ok && q < e && (*q == ',' || *q == ']' || *q == '}' || *q == ' ' || *q == '\n' ||
                                 *q == '\t' || *q == '\r')) {
                 const double x = frac ? (double)m / P10[frac] : (double)m;
-                v = neg ? -x : x;
+                // ("-0" is an int to json.load, 0, and +0.0 as a double; "-0.0" is -0.0)
+                v = neg && (m || frac) ? -x : x;
                 p = q;
                 return true;
             }

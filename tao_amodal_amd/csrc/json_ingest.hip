@@ -281,9 +281,17 @@ __device__ bool js_object(const JsParseArgs &a, int64_t i)
     auto number = [&](double &v, bool *is_int, int64_t *iv) {
         const int64_t avail = e - p;
         const int n = avail > 64 ? 64 : (int)avail;
+        bool whole = false;
+        int64_t wv = 0;
         const int used = decf::parse_json_number([&](int k) { return (unsigned)t[p + k]; }, n, v,
-                                                 is_int, iv);
+                                                 &whole, &wv);
         if (used == 0 || (used == n && n == 64)) return false;
+        // ("-0" is an int to json.load, 0, and +0.0 as a double; "-0.0" is -0.0)
+        if (whole && wv == 0) v = 0.0;
+        if (is_int) {
+            *is_int = whole;
+            *iv = wv;
+        }
         p += used;
         return p < e && js_delim(t[p]);
     };
