@@ -1156,10 +1156,11 @@ __global__ __launch_bounds__(FW * WAVE) void acc_fused_kernel(AccArgs a, RecThr 
 //   order of pr_better):
 //     * later chunks of the same SC: after a barrier, from LDS, by the
 //       wavefront that wrote the records (it re-reads its own stores);
-//     * later SCs: acc_raise_kernel, a wavefront per (category, range,
-//       threshold) row, from two small per-SC tables: sc_max (largest
-//       precision record of the SC) and sc_jhi (recall thresholds reached up
-//       to its end).
+//     * later SCs: from two small per-SC tables, sc_max (largest precision
+//       record of the SC) and sc_jhi (recall thresholds reached up to its
+//       end) -- by the layout pass where it is val's only reader
+//       (acc_finalize_raise_kernel, accumulate_all), else by acc_raise_kernel,
+//       a wavefront per (category, range, threshold) row.
 //
 // The walk itself (emit_block) is the chunked path's, statement by statement.
 // ===========================================================================
@@ -1491,9 +1492,65 @@ __device__ __forceinline__ uint64_t pr_max(uint64_t a, uint64_t b)
 {
     return pr_better((uint32_t)(a >> 32), (uint32_t)a, b) ? a : b;
 }
+// One round of pass 1 for a group of W lanes (W = 8 .. 64, a power of two; p =
+// the lane's place in its group): lane p holds SC top - 1 - p of the category's
+// SCs [s0, s1) -- the scan runs towards higher places --, its maximum and the
+// thresholds [jl, jh) it emitted.  `on`: the group has a row at all.  combo ->
+// offset inside an SC's [word][64] entries: the combo itself.
+struct ScRound {
+    uint64_t v;
+    int jh, jl;
+};
+__device__ __forceinline__ ScRound sc_round_load(const uint64_t *__restrict__ sc_max,
+                                                 const uint8_t *__restrict__ sc_jhi,
+                                                 int32_t n_words, int32_t s0, int32_t top,
+                                                 int combo, int p, bool on = true)
+{
+    const int64_t step = (int64_t)n_words * WAVE;
+    const int32_t sc = top - 1 - p;
+    const bool have = on && sc >= s0;
+    const int64_t o = (int64_t)(have ? sc : s0) * step + combo;
+    ScRound r;
+    r.v = have ? sc_max[o] : PR_ZERO;
+    r.jh = have ? min((int)sc_jhi[o], N_REC) : 0;
+    r.jl = (have && sc > s0) ? (int)sc_jhi[o - step] : 0;
+    return r;
+}
+
+// ... and its scan: what lies BEHIND each lane's SC -- the maximum over the
+// lower places of the group (= the later SCs) and `behind`, the maximum of the
+// rounds before this one, which takes this round's SCs in on the way out.
+// Both forms of the raise get the envelope from here.
+__device__ __forceinline__ uint64_t sc_round_after(uint64_t v, int W, int p, uint64_t &behind)
+{
+    // inclusive prefix maximum over the places below
+    for (int d = 1; d < W; d <<= 1) {
+        const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d, W);
+        const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d, W);
+        const uint64_t u = ((uint64_t)hi << 32) | lo;
+        if (p >= d) v = pr_max(u, v);
+    }
+    // exclusive: what lies behind this lane's SC
+    const uint32_t elo = (uint32_t)__shfl_up((int)(uint32_t)v, 1, W);
+    const uint32_t ehi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), 1, W);
+    uint64_t after = p > 0 ? (((uint64_t)ehi << 32) | elo) : PR_ZERO;
+    after = pr_max(after, behind);
+    const uint32_t tlo = (uint32_t)__shfl((int)(uint32_t)v, W - 1, W);
+    const uint32_t thi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), W - 1, W);
+    behind = pr_max(behind, ((uint64_t)thi << 32) | tlo);
+    return after;
+}
+
+// v raised to the envelope entry e (PR_ZERO: nothing behind, v stays)
+__device__ __forceinline__ uint64_t pr_raised(uint64_t e, uint64_t v)
+{
+    return e != PR_ZERO && pr_better((uint32_t)(e >> 32), (uint32_t)e, v) ? e : v;
+}
+
 __global__ __launch_bounds__(256) void acc_raise_kernel(AccArgs a)
 {
     __shared__ uint64_t s_env[4][N_REC + 3];
+    static_assert(N_REC > WAVE && N_REC <= 2 * WAVE, "a row's records: two per lane");
     const int lane = lane_id();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t row = (int64_t)blockIdx.x * 4 + wave;
@@ -1504,45 +1561,27 @@ __global__ __launch_bounds__(256) void acc_raise_kernel(AccArgs a)
     const int32_t s0 = a.cat_chunk_off[k], s1 = a.cat_chunk_off[k + 1];
     if (s1 - s0 < 2) return;
     if (a.num_gt[(int64_t)k * a.n_rng + combo / N_THR] <= 0) return;
+    // the row's records do not depend on the envelope: fetched beside the
+    // first round of SCs, not behind the scan
+    uint64_t *__restrict__ out = a.val + ((int64_t)k * a.n_rng * N_THR + combo) * N_REC;
+    const bool two = lane + WAVE < N_REC;
+    const uint64_t v0 = out[lane], v1 = two ? out[lane + WAVE] : PR_ZERO;
     uint64_t *env = s_env[wave];
     for (int j = lane; j < N_REC; j += WAVE) env[j] = PR_ZERO;
-    const int64_t step = (int64_t)a.n_words * WAVE;
-    const int64_t o0 = ((int64_t)combo / WAVE) * WAVE + combo % WAVE;
-    uint64_t behind = PR_ZERO;            // maximum of the SCs of the later passes
+    uint64_t behind = PR_ZERO;            // maximum of the SCs of the later rounds
     for (int32_t top = s1; top > s0; top -= WAVE) {
-        // lane l holds SC top - 1 - l: the scan runs towards higher lanes
-        const int32_t sc = top - 1 - lane;
-        const bool have = sc >= s0;
-        const int64_t o = (int64_t)(have ? sc : s0) * step + o0;
-        uint64_t v = have ? a.sc_max[o] : PR_ZERO;
-        const int jh = have ? (int)a.sc_jhi[o] : 0;
-        const int jl = (have && sc > s0) ? (int)a.sc_jhi[o - step] : 0;
-        // inclusive prefix maximum over the lanes below (= the later SCs)
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-            const uint32_t lo = (uint32_t)__shfl_up((int)(uint32_t)v, d, WAVE);
-            const uint32_t hi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), d, WAVE);
-            const uint64_t u = ((uint64_t)hi << 32) | lo;
-            if (lane >= d) v = pr_max(u, v);
-        }
-        // exclusive: what lies behind SC `sc`
-        const uint32_t elo = (uint32_t)__shfl_up((int)(uint32_t)v, 1, WAVE);
-        const uint32_t ehi = (uint32_t)__shfl_up((int)(uint32_t)(v >> 32), 1, WAVE);
-        uint64_t after = lane > 0 ? (((uint64_t)ehi << 32) | elo) : PR_ZERO;
-        after = pr_max(after, behind);
-        if (have && after != PR_ZERO)
-            for (int j = jl; j < jh; j++) env[j] = after;
-        behind = pr_max(behind, readlane_u64(v, WAVE - 1));
+        const ScRound rd = sc_round_load(a.sc_max, a.sc_jhi, a.n_words, s0, top, combo, lane);
+        const uint64_t after = sc_round_after(rd.v, WAVE, lane, behind);
+        if (after != PR_ZERO)
+            for (int j = rd.jl; j < rd.jh; j++) env[j] = after;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
-    uint64_t *__restrict__ out = a.val + ((int64_t)k * a.n_rng * N_THR + combo) * N_REC;
-    for (int j = lane; j < N_REC; j += WAVE) {
-        const uint64_t e = env[j];
-        if (e != PR_ZERO) {
-            const uint64_t v = out[j];
-            if (pr_better((uint32_t)(e >> 32), (uint32_t)e, v)) out[j] = e;
-        }
+    const uint64_t r0 = pr_raised(env[lane], v0);
+    if (r0 != v0) out[lane] = r0;
+    if (two) {
+        const uint64_t r1 = pr_raised(env[lane + WAVE], v1);
+        if (r1 != v1) out[lane + WAVE] = r1;
     }
 }
 
@@ -1621,6 +1660,199 @@ __global__ __launch_bounds__(256) void acc_finalize_kernel(FinArgs a)
             if (row < KR)
                 a.recall[(int64_t)t * KR + row] =
                     a.num_gt[row] > 0 ? a.rec[row * N_THR + t] : -1.0;
+        }
+    }
+}
+
+// The layout pass behind a one-pass sweep whose val nobody else reads
+// (accumulate_all): the later SCs' envelope is applied to the records on their
+// way through, so acc_raise_kernel's pass over val, its launch and the gap in
+// front of it are gone.  Same output as acc_raise_kernel + acc_finalize_kernel.
+//
+// One workgroup: 64 (k, r) rows x the 101 records of ONE threshold, so that a
+// (category, range, threshold) envelope is worked out once per pass (64-column
+// tiles cut a threshold's records in two or three, and every scan would be
+// repeated in each).  Wavefront w takes the live ones of the rows 8 w .. 8 w + 7
+// (neighbours: a category's ranges, which share its SCs and their number):
+//   * their raw records go into the tile, all loads in flight together;
+//   * their categories' SCs are scanned SEVERAL ROWS A ROUND: most categories
+//     have a handful of SCs, so the wavefront is cut into groups of W = 8 .. 64
+//     lanes (the longest category among its rows decides), a row per group,
+//     lane = SC (sc_round_load / sc_round_after, as in acc_raise_kernel);
+//   * lane = column then finds, for each row of the round, the SC that emitted
+//     its column -- jhi grows along a category's SCs, so that is the number of
+//     SCs whose jhi lies above the column, counted eight SCs at a time from a
+//     byte table in LDS -- and raises the record in the tile with what lies
+//     behind that SC.  No envelope is written out, no lane walks a segment.
+// The store loop divides (lane = row; the odd row stride keeps its reads free
+// of bank conflicts): every column leaves as 64 consecutive rows (512 B), dead
+// rows are never read.
+// XCD order: the ten threshold tiles of a row block run behind one L2, which
+// then fetches the row block's lines of sc_max / sc_jhi (shared by thresholds
+// and ranges: a category's combos are neighbours) once.
+struct FinEnv {
+    const uint64_t *sc_max;
+    const uint8_t *sc_jhi;
+    const int32_t *cat_chunk_off;
+    int32_t n_words;
+};
+#define FINR_WAVES 8
+#define FINR_ROWS (FIN_RT / FINR_WAVES)       // rows of the tile a wavefront fetches and raises
+
+__device__ __forceinline__ uint64_t shfl_u64(uint64_t v, int src)
+{
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)v, src, WAVE);
+    const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(v >> 32), src, WAVE);
+    return ((uint64_t)hi << 32) | lo;
+}
+
+__global__ __launch_bounds__(FINR_WAVES * WAVE) void acc_finalize_raise_kernel(FinArgs a, FinEnv e)
+{
+    __shared__ uint64_t tile[FIN_RT][N_REC];
+    // lane = SC: its jhi, a byte each (with more than this beside the tile a
+    // CU holds two workgroups, not three)
+    __shared__ uint64_t s_jh[FINR_WAVES][WAVE / 8];
+    static_assert(N_REC % 2 == 1, "odd row stride of the tile");
+    static_assert(N_REC < 128, "jhi compared as the low seven bits of a byte");
+    static_assert(N_REC > WAVE && N_REC <= 2 * WAVE, "a row's records: two per lane");
+    static_assert(FIN_RT == 64 && FINR_ROWS == 8, "one mask word, a byte of it per wavefront");
+    const int64_t KR = (int64_t)a.n_cat * a.n_rng;
+    const int64_t COLS = (int64_t)N_THR * N_REC;
+    const uint32_t xcd = blockIdx.x % N_XCD, slot = blockIdx.x / N_XCD;
+    const int64_t row0 = ((int64_t)(slot / N_THR) * N_XCD + xcd) * FIN_RT;
+    const int t = (int)(slot % N_THR);
+    if (row0 >= KR) return;
+    const int lane = lane_id();
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t orow = row0 + lane;                    // lane = row of the tile
+    const bool olive = orow < KR && a.num_gt[orow] > 0;
+    // lane = row: the SCs of the row's category (fetched beside num_gt, not
+    // behind it; KR < 2^31, accumulate_all)
+    const uint32_t k = (uint32_t)min(orow, KR - 1) / (uint32_t)a.n_rng;
+    const int32_t my_s0 = e.cat_chunk_off[k], my_s1 = e.cat_chunk_off[k + 1];
+    const uint64_t live_rows = __ballot(olive);          // same in every wavefront
+    // (eight rows in a row: a category's ranges, which share its SCs)
+    const uint64_t mine = live_rows & (0xffull << (FINR_ROWS * wave));
+    if (mine != 0) {
+        const uint64_t *__restrict__ src = a.val + row0 * COLS + (int64_t)t * N_REC;
+        const bool two = lane + WAVE < N_REC;
+        int idx[FINR_ROWS];
+        {
+            uint64_t m = mine;
+#pragma unroll
+            for (int q = 0; q < FINR_ROWS; q++) {
+                idx[q] = m != 0 ? __builtin_ctzll(m) : -1;
+                if (m != 0) m &= m - 1;
+            }
+        }
+        uint64_t v0[FINR_ROWS], v1[FINR_ROWS];
+#pragma unroll
+        for (int q = 0; q < FINR_ROWS; q++) {
+            const uint64_t *__restrict__ p = src + (int64_t)max(idx[q], 0) * COLS;
+            v0[q] = idx[q] >= 0 ? p[lane] : PR_ZERO;
+            v1[q] = idx[q] >= 0 && two ? p[lane + WAVE] : PR_ZERO;
+        }
+        // lane q keeps my q-th row that has SCs behind its first (-1: none) and
+        // that row's SCs
+        int l_row = -1;
+        int32_t l_s0 = 0, l_s1 = 0, nmax = 0;
+#pragma unroll
+        for (int q = 0; q < FINR_ROWS; q++) {
+            const int i = max(idx[q], 0);
+            const int32_t s0 = __builtin_amdgcn_readlane(my_s0, i);
+            const int32_t s1 = __builtin_amdgcn_readlane(my_s1, i);
+            if (idx[q] >= 0 && s1 - s0 >= 2) {
+                nmax = max(nmax, s1 - s0);
+                if (lane == q) {
+                    l_row = idx[q];
+                    l_s0 = s0;
+                    l_s1 = s1;
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < FINR_ROWS; q++) {
+            if (idx[q] < 0) continue;
+            tile[idx[q]][lane] = v0[q];
+            if (two) tile[idx[q]][lane + WAVE] = v1[q];
+        }
+        if (nmax != 0) {
+            // (a record is raised by the lane that parked it: no fence needed
+            // between the two)
+            const int lg = nmax <= 8 ? 3 : nmax <= 16 ? 4 : nmax <= 32 ? 5 : 6;
+            const int W = 1 << lg, G = WAVE >> lg;       // lanes a group, groups = rows a round
+            const int p = lane & (W - 1), g = lane >> lg;
+            const uint64_t top8 = 0x8080808080808080ull, ones8 = 0x0101010101010101ull;
+            const uint64_t col0 = (uint64_t)(lane + 1) * ones8;
+            const uint64_t col1 = (uint64_t)(lane + WAVE + 1) * ones8;
+            for (int q0 = 0; q0 < FINR_ROWS; q0 += G) {
+                const int row = __shfl(l_row, q0 + g, WAVE);
+                const int32_t s0 = __shfl(l_s0, q0 + g, WAVE);
+                const int32_t s1 = __shfl(l_s1, q0 + g, WAVE);
+                const bool on = row >= 0;
+                if (__ballot(on) == 0) continue;
+                const int combo =
+                    (int)((uint32_t)(row0 + max(row, 0)) % (uint32_t)a.n_rng) * N_THR + t;
+                uint64_t behind = PR_ZERO;       // maximum of the SCs of the later rounds
+                // (a second round: categories of more than 64 SCs, one row a round)
+                for (int32_t top = s1;;) {
+                    const ScRound rd = sc_round_load(e.sc_max, e.sc_jhi, e.n_words, s0, top,
+                                                     combo, p, on);
+                    const uint64_t after = sc_round_after(rd.v, W, p, behind);
+                    ((uint8_t *)s_jh[wave])[lane] = (uint8_t)rd.jh;
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+                    __builtin_amdgcn_wave_barrier();
+                    for (int gg = 0; gg < G; gg++) {
+                        const int r = __builtin_amdgcn_readlane(l_row, q0 + gg);
+                        if (r < 0) continue;
+                        // SCs of this round whose jhi lies above my columns,
+                        // eight SCs a word: bit 7 of a byte (jhi | 0x80) -
+                        // (column + 1) is left standing where jhi > column
+                        const int n_sc = min(W, __builtin_amdgcn_readlane(l_s1 - l_s0, q0 + gg));
+                        const int base = gg << lg;
+                        int c0 = 0, c1 = 0;
+                        for (int w8 = 0; w8 * 8 < n_sc; w8++) {
+                            const uint64_t jh8 = s_jh[wave][(base >> 3) + w8] | top8;
+                            c0 += __popcll((jh8 - col0) & top8);
+                            c1 += __popcll((jh8 - col1) & top8);
+                        }
+                        // (the round's earliest SC starts at jl: the columns in
+                        // front of it belong to the next round's SCs)
+                        const int jl = __builtin_amdgcn_readlane(rd.jl, base + W - 1);
+                        const uint64_t e0 = shfl_u64(after, base + max(c0, 1) - 1);
+                        const uint64_t e1 = shfl_u64(after, base + max(c1, 1) - 1);
+                        if (c0 > 0 && (c0 < W || lane >= jl)) {
+                            const uint64_t v = tile[r][lane], u = pr_raised(e0, v);
+                            if (u != v) tile[r][lane] = u;
+                        }
+                        if (two && c1 > 0 && (c1 < W || lane + WAVE >= jl)) {
+                            const uint64_t v = tile[r][lane + WAVE], u = pr_raised(e1, v);
+                            if (u != v) tile[r][lane + WAVE] = u;
+                        }
+                    }
+                    // (the tables are written again in the next round)
+                    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+                    __builtin_amdgcn_wave_barrier();
+                    top -= W;
+                    if (__ballot(on && top > s0) == 0) break;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // the one fp64 division of a precision value, tp / (n + eps), happens here
+    if (orow < KR)
+        for (int c = wave; c < N_REC; c += FINR_WAVES)
+            a.precision[((int64_t)t * N_REC + c) * KR + orow] =
+                olive ? pr_value(tile[lane][c]) : -1.0;
+    // recall: the first threshold's tile also transposes rec[KR][T]
+    if (t == 0) {
+        for (int i = threadIdx.x; i < FIN_RT * N_THR; i += FINR_WAVES * WAVE) {
+            const int64_t row = row0 + i / N_THR;
+            const int tt = i % N_THR;
+            if (row < KR)
+                a.recall[(int64_t)tt * KR + row] =
+                    a.num_gt[row] > 0 ? a.rec[row * N_THR + tt] : -1.0;
         }
     }
 }
@@ -1785,8 +2017,13 @@ static int accumulate_compact(int64_t n_dt, int32_t n_cat, int32_t n_rng,
                               int32_t max_segment, double *val, double *rec,
                               void *workspace, size_t workspace_bytes, void *stream,
                               int phase = ACC_ALL, int force_mode = SWEEP_AUTO,
-                              const uint32_t *compact = nullptr)
+                              const uint32_t *compact = nullptr,
+                              AccArgs *raise_left = nullptr)
 {
+    // raise_left (accumulate_all: val is the workspace's, read by its layout
+    // pass alone): a one-pass sweep leaves the later SCs' envelope to that pass
+    // and hands over its arguments here; sc_rows stays 0 on every other path
+    if (raise_left) raise_left->sc_rows = 0;
     if (n_cat <= 0 || n_rng < 1 || n_rng > 32) return TAOAMD_ERR_ARG;
     if (k_begin < 0 || k_end > n_cat || k_begin > k_end) return TAOAMD_ERR_ARG;
     if (!cat_off || !workspace) return TAOAMD_ERR_ARG;
@@ -1921,9 +2158,14 @@ static int accumulate_compact(int64_t n_dt, int32_t n_cat, int32_t n_rng,
             TAO_TIMED("acc_sccount_kernel", s, (acc_sweep_kernel<SWEEP_SW, 2><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
             TAO_TIMED("acc_sweep_kernel", s, (acc_sweep_kernel<SWEEP_SW, 1><<<grid, SWEEP_SW * WAVE, 0, s>>>(a, rec_thr())));
         }
-        // the later SCs' envelope into the records (val final after this)
-        const int64_t rows = (int64_t)(k_end - k_begin) * n_rng * N_THR;
-        TAO_TIMED("acc_raise_kernel", s, acc_raise_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, s>>>(a));
+        // the later SCs' envelope into the records (val final after this),
+        // unless the caller's layout pass applies it
+        if (raise_left) {
+            *raise_left = a;
+        } else {
+            const int64_t rows = (int64_t)(k_end - k_begin) * n_rng * N_THR;
+            TAO_TIMED("acc_raise_kernel", s, acc_raise_kernel<<<(unsigned)((rows + 3) / 4), 256, 0, s>>>(a));
+        }
         TAO_LAUNCH_CHECK();
         return TAOAMD_OK;
     }
@@ -2005,11 +2247,32 @@ static int accumulate_all(int64_t n_dt, int32_t n_cat, int32_t n_rng,
     double *val, *rec;
     acc_full_layout(c, n_dt, n_cat, n_rng, val, rec);
     if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
+    // (the raising layout pass works out (k, r) of a row in 32 bits)
+    AccArgs left;
+    left.sc_rows = 0;
+    const bool raise_in_layout = (int64_t)n_cat * n_rng < ((int64_t)1 << 31);
     int st = accumulate_compact(n_dt, n_cat, n_rng, cat_off, order, matched, ignored,
                                 num_gt, 0, n_cat, max_segment, val, rec, workspace,
-                                workspace_bytes, stream, phase, force_mode, compact);
+                                workspace_bytes, stream, phase, force_mode, compact,
+                                raise_in_layout ? &left : nullptr);
     if (st != TAOAMD_OK || phase == ACC_PLAN) return st;
-    return taoamd_finalize(n_cat, n_rng, num_gt, val, rec, precision, recall, stream);
+    if (left.sc_rows == 0)
+        return taoamd_finalize(n_cat, n_rng, num_gt, val, rec, precision, recall, stream);
+    // behind a one-pass sweep: the layout pass that raises (timed under the
+    // plain kernel's name: one entry for the layout pass whatever its form)
+    if (!precision || !recall) return TAOAMD_ERR_ARG;
+    FinArgs f;
+    f.n_cat = n_cat; f.n_rng = n_rng; f.num_gt = num_gt; f.val = (const uint64_t *)val; f.rec = rec;
+    f.precision = precision; f.recall = recall;
+    FinEnv e;
+    e.sc_max = left.sc_max; e.sc_jhi = left.sc_jhi; e.cat_chunk_off = left.cat_chunk_off;
+    e.n_words = left.n_words;
+    const int64_t KR = (int64_t)n_cat * n_rng;
+    const int64_t row_blocks = (KR + FIN_RT - 1) / FIN_RT;
+    const unsigned grid = (unsigned)((row_blocks + N_XCD - 1) / N_XCD * N_XCD * N_THR);
+    TAO_TIMED("acc_finalize_kernel", (hipStream_t)stream, acc_finalize_raise_kernel<<<grid, FINR_WAVES * WAVE, 0, (hipStream_t)stream>>>(f, e));
+    TAO_LAUNCH_CHECK();
+    return TAOAMD_OK;
 }
 
 extern "C" int taoamd_accumulate(int64_t n_dt, int32_t n_cat, int32_t n_rng,
