@@ -156,6 +156,32 @@ __device__ __forceinline__ double pr_value(uint64_t p)
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & (WAVE - 1); }
 
+// One add per distinct key among the wavefront's live lanes: the leader of the
+// lanes that share a key adds their number to base[key].  (Rows and ground
+// truths lie category-major: a wavefront's lanes share one or two keys.)
+template <typename T>
+__device__ __forceinline__ void wave_count(T *base, bool live, int32_t key)
+{
+    uint64_t left = __ballot(live);
+    while (left) {
+        const int lead = __builtin_ctzll(left);
+        const int32_t k = __builtin_amdgcn_readlane(key, lead);
+        const uint64_t same = __ballot(live && key == k);
+        if (lane_id() == lead) atomicAdd(base + k, (T)__popcll(same));
+        left &= ~same;
+    }
+}
+
+// The error types of the breakdowns (error_types.hip, track_error_types.hip)
+// and of the impact sweep that reads their type bytes (error_impact.hip): the
+// numbering of include/tao_amodal_hip.h ("0 TP" .. "6 BKG"), which is the
+// order of _lib.ERROR_TYPES -- the names of dt_counts' last axis.  ERR_NGT: the
+// counts per ground truth (evaluated, missed, missed_loc).
+enum { ERR_TP = 0, ERR_IGNORED, ERR_DUP, ERR_LOC, ERR_CLS, ERR_BOTH, ERR_BKG };
+#define ERR_NTYPE 7
+#define ERR_NGT 3
+static_assert(ERR_BKG + 1 == ERR_NTYPE, "seven types, as _lib.ERROR_TYPES lists them");
+
 // XCD-aware block order.  The dispatcher deals workgroups to the 8 XCDs round
 // robin (block b runs on XCD b % 8 -- observed, MI355X_MICROARCH.md; a matter
 // of speed only, nothing here depends on it for correctness).  Kernels whose

@@ -45,7 +45,6 @@ using namespace taoamd;
 #define IMP_NLIST 7            // distinct row lists: MISS and FN sweep BASE's
 #define IMP_RMAX 8             // ranges of the image level; the track level has TAOAMD_TAO_RNG
 
-enum { T_TP = 0, T_IGNORED, T_DUP, T_LOC, T_CLS, T_BOTH, T_BKG };
 enum { V_BASE = 0, V_CLS, V_LOC, V_BOTH, V_DUP, V_BKG, V_MISS, V_FP, V_FN };
 
 struct ImpArgs {
@@ -82,8 +81,8 @@ __device__ __forceinline__ bool imp_claim(const ImpArgs &a, int64_t d, int r, in
     const int32_t cat = a.dt_cat[d];
     if (cat < 0 || cat >= a.n_cat) return false;
     const int ty = a.dt_type[d * a.n_rng + r];
-    if (ty != T_LOC && ty != T_CLS) return false;
-    tab = ty == T_CLS;
+    if (ty != ERR_LOC && ty != ERR_CLS) return false;
+    tab = ty == ERR_CLS;
     const int64_t g = tab ? a.link_other[d * a.n_rng + r] : a.link_same[d * a.n_rng + r];
     if (g < 0 || g >= a.n_gt) return false;
     if (a.held[(int64_t)r * a.n_gt + g]) return false;
@@ -147,20 +146,6 @@ __global__ __launch_bounds__(256) void imp_adopt_kernel(ImpArgs a)
     atomicAdd(a.adopt + (int64_t)r * (a.n_dt + a.n_cat) + l + k, 1u);
 }
 
-// One add per distinct key among the wavefront's live lanes (ground truths lie
-// category-major: a wavefront's lanes share one or two keys)
-__device__ __forceinline__ void imp_count(uint32_t *base, bool live, int32_t key)
-{
-    uint64_t left = __ballot(live);
-    while (left) {
-        const int lead = __builtin_ctzll(left);
-        const int32_t k = __builtin_amdgcn_readlane(key, lead);
-        const uint64_t same = __ballot(live && key == k);
-        if (lane_id() == lead) atomicAdd(base + k, (uint32_t)__popcll(same));
-        left &= ~same;
-    }
-}
-
 template <int RMAX>
 __global__ __launch_bounds__(256) void imp_gt_kernel(ImpArgs a)
 {
@@ -178,9 +163,9 @@ __global__ __launch_bounds__(256) void imp_gt_kernel(ImpArgs a)
         const bool missed = ev && a.held[at] == 0;
         const bool lone = missed && a.best[at] == 0 && a.best[(int64_t)a.n_rng * a.n_gt + at] == 0;
         const int32_t key = cat * a.n_rng + r;
-        imp_count(a.cnt, ev, key);
-        imp_count(a.cnt + plane, lone, key);
-        imp_count(a.cnt + 2 * plane, missed, key);
+        wave_count(a.cnt, ev, key);
+        wave_count(a.cnt + plane, lone, key);
+        wave_count(a.cnt + 2 * plane, missed, key);
     }
 }
 
@@ -237,23 +222,23 @@ __global__ __launch_bounds__(IMP_CHUNK) void imp_sweep_kernel(ImpArgs a, RecThr 
             d = a.order[lo + p];
             if (d >= 0 && d < a.n_dt) ty = a.dt_type[d * a.n_rng + r];
         }
-        const bool kept = ty == T_TP || (ty >= T_DUP && ty <= T_BKG);
-        const unsigned long long row = !kept ? 0 : (ty == T_TP ? ONE_TP : ONE_FP);
+        const bool kept = ty == ERR_TP || (ty >= ERR_DUP && ty <= ERR_BKG);
+        const unsigned long long row = !kept ? 0 : (ty == ERR_TP ? ONE_TP : ONE_FP);
         unsigned long long inc[IMP_NLIST], own[IMP_NLIST];
         own[0] = row;
-        own[1] = ty == T_CLS ? 0 : row;
+        own[1] = ty == ERR_CLS ? 0 : row;
         own[2] = row;
-        if (ty == T_LOC) {
+        if (ty == ERR_LOC) {
             const int64_t g = a.link_same[d * a.n_rng + r];
             if (g >= 0 && g < a.n_gt) {
                 const int64_t at = (int64_t)r * a.n_gt + g;
                 own[2] = !a.held[at] && a.win[at] == (uint32_t)d ? ONE_TP : 0;
             }
         }
-        own[3] = ty == T_BOTH ? 0 : row;
-        own[4] = ty == T_DUP ? 0 : row;
-        own[5] = ty == T_BKG ? 0 : row;
-        own[6] = ty == T_TP ? row : 0;
+        own[3] = ty == ERR_BOTH ? 0 : row;
+        own[4] = ty == ERR_DUP ? 0 : row;
+        own[5] = ty == ERR_BKG ? 0 : row;
+        own[6] = ty == ERR_TP ? row : 0;
 #pragma unroll
         for (int L = 0; L < IMP_NLIST; L++) inc[L] = own[L];
         inc[1] += ((unsigned long long)m << 32) | m;

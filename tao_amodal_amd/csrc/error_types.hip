@@ -46,10 +46,6 @@ using namespace taoamd;
 
 #define ERR_TILE TAOAMD_ERROR_TYPES_TILE   // ground truths per LDS tile = lanes of a workgroup
 #define ERR_RMAX TAOAMD_ERROR_TYPES_MAX_RNG
-#define ERR_NTYPE 7
-#define ERR_NGT 3
-
-enum { ERR_TP = 0, ERR_IGNORED, ERR_DUP, ERR_LOC, ERR_CLS, ERR_BOTH, ERR_BKG };
 
 struct ErrArgs {
     int64_t n_dt, n_gt;
@@ -72,20 +68,6 @@ struct ErrArgs {
     uint8_t *gt_hit, *gt_loc;        // [n_rng][n_gt]
     int32_t *link_same, *link_other; // [n_dt][n_rng], taoamd_error_types_links only
 };
-
-// One add per distinct key among the wavefront's live lanes: the leader of the
-// lanes that share a key adds their number to base[key].
-__device__ __forceinline__ void err_count(unsigned long long *base, bool live, int32_t key)
-{
-    uint64_t left = __ballot(live);
-    while (left) {
-        const int lead = __builtin_ctzll(left);
-        const int32_t k = __builtin_amdgcn_readlane(key, lead);
-        const uint64_t same = __ballot(live && key == k);
-        if (lane_id() == lead) atomicAdd(base + k, (unsigned long long)__popcll(same));
-        left &= ~same;
-    }
-}
 
 // LINKS: the argmax of o under the rule of s, and both argmaxes stored per
 // (detection, range) -- what a fix would hand the detection (error_impact.hip)
@@ -216,8 +198,8 @@ __global__ __launch_bounds__(256) void err_count_kernel(ErrArgs a)
         if (r >= a.n_rng) continue;                            // (uniform)
         const int ty = valid ? a.types[d * a.n_rng + r] : 0;
         // (a row no image lists keeps whatever byte the table held)
-        err_count(a.dt_counts + (int64_t)r * a.n_cat * ERR_NTYPE, ok && ty < ERR_NTYPE,
-                  cat * ERR_NTYPE + ty);
+        wave_count(a.dt_counts + (int64_t)r * a.n_cat * ERR_NTYPE, ok && ty < ERR_NTYPE,
+                   cat * ERR_NTYPE + ty);
     }
 }
 
@@ -235,9 +217,9 @@ __global__ __launch_bounds__(256) void err_tally_kernel(ErrArgs a)
         const bool miss = ev && a.gt_hit[(int64_t)r * a.n_gt + g] == 0;
         const bool loc = miss && a.gt_loc[(int64_t)r * a.n_gt + g] != 0;
         unsigned long long *base = a.gt_counts + (int64_t)r * a.n_cat * ERR_NGT;
-        err_count(base, ev, cat * ERR_NGT);
-        err_count(base, miss, cat * ERR_NGT + 1);
-        err_count(base, loc, cat * ERR_NGT + 2);
+        wave_count(base, ev, cat * ERR_NGT);
+        wave_count(base, miss, cat * ERR_NGT + 1);
+        wave_count(base, loc, cat * ERR_NGT + 2);
     }
 }
 

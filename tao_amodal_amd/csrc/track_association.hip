@@ -174,7 +174,7 @@ __device__ __forceinline__ long long wave_sum(long long v)
 
 // base[key * N + c] += the sum of v[c] over the wavefront's live lanes of that
 // key: one add per (distinct key, column with a sum), by the key's first lane
-// (trk_err_count of track_error_types.hip with amounts instead of ones).
+// (wave_count of common.hpp with amounts instead of ones).
 template <int N>
 __device__ __forceinline__ void assoc_add(unsigned long long *base, bool live, int32_t key,
                                           const int32_t (&v)[N])

@@ -50,12 +50,8 @@ using namespace taoamd;
 #define TE_P 8                               // timeline positions per chunk
 #define TE_LANES 256                         // detection tracks per round of a video
 #define TE_RMAX TAOAMD_TAO_RNG
-#define TE_NTYPE 7
-#define TE_NGT 3
 
 static_assert(TE_G * TE_P <= TE_LANES && (TE_G * TE_P) % WAVE == 0, "whole wavefronts stage a chunk");
-
-enum { TE_TP = 0, TE_IGNORED, TE_DUP, TE_LOC, TE_CLS, TE_BOTH, TE_BKG };
 
 struct TrkErrArgs {
     int64_t n_dt, n_gt, n_iou, n_cells;
@@ -83,20 +79,6 @@ struct TrkErrArgs {
     uint8_t *gt_hit, *gt_loc;        // [n_rng][n_gt]
     int32_t *link_same, *link_other; // [n_dt][n_rng], taoamd_track_error_types_links only
 };
-
-// One add per distinct key among the wavefront's live lanes (as err_count of
-// the image level): the leader of the lanes that share a key adds their number.
-__device__ __forceinline__ void trk_err_count(unsigned long long *base, bool live, int32_t key)
-{
-    uint64_t left = __ballot(live);
-    while (left) {
-        const int lead = __builtin_ctzll(left);
-        const int32_t k = __builtin_amdgcn_readlane(key, lead);
-        const uint64_t same = __ballot(live && key == k);
-        if (lane_id() == lead) atomicAdd(base + k, (unsigned long long)__popcll(same));
-        left &= ~same;
-    }
-}
 
 // A lane's own track: the current frame and the one behind it in registers, so
 // that the step to the next frame does not wait for the load it issues.
@@ -381,29 +363,29 @@ __global__ __launch_bounds__(256) void trk_err_class_kernel(TrkErrArgs a)
 #pragma unroll
     for (int r = 0; r < TE_RMAX; r++) {
         if (r >= a.n_rng) continue;                            // (uniform)
-        int ty = TE_BKG;
+        int ty = ERR_BKG;
         const int32_t m = valid ? a.match_gt[d * a.match_stride + (int64_t)r * N_THR + a.slot] : -1;
         const int64_t grow = (int64_t)gt0 + m;
         if (m >= 0 && grow >= 0 && grow < a.n_gt) {
-            ty = ((a.gt_rng[grow] >> r) & 1u) ? TE_IGNORED : TE_TP;
+            ty = ((a.gt_rng[grow] >> r) & 1u) ? ERR_IGNORED : ERR_TP;
             a.gt_hit[(int64_t)r * a.n_gt + grow] = 1;
         } else if ((drng >> r) & 1u) {
-            ty = TE_IGNORED;
+            ty = ERR_IGNORED;
         } else if (s[r] >= a.tf) {
-            ty = TE_DUP;
+            ty = ERR_DUP;
         } else if (s[r] >= a.tb) {
-            ty = TE_LOC;
+            ty = ERR_LOC;
             if (arg[r] >= 0) a.gt_loc[(int64_t)r * a.n_gt + gt0 + arg[r]] = 1;
         } else if ((hi >> r) & 1u) {
-            ty = TE_CLS;
+            ty = ERR_CLS;
         } else if ((lo >> r) & 1u) {
-            ty = TE_BOTH;
+            ty = ERR_BOTH;
         }
         if (valid && a.dt_type) a.dt_type[d * a.n_rng + r] = (uint8_t)ty;
         if constexpr (LINKS) {
             if (valid) a.link_same[d * a.n_rng + r] = arg[r] >= 0 ? gt0 + arg[r] : -1;
         }
-        trk_err_count(a.dt_counts + (int64_t)r * a.n_cat * TE_NTYPE, ok, cat * TE_NTYPE + ty);
+        wave_count(a.dt_counts + (int64_t)r * a.n_cat * ERR_NTYPE, ok, cat * ERR_NTYPE + ty);
     }
 }
 
@@ -418,10 +400,10 @@ __global__ __launch_bounds__(256) void trk_err_tally_kernel(TrkErrArgs a)
         const bool ev = ok && !((rng >> r) & 1u);
         const bool miss = ev && a.gt_hit[(int64_t)r * a.n_gt + g] == 0;
         const bool loc = miss && a.gt_loc[(int64_t)r * a.n_gt + g] != 0;
-        unsigned long long *base = a.gt_counts + (int64_t)r * a.n_cat * TE_NGT;
-        trk_err_count(base, ev, cat * TE_NGT);
-        trk_err_count(base, miss, cat * TE_NGT + 1);
-        trk_err_count(base, loc, cat * TE_NGT + 2);
+        unsigned long long *base = a.gt_counts + (int64_t)r * a.n_cat * ERR_NGT;
+        wave_count(base, ev, cat * ERR_NGT);
+        wave_count(base, miss, cat * ERR_NGT + 1);
+        wave_count(base, loc, cat * ERR_NGT + 2);
     }
 }
 
@@ -489,8 +471,8 @@ static int trk_err_run(
     a.link_same = link_same; a.link_other = link_other;
     if (links) a.gt_hit = held;      // the marks of the class kernel, in the caller's table
     const size_t cells = (size_t)n_rng * n_cat;
-    TAO_HIP(hipMemsetAsync(dt_counts, 0, cells * TE_NTYPE * sizeof(int64_t), s));
-    TAO_HIP(hipMemsetAsync(gt_counts, 0, cells * TE_NGT * sizeof(int64_t), s));
+    TAO_HIP(hipMemsetAsync(dt_counts, 0, cells * ERR_NTYPE * sizeof(int64_t), s));
+    TAO_HIP(hipMemsetAsync(gt_counts, 0, cells * ERR_NGT * sizeof(int64_t), s));
     if (n_gt > 0) {
         TAO_HIP(hipMemsetAsync(a.gt_hit, 0, (size_t)n_gt * n_rng, s));
         TAO_HIP(hipMemsetAsync(a.gt_loc, 0, (size_t)n_gt * n_rng, s));

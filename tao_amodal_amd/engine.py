@@ -197,6 +197,9 @@ class DeviceProblem:
         self.n_pairs = int(flat.n_pairs)
         # image / video of every cell (host): the error breakdown groups rows by it
         self.cell_unit_host = flat.get("cell_unit")
+        # its per-unit row lists, built by the first breakdown (_error_tabs), and
+        # the image level's column beside them
+        self.err_tabs = self.err_dt_gt0 = None
         # tables a device-side build (flatten_dev.DeviceFlat) already holds in HBM
         on_dev = getattr(flat, "dev", {})
         d_cnt = np.diff(flat.cell_dt_off).astype(np.int64)
@@ -577,6 +580,14 @@ class Workspace:
             if dp.kind == "lvis":
                 self.ious_out = torch.empty(max(dp.n_iou, 1),
                                             dtype=torch.float64, device=dev)
+        # the on-request analyses (stage_scores, the error breakdown and its
+        # impact, stage_track_association): allocated by their first call
+        self.scores = None
+        self.err_match_gt = self.err_dt_counts = self.err_gt_counts = self.err_dt_type = None
+        self.err_link_same = self.err_link_other = self.err_held = None
+        self.imp_ws = self.imp_precision = self.imp_num_gt = None
+        self.assoc_gt = self.assoc_vis_counts = None
+        self.pairs_counted = False        # stage_track_iou counted the pairs' common frames
 
 
 def _order_of(ws):
@@ -754,7 +765,7 @@ def stage_track_iou(dp, ws):
         # quoted in) are a constant of the problem: counted by the first pass
         # over a workspace, which later passes leave as it is -- the 3D IoU's
         # arithmetic needs no frame masks, the kernel is 5 % shorter without them
-        counted = getattr(ws, "pairs_counted", False) and dp.iou_mode == 0
+        counted = ws.pairs_counted and dp.iou_mode == 0
         _lib.check(lib.taoamd_track_iou_planned(
             dp.n_tasks, _ptr(t["tasks"]), _ptr(t["task_rows"]),
             _ptr(t["task_pairs"]), _ptr(t["task_out"]), _ptr(t["frames"]),
@@ -1064,7 +1075,7 @@ def stage_scores(dp, ws):
     thread's thresholds.  Its buffers are allocated on the first call: a
     workspace that is never asked pays nothing."""
     lib, t, s = _lib.load(), dp.t, _stream()
-    if getattr(ws, "scores", None) is None:
+    if ws.scores is None:
         ws.score_bytes = lib.taoamd_score_at_recall_workspace(dp.n_dt, dp.n_cat, dp.n_rng)
         ws.score_ws = torch.empty(max(int(ws.score_bytes), 256), dtype=torch.uint8,
                                   device=dp.device)
@@ -1094,12 +1105,130 @@ def error_match_gt(dp, ws):
     """The table stage_error_types reads the match indices from where the
     workspace keeps none of its own: int32[n_dt, n_rng * 10], allocated on the
     first call and kept with the workspace (240 bytes a row: 5.1 GB at 21.4 M
-    rows; `del ws.err_match_gt` gives it back).  A caller that runs the match
+    rows; `ws.err_match_gt = None` gives it back).  A caller that runs the match
     itself passes it as stage_match(match_gt=...) / run_guarded(match_gt=...)."""
-    if getattr(ws, "err_match_gt", None) is None:
+    if ws.err_match_gt is None:
         ws.err_match_gt = torch.empty((max(dp.n_dt, 1), dp.n_rng * N_THR), dtype=torch.int32,
                                       device=dp.device)
     return ws.err_match_gt
+
+
+def _error_tabs(dp):
+    """The breakdown's per-unit (image / video) row lists, built once per
+    problem: dp.err_tabs = (units, gt_off, gt_rows, dt_off, dt_rows), the CSRs of
+    _rows_by_unit; beside it dp.err_dt_gt0, the image level's column of every
+    row's first ground truth."""
+    if dp.err_tabs is None:
+        t, dev = dp.t, dp.device
+        cell_unit = torch.from_numpy(np.ascontiguousarray(dp.cell_unit_host, dtype=np.int64)
+                                     ).to(dev)
+        n_unit = int(dp.cell_unit_host.max()) + 1 if dp.n_cells else 0
+        cells = torch.arange(dp.n_cells, dtype=torch.int64, device=dev)
+        gt_cell = torch.repeat_interleave(
+            cells, (t["cell_gt_off"][1:] - t["cell_gt_off"][:-1]).long())
+        dt_cell = t["dt_cell"][:dp.n_dt].long()
+        dp.err_tabs = (n_unit,) + _rows_by_unit(cell_unit[gt_cell], n_unit) \
+            + _rows_by_unit(cell_unit[dt_cell], n_unit)
+        if dp.kind == "lvis":
+            dp.err_dt_gt0 = t["dt_group"][:, 0].contiguous()
+    return dp.err_tabs
+
+
+def _error_buffers(dp, ws, lib, per_detection, links):
+    """The breakdown's buffers, each allocated where first asked for: the
+    counts and the level's workspace, ws.err_dt_type with `per_detection`, the
+    link tables and ws.err_held with `links`."""
+    dev = dp.device
+    if ws.err_dt_counts is None:
+        sized = lib.taoamd_error_types_workspace if dp.kind == "lvis" else \
+            lib.taoamd_track_error_types_workspace
+        ws.err_bytes = sized(dp.n_dt, dp.n_gt, dp.n_rng)
+        ws.err_ws = torch.empty(max(int(ws.err_bytes), 256), dtype=torch.uint8, device=dev)
+        ws.err_dt_counts = torch.empty((dp.n_rng, dp.n_cat, 7), dtype=torch.int64, device=dev)
+        ws.err_gt_counts = torch.empty((dp.n_rng, dp.n_cat, 3), dtype=torch.int64, device=dev)
+    shape = (max(dp.n_dt, 1), dp.n_rng)
+    if per_detection and ws.err_dt_type is None:
+        ws.err_dt_type = torch.empty(shape, dtype=torch.uint8, device=dev)
+    if links and ws.err_link_same is None:
+        ws.err_link_same = torch.empty(shape, dtype=torch.int32, device=dev)
+        ws.err_link_other = torch.empty(shape, dtype=torch.int32, device=dev)
+        ws.err_held = torch.empty((dp.n_rng, max(dp.n_gt, 1)), dtype=torch.uint8, device=dev)
+
+
+def _error_match_gt(dp, ws):
+    """The match indices the breakdown reads: the workspace's own table (detail
+    mode), else error_match_gt(), filled by one more match unless the caller's
+    match already wrote it."""
+    if ws.match_gt is not None:
+        return ws.match_gt
+    if ws.err_match_gt is None and dp.n_dt:
+        stage_match(dp, ws, scatter=not ws.cell_order, match_gt=error_match_gt(dp, ws))
+    return ws.err_match_gt
+
+
+def _error_pass(dp, ws, slot, tb, per_detection, links, kind):
+    """stage_error_types (`kind` "lvis") / stage_track_error_types ("tao"):
+    `kind` is the level the caller's name promises, refused where the problem
+    is of the other.  `links`: through the level's *_links entry point, which
+    also fills ws.err_link_same, ws.err_link_other and ws.err_held."""
+    track = kind == "tao"
+    if dp.kind != kind or dp.mask_iou:
+        raise _lib.TaoAmdError("the track-level error breakdown is the track level's, on boxes"
+                               if track else "the error breakdown is the image level's, on boxes")
+    if track and dp.iou_mode != 0:
+        raise _lib.TaoAmdError("the track-level error breakdown is defined for the 3d_iou metric")
+    if dp.cell_unit_host is None:
+        raise _lib.TaoAmdError("the error breakdown needs the cells' %s (flat.cell_unit)"
+                               % ("videos" if track else "images"))
+    lib, t, s = _lib.load(), dp.t, _stream()
+    n_unit, *lists = _error_tabs(dp)
+    _error_buffers(dp, ws, lib, per_detection, links)
+    match_gt = _error_match_gt(dp, ws)
+    lists = tuple(_ptr(x) for x in lists)
+    out = (_ptr(ws.err_dt_counts), _ptr(ws.err_gt_counts),
+           _ptr(ws.err_dt_type) if per_detection else None)
+    if kind == "lvis":
+        name = "taoamd_error_types"
+        args = (dp.n_dt, dp.n_gt, n_unit, dp.n_cat, dp.n_rng, int(slot), float(tb),
+                _ptr(t["dt_cat"]), _ptr(t["dt_box"]), _ptr(t["dt_flags"]), _ptr(dp.err_dt_gt0),
+                _ptr(match_gt), dp.n_rng * N_THR, _ptr(t["gt_cat"]), _ptr(t["gt_box"]),
+                _ptr(ws.gt_rng)) + lists + out
+    else:
+        name = "taoamd_track_error_types"
+        args = (dp.n_dt, dp.n_gt, dp.n_cells, dp.n_iou, n_unit, dp.n_cat, dp.n_rng, int(slot),
+                float(tb), _ptr(t["dt_cat"]), _ptr(ws.dt_rng), _ptr(t["dt_group"]),
+                _ptr(t["cell_iou_off"]), _ptr(ws.iou), _ptr(match_gt), dp.n_rng * N_THR,
+                _ptr(t["gt_cat"]), _ptr(ws.gt_rng),
+                _ptr(t["dt_frame_off"]), _ptr(t["dt_frame_pos"]), _ptr(t["dt_frame_box"]),
+                _ptr(t["gt_frame_off"]), _ptr(t["gt_frame_pos"]), _ptr(t["gt_frame_box"])) \
+            + lists + out + (None,)
+    if links:
+        name += "_links"
+        args += (_ptr(ws.err_link_same), _ptr(ws.err_link_other), _ptr(ws.err_held))
+    _lib.check(getattr(lib, name)(*args, _ptr(ws.err_ws), ws.err_bytes, s), name)
+
+
+def _error_impact(dp, ws, slot, tb, kind):
+    """stage_error_impact (`kind` "lvis") / stage_track_error_impact ("tao"): the
+    level's links pass, then the sweep of the nine variants through the level's
+    entry point -- the two share their signature."""
+    _error_pass(dp, ws, slot, tb, True, True, kind)
+    lib, t, dev = _lib.load(), dp.t, dp.device
+    name = "taoamd_error_impact" if kind == "lvis" else "taoamd_track_error_impact"
+    if ws.imp_ws is None:
+        ws.imp_bytes = getattr(lib, name + "_workspace")(dp.n_dt, dp.n_gt, dp.n_cat, dp.n_rng)
+        ws.imp_ws = torch.empty(max(int(ws.imp_bytes), 256), dtype=torch.uint8, device=dev)
+        ws.imp_precision = torch.empty((len(_lib.ERROR_FIXES), N_REC, dp.n_cat, dp.n_rng),
+                                       dtype=torch.float64, device=dev)
+        ws.imp_num_gt = torch.empty((len(_lib.ERROR_FIXES), dp.n_cat, dp.n_rng),
+                                    dtype=torch.int32, device=dev)
+    ws.imp_order = ws.order          # (derived on demand: alive while the pass runs)
+    _lib.check(getattr(lib, name)(
+        dp.n_dt, dp.n_gt, dp.n_cat, dp.n_rng, _ptr(t["cat_off"]), _ptr(ws.imp_order),
+        _ptr(t["dt_score"]), _ptr(t["dt_cat"]), _ptr(ws.err_dt_type), _ptr(ws.err_link_same),
+        _ptr(ws.err_link_other), _ptr(t["gt_cat"]), _ptr(ws.gt_rng), _ptr(ws.err_held),
+        _ptr(ws.imp_precision), _ptr(ws.imp_num_gt), _ptr(ws.imp_ws), ws.imp_bytes, _stream()),
+        name)
 
 
 def stage_error_types(dp, ws, slot, tb, per_detection=False):
@@ -1114,56 +1243,7 @@ def stage_error_types(dp, ws, slot, tb, per_detection=False):
     error_match_gt(), filled here by one more match with match_gt requested
     unless the caller's match already wrote it.  Buffers are allocated on the
     first call."""
-    _error_types_pass(dp, ws, slot, tb, per_detection, links=False)
-
-
-def _error_types_pass(dp, ws, slot, tb, per_detection, links):
-    """stage_error_types; `links`: through taoamd_error_types_links, which also
-    fills ws.err_link_same, ws.err_link_other and ws.err_held."""
-    if dp.kind != "lvis" or dp.mask_iou:
-        raise _lib.TaoAmdError("the error breakdown is the image level's, on boxes")
-    if dp.cell_unit_host is None:
-        raise _lib.TaoAmdError("the error breakdown needs the cells' images (flat.cell_unit)")
-    lib, t, s = _lib.load(), dp.t, _stream()
-    dev = dp.device
-    if getattr(dp, "err_tabs", None) is None:
-        cell_unit = torch.from_numpy(np.ascontiguousarray(dp.cell_unit_host, dtype=np.int64)
-                                     ).to(dev)
-        n_img = int(dp.cell_unit_host.max()) + 1 if dp.n_cells else 0
-        cells = torch.arange(dp.n_cells, dtype=torch.int64, device=dev)
-        gt_cell = torch.repeat_interleave(
-            cells, (t["cell_gt_off"][1:] - t["cell_gt_off"][:-1]).long())
-        dt_cell = t["dt_cell"][:dp.n_dt].long()
-        dp.err_tabs = (n_img,) + _rows_by_unit(cell_unit[gt_cell], n_img) \
-            + _rows_by_unit(cell_unit[dt_cell], n_img) \
-            + (t["dt_group"][:, 0].contiguous(),)
-    n_img, img_gt_off, img_gt, img_dt_off, img_dt, dt_gt0 = dp.err_tabs
-    if getattr(ws, "err_dt_counts", None) is None:
-        ws.err_bytes = lib.taoamd_error_types_workspace(dp.n_dt, dp.n_gt, dp.n_rng)
-        ws.err_ws = torch.empty(max(int(ws.err_bytes), 256), dtype=torch.uint8, device=dev)
-        ws.err_dt_counts = torch.empty((dp.n_rng, dp.n_cat, 7), dtype=torch.int64, device=dev)
-        ws.err_gt_counts = torch.empty((dp.n_rng, dp.n_cat, 3), dtype=torch.int64, device=dev)
-        ws.err_dt_type = None
-    match_gt = ws.match_gt
-    if match_gt is None:
-        if getattr(ws, "err_match_gt", None) is None and dp.n_dt:
-            stage_match(dp, ws, scatter=not ws.cell_order, match_gt=error_match_gt(dp, ws))
-        match_gt = getattr(ws, "err_match_gt", None)
-    if per_detection and ws.err_dt_type is None:
-        ws.err_dt_type = torch.empty((max(dp.n_dt, 1), dp.n_rng), dtype=torch.uint8, device=dev)
-    head = (dp.n_dt, dp.n_gt, n_img, dp.n_cat, dp.n_rng, int(slot), float(tb),
-            _ptr(t["dt_cat"]), _ptr(t["dt_box"]), _ptr(t["dt_flags"]), _ptr(dt_gt0),
-            _ptr(match_gt), dp.n_rng * N_THR, _ptr(t["gt_cat"]), _ptr(t["gt_box"]),
-            _ptr(ws.gt_rng), _ptr(img_gt_off), _ptr(img_gt), _ptr(img_dt_off), _ptr(img_dt),
-            _ptr(ws.err_dt_counts), _ptr(ws.err_gt_counts),
-            _ptr(ws.err_dt_type) if per_detection else None)
-    if links:
-        _lib.check(lib.taoamd_error_types_links(
-            *head, _ptr(ws.err_link_same), _ptr(ws.err_link_other), _ptr(ws.err_held),
-            _ptr(ws.err_ws), ws.err_bytes, s), "taoamd_error_types_links")
-    else:
-        _lib.check(lib.taoamd_error_types(*head, _ptr(ws.err_ws), ws.err_bytes, s),
-                   "taoamd_error_types")
+    _error_pass(dp, ws, slot, tb, per_detection, False, "lvis")
 
 
 def stage_error_impact(dp, ws, slot, tb):
@@ -1177,30 +1257,9 @@ def stage_error_impact(dp, ws, slot, tb):
     ws.imp_num_gt[9, n_cat, n_rng].  Buffers are allocated on the first call and
     kept with the workspace: the two link tables are 8 bytes per (row, range)
     together -- 1.0 GB at 21.4 M rows and 6 ranges --, the sweep's own workspace
-    another 4 (`del ws.err_link_same, ws.err_link_other, ws.imp_ws` gives them
-    back)."""
-    lib, dev = _lib.load(), dp.device
-    if getattr(ws, "err_link_same", None) is None:
-        shape = (max(dp.n_dt, 1), dp.n_rng)
-        ws.err_link_same = torch.empty(shape, dtype=torch.int32, device=dev)
-        ws.err_link_other = torch.empty(shape, dtype=torch.int32, device=dev)
-        ws.err_held = torch.empty((dp.n_rng, max(dp.n_gt, 1)), dtype=torch.uint8, device=dev)
-    _error_types_pass(dp, ws, slot, tb, per_detection=True, links=True)
-    if getattr(ws, "imp_ws", None) is None:
-        ws.imp_bytes = lib.taoamd_error_impact_workspace(dp.n_dt, dp.n_gt, dp.n_cat, dp.n_rng)
-        ws.imp_ws = torch.empty(max(int(ws.imp_bytes), 256), dtype=torch.uint8, device=dev)
-        ws.imp_precision = torch.empty((len(_lib.ERROR_FIXES), N_REC, dp.n_cat, dp.n_rng),
-                                       dtype=torch.float64, device=dev)
-        ws.imp_num_gt = torch.empty((len(_lib.ERROR_FIXES), dp.n_cat, dp.n_rng),
-                                    dtype=torch.int32, device=dev)
-    t = dp.t
-    ws.imp_order = ws.order          # (derived on demand: alive while the pass runs)
-    _lib.check(lib.taoamd_error_impact(
-        dp.n_dt, dp.n_gt, dp.n_cat, dp.n_rng, _ptr(t["cat_off"]), _ptr(ws.imp_order),
-        _ptr(t["dt_score"]), _ptr(t["dt_cat"]), _ptr(ws.err_dt_type), _ptr(ws.err_link_same),
-        _ptr(ws.err_link_other), _ptr(t["gt_cat"]), _ptr(ws.gt_rng), _ptr(ws.err_held),
-        _ptr(ws.imp_precision), _ptr(ws.imp_num_gt), _ptr(ws.imp_ws), ws.imp_bytes, _stream()),
-        "taoamd_error_impact")
+    another 4 (`ws.err_link_same = ws.err_link_other = ws.imp_ws = None` gives
+    them back)."""
+    _error_impact(dp, ws, slot, tb, "lvis")
 
 
 def stage_track_error_types(dp, ws, slot, tb, per_detection=False):
@@ -1216,59 +1275,7 @@ def stage_track_error_types(dp, ws, slot, tb, per_detection=False):
     workspace's own table (detail mode), else from error_match_gt() (800 bytes
     a row), filled here by one more match unless the caller's match already
     wrote it.  Buffers are allocated on the first call."""
-    _track_error_types_pass(dp, ws, slot, tb, per_detection, links=False)
-
-
-def _track_error_types_pass(dp, ws, slot, tb, per_detection, links):
-    """stage_track_error_types; `links`: through taoamd_track_error_types_links,
-    which also fills ws.err_link_same, ws.err_link_other and ws.err_held."""
-    if dp.kind != "tao" or dp.mask_iou:
-        raise _lib.TaoAmdError("the track-level error breakdown is the track level's, on boxes")
-    if dp.iou_mode != 0:
-        raise _lib.TaoAmdError("the track-level error breakdown is defined for the 3d_iou metric")
-    if dp.cell_unit_host is None:
-        raise _lib.TaoAmdError("the error breakdown needs the cells' videos (flat.cell_unit)")
-    lib, t, s = _lib.load(), dp.t, _stream()
-    dev = dp.device
-    if getattr(dp, "err_tabs", None) is None:
-        cell_unit = torch.from_numpy(np.ascontiguousarray(dp.cell_unit_host, dtype=np.int64)
-                                     ).to(dev)
-        n_vid = int(dp.cell_unit_host.max()) + 1 if dp.n_cells else 0
-        cells = torch.arange(dp.n_cells, dtype=torch.int64, device=dev)
-        gt_cell = torch.repeat_interleave(
-            cells, (t["cell_gt_off"][1:] - t["cell_gt_off"][:-1]).long())
-        dt_cell = t["dt_cell"][:dp.n_dt].long()
-        dp.err_tabs = (n_vid,) + _rows_by_unit(cell_unit[gt_cell], n_vid) \
-            + _rows_by_unit(cell_unit[dt_cell], n_vid)
-    n_vid, vid_gt_off, vid_gt, vid_dt_off, vid_dt = dp.err_tabs
-    if getattr(ws, "err_dt_counts", None) is None:
-        ws.err_bytes = lib.taoamd_track_error_types_workspace(dp.n_dt, dp.n_gt, dp.n_rng)
-        ws.err_ws = torch.empty(max(int(ws.err_bytes), 256), dtype=torch.uint8, device=dev)
-        ws.err_dt_counts = torch.empty((dp.n_rng, dp.n_cat, 7), dtype=torch.int64, device=dev)
-        ws.err_gt_counts = torch.empty((dp.n_rng, dp.n_cat, 3), dtype=torch.int64, device=dev)
-        ws.err_dt_type = None
-    match_gt = ws.match_gt
-    if match_gt is None:
-        if getattr(ws, "err_match_gt", None) is None and dp.n_dt:
-            stage_match(dp, ws, scatter=not ws.cell_order, match_gt=error_match_gt(dp, ws))
-        match_gt = getattr(ws, "err_match_gt", None)
-    if per_detection and ws.err_dt_type is None:
-        ws.err_dt_type = torch.empty((max(dp.n_dt, 1), dp.n_rng), dtype=torch.uint8, device=dev)
-    head = (dp.n_dt, dp.n_gt, dp.n_cells, dp.n_iou, n_vid, dp.n_cat, dp.n_rng, int(slot),
-            float(tb), _ptr(t["dt_cat"]), _ptr(ws.dt_rng), _ptr(t["dt_group"]),
-            _ptr(t["cell_iou_off"]), _ptr(ws.iou), _ptr(match_gt), dp.n_rng * N_THR, _ptr(t["gt_cat"]), _ptr(ws.gt_rng),
-            _ptr(t["dt_frame_off"]), _ptr(t["dt_frame_pos"]), _ptr(t["dt_frame_box"]),
-            _ptr(t["gt_frame_off"]), _ptr(t["gt_frame_pos"]), _ptr(t["gt_frame_box"]),
-            _ptr(vid_gt_off), _ptr(vid_gt), _ptr(vid_dt_off), _ptr(vid_dt),
-            _ptr(ws.err_dt_counts), _ptr(ws.err_gt_counts),
-            _ptr(ws.err_dt_type) if per_detection else None, None)
-    if links:
-        _lib.check(lib.taoamd_track_error_types_links(
-            *head, _ptr(ws.err_link_same), _ptr(ws.err_link_other), _ptr(ws.err_held),
-            _ptr(ws.err_ws), ws.err_bytes, s), "taoamd_track_error_types_links")
-    else:
-        _lib.check(lib.taoamd_track_error_types(*head, _ptr(ws.err_ws), ws.err_bytes, s),
-                   "taoamd_track_error_types")
+    _error_pass(dp, ws, slot, tb, per_detection, False, "tao")
 
 
 def stage_track_error_impact(dp, ws, slot, tb):
@@ -1282,31 +1289,9 @@ def stage_track_error_impact(dp, ws, slot, tb):
     thresholds and ws.imp_num_gt[9, n_cat, n_rng].  Buffers are allocated on the
     first call and kept with the workspace: the two link tables are 8 bytes per
     (track, range) together -- 58 MB at 361 577 tracks and 20 ranges --, the
-    sweep's own workspace another 4 (`del ws.err_link_same, ws.err_link_other,
-    ws.imp_ws` gives them back)."""
-    lib, dev = _lib.load(), dp.device
-    if getattr(ws, "err_link_same", None) is None:
-        shape = (max(dp.n_dt, 1), dp.n_rng)
-        ws.err_link_same = torch.empty(shape, dtype=torch.int32, device=dev)
-        ws.err_link_other = torch.empty(shape, dtype=torch.int32, device=dev)
-        ws.err_held = torch.empty((dp.n_rng, max(dp.n_gt, 1)), dtype=torch.uint8, device=dev)
-    _track_error_types_pass(dp, ws, slot, tb, per_detection=True, links=True)
-    if getattr(ws, "imp_ws", None) is None:
-        ws.imp_bytes = lib.taoamd_track_error_impact_workspace(dp.n_dt, dp.n_gt, dp.n_cat,
-                                                               dp.n_rng)
-        ws.imp_ws = torch.empty(max(int(ws.imp_bytes), 256), dtype=torch.uint8, device=dev)
-        ws.imp_precision = torch.empty((len(_lib.ERROR_FIXES), N_REC, dp.n_cat, dp.n_rng),
-                                       dtype=torch.float64, device=dev)
-        ws.imp_num_gt = torch.empty((len(_lib.ERROR_FIXES), dp.n_cat, dp.n_rng),
-                                    dtype=torch.int32, device=dev)
-    t = dp.t
-    ws.imp_order = ws.order          # (derived on demand: alive while the pass runs)
-    _lib.check(lib.taoamd_track_error_impact(
-        dp.n_dt, dp.n_gt, dp.n_cat, dp.n_rng, _ptr(t["cat_off"]), _ptr(ws.imp_order),
-        _ptr(t["dt_score"]), _ptr(t["dt_cat"]), _ptr(ws.err_dt_type), _ptr(ws.err_link_same),
-        _ptr(ws.err_link_other), _ptr(t["gt_cat"]), _ptr(ws.gt_rng), _ptr(ws.err_held),
-        _ptr(ws.imp_precision), _ptr(ws.imp_num_gt), _ptr(ws.imp_ws), ws.imp_bytes, _stream()),
-        "taoamd_track_error_impact")
+    sweep's own workspace another 4 (`ws.err_link_same = ws.err_link_other =
+    ws.imp_ws = None` gives them back)."""
+    _error_impact(dp, ws, slot, tb, "tao")
 
 
 def set_frame_visibility(dp, vis):
@@ -1344,7 +1329,7 @@ def stage_track_association(dp, ws, frame_thr, vis_rng):
         raise _lib.TaoAmdError("visibility windows need the frames' visibility "
                                "(engine.set_frame_visibility)")
     n_df, n_gf = int(t["dt_frame_pos"].numel()), int(t["gt_frame_pos"].numel())
-    if getattr(ws, "assoc_gt", None) is None:
+    if ws.assoc_gt is None:
         ws.assoc_bytes = lib.taoamd_track_association_workspace(dp.n_dt, dp.n_gt, n_gf)
         ws.assoc_ws = torch.empty(max(int(ws.assoc_bytes), 256), dtype=torch.uint8, device=dev)
         ws.assoc_follow = torch.empty(max(dp.n_iou, 1), dtype=torch.int32, device=dev)

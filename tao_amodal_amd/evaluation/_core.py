@@ -600,6 +600,103 @@ def operating_points(scores, iou_thrs, rec_thrs, cat_ids, iou_thr, recall):
     return {int(c): float(v) for c, v in zip(cat_ids, col.tolist()) if v != -1}
 
 
+# The on-request analyses of LVISEval and TaoEval: one body each; the methods
+# of the two classes hold the documentation and call these.  What a class `ev`
+# supplies: _rng_lbl() = the label of every range; _rng_text(label) = how a
+# line names it; _dt_ids() = the column that identifies a row of "dt_type";
+# _level = "" / " track", the word of the tables' titles.
+
+def error_key(iou_thrs, iou_thr, bg_thr):
+    """(index of `iou_thr` in params.iou_thrs, bg_thr): what the kernels are
+    asked for and the key the analyses are cached under.  `iou_thr` is looked
+    up like _summarize's; 0 <= bg_thr < tf = min(iou_thr, 1 - 1e-10)."""
+    at = np.where(iou_thr == np.asarray(iou_thrs))[0]
+    if len(at) == 0:
+        raise ValueError("iou_thr: {} is not one of params.iou_thrs".format(iou_thr))
+    tf = min(float(np.asarray(iou_thrs)[at[0]]), 1 - 1e-10)
+    if not 0 <= bg_thr < tf:
+        raise ValueError("bg_thr: {} is not in [0, {})".format(bg_thr, tf))
+    return int(at[0]), float(bg_thr)
+
+
+def _params_cats(ev, table, axis):
+    """`table` with its category axis in the order of params.cat_ids."""
+    if ev._cat_pos is None:
+        return table
+    return np.ascontiguousarray(table[(slice(None),) * axis + (ev._cat_pos,)])
+
+
+def score_at_recall(ev):
+    if not ev.eval:
+        raise RuntimeError("Please run accumulate() first.")
+    if "scores" not in ev.eval:
+        scores = _params_cats(ev, ev._run.score_table(), 2)
+        # (the track level's two range axes; the image level's shape as it is)
+        ev.eval["scores"] = scores.reshape(ev.eval["precision"].shape)
+    return ev.eval["scores"]
+
+
+def error_types(ev, iou_thr, bg_thr, per_detection):
+    if ev._run is None:
+        raise RuntimeError("Please run evaluate() first.")
+    key = error_key(ev.params.iou_thrs, iou_thr, bg_thr)
+    hit = ev._error_types.get(key)
+    if hit is None or (per_detection and "dt_type" not in hit):
+        dt_counts, gt_counts, dt_type = ev._run.error_table(key[0], key[1], per_detection)
+        from .._lib import ERROR_TYPES
+        hit = {"types": list(ERROR_TYPES), "dt_counts": _params_cats(ev, dt_counts, 1),
+               "gt_counts": _params_cats(ev, gt_counts, 1), "rng_lbl": ev._rng_lbl()}
+        if per_detection:
+            hit["dt_type"] = (ev._dt_ids(), dt_type)
+        ev._error_types[key] = hit
+    return hit if per_detection else {k: v for k, v in hit.items() if k != "dt_type"}
+
+
+def error_impact(ev, iou_thr, bg_thr):
+    if ev._run is None:
+        raise RuntimeError("Please run evaluate() first.")
+    key = error_key(ev.params.iou_thrs, iou_thr, bg_thr)
+    hit = ev._error_impact.get(key)
+    if hit is None:
+        precision = _params_cats(ev, ev._run.impact_table(key[0], key[1])[0], 2)
+        from .._lib import ERROR_FIXES
+        ap = np.array([[masked_mean(precision[v, :, :, a])
+                        for a in range(precision.shape[3])]
+                       for v in range(precision.shape[0])], dtype=np.float64)
+        hit = {"fixes": list(ERROR_FIXES), "precision": precision, "ap": ap,
+               "dap": ap[1:] - ap[0], "rng_lbl": ev._rng_lbl()}
+        ev._error_impact[key] = hit
+    return dict(hit)
+
+
+def _range_lines(ev, e, what, iou_thr, bg_thr, cols, rows, cell):
+    """A title, the column names and a line per range (row of `rows`), every
+    value through the format `cell`; a range past the labels goes by its index."""
+    lbl = [ev._rng_text(e["rng_lbl"][a]) if a < len(e["rng_lbl"]) else str(a)
+           for a in range(len(rows))]
+    w = max([len(x) for x in lbl] + [10])
+    width = len(cell.format(0))         # the column names as wide as the cells
+    lines = ["{} {} @[ IoU={:0.2f} | bg={:0.2f} ]".format(ev._level, what, iou_thr, bg_thr),
+             " " + " " * w + "".join(c.rjust(width) for c in cols)]
+    for name, r in zip(lbl, rows):
+        lines.append(" " + name.ljust(w) + "".join(cell.format(v) for v in r.tolist()))
+    return lines
+
+
+def error_lines(ev, iou_thr, bg_thr):
+    e = ev.error_types(iou_thr, bg_thr)
+    rows = np.concatenate([e["dt_counts"].sum(1), e["gt_counts"].sum(1)], axis=1)
+    return _range_lines(ev, e, "error types", iou_thr, bg_thr,
+                        e["types"] + ["GT", "missed", "missed_loc"], rows, "{:>11d}")
+
+
+def impact_lines(ev, iou_thr, bg_thr):
+    e = ev.error_impact(iou_thr, bg_thr)
+    rows = np.concatenate([e["ap"][:1], e["dap"]]).T
+    return _range_lines(ev, e, "error impact", iou_thr, bg_thr,
+                        ["AP"] + ["d" + name for name in e["fixes"][1:]], rows, "{:>9.4f}")
+
+
 def now():
     return datetime.datetime.now().strftime("%Y-%m-%d %H:%M:%S")
 

@@ -11,6 +11,7 @@ from collections.abc import Sequence
 import numpy as np
 
 from ... import flatten
+from .. import _core
 from .._core import (N_REC, N_THR, CellView, GpuRun, LazyIous, LazyPointers,
                      EvalConstants, restrict_to_params,
                      masked_mean, now, operating_points, summaries, timed)
@@ -223,20 +224,23 @@ class LVISEval:
             "dt_pointers": LazyPointers(self._run, n_rng, (n_rng,), self._cat_pos),
         }
 
+    # what the shared bodies of the on-request analyses (_core) ask of the level
+    _level = ""
+    _rng_text = staticmethod(str)
+
+    def _rng_lbl(self):
+        return list(self.params.visibility_rng_lbl)
+
+    def _dt_ids(self):
+        return np.asarray(self.flat.dt_row)
+
     def score_at_recall(self):
         """eval["scores"][T, R, K, visibility range], pycocotools' table beside
         eval["precision"]: the score of the detection at which recall first
         reaches each recall threshold (-1: no evaluated ground truth, 0: never
         reached).  Computed on the first call, from what accumulate() left on
         the device."""
-        if not self.eval:
-            raise RuntimeError("Please run accumulate() first.")
-        if "scores" not in self.eval:
-            scores = self._run.score_table()
-            if self._cat_pos is not None:
-                scores = np.ascontiguousarray(scores[:, :, self._cat_pos])
-            self.eval["scores"] = scores
-        return self.eval["scores"]
+        return _core.score_at_recall(self)
 
     def operating_points(self, iou_thr, recall, rng="all"):
         """{category id: score threshold} at which the category reaches
@@ -283,45 +287,13 @@ class LVISEval:
         reference (dt_m == 0), sees it as unmatched.  Not available:
         iou_type="segm", use_cats = 0, more than one block of edited constants,
         multi-GPU runs.  The track level has its own, TaoEval.error_types()."""
-        if self._run is None:
-            raise RuntimeError("Please run evaluate() first.")
-        P = self.params
-        at = np.where(iou_thr == np.asarray(P.iou_thrs))[0]
-        if len(at) == 0:
-            raise ValueError("iou_thr: {} is not one of params.iou_thrs".format(iou_thr))
-        tf = min(float(np.asarray(P.iou_thrs)[at[0]]), 1 - 1e-10)
-        if not 0 <= bg_thr < tf:
-            raise ValueError("bg_thr: {} is not in [0, {})".format(bg_thr, tf))
-        key = (int(at[0]), float(bg_thr))
-        hit = self._error_types.get(key)
-        if hit is None or (per_detection and "dt_type" not in hit):
-            dt_counts, gt_counts, dt_type = self._run.error_table(
-                key[0], key[1], per_detection)
-            if self._cat_pos is not None:
-                dt_counts = np.ascontiguousarray(dt_counts[:, self._cat_pos])
-                gt_counts = np.ascontiguousarray(gt_counts[:, self._cat_pos])
-            from ..._lib import ERROR_TYPES
-            hit = {"types": list(ERROR_TYPES), "dt_counts": dt_counts,
-                   "gt_counts": gt_counts, "rng_lbl": list(P.visibility_rng_lbl)}
-            if per_detection:
-                hit["dt_type"] = (np.asarray(self.flat.dt_row), dt_type)
-            self._error_types[key] = hit
-        return hit if per_detection else {k: v for k, v in hit.items() if k != "dt_type"}
+        return _core.error_types(self, iou_thr, bg_thr, per_detection)
 
     def error_lines(self, iou_thr=0.5, bg_thr=0.1):
         """error_types() as a small text table: a line per visibility range,
         the seven types and the three ground-truth counts summed over the
         categories.  Returned, not printed."""
-        e = self.error_types(iou_thr, bg_thr)
-        cols = e["types"] + ["GT", "missed", "missed_loc"]
-        rows = np.concatenate([e["dt_counts"].sum(1), e["gt_counts"].sum(1)], axis=1)
-        lbl = [e["rng_lbl"][a] if a < len(e["rng_lbl"]) else str(a) for a in range(len(rows))]
-        w = max([len(x) for x in lbl] + [10])
-        lines = [" error types @[ IoU={:0.2f} | bg={:0.2f} ]".format(iou_thr, bg_thr),
-                 " " + " " * w + "".join("{:>11s}".format(c) for c in cols)]
-        for name, r in zip(lbl, rows):
-            lines.append(" " + name.ljust(w) + "".join("{:>11d}".format(int(v)) for v in r))
-        return lines
+        return _core.error_lines(self, iou_thr, bg_thr)
 
     def error_impact(self, iou_thr=0.5, bg_thr=0.1):
         """The AP each error type costs, per visibility range: TIDE's dAP (Bolya
@@ -349,43 +321,12 @@ class LVISEval:
         summarize() reports as AP at `iou_thr`, except where a ground truth
         whose id is 0 holds a detection (see error_types()).  Not available
         where error_types() is not."""
-        if self._run is None:
-            raise RuntimeError("Please run evaluate() first.")
-        P = self.params
-        at = np.where(iou_thr == np.asarray(P.iou_thrs))[0]
-        if len(at) == 0:
-            raise ValueError("iou_thr: {} is not one of params.iou_thrs".format(iou_thr))
-        tf = min(float(np.asarray(P.iou_thrs)[at[0]]), 1 - 1e-10)
-        if not 0 <= bg_thr < tf:
-            raise ValueError("bg_thr: {} is not in [0, {})".format(bg_thr, tf))
-        key = (int(at[0]), float(bg_thr))
-        hit = self._error_impact.get(key)
-        if hit is None:
-            precision, _ = self._run.impact_table(key[0], key[1])
-            if self._cat_pos is not None:
-                precision = np.ascontiguousarray(precision[:, :, self._cat_pos])
-            from ..._lib import ERROR_FIXES
-            ap = np.array([[masked_mean(precision[v, :, :, a])
-                            for a in range(precision.shape[3])]
-                           for v in range(precision.shape[0])], dtype=np.float64)
-            hit = {"fixes": list(ERROR_FIXES), "precision": precision, "ap": ap,
-                   "dap": ap[1:] - ap[0], "rng_lbl": list(P.visibility_rng_lbl)}
-            self._error_impact[key] = hit
-        return dict(hit)
+        return _core.error_impact(self, iou_thr, bg_thr)
 
     def impact_lines(self, iou_thr=0.5, bg_thr=0.1):
         """error_impact() as a small text table: a line per visibility range,
         AP and the dAP of the eight fixes.  Returned, not printed."""
-        e = self.error_impact(iou_thr, bg_thr)
-        cols = ["AP"] + ["d" + name for name in e["fixes"][1:]]
-        rows = np.concatenate([e["ap"][:1], e["dap"]]).T
-        lbl = [e["rng_lbl"][a] if a < len(e["rng_lbl"]) else str(a) for a in range(len(rows))]
-        w = max([len(x) for x in lbl] + [10])
-        lines = [" error impact @[ IoU={:0.2f} | bg={:0.2f} ]".format(iou_thr, bg_thr),
-                 " " + " " * w + "".join("{:>9s}".format(c) for c in cols)]
-        for name, r in zip(lbl, rows):
-            lines.append(" " + name.ljust(w) + "".join("{:>9.4f}".format(float(v)) for v in r))
-        return lines
+        return _core.impact_lines(self, iou_thr, bg_thr)
 
     def _summarize(self, summary_type, iou_thr=None, visibility_rng="all",
                    freq_group_idx=None):

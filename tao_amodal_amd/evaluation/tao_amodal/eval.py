@@ -14,6 +14,7 @@ from collections.abc import Mapping
 
 import numpy as np
 
+from .. import _core
 from .._core import (N_REC, N_THR, CellView, GpuRun, LazyIous, LazyPointers,
                      EvalConstants,
                      masked_mean, now, operating_points, summaries, timed)
@@ -259,20 +260,33 @@ class TaoEval:
             "dt_pointers": LazyPointers(self._run, A * T, (A, T), self._cat_pos),
         }
 
+    # what the shared bodies of the on-request analyses (_core) ask of the level
+    _level = " track"
+
+    @staticmethod
+    def _rng_text(lbl):
+        return "{}/{}".format(*lbl)
+
+    def _rng_lbl(self):
+        """The (area label, time label) of every range; an index where the
+        labels run out."""
+        P = self.params
+
+        def lbl(names, i):
+            return names[i] if i < len(names) else str(i)
+        return [(lbl(P.area_rng_lbl, a), lbl(P.time_rng_lbl, t))
+                for a in range(len(P.area_rng)) for t in range(len(P.time_rng))]
+
+    def _dt_ids(self):
+        return np.asarray(self._run.flat.dt_id)
+
     def score_at_recall(self):
         """eval["scores"][T, R, K, area range, time range], pycocotools' table
         beside eval["precision"]: the score of the track at which recall first
         reaches each recall threshold (-1: no evaluated ground truth, 0: never
         reached).  Computed on the first call, from what accumulate() left on
         the device."""
-        if not self.eval:
-            raise RuntimeError("Please run accumulate() first.")
-        if "scores" not in self.eval:
-            scores = self._run.score_table()
-            if self._cat_pos is not None:
-                scores = np.ascontiguousarray(scores[:, :, self._cat_pos])
-            self.eval["scores"] = scores.reshape(self.eval["precision"].shape)
-        return self.eval["scores"]
+        return _core.score_at_recall(self)
 
     def operating_points(self, iou_thr, recall, rng=("all", "all")):
         """{category id: track score threshold} at which the category reaches
@@ -322,52 +336,13 @@ class TaoEval:
         accumulate(), like the reference, sees it as unmatched.  Not available:
         iou_type="segm", use_cats = 0, an iou_3d_type other than "3d_iou", more
         than one block of edited constants, multi-GPU runs."""
-        if self._run is None:
-            raise RuntimeError("Please run evaluate() first.")
-        P = self.params
-        at = np.where(iou_thr == np.asarray(P.iou_thrs))[0]
-        if len(at) == 0:
-            raise ValueError("iou_thr: {} is not one of params.iou_thrs".format(iou_thr))
-        tf = min(float(np.asarray(P.iou_thrs)[at[0]]), 1 - 1e-10)
-        if not 0 <= bg_thr < tf:
-            raise ValueError("bg_thr: {} is not in [0, {})".format(bg_thr, tf))
-        key = (int(at[0]), float(bg_thr))
-        hit = self._error_types.get(key)
-        if hit is None or (per_detection and "dt_type" not in hit):
-            dt_counts, gt_counts, dt_type = self._run.error_table(
-                key[0], key[1], per_detection)
-            if self._cat_pos is not None:
-                dt_counts = np.ascontiguousarray(dt_counts[:, self._cat_pos])
-                gt_counts = np.ascontiguousarray(gt_counts[:, self._cat_pos])
-            from ..._lib import ERROR_TYPES
-
-            def lbl(names, i):
-                return names[i] if i < len(names) else str(i)
-            hit = {"types": list(ERROR_TYPES), "dt_counts": dt_counts,
-                   "gt_counts": gt_counts,
-                   "rng_lbl": [(lbl(P.area_rng_lbl, a), lbl(P.time_rng_lbl, t))
-                               for a in range(len(P.area_rng))
-                               for t in range(len(P.time_rng))]}
-            if per_detection:
-                hit["dt_type"] = (np.asarray(self._run.flat.dt_id), dt_type)
-            self._error_types[key] = hit
-        return hit if per_detection else {k: v for k, v in hit.items() if k != "dt_type"}
+        return _core.error_types(self, iou_thr, bg_thr, per_detection)
 
     def error_lines(self, iou_thr=0.5, bg_thr=0.1):
         """error_types() as a small text table: a line per (area, time) range,
         the seven types and the three ground-truth counts summed over the
         categories.  Returned, not printed."""
-        e = self.error_types(iou_thr, bg_thr)
-        cols = e["types"] + ["GT", "missed", "missed_loc"]
-        rows = np.concatenate([e["dt_counts"].sum(1), e["gt_counts"].sum(1)], axis=1)
-        lbl = ["{}/{}".format(*e["rng_lbl"][a]) if a < len(e["rng_lbl"]) else str(a)
-               for a in range(len(rows))]
-        w = max([len(x) for x in lbl] + [10])
-        lines = [" track error types @[ IoU={:0.2f} | bg={:0.2f} ]".format(iou_thr, bg_thr),
-                 " " + " " * w + "".join("{:>11s}".format(c) for c in cols)]
-        for name, r in zip(lbl, rows):
-            lines.append(" " + name.ljust(w) + "".join("{:>11d}".format(int(v)) for v in r))
-        return lines
+        return _core.error_lines(self, iou_thr, bg_thr)
 
     def error_impact(self, iou_thr=0.5, bg_thr=0.1):
         """The Track-AP each error type costs, per (area, time) range: TIDE's
@@ -397,35 +372,7 @@ class TaoEval:
         "unmatched" sentinel holds a detection track (see error_types()).  Not
         available where error_types() is not, nor with more than 101 recall
         thresholds."""
-        if self._run is None:
-            raise RuntimeError("Please run evaluate() first.")
-        P = self.params
-        at = np.where(iou_thr == np.asarray(P.iou_thrs))[0]
-        if len(at) == 0:
-            raise ValueError("iou_thr: {} is not one of params.iou_thrs".format(iou_thr))
-        tf = min(float(np.asarray(P.iou_thrs)[at[0]]), 1 - 1e-10)
-        if not 0 <= bg_thr < tf:
-            raise ValueError("bg_thr: {} is not in [0, {})".format(bg_thr, tf))
-        key = (int(at[0]), float(bg_thr))
-        hit = self._error_impact.get(key)
-        if hit is None:
-            precision, _ = self._run.impact_table(key[0], key[1])
-            if self._cat_pos is not None:
-                precision = np.ascontiguousarray(precision[:, :, self._cat_pos])
-            from ..._lib import ERROR_FIXES
-            ap = np.array([[masked_mean(precision[v, :, :, a])
-                            for a in range(precision.shape[3])]
-                           for v in range(precision.shape[0])], dtype=np.float64)
-
-            def lbl(names, i):
-                return names[i] if i < len(names) else str(i)
-            hit = {"fixes": list(ERROR_FIXES), "precision": precision, "ap": ap,
-                   "dap": ap[1:] - ap[0],
-                   "rng_lbl": [(lbl(P.area_rng_lbl, a), lbl(P.time_rng_lbl, t))
-                               for a in range(len(P.area_rng))
-                               for t in range(len(P.time_rng))]}
-            self._error_impact[key] = hit
-        return dict(hit)
+        return _core.error_impact(self, iou_thr, bg_thr)
 
     def association(self, frame_thr=0.5, vis_rng=None, vis_lbl=None, per_track=False,
                     per_frame=False):
@@ -546,17 +493,7 @@ class TaoEval:
     def impact_lines(self, iou_thr=0.5, bg_thr=0.1):
         """error_impact() as a small text table: a line per (area, time) range,
         AP and the dAP of the eight fixes.  Returned, not printed."""
-        e = self.error_impact(iou_thr, bg_thr)
-        cols = ["AP"] + ["d" + name for name in e["fixes"][1:]]
-        rows = np.concatenate([e["ap"][:1], e["dap"]]).T
-        lbl = ["{}/{}".format(*e["rng_lbl"][a]) if a < len(e["rng_lbl"]) else str(a)
-               for a in range(len(rows))]
-        w = max([len(x) for x in lbl] + [10])
-        lines = [" track error impact @[ IoU={:0.2f} | bg={:0.2f} ]".format(iou_thr, bg_thr),
-                 " " + " " * w + "".join("{:>9s}".format(c) for c in cols)]
-        for name, r in zip(lbl, rows):
-            lines.append(" " + name.ljust(w) + "".join("{:>9.4f}".format(float(v)) for v in r))
-        return lines
+        return _core.impact_lines(self, iou_thr, bg_thr)
 
     def _summarize(self, summary_type, iou_thr=None, area_rng="all",
                    time_rng="all", freq_group_idx=None):

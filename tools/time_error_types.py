@@ -145,7 +145,7 @@ def track_level(a, gt, dt, dev, V):
         engine.stage_track_error_impact(dp, ws, 0, a.bg_thr)
         torch.cuda.synchronize()
         res["track_error_types_links"] = timed(
-            lambda: engine._track_error_types_pass(dp, ws, 0, a.bg_thr, True, links=True))
+            lambda: engine._error_pass(dp, ws, 0, a.bg_thr, True, True, "tao"))
         res["track_error_impact_links_and_sweep"] = timed(
             lambda: engine.stage_track_error_impact(dp, ws, 0, a.bg_thr))
         _lib.kernel_timing(True)
@@ -260,7 +260,7 @@ def main():
     res["error_types"] = timed(lambda: engine.stage_error_types(dp, ws, 0, a.bg_thr))
     res["error_types_per_detection"] = timed(
         lambda: engine.stage_error_types(dp, ws, 0, a.bg_thr, per_detection=True))
-    n_img, g_off, _, d_off, _, _ = dp.err_tabs
+    n_img, g_off, _, d_off, _ = dp.err_tabs
     g_cnt = (g_off[1:] - g_off[:-1]).long()
     d_cnt = (d_off[1:] - d_off[:-1]).long()
     res["images"] = n_img
@@ -279,7 +279,7 @@ def main():
         engine.stage_error_impact(dp, ws, 0, a.bg_thr)
         torch.cuda.synchronize()
         res["error_types_links"] = timed(
-            lambda: engine._error_types_pass(dp, ws, 0, a.bg_thr, True, links=True))
+            lambda: engine._error_pass(dp, ws, 0, a.bg_thr, True, True, "lvis"))
         res["error_impact_links_and_sweep"] = timed(
             lambda: engine.stage_error_impact(dp, ws, 0, a.bg_thr))
         _lib.kernel_timing(True)
