@@ -1116,6 +1116,80 @@ int taoamd_track_error_impact(int64_t n_dt, int64_t n_gt, int32_t n_cat, int32_t
                               int32_t *num_gt, void *workspace, size_t workspace_bytes,
                               void *stream);
 
+/* ---- confusion: which category pairs the CLS and BOTH errors confuse (csrc/confusion.hip)
+ * For every CLS or BOTH row: the category of the ground truth it was taken
+ * for.  The definition is this library's.  Level-agnostic like the error
+ * impact: one entry point serves the tables of taoamd_error_types_links and of
+ * taoamd_track_error_types_links, n_rng in [1, TAOAMD_TAO_RNG].
+ *
+ * Context: one error_types call (one slot, tf, tb, all n_rng ranges) and its
+ * tables, as taoamd_error_impact takes them; the rows lie category-major: the
+ * rows of category c are [cat_off[c], cat_off[c + 1]), clamped to the table.
+ * What a row contributes: row d of the segment of c, with dt_cat[d] == c; for
+ * range a let ty = dt_type[d][a] and g = link_other[d][a].  The row contributes
+ * only if ty is CLS (4) or BOTH (5), g lies in [0, n_gt) and c' = gt_cat[g]
+ * lies in [0, n_cat); then to the pair (a, c, c').  Every other row contributes
+ * nothing and is never dereferenced through its link: a link of -1, a link or
+ * a category outside the tables, a dt_cat that is not its segment's, a type
+ * byte >= 7.
+ * Four int32 counters per pair, in this order:
+ *   0 cls      the CLS rows
+ *   1 both     the BOTH rows
+ *   2 unheld   the CLS rows with held[a][g] == 0: the ground truth is missed
+ *   3 adopted  the CLS rows that are the WINNER of (a, g) with held[a][g] == 0
+ * WINNER: the rule of the error impact word for word -- the greatest score;
+ * equal scores (-0.0 == 0.0) go to the lowest table row; a NaN score loses to
+ * every number, between two NaNs the lower row wins -- among the CLS rows of
+ * range a linking g, of EVERY predicted category (every row of the table whose
+ * dt_cat lies in [0, n_cat), as taoamd_error_impact takes them).  These are
+ * the rows variant 1 (CLS) of the impact adopts into c', so one missed ground
+ * truth is `adopted` in one pair only.
+ * It follows that
+ *   sum over c' of cls[a, c, :] == dt_counts[a][c][CLS] less the CLS rows
+ *     skipped above, likewise both; on tables that taoamd_*_error_types_links
+ *     produced nothing is skipped;
+ *   adopted <= unheld <= cls for every pair;
+ *   sum over c of adopted[a, :, c'] == the rows the impact's CLS variant
+ *     adopts into (c', a).
+ *
+ * Sparse result: the pairs with cls + both > 0 in ascending (a, c, c'), as a
+ * CSR over (a, c), the row of (a, c) at a * n_cat + c:
+ *   ent_off    int64[n_rng * n_cat + 1]
+ *   ent_gt_cat int32[n_ent]       c' of the entry
+ *   ent_counts int32[n_ent][4]    16-byte aligned: an entry leaves as one store
+ * (dense, [n_rng][K][K][4] int32 is 139 MB at K = 1203 and 6 ranges, 463 MB at
+ * 20, nearly all of it zero).  Every value is an integer and every entry has
+ * one place: the result is exact and byte-identical from run to run.
+ *
+ * Two calls, so that the caller sizes the entry arrays between them:
+ * taoamd_confusion_count fills the whole of ent_off (ent_off[n_rng * n_cat] =
+ * n_ent); taoamd_confusion_fill, with the same tables, the same workspace --
+ * its contents are kept between the two calls -- and on the same stream,
+ * stores the entries of every (a, c) row with ent_off[row + 1] <= cap and
+ * nothing at or beyond entry `cap`.
+ * TAOAMD_ERR_ARG: n_rng outside [1, TAOAMD_TAO_RNG], n_cat <= 0, sizes outside
+ * [0, 2^31), a missing table, cap < 0, ent_counts not 16-byte aligned;
+ * TAOAMD_ERR_WORKSPACE (before any device call): fewer bytes than
+ * taoamd_confusion_workspace(n_dt, n_gt, n_cat, n_rng) -- the winners, 12 bytes
+ * per (range, ground truth), and the entries per (a, c) row, 4 bytes per
+ * (range, category); any base address, contents need not be initialised.
+ * TAOAMD_CONFUSION_TILE: the ground-truth categories one LDS table of the
+ * histogram holds (16 bytes each, 32 KB); more categories than that and a
+ * category's rows are walked once per tile. */
+#define TAOAMD_CONFUSION_TILE 2048
+size_t taoamd_confusion_workspace(int64_t n_dt, int64_t n_gt, int32_t n_cat, int32_t n_rng);
+int taoamd_confusion_count(int64_t n_dt, int64_t n_gt, int32_t n_cat, int32_t n_rng,
+                           const int32_t *cat_off, const double *score, const int32_t *dt_cat,
+                           const uint8_t *dt_type, const int32_t *link_other,
+                           const int32_t *gt_cat, const uint8_t *held, int64_t *ent_off,
+                           void *workspace, size_t workspace_bytes, void *stream);
+int taoamd_confusion_fill(int64_t n_dt, int64_t n_gt, int32_t n_cat, int32_t n_rng,
+                          const int32_t *cat_off, const double *score, const int32_t *dt_cat,
+                          const uint8_t *dt_type, const int32_t *link_other,
+                          const int32_t *gt_cat, const uint8_t *held, const int64_t *ent_off,
+                          int64_t cap, int32_t *ent_gt_cat, int32_t *ent_counts,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- track-level error breakdown per range (csrc/track_error_types.hip) ------------
  * WHY a detection track is no true positive, per (area, time) range and
  * category: the section above, rule for rule, on the track tables.  The

@@ -24,6 +24,8 @@ TRACK_ERROR_TYPES_TILE = 16
 ERROR_TYPES = ("TP", "IGNORED", "DUP", "LOC", "CLS", "BOTH", "BKG")
 ERROR_IMPACT_CHUNK = 256
 ERROR_FIXES = ("BASE", "CLS", "LOC", "BOTH", "DUP", "BKG", "MISS", "FP", "FN")
+CONFUSION_TILE = 2048
+CONFUSION_COLUMNS = ("cls", "both", "unheld", "adopted")
 TRACK_ASSOCIATION_TILE = 64
 TRACK_ASSOCIATION_VIS = 8
 ASSOC_TRACK_COLUMNS = ("frames", "covered", "ids", "switches", "fragments", "primary",
@@ -221,7 +223,12 @@ SIGNATURES = {
     "taoamd_track_error_impact_workspace": (_sz, [_i64, _i64, _i32, _i32]),
     "taoamd_track_error_impact": (C.c_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_track_association_workspace": (_sz, [_i64, _i64, _i64]),
+    "taoamd_confusion_workspace": (_sz, [_i64, _i64, _i32, _i32]),
+    "taoamd_confusion_count": (C.c_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _sz, _vp]),
+    "taoamd_confusion_fill": (C.c_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "taoamd_track_association_workspace":(_sz, [_i64, _i64, _i64]),
     "taoamd_track_association": (C.c_int, [_i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32,
                                            C.c_double] + [_vp] * 20 + [_sz, _vp]),
 }

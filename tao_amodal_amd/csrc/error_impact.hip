@@ -36,6 +36,7 @@
 // are the precisions.  Values are doubles computed by the reference's
 // expression; a maximum of doubles depends on no order.
 #include "common.hpp"
+#include "winner.hpp"
 #include "workspace.hpp"
 
 using namespace taoamd;
@@ -66,26 +67,15 @@ struct ImpArgs {
     uint32_t *cnt;                           // [3][n_cat][n_rng] evaluated, missed and unlinked, missed
 };
 
-// Greater key = better claim: greater score, -0.0 == 0.0, a NaN below every
-// number; never 0.
-__device__ __forceinline__ unsigned long long imp_key(double s)
-{
-    return ~score_desc_key(s);
-}
-
-// The claim of (row d, range r): which table (0 LOC by link_same, 1 CLS by
-// link_other) and which ground truth; false where the row claims nothing
+// The claim of (row d, range r), by the rule winner.hpp shares with
+// confusion.hip: its table (0 LOC, 1 CLS) and its slot in best[] / win[]
 __device__ __forceinline__ bool imp_claim(const ImpArgs &a, int64_t d, int r, int &tab,
                                           int64_t &slot)
 {
-    const int32_t cat = a.dt_cat[d];
-    if (cat < 0 || cat >= a.n_cat) return false;
-    const int ty = a.dt_type[d * a.n_rng + r];
-    if (ty != ERR_LOC && ty != ERR_CLS) return false;
-    tab = ty == ERR_CLS;
-    const int64_t g = tab ? a.link_other[d * a.n_rng + r] : a.link_same[d * a.n_rng + r];
-    if (g < 0 || g >= a.n_gt) return false;
-    if (a.held[(int64_t)r * a.n_gt + g]) return false;
+    const ClaimTabs t = {a.n_gt, a.n_cat, a.n_rng, a.dt_cat, a.dt_type,
+                         a.link_same, a.link_other, a.held};
+    int64_t g;
+    if (!claim_of(t, d, r, tab, g)) return false;
     slot = ((int64_t)tab * a.n_rng + r) * a.n_gt + g;
     return true;
 }
@@ -98,7 +88,7 @@ __global__ __launch_bounds__(256) void imp_best_kernel(ImpArgs a)
     int tab;
     int64_t slot;
     if (!imp_claim(a, d, (int)(i - d * a.n_rng), tab, slot)) return;
-    atomicMax(a.best + slot, imp_key(a.score[d]));
+    claim_best(a.best, slot, a.score[d]);
 }
 
 __global__ __launch_bounds__(256) void imp_win_kernel(ImpArgs a)
@@ -109,7 +99,7 @@ __global__ __launch_bounds__(256) void imp_win_kernel(ImpArgs a)
     int tab;
     int64_t slot;
     if (!imp_claim(a, d, (int)(i - d * a.n_rng), tab, slot)) return;
-    if (a.best[slot] == imp_key(a.score[d])) atomicMin(a.win + slot, (uint32_t)d);
+    claim_win(a.best, a.win, slot, a.score[d], d);
 }
 
 // rows of category k in order[]: [lo, hi), clamped to the table

@@ -580,12 +580,14 @@ class Workspace:
             if dp.kind == "lvis":
                 self.ious_out = torch.empty(max(dp.n_iou, 1),
                                             dtype=torch.float64, device=dev)
-        # the on-request analyses (stage_scores, the error breakdown and its
-        # impact, stage_track_association): allocated by their first call
+        # the on-request analyses (stage_scores, the error breakdown, its impact
+        # and its confusion, stage_track_association): allocated by their first call
         self.scores = None
         self.err_match_gt = self.err_dt_counts = self.err_gt_counts = self.err_dt_type = None
         self.err_link_same = self.err_link_other = self.err_held = None
         self.imp_ws = self.imp_precision = self.imp_num_gt = None
+        self.conf_ws = self.conf_off = self.conf_gt_cat = self.conf_counts = None
+        self.conf_n = 0                   # entries of the last stage_confusion
         self.assoc_gt = self.assoc_vis_counts = None
         self.pairs_counted = False        # stage_track_iou counted the pairs' common frames
 
@@ -1292,6 +1294,44 @@ def stage_track_error_impact(dp, ws, slot, tb):
     sweep's own workspace another 4 (`ws.err_link_same = ws.err_link_other =
     ws.imp_ws = None` gives them back)."""
     _error_impact(dp, ws, slot, tb, "tao")
+
+
+def stage_confusion(dp, ws, slot, tb):
+    """Which category pairs the CLS and BOTH errors confuse, of the pass the
+    workspace holds (after stage_ranges .. stage_match): the level's breakdown
+    once more with its links (dp.kind picks taoamd_error_types_links or
+    taoamd_track_error_types_links, so the refusals are the breakdown's own),
+    then the sparse histogram (taoamd_confusion_count, taoamd_confusion_fill;
+    the definition is in include/tao_amodal_hip.h): a CSR over (range, predicted
+    category), ws.conf_off int64[n_rng * n_cat + 1], ws.conf_gt_cat int32[n_ent],
+    ws.conf_counts int32[n_ent, 4] (cls, both, unheld, adopted); ws.conf_n =
+    n_ent.  The number of entries is read between the two calls: one
+    synchronisation of the current stream.  Buffers are allocated on the first
+    call and kept with the workspace: the link tables as for the impact, 8
+    bytes per (row, range) together; the histogram's workspace 12 bytes per
+    (range, ground truth) and 4 per (range, category); ws.conf_off 8 bytes per
+    (range, category); the entries 20 bytes each, regrown where a call finds
+    more (`ws.conf_ws = ws.conf_off = ws.conf_gt_cat = ws.conf_counts = None`
+    gives them back)."""
+    _error_pass(dp, ws, slot, tb, True, True, dp.kind)
+    lib, t, dev, s = _lib.load(), dp.t, dp.device, _stream()
+    n_rows = dp.n_rng * dp.n_cat
+    if ws.conf_ws is None:
+        ws.conf_bytes = lib.taoamd_confusion_workspace(dp.n_dt, dp.n_gt, dp.n_cat, dp.n_rng)
+        ws.conf_ws = torch.empty(max(int(ws.conf_bytes), 256), dtype=torch.uint8, device=dev)
+        ws.conf_off = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+    tables = (dp.n_dt, dp.n_gt, dp.n_cat, dp.n_rng, _ptr(t["cat_off"]), _ptr(t["dt_score"]),
+              _ptr(t["dt_cat"]), _ptr(ws.err_dt_type), _ptr(ws.err_link_other),
+              _ptr(t["gt_cat"]), _ptr(ws.err_held), _ptr(ws.conf_off))
+    _lib.check(lib.taoamd_confusion_count(*tables, _ptr(ws.conf_ws), ws.conf_bytes, s),
+               "taoamd_confusion_count")
+    ws.conf_n = int(ws.conf_off[-1].item())         # (synchronises)
+    if ws.conf_gt_cat is None or ws.conf_gt_cat.numel() < ws.conf_n:
+        ws.conf_gt_cat = torch.empty(max(ws.conf_n, 1), dtype=torch.int32, device=dev)
+        ws.conf_counts = torch.empty((max(ws.conf_n, 1), 4), dtype=torch.int32, device=dev)
+    _lib.check(lib.taoamd_confusion_fill(
+        *tables, ws.conf_n, _ptr(ws.conf_gt_cat), _ptr(ws.conf_counts), _ptr(ws.conf_ws),
+        ws.conf_bytes, s), "taoamd_confusion_fill")
 
 
 def set_frame_visibility(dp, vis):

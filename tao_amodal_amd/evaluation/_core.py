@@ -272,9 +272,9 @@ class GpuRun:
         return [k for k, _ in sorted(c.rng_blocks[0][1], key=lambda ki: ki[1])]
 
     def _error_pass_at(self, thr_index):
-        """What error_table() and impact_table() share: the refusals, the
-        kernels' slot of the caller's threshold, and the match pass where
-        evaluate() left it out.  Returns (constants, slot)."""
+        """What error_table(), impact_table() and confusion_table() share: the
+        refusals, the kernels' slot of the caller's threshold, and the match
+        pass where evaluate() left it out.  Returns (constants, slot)."""
         c = self.constants
         track = self.flat.kind == "tao"
         if track and self.iou_3d_type != "3d_iou":
@@ -335,6 +335,38 @@ class GpuRun:
             # first threshold the category never reaches (see accumulate)
             out[np.maximum.accumulate(out == 0, axis=1)] = 0
         return out, num_gt[..., ks]
+
+    def confusion_table(self, thr_index, bg_thr):
+        """(rng int32[n], dt_cat int64[n], gt_cat int64[n], counts int64[n, 4],
+        K): the category pairs the CLS and BOTH rows confuse at the caller's
+        `thr_index`-th IoU threshold (engine.stage_confusion; the definition is
+        in include/tao_amodal_hip.h): the caller's range index, the two
+        categories as indices into the tables' K categories and (cls, both,
+        unheld, adopted), sorted by (range, dt_cat, gt_cat), from the pass the
+        workspace holds after evaluate().  Refuses what error_table() refuses,
+        in its words."""
+        c, slot = self._error_pass_at(thr_index)
+        with timed("kernels"), applied(c):
+            self.engine.stage_confusion(self.dp, self.ws, slot, bg_thr)
+            self.torch.cuda.synchronize(self.device)
+        with timed("download"):
+            ws, n = self.ws, self.ws.conf_n
+            off = ws.conf_off.cpu().numpy()
+            gt_cat = ws.conf_gt_cat[:n].cpu().numpy().astype(np.int64)
+            counts = ws.conf_counts[:n].cpu().numpy().astype(np.int64)
+        K = self.dp.n_cat
+        row = np.repeat(np.arange(len(off) - 1, dtype=np.int64), np.diff(off))
+        rng, dt_cat = row // K, row % K
+        if c is not None:
+            # kernel range slot -> the caller's range; the slots it has no range for go
+            to = np.full((len(off) - 1) // K, -1, dtype=np.int64)
+            ks = self._range_slots(c)
+            to[ks] = np.arange(len(ks))
+            rng = to[rng]
+            keep = np.flatnonzero(rng >= 0)
+            keep = keep[np.argsort(rng[keep], kind="stable")]
+            rng, dt_cat, gt_cat, counts = rng[keep], dt_cat[keep], gt_cat[keep], counts[keep]
+        return rng.astype(np.int32), dt_cat, gt_cat, counts, K
 
     def association_table(self, frame_thr, vis_rng, ann_vis):
         """The per-frame followers of the ground-truth tracks
@@ -604,7 +636,8 @@ def operating_points(scores, iou_thrs, rec_thrs, cat_ids, iou_thr, recall):
 # of the two classes hold the documentation and call these.  What a class `ev`
 # supplies: _rng_lbl() = the label of every range; _rng_text(label) = how a
 # line names it; _dt_ids() = the column that identifies a row of "dt_type";
-# _level = "" / " track", the word of the tables' titles.
+# _level = "" / " track", the word of the tables' titles; _cats() = the
+# annotation file's categories by id.
 
 def error_key(iou_thrs, iou_thr, bg_thr):
     """(index of `iou_thr` in params.iou_thrs, bg_thr): what the kernels are
@@ -669,14 +702,23 @@ def error_impact(ev, iou_thr, bg_thr):
     return dict(hit)
 
 
+def _title(ev, what, iou_thr, bg_thr, more=""):
+    """The title line of an analysis' text table."""
+    return "{} {} @[ IoU={:0.2f} | bg={:0.2f}{} ]".format(ev._level, what, iou_thr, bg_thr, more)
+
+
+def _range_name(ev, e, a):
+    """How a line names range `a`; a range past the labels goes by its index."""
+    return ev._rng_text(e["rng_lbl"][a]) if a < len(e["rng_lbl"]) else str(a)
+
+
 def _range_lines(ev, e, what, iou_thr, bg_thr, cols, rows, cell):
     """A title, the column names and a line per range (row of `rows`), every
     value through the format `cell`; a range past the labels goes by its index."""
-    lbl = [ev._rng_text(e["rng_lbl"][a]) if a < len(e["rng_lbl"]) else str(a)
-           for a in range(len(rows))]
+    lbl = [_range_name(ev, e, a) for a in range(len(rows))]
     w = max([len(x) for x in lbl] + [10])
     width = len(cell.format(0))         # the column names as wide as the cells
-    lines = ["{} {} @[ IoU={:0.2f} | bg={:0.2f} ]".format(ev._level, what, iou_thr, bg_thr),
+    lines = [_title(ev, what, iou_thr, bg_thr),
              " " + " " * w + "".join(c.rjust(width) for c in cols)]
     for name, r in zip(lbl, rows):
         lines.append(" " + name.ljust(w) + "".join(cell.format(v) for v in r.tolist()))
@@ -695,6 +737,71 @@ def impact_lines(ev, iou_thr, bg_thr):
     rows = np.concatenate([e["ap"][:1], e["dap"]]).T
     return _range_lines(ev, e, "error impact", iou_thr, bg_thr,
                         ["AP"] + ["d" + name for name in e["fixes"][1:]], rows, "{:>9.4f}")
+
+
+def confusion(ev, iou_thr, bg_thr):
+    if ev._run is None:
+        raise RuntimeError("Please run evaluate() first.")
+    key = error_key(ev.params.iou_thrs, iou_thr, bg_thr)
+    hit = ev._confusion.get(key)
+    if hit is None:
+        rng, dt_cat, gt_cat, counts, K = ev._run.confusion_table(key[0], key[1])
+        ids = np.asarray(ev.params.cat_ids, dtype=np.int64).reshape(-1)
+        if ev._cat_pos is not None:
+            # table category -> its place in params.cat_ids; the others are not asked for
+            place = np.full(K, -1, dtype=np.int64)
+            place[ev._cat_pos] = np.arange(len(ev._cat_pos))
+            dt_cat, gt_cat = place[dt_cat], place[gt_cat]
+            keep = np.flatnonzero((dt_cat >= 0) & (gt_cat >= 0))
+            keep = keep[np.lexsort((gt_cat[keep], dt_cat[keep], rng[keep]))]
+            rng, dt_cat, gt_cat, counts = rng[keep], dt_cat[keep], gt_cat[keep], counts[keep]
+        from .._lib import CONFUSION_COLUMNS
+        hit = {"columns": list(CONFUSION_COLUMNS), "rng_lbl": ev._rng_lbl(), "rng": rng,
+               "dt_cat": ids[dt_cat], "gt_cat": ids[gt_cat], "counts": counts}
+        ev._confusion[key] = hit
+    return dict(hit)
+
+
+def confusion_matrix(ev, iou_thr, bg_thr, rng, column):
+    e = ev.confusion(iou_thr, bg_thr)
+    if column not in e["columns"]:
+        raise ValueError("column: {!r} is not one of {}".format(column, e["columns"]))
+    ids = np.asarray(ev.params.cat_ids, dtype=np.int64).reshape(-1)
+    place = {int(c): i for i, c in enumerate(ids.tolist())}
+    sel = np.flatnonzero(e["rng"] == rng)
+    out = np.zeros((len(ids), len(ids)), dtype=np.int64)
+    at = [place[c] for c in e["dt_cat"][sel].tolist()]
+    to = [place[c] for c in e["gt_cat"][sel].tolist()]
+    out[at, to] = e["counts"][sel, e["columns"].index(column)]
+    return out
+
+
+def confusion_lines(ev, iou_thr, bg_thr, rng, top):
+    e = ev.confusion(iou_thr, bg_thr)
+    sel = np.flatnonzero(e["rng"] == rng)
+    cols = e["columns"]
+    n = e["counts"][sel]
+    # most adopted first, then most CLS rows; the entries come by (dt_cat, gt_cat)
+    # places, the ids break what ties remain: a total order
+    by = np.lexsort((e["gt_cat"][sel], e["dt_cat"][sel], -n[:, cols.index("cls")],
+                     -n[:, cols.index("adopted")]))
+    sel = sel[by[:max(int(top), 0)]]
+    cats = ev._cats()
+
+    def name(c):
+        got = cats.get(c, {}).get("name")
+        return str(c) if got is None else str(got)
+    dt = [(int(c), name(int(c))) for c in e["dt_cat"][sel].tolist()]
+    gt = [(int(c), name(int(c))) for c in e["gt_cat"][sel].tolist()]
+    wd = max([len(x) for _, x in dt] + [len("predicted")])
+    wg = max([len(x) for _, x in gt] + [len("ground truth")])
+    lines = [_title(ev, "confusion", iou_thr, bg_thr, " | rng={}".format(_range_name(ev, e, rng))),
+             " " + "id".rjust(8) + " " + "predicted".ljust(wd) + " " + "id".rjust(8) + " "
+             + "ground truth".ljust(wg) + "".join(c.rjust(9) for c in cols)]
+    for (d, dn), (g, gn), r in zip(dt, gt, e["counts"][sel].tolist()):
+        lines.append(" {:>8d} {} {:>8d} {}".format(d, dn.ljust(wd), g, gn.ljust(wg))
+                     + "".join("{:>9d}".format(v) for v in r))
+    return lines
 
 
 def now():

@@ -426,6 +426,9 @@ class DistRun:
     def impact_table(self, thr_index, bg_thr):
         return self.error_table(thr_index, bg_thr)         # raises
 
+    def confusion_table(self, thr_index, bg_thr):
+        return self.error_table(thr_index, bg_thr)         # raises
+
     def association_table(self, frame_thr, vis_rng, ann_vis):
         raise NotImplementedError("association() in a multi-GPU run")
 

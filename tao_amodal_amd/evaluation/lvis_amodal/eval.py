@@ -99,6 +99,7 @@ class LVISEval:
         self._cat_pos = None
         self._error_types = {}
         self._error_impact = {}
+        self._confusion = {}
 
     # ------------------------------------------------------------ stages
     def evaluate(self):
@@ -141,6 +142,7 @@ class LVISEval:
             self._run = GpuRun(flat, self.device, constants=constants)
         self._error_types = {}
         self._error_impact = {}
+        self._confusion = {}
         self._run.evaluate()
         view = CellView(self._run, flat.img_ids, 0, "image_id", "visibility_rng",
                         self.params.visibility_rng)
@@ -230,6 +232,9 @@ class LVISEval:
 
     def _rng_lbl(self):
         return list(self.params.visibility_rng_lbl)
+
+    def _cats(self):
+        return self.lvis_gt.cats
 
     def _dt_ids(self):
         return np.asarray(self.flat.dt_row)
@@ -327,6 +332,47 @@ class LVISEval:
         """error_impact() as a small text table: a line per visibility range,
         AP and the dAP of the eight fixes.  Returned, not printed."""
         return _core.impact_lines(self, iou_thr, bg_thr)
+
+    def confusion(self, iou_thr=0.5, bg_thr=0.1):
+        """Which category each CLS and BOTH detection of error_types(iou_thr,
+        bg_thr) was taken for, per visibility range: for every (range,
+        predicted category, ground-truth category) with at least one such
+        detection, how many CLS detections of the predicted category overlap a
+        ground truth of the other one best (`cls`), how many BOTH detections
+        (`both`), how many of the CLS ones lie on a ground truth that is missed
+        (`unheld`), and how many are the detection that error_impact()'s CLS fix
+        hands to that ground truth (`adopted`: per missed ground truth the
+        best-scored CLS detection linking it, of whatever predicted category).
+        Computed on the device on request (csrc/confusion.hip) from the links
+        of the breakdown, as a sparse table -- dense it would be K x K counters
+        per range, nearly all zero.  Callable after evaluate(), cached per
+        (iou_thr, bg_thr).  The exact rules are in include/tao_amodal_hip.h,
+        section "confusion".
+
+        Returns {"columns": ["cls", "both", "unheld", "adopted"], "rng_lbl":
+        params.visibility_rng_lbl, "rng": int32[n] the range index, "dt_cat",
+        "gt_cat": int64[n] category ids, "counts": int64[n, 4]}, sorted by
+        (range, place of dt_cat in params.cat_ids, place of gt_cat); with a
+        params.cat_ids subset only pairs of those categories.  Per (range,
+        predicted category) `cls` and `both` add up to error_types()'s CLS and
+        BOTH counts (with a subset: less the pairs left out); adopted <= unheld
+        <= cls.  Not available where error_types() is not."""
+        return _core.confusion(self, iou_thr, bg_thr)
+
+    def confusion_matrix(self, iou_thr=0.5, bg_thr=0.1, rng=0, column="cls"):
+        """One column of confusion() for the range of index `rng` as a dense
+        int64[K, K] in the order of params.cat_ids, rows the predicted
+        category; scattered on the host.  The diagonal is zero: a CLS link
+        names a ground truth of another category."""
+        return _core.confusion_matrix(self, iou_thr, bg_thr, rng, column)
+
+    def confusion_lines(self, iou_thr=0.5, bg_thr=0.1, rng=0, top=10):
+        """confusion() as a small text table: the `top` pairs of the range of
+        index `rng`, most `adopted` first, then most `cls`, then by (dt_cat,
+        gt_cat); both ids with the annotation file's category names (the id
+        again where a category has none) and the four counts.  Returned, not
+        printed."""
+        return _core.confusion_lines(self, iou_thr, bg_thr, rng, top)
 
     def _summarize(self, summary_type, iou_thr=None, visibility_rng="all",
                    freq_group_idx=None):

@@ -113,6 +113,7 @@ class TaoEval:
         self._cat_pos = None
         self._error_types = {}
         self._error_impact = {}
+        self._confusion = {}
         self._association = {}
         self._gt_columns = None
 
@@ -170,6 +171,7 @@ class TaoEval:
                                constants=constants)
         self._error_types = {}
         self._error_impact = {}
+        self._confusion = {}
         self._association = {}
         self._gt_columns = gt_cols      # the annotation rows the tables' frames name
         self._run.evaluate()
@@ -276,6 +278,9 @@ class TaoEval:
             return names[i] if i < len(names) else str(i)
         return [(lbl(P.area_rng_lbl, a), lbl(P.time_rng_lbl, t))
                 for a in range(len(P.area_rng)) for t in range(len(P.time_rng))]
+
+    def _cats(self):
+        return self.tao_gt.cats
 
     def _dt_ids(self):
         return np.asarray(self._run.flat.dt_id)
@@ -494,6 +499,42 @@ class TaoEval:
         """error_impact() as a small text table: a line per (area, time) range,
         AP and the dAP of the eight fixes.  Returned, not printed."""
         return _core.impact_lines(self, iou_thr, bg_thr)
+
+    def confusion(self, iou_thr=0.5, bg_thr=0.1):
+        """Which category each CLS and BOTH detection track of
+        error_types(iou_thr, bg_thr) was taken for, per (area, time) range:
+        LVISEval.confusion() rule for rule on tracks.  For every (range,
+        predicted category, ground-truth category) with at least one such
+        track: `cls`, `both`, `unheld` (CLS tracks on a ground-truth track that
+        is missed) and `adopted` (the track error_impact()'s CLS fix hands to
+        that ground-truth track).  Computed on the device on request
+        (csrc/confusion.hip, the kernels of the image level) from the links of
+        the track-level breakdown, as a sparse table.  Callable after
+        evaluate(), cached per (iou_thr, bg_thr).  The exact rules are in
+        include/tao_amodal_hip.h, section "confusion".
+
+        Returns {"columns": ["cls", "both", "unheld", "adopted"], "rng_lbl":
+        the (area label, time label) of every range, "rng": int32[n] the range
+        index (area x durations flattened, as in error_types()), "dt_cat",
+        "gt_cat": int64[n] category ids, "counts": int64[n, 4]}, sorted by
+        (range, place of dt_cat in params.cat_ids, place of gt_cat); with a
+        params.cat_ids subset only pairs of those categories.  Not available
+        where error_types() is not."""
+        return _core.confusion(self, iou_thr, bg_thr)
+
+    def confusion_matrix(self, iou_thr=0.5, bg_thr=0.1, rng=0, column="cls"):
+        """One column of confusion() for the range of index `rng` as a dense
+        int64[K, K] in the order of params.cat_ids, rows the predicted
+        category; scattered on the host.  The diagonal is zero."""
+        return _core.confusion_matrix(self, iou_thr, bg_thr, rng, column)
+
+    def confusion_lines(self, iou_thr=0.5, bg_thr=0.1, rng=0, top=10):
+        """confusion() as a small text table: the `top` pairs of the range of
+        index `rng`, most `adopted` first, then most `cls`, then by (dt_cat,
+        gt_cat); both ids with the annotation file's category names (the id
+        again where a category has none) and the four counts.  Returned, not
+        printed."""
+        return _core.confusion_lines(self, iou_thr, bg_thr, rng, top)
 
     def _summarize(self, summary_type, iou_thr=None, area_rng="all",
                    time_rng="all", freq_group_idx=None):

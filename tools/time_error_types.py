@@ -4,7 +4,7 @@ taoamd_track_error_types) on the synthetic configurations of bench.py, with HIP
 events:
 
     python tools/time_error_types.py [--level image|track] [--config 3s] [--reps 20] [--warmup 3]
-                                     [--impact] [--association]
+                                     [--impact] [--association] [--confusion]
 
 Times, on the image level's tables of that configuration, each alone on an idle
 stream: the fused match as a benchmark step runs it (the yardstick), the
@@ -23,7 +23,11 @@ nine variants (engine.stage_error_impact / engine.stage_track_error_impact),
 the kernels of both, and AP and dAP over all categories in range 0.  --level
 track --association times, instead of the breakdown, the per-frame followers
 (engine.stage_track_association) and the plan-less taoamd_track_iou over the
-same cells in the same process.  Prints one JSON line."""
+same cells in the same process.  --confusion (both levels) adds the confusion
+table: the level's links pass, taoamd_confusion_count and taoamd_confusion_fill,
+each alone between HIP events in the same process, the whole stage with its
+read of the entry count, the kernels, and the number of entries beside the
+cells of the dense table.  Prints one JSON line."""
 import argparse
 import json
 import os
@@ -163,7 +167,54 @@ def track_level(a, gt, dt, dev, V):
         res["fixes"] = list(_lib.ERROR_FIXES)
         res["ap_range0"] = [round(v, 6) for v in ap_]
         res["dap_range0"] = [round(v - ap_[0], 6) for v in ap_[1:]]
+    if a.confusion:
+        confusion(a, res, dp, ws, timed)
     print(json.dumps(res))
+
+
+def confusion(a, res, dp, ws, timed):
+    """--confusion: the links pass of the level, then taoamd_confusion_count and
+    taoamd_confusion_fill on its tables, each alone; engine.stage_confusion as a
+    whole (links, count, the read of the entry count, fill)."""
+    import torch
+    from tao_amodal_amd import _lib, engine
+    lib = _lib.load()
+    # the first call allocates the link tables, the workspace and the entries
+    engine.stage_confusion(dp, ws, 0, a.bg_thr)
+    torch.cuda.synchronize()
+    t, stream = dp.t, torch.cuda.current_stream().cuda_stream
+    tables = (dp.n_dt, dp.n_gt, dp.n_cat, dp.n_rng, t["cat_off"].data_ptr(),
+              t["dt_score"].data_ptr(), t["dt_cat"].data_ptr(), ws.err_dt_type.data_ptr(),
+              ws.err_link_other.data_ptr(), t["gt_cat"].data_ptr(), ws.err_held.data_ptr(),
+              ws.conf_off.data_ptr())
+
+    def count():
+        _lib.check(lib.taoamd_confusion_count(*tables, ws.conf_ws.data_ptr(), ws.conf_bytes,
+                                              stream), "taoamd_confusion_count")
+
+    def fill():
+        _lib.check(lib.taoamd_confusion_fill(
+            *tables, ws.conf_n, ws.conf_gt_cat.data_ptr(), ws.conf_counts.data_ptr(),
+            ws.conf_ws.data_ptr(), ws.conf_bytes, stream), "taoamd_confusion_fill")
+    res["confusion_links_pass"] = timed(
+        lambda: engine._error_pass(dp, ws, 0, a.bg_thr, True, True, dp.kind))
+    res["confusion_count"] = timed(count)
+    res["confusion_fill"] = timed(fill)
+    res["confusion_stage"] = timed(lambda: engine.stage_confusion(dp, ws, 0, a.bg_thr))
+    _lib.kernel_timing(True)
+    for _ in range(a.reps):
+        count()
+        fill()
+    res["confusion_kernels_ms"] = {k: round(ms / n, 4)
+                                   for k, (ms, n) in _lib.kernel_timings().items()}
+    _lib.kernel_timing(False)
+    res["confusion_entries"] = int(ws.conf_n)
+    res["confusion_dense_cells"] = dp.n_rng * dp.n_cat * dp.n_cat
+    res["confusion_workspace_bytes"] = int(ws.conf_bytes)
+    res["confusion_entry_bytes"] = 20 * int(ws.conf_n) + 8 * int(ws.conf_off.numel())
+    off0 = int(ws.conf_off[dp.n_cat].item())
+    res["confusion_columns"] = list(_lib.CONFUSION_COLUMNS)
+    res["confusion_counts_range0"] = ws.conf_counts[:off0].sum(0).tolist() if off0 else [0] * 4
 
 
 def association(a, res, gt, fl, dp, ws, timed):
@@ -228,6 +279,7 @@ def main():
     ap.add_argument("--bg-thr", type=float, default=0.1)
     ap.add_argument("--impact", action="store_true")
     ap.add_argument("--association", action="store_true")
+    ap.add_argument("--confusion", action="store_true")
     a = ap.parse_args()
     if a.association and a.level != "track":
         ap.error("--association is the track level's: --level track")
@@ -296,6 +348,8 @@ def main():
         res["fixes"] = list(_lib.ERROR_FIXES)
         res["ap_range0"] = [round(v, 6) for v in ap_]
         res["dap_range0"] = [round(v - ap_[0], 6) for v in ap_[1:]]
+    if a.confusion:
+        confusion(a, res, dp, ws, timed)
     print(json.dumps(res))
 
 
