@@ -1398,6 +1398,87 @@ int taoamd_track_association(int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_
                              int64_t *vis_counts, int32_t *best, double *best_iou,
                              void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- track-level occlusion episodes: is the follower kept (csrc/track_occlusion.hip)
+ * Whether the detection track that follows a ground-truth track HOLDS it while
+ * the object is hidden: what the association's per-window coverage, which counts
+ * every frame on its own, cannot say.  The reference has no counterpart; the
+ * definition is this library's.  The pass reads the per-frame followers of
+ * taoamd_track_association (its `best`) and the frames' visibility, nothing else.
+ *
+ * Ground-truth track g has the frames k = 0 .. L - 1 of its OWN frame list
+ * (neighbours are list neighbours, not timeline positions, as for `fragments`),
+ * each with a visibility vis_k and a follower best_k: the association's in-cell
+ * index, or -1.
+ *   occ_k     lo <= vis_k <= hi: the window is closed; a NaN visibility is not
+ *             occluded.
+ *   EPISODE   a maximal run a .. b of occluded frames; its length n = b - a + 1.
+ *   entry     best_{a-1}, or -1 if a == 0: no look-back beyond that one frame.
+ *   covered   the frames of a .. b with best_k >= 0.
+ *   held      the frames of a .. b with best_k == entry; 0 when entry < 0.
+ *   after, gap  from the frames b + 1 .. min(b + recover, L - 1), whatever their
+ *             visibility: with frame b + r the first covered one among them,
+ *             after = best_{b+r} and gap = r - 1; if none is covered, after = -1
+ *             and gap = 0.  recover is an integer in [1, 64].
+ *   outcome   one value, the first rule that applies:
+ *               0 START       a == 0
+ *               1 UNFOLLOWED  entry < 0
+ *               2 END         b == L - 1
+ *               3 KEPT        after == entry
+ *               4 SWITCHED    after >= 0 and after != entry
+ *               5 LOST        after < 0
+ *             For START, UNFOLLOWED and END, after = -1 and gap = 0.
+ *   bucket    len_edges int32[n_len] (HOST memory), n_len in [1, 8], len_edges[0]
+ *             == 1, strictly ascending: bucket j holds len_edges[j] <= n <
+ *             len_edges[j + 1], the last bucket is open.
+ * Per episode, episodes int32[n_ep][9] = {ground-truth row, a, n, outcome, entry,
+ * after, gap, covered, held}, rows ascending by (ground-truth row, a).
+ * Per ground-truth track, gt_occ int32[n_gt][4] = {episodes, occluded frames,
+ * kept, switched + lost}.
+ * Per (category, bucket), counts int64[n_cat][n_len][11] over the tracks whose
+ * gt_flags lacks TAOAMD_GT_IGNORE (and whose category lies in [0, n_cat)):
+ * {episodes, frames, covered, held, start, unfollowed, end, kept, switched, lost,
+ * gap}, the sums of n, covered, held and gap and the number of episodes of each
+ * outcome.  Ignored tracks appear in episodes and gt_occ, and in no count.
+ * Example, window [0, 0.1]: best = [0,0,-1,0,0,1,1,-1,-1,0], vis = [1,.1,0,1,.05,
+ * .05,1,0,1,1] has three episodes (a, n, outcome, entry, after, gap, covered,
+ * held): (1,2,KEPT,0,0,0,1,1), (4,2,SWITCHED,0,1,0,2,1) and (7,1,LOST,1,-1,0,0,0)
+ * at recover = 1, (7,1,SWITCHED,1,0,1,0,0) at recover >= 2.
+ *
+ * Two calls, so that the caller sizes the records between them:
+ * taoamd_track_occlusion_count fills gt_occ, counts and the whole of ep_off
+ * int64[n_gt + 1], the exclusive prefix sum of the tracks' episode counts
+ * (ep_off[n_gt] = n_ep); taoamd_track_occlusion_fill, with the same tables,
+ * stores the episodes of the tracks with ep_off[g + 1] <= cap and nothing at or
+ * beyond record `cap`.  Every output is an integer and every record has one
+ * place; the counts are integer adds, whose sum does not depend on the order of
+ * arrival; no float is ever added: the result is exact and the same from run to
+ * run.
+ * TAOAMD_ERR_ARG: recover outside [1, 64], n_len outside [1, 8], edges that do
+ * not start at 1 or do not strictly ascend, vis_lo > vis_hi or either a NaN, a
+ * size below 0, n_cat <= 0, cap < 0, a missing table; TAOAMD_ERR_WORKSPACE:
+ * fewer bytes than taoamd_track_occlusion_workspace(n_gt, n_gt_frames, n_len)
+ * (the episodes of every track, 4 bytes each; any base address, contents need
+ * not be initialised; the size function answers 0 to sizes it refuses).  Both
+ * are answered before the first device call.  Rows and frames named by the CSR
+ * table that lie outside the tables are skipped, never dereferenced. */
+#define TAOAMD_TRACK_OCCLUSION_LEN 8        /* length buckets, at most */
+#define TAOAMD_TRACK_OCCLUSION_RECOVER 64   /* recover, at most: a chunk of frames */
+size_t taoamd_track_occlusion_workspace(int64_t n_gt, int64_t n_gt_frames, int32_t n_len);
+int taoamd_track_occlusion_count(int64_t n_gt, int64_t n_gt_frames, int32_t n_cat,
+                                 int32_t n_len, int32_t recover, double vis_lo, double vis_hi,
+                                 const int32_t *len_edges, const int32_t *gt_cat,
+                                 const uint8_t *gt_flags, const int32_t *gt_frame_off,
+                                 const double *gt_frame_vis, const int32_t *best,
+                                 int32_t *gt_occ, int64_t *ep_off, int64_t *counts,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+int taoamd_track_occlusion_fill(int64_t n_gt, int64_t n_gt_frames, int32_t n_cat,
+                                int32_t n_len, int32_t recover, double vis_lo, double vis_hi,
+                                const int32_t *len_edges, const int32_t *gt_cat,
+                                const uint8_t *gt_flags, const int32_t *gt_frame_off,
+                                const double *gt_frame_vis, const int32_t *best,
+                                const int64_t *ep_off, int64_t cap, int32_t *episodes,
+                                void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- multi-GPU result exchange (category-partitioned evaluation) -------------------
  * No reference counterpart (the reference is single-process); these carry the
  * tables of taoamd_accumulate_compact between ranks and end in the layout of

@@ -33,6 +33,13 @@ ASSOC_TRACK_COLUMNS = ("frames", "covered", "ids", "switches", "fragments", "pri
 ASSOC_CAT_COLUMNS = ("tracks", "frames", "covered", "ids", "switches", "fragments",
                      "mostly_tracked", "mostly_lost")
 ASSOC_VIS_COLUMNS = ("frames", "covered", "primary")
+TRACK_OCCLUSION_LEN = 8
+TRACK_OCCLUSION_RECOVER = 64
+OCC_OUTCOMES = ("START", "UNFOLLOWED", "END", "KEPT", "SWITCHED", "LOST")
+OCC_EPISODE_COLUMNS = ("gt", "a", "n", "outcome", "entry", "after", "gap", "covered", "held")
+OCC_TRACK_COLUMNS = ("episodes", "frames", "kept", "switched_lost")
+OCC_COUNT_COLUMNS = ("episodes", "frames", "covered", "held", "start", "unfollowed", "end",
+                     "kept", "switched", "lost", "gap")
 
 _vp, _i64, _i32, _sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
 
@@ -231,6 +238,12 @@ SIGNATURES = {
     "taoamd_track_association_workspace":(_sz, [_i64, _i64, _i64]),
     "taoamd_track_association": (C.c_int, [_i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32,
                                            C.c_double] + [_vp] * 20 + [_sz, _vp]),
+    "taoamd_track_occlusion_workspace": (_sz, [_i64, _i64, _i32]),
+    "taoamd_track_occlusion_count": (C.c_int, [_i64, _i64, _i32, _i32, _i32, C.c_double,
+                                               C.c_double] + [_vp] * 10 + [_sz, _vp]),
+    "taoamd_track_occlusion_fill": (C.c_int, [_i64, _i64, _i32, _i32, _i32, C.c_double,
+                                              C.c_double] + [_vp] * 7 + [_i64, _vp, _vp, _sz,
+                                                                         _vp]),
 }
 
 _lib = None

@@ -581,7 +581,8 @@ class Workspace:
                 self.ious_out = torch.empty(max(dp.n_iou, 1),
                                             dtype=torch.float64, device=dev)
         # the on-request analyses (stage_scores, the error breakdown, its impact
-        # and its confusion, stage_track_association): allocated by their first call
+        # and its confusion, stage_track_association, stage_track_occlusion): allocated
+        # by their first call
         self.scores = None
         self.err_match_gt = self.err_dt_counts = self.err_gt_counts = self.err_dt_type = None
         self.err_link_same = self.err_link_other = self.err_held = None
@@ -589,6 +590,9 @@ class Workspace:
         self.conf_ws = self.conf_off = self.conf_gt_cat = self.conf_counts = None
         self.conf_n = 0                   # entries of the last stage_confusion
         self.assoc_gt = self.assoc_vis_counts = None
+        self.assoc_frame_thr = None       # the frame_thr ws.assoc_best holds the followers of
+        self.occ_ws = self.occ_gt = self.occ_off = self.occ_counts = self.occ_episodes = None
+        self.occ_n = None                 # episodes of the last stage_track_occlusion that read them
         self.pairs_counted = False        # stage_track_iou counted the pairs' common frames
 
 
@@ -1398,6 +1402,64 @@ def stage_track_association(dp, ws, frame_thr, vis_rng):
         _ptr(ws.assoc_ws), ws.assoc_bytes, _stream()), "taoamd_track_association")
     # (the windows' upload is read by the kernels of this stream: alive until they ran)
     ws.assoc_vis_rng = rng_t
+    ws.assoc_frame_thr = float(frame_thr)
+
+
+def stage_track_occlusion(dp, ws, frame_thr, vis_lo, vis_hi, recover, len_edges, episodes=False):
+    """Is a ground-truth track's follower kept through occlusion
+    (taoamd_track_occlusion_count, taoamd_track_occlusion_fill; the definition is
+    in include/tao_amodal_hip.h): the runs of frames with vis_lo <= visibility <=
+    vis_hi, over the followers ws.assoc_best of stage_track_association at
+    `frame_thr` -- reused where the workspace holds them for that threshold, else
+    that stage runs first, without windows.  ws.occ_gt int32[n_gt, 4], ws.occ_off
+    int64[n_gt + 1] (the tracks' first episode), ws.occ_counts int64[n_cat, n_len,
+    11]; with episodes=True also ws.occ_episodes int32[>= n_ep, 9] and ws.occ_n =
+    n_ep, read between the two calls: one synchronisation of the current stream
+    (ws.occ_n is None otherwise).  `recover` in [1, 64], `len_edges` up to 8
+    ascending lengths that start at 1.  Needs set_frame_visibility.  On request
+    only.  Buffers are allocated on the first call and kept with the workspace:
+    4 bytes per ground-truth track of workspace, 24 per track and 88 per
+    (category, bucket) of results, 36 per episode, regrown where a call finds more."""
+    if dp.kind != "tao" or dp.mask_iou:
+        raise _lib.TaoAmdError("the track occlusions are the track level's, on boxes")
+    lib, t, dev, s = _lib.load(), dp.t, dp.device, _stream()
+    if t.get("gt_frame_vis") is None:
+        raise _lib.TaoAmdError("the occlusion episodes need the frames' visibility "
+                               "(engine.set_frame_visibility)")
+    edges = np.ascontiguousarray(len_edges, dtype=np.int32).reshape(-1)
+    n_len = len(edges)
+    if not 1 <= n_len <= _lib.TRACK_OCCLUSION_LEN:
+        raise _lib.TaoAmdError("%d length buckets; the kernels take 1 to %d"
+                               % (n_len, _lib.TRACK_OCCLUSION_LEN))
+    frame_thr = float(frame_thr)
+    if ws.assoc_gt is None or ws.assoc_frame_thr != frame_thr:
+        stage_track_association(dp, ws, frame_thr, [])
+    n_gf = int(t["gt_frame_pos"].numel())
+    if ws.occ_ws is None:
+        ws.occ_bytes = lib.taoamd_track_occlusion_workspace(dp.n_gt, n_gf, n_len)
+        ws.occ_ws = torch.empty(max(int(ws.occ_bytes), 256), dtype=torch.uint8, device=dev)
+        ws.occ_gt = torch.empty((max(dp.n_gt, 1), len(_lib.OCC_TRACK_COLUMNS)),
+                                dtype=torch.int32, device=dev)
+        ws.occ_off = torch.empty(dp.n_gt + 1, dtype=torch.int64, device=dev)
+    if ws.occ_counts is None or ws.occ_counts.shape[1] != n_len:
+        ws.occ_counts = torch.empty((dp.n_cat, n_len, len(_lib.OCC_COUNT_COLUMNS)),
+                                    dtype=torch.int64, device=dev)
+    tables = (dp.n_gt, n_gf, dp.n_cat, n_len, int(recover), float(vis_lo), float(vis_hi),
+              edges.ctypes.data, _ptr(t["gt_cat"]), _ptr(t["gt_flags"]),
+              _ptr(t["gt_frame_off"]), _ptr(t["gt_frame_vis"]), _ptr(ws.assoc_best))
+    _lib.check(lib.taoamd_track_occlusion_count(
+        *tables, _ptr(ws.occ_gt), _ptr(ws.occ_off), _ptr(ws.occ_counts), _ptr(ws.occ_ws),
+        ws.occ_bytes, s), "taoamd_track_occlusion_count")
+    ws.occ_n = None
+    if not episodes:
+        return
+    ws.occ_n = int(ws.occ_off[-1].item())           # (synchronises)
+    if ws.occ_episodes is None or ws.occ_episodes.shape[0] < ws.occ_n:
+        ws.occ_episodes = torch.empty((max(ws.occ_n, 1), len(_lib.OCC_EPISODE_COLUMNS)),
+                                      dtype=torch.int32, device=dev)
+    _lib.check(lib.taoamd_track_occlusion_fill(
+        *tables, _ptr(ws.occ_off), ws.occ_n, _ptr(ws.occ_episodes), _ptr(ws.occ_ws),
+        ws.occ_bytes, s), "taoamd_track_occlusion_fill")
 
 
 def stage_track_iou_guarded(dp, ws):

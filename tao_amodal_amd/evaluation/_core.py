@@ -368,6 +368,24 @@ class GpuRun:
             rng, dt_cat, gt_cat, counts = rng[keep], dt_cat[keep], gt_cat[keep], counts[keep]
         return rng.astype(np.int32), dt_cat, gt_cat, counts, K
 
+    def _followers_at(self, what, ann_vis):
+        """What association_table() and occlusion_table() share: the refusals, in
+        the name `what` of the caller's method, and the frames' own visibility,
+        gathered from the annotations' column and uploaded on the first call."""
+        if self.flat.kind != "tao":
+            raise NotImplementedError(what + " is the track level's")
+        if self.dp.mask_iou:
+            raise NotImplementedError(what + " with iou_type='segm': boxes only")
+        if not self.flat.get("use_cats", True):
+            raise NotImplementedError(
+                what + " with use_cats = 0: the candidates of a ground-truth track "
+                "are the detection tracks of its category")
+        if self.dp.t.get("gt_frame_vis") is None:
+            with timed("upload+plan"):
+                rows = self.flat.gt_frame_box.index
+                self.engine.set_frame_visibility(
+                    self.dp, np.asarray(ann_vis, dtype=np.float64)[rows])
+
     def association_table(self, frame_thr, vis_rng, ann_vis):
         """The per-frame followers of the ground-truth tracks
         (engine.stage_track_association; the definition is in
@@ -378,19 +396,8 @@ class GpuRun:
         the `visibility` column of the ground-truth annotations the tables were
         built from; the frames' own is gathered and uploaded on the first call.
         Reads the track tables alone: no constants, no match, no IoU matrix."""
-        if self.flat.kind != "tao":
-            raise NotImplementedError("association() is the track level's")
-        if self.dp.mask_iou:
-            raise NotImplementedError("association() with iou_type='segm': boxes only")
-        if not self.flat.get("use_cats", True):
-            raise NotImplementedError(
-                "association() with use_cats = 0: the candidates of a ground-truth track "
-                "are the detection tracks of its category")
+        self._followers_at("association()", ann_vis)
         e, dp, ws = self.engine, self.dp, self.ws
-        if dp.t.get("gt_frame_vis") is None:
-            with timed("upload+plan"):
-                rows = self.flat.gt_frame_box.index
-                e.set_frame_visibility(dp, np.asarray(ann_vis, dtype=np.float64)[rows])
         with timed("kernels"):
             e.stage_track_association(dp, ws, frame_thr, vis_rng)
             self.torch.cuda.synchronize(self.device)
@@ -403,6 +410,25 @@ class GpuRun:
                     np.zeros((0, dp.n_cat, 3), dtype=np.int64),
                     "best": ws.assoc_best[:n_gf].cpu().numpy(),
                     "best_iou": ws.assoc_best_iou[:n_gf].cpu().numpy()}
+
+    def occlusion_table(self, frame_thr, vis_rng, recover, len_edges, ann_vis):
+        """Whether the follower of a ground-truth track is kept through occlusion
+        (engine.stage_track_occlusion; the definition is in
+        include/tao_amodal_hip.h): the runs of frames whose visibility lies in
+        the closed window `vis_rng` = (lo, hi), over the followers at `frame_thr`:
+        dict(gt_occ int32[n_gt, 4], counts int64[K, n_len, 11], episodes
+        int32[n_ep, 9] with entry and after as in-cell indices).  `ann_vis` as for
+        association_table(); refuses what it refuses."""
+        self._followers_at("occlusions()", ann_vis)
+        dp, ws = self.dp, self.ws
+        with timed("kernels"):
+            self.engine.stage_track_occlusion(dp, ws, frame_thr, vis_rng[0], vis_rng[1], recover,
+                                              len_edges, episodes=True)
+            self.torch.cuda.synchronize(self.device)
+        with timed("download"):
+            return {"gt_occ": ws.occ_gt[:dp.n_gt].cpu().numpy(),
+                    "counts": ws.occ_counts.cpu().numpy(),
+                    "episodes": ws.occ_episodes[:ws.occ_n].cpu().numpy()}
 
     def pointer_tables(self):
         """What eval['dt_pointers'] is read from: the detections' ids and
@@ -801,6 +827,27 @@ def confusion_lines(ev, iou_thr, bg_thr, rng, top):
     for (d, dn), (g, gn), r in zip(dt, gt, e["counts"][sel].tolist()):
         lines.append(" {:>8d} {} {:>8d} {}".format(d, dn.ljust(wd), g, gn.ljust(wg))
                      + "".join("{:>9d}".format(v) for v in r))
+    return lines
+
+
+def occlusion_lines(e):
+    """TaoEval.occlusions()'s result `e` as a small text table, the totals over
+    the categories: a line per length bucket."""
+    cols = e["columns"]["counts"]
+
+    def pct(n, d):
+        return "{:>10.2f}".format(100.0 * float(n) / float(d)) if d else "{:>10s}".format("-")
+    w = max([len(x) for x in e["len_lbl"]] + [len("length")])
+    lines = [" track occlusions @[ frame IoU={:0.2f} | vis=[{:g}, {:g}] | recover={} ]".format(
+                 e["frame_thr"], e["vis_rng"][0], e["vis_rng"][1], e["recover"]),
+             " " + "length".ljust(w) + "".join(
+                 c.rjust(10) for c in ("episodes", "kept%", "switched%", "lost%", "held%"))]
+    for name, v in zip(e["len_lbl"], e["counts"].sum(0).tolist()):
+        c = dict(zip(cols, v))
+        out = c["kept"] + c["switched"] + c["lost"]
+        lines.append(" " + name.ljust(w) + "{:>10d}".format(c["episodes"])
+                     + pct(c["kept"], out) + pct(c["switched"], out) + pct(c["lost"], out)
+                     + pct(c["held"], c["frames"]))
     return lines
 
 

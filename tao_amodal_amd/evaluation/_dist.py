@@ -432,6 +432,9 @@ class DistRun:
     def association_table(self, frame_thr, vis_rng, ann_vis):
         raise NotImplementedError("association() in a multi-GPU run")
 
+    def occlusion_table(self, frame_thr, vis_rng, recover, len_edges, ann_vis):
+        raise NotImplementedError("occlusions() in a multi-GPU run")
+
     def pointer_tables(self):
         if self._pointers is None:
             raise NotImplementedError(

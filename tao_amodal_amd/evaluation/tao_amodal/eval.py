@@ -115,6 +115,7 @@ class TaoEval:
         self._error_impact = {}
         self._confusion = {}
         self._association = {}
+        self._occlusions = {}
         self._gt_columns = None
 
     # ------------------------------------------------------------ stages
@@ -173,6 +174,7 @@ class TaoEval:
         self._error_impact = {}
         self._confusion = {}
         self._association = {}
+        self._occlusions = {}
         self._gt_columns = gt_cols      # the annotation rows the tables' frames name
         self._run.evaluate()
         P = self.params
@@ -455,16 +457,8 @@ class TaoEval:
             tracks[:, 5] = np.where(prim >= 0, dt_id[np.maximum(prim, 0)], -1) if len(dt_id) \
                 else -1
             # frames: the image at (video, timeline position), the follower's id
-            foff = np.asarray(flat.gt_frame_off, dtype=np.int64)
-            g_of = np.repeat(np.arange(len(foff) - 1), np.diff(foff))
-            cell = np.asarray(flat.gt_cell, dtype=np.int64)[g_of]
-            vid = np.asarray(flat.cell_unit, dtype=np.int64)[cell]
-            img = np.asarray(flat.tl_image_id)[np.asarray(flat.tl_vid_start, dtype=np.int64)[vid]
-                                               + np.asarray(flat.gt_frame_pos, dtype=np.int64)]
-            best = t["best"].astype(np.int64)
-            row = np.asarray(flat.cell_dt_off, dtype=np.int64)[cell] + best
-            best_id = np.where(best >= 0, dt_id[np.where(best >= 0, row, 0)], -1) \
-                if len(dt_id) else np.full(len(best), -1, dtype=np.int64)
+            foff, cell, img = self._gt_frame_tables()
+            best_id = self._follower_ids(cell, t["best"])
             hit = {"columns": {"tracks": list(ASSOC_TRACK_COLUMNS),
                                "cat_counts": list(ASSOC_CAT_COLUMNS),
                                "vis_counts": list(ASSOC_VIS_COLUMNS)},
@@ -494,6 +488,123 @@ class TaoEval:
             lines.append(" " + name.ljust(w) + "{:>11d}".format(int(v[0]))
                          + pct(v[1], v[0]) + pct(v[2], v[0]))
         return lines
+
+    def _gt_frame_tables(self):
+        """(frame_off int64[n_gt + 1], the cell and the image id of every
+        ground-truth frame): the image at (video, timeline position)."""
+        flat = self._run.flat
+        foff = np.asarray(flat.gt_frame_off, dtype=np.int64)
+        g_of = np.repeat(np.arange(len(foff) - 1), np.diff(foff))
+        cell = np.asarray(flat.gt_cell, dtype=np.int64)[g_of]
+        vid = np.asarray(flat.cell_unit, dtype=np.int64)[cell]
+        img = np.asarray(flat.tl_image_id)[np.asarray(flat.tl_vid_start, dtype=np.int64)[vid]
+                                           + np.asarray(flat.gt_frame_pos, dtype=np.int64)]
+        return foff, cell, img
+
+    def _follower_ids(self, cell, best):
+        """In-cell followers `best` of the cells `cell` as detection track ids, -1
+        for none."""
+        flat = self._run.flat
+        dt_id = np.asarray(flat.dt_id, dtype=np.int64)
+        best = np.asarray(best).astype(np.int64)
+        if not len(dt_id):
+            return np.full(len(best), -1, dtype=np.int64)
+        row = np.asarray(flat.cell_dt_off, dtype=np.int64)[cell] + best
+        return np.where(best >= 0, dt_id[np.where(best >= 0, row, 0)], -1)
+
+    def occlusions(self, frame_thr=0.5, vis_rng=(0.0, 0.1), recover=3, len_edges=(1, 3, 6, 11),
+                   per_track=False, per_episode=False):
+        """Whether a ground-truth track's follower is KEPT while the object is
+        hidden -- what association()'s coverage per visibility window, which
+        counts every frame on its own, cannot say: a tracker that keeps the id
+        across every occlusion and one that drops the object and re-acquires it
+        under a new id have the same coverage.  No counterpart in the reference.
+        Callable after evaluate(), computed on the device on request
+        (csrc/track_occlusion.hip) from association(frame_thr)'s per-frame
+        followers, cached per argument set.
+
+        A frame of a ground-truth track is occluded when its visibility lies in
+        the closed window `vis_rng` = (lo, hi); a NaN visibility is not.  An
+        episode is a maximal run of occluded frames of the track's own frame
+        list, `n` frames from frame `a` on.  `entry` is the follower of the frame
+        before the run, `covered` the run's frames with a follower, `held` those
+        followed by `entry`; `after` is the follower of the first covered frame
+        among the `recover` (1 to 64) frames behind the run and `gap` the
+        uncovered frames before it.  One outcome each, the first that applies:
+        START (the run begins the track), UNFOLLOWED (nobody follows on entry),
+        END (the run ends the track), KEPT (after == entry), SWITCHED (another
+        track follows), LOST (none within `recover` frames).  Episodes are
+        grouped by length: `len_edges`, up to 8 ascending lengths that start at
+        1, bucket j holds len_edges[j] <= n < len_edges[j + 1], the last is open.
+        The exact rules are in include/tao_amodal_hip.h, section "track-level
+        occlusion episodes".
+
+        Returns {"columns": {"counts": ..., "tracks": ..., "episodes": ...,
+        "outcomes": ...} (the column and outcome names), "counts": int64[K, n_len,
+        11] over the ground-truth tracks that are not ignored = episodes, frames,
+        covered, held, start, unfollowed, end, kept, switched, lost, gap, with
+        the category axis in the order of params.cat_ids, "len_edges", "len_lbl",
+        "vis_rng", "frame_thr", "recover"}; with per_track=True "tracks":
+        (ground-truth track ids, int64[n_gt, 4] = episodes, occluded frames,
+        kept, switched + lost), ignored tracks included; with per_episode=True
+        "episodes": (ground-truth track ids, first image ids, last image ids,
+        int64[n_ep, 9] = ground-truth row, a, n, outcome, entry, after, gap,
+        covered, held with entry and after as detection track ids, -1 for none),
+        by ascending (row, a).  Not available: iou_type="segm", use_cats = 0,
+        multi-GPU runs."""
+        if self._run is None:
+            raise RuntimeError("Please run evaluate() first.")
+        frame_thr = float(frame_thr)
+        if not 0 < frame_thr <= 1:
+            raise ValueError("frame_thr: {} is not in (0, 1]".format(frame_thr))
+        rng = np.asarray(vis_rng, dtype=np.float64).reshape(-1)
+        if len(rng) != 2 or not rng[0] <= rng[1]:
+            raise ValueError("vis_rng: {} is not one window lo <= hi".format(vis_rng))
+        if int(recover) != recover or not 1 <= recover <= 64:
+            raise ValueError("recover: {} is not an integer in [1, 64]".format(recover))
+        edges = [int(x) for x in np.asarray(len_edges).reshape(-1).tolist()]
+        if not 1 <= len(edges) <= 8 or edges[0] != 1 \
+                or any(a >= b for a, b in zip(edges, edges[1:])) \
+                or edges != np.asarray(len_edges).reshape(-1).tolist():
+            raise ValueError("len_edges: {} is not 1 to 8 ascending integers that start at 1"
+                             .format(len_edges))
+        key = (frame_thr, float(rng[0]), float(rng[1]), int(recover), tuple(edges))
+        hit = self._occlusions.get(key)
+        if hit is None:
+            from ..._lib import (OCC_COUNT_COLUMNS, OCC_EPISODE_COLUMNS, OCC_OUTCOMES,
+                                 OCC_TRACK_COLUMNS)
+            t = self._run.occlusion_table(frame_thr, key[1:3], key[3], edges,
+                                          self._gt_columns.ann_vis)
+            counts = t["counts"]
+            if self._cat_pos is not None:
+                counts = np.ascontiguousarray(counts[self._cat_pos])
+            gt_id = np.asarray(self._run.flat.gt_id)
+            foff, cell, img = self._gt_frame_tables()
+            ep = t["episodes"].astype(np.int64)
+            first = foff[ep[:, 0]] + ep[:, 1]
+            for col in (4, 5):
+                ep[:, col] = self._follower_ids(cell[first], ep[:, col])
+            lbl = ["{}-{}".format(a, b - 1) if b - 1 > a else str(a)
+                   for a, b in zip(edges, edges[1:])] + ["{}+".format(edges[-1])]
+            hit = {"columns": {"counts": list(OCC_COUNT_COLUMNS), "tracks": list(OCC_TRACK_COLUMNS),
+                               "episodes": list(OCC_EPISODE_COLUMNS),
+                               "outcomes": list(OCC_OUTCOMES)},
+                   "counts": counts, "len_edges": edges, "len_lbl": lbl,
+                   "vis_rng": [key[1], key[2]], "frame_thr": frame_thr, "recover": key[3],
+                   "tracks": (gt_id, t["gt_occ"].astype(np.int64)),
+                   "episodes": (gt_id[ep[:, 0]], np.asarray(img)[first],
+                                np.asarray(img)[first + ep[:, 2] - 1], ep)}
+            self._occlusions[key] = hit
+        drop = [k for k, on in (("tracks", per_track), ("episodes", per_episode)) if not on]
+        return {k: v for k, v in hit.items() if k not in drop}
+
+    def occlusion_lines(self, frame_thr=0.5, vis_rng=(0.0, 0.1), recover=3,
+                        len_edges=(1, 3, 6, 11)):
+        """occlusions() as a small text table, the totals over the categories: a
+        line per length bucket with its episodes, the kept / switched / lost
+        shares of the episodes that have one of these three outcomes, and held /
+        frames, in per cent.  Returned, not printed."""
+        return _core.occlusion_lines(self.occlusions(frame_thr, vis_rng, recover, len_edges))
 
     def impact_lines(self, iou_thr=0.5, bg_thr=0.1):
         """error_impact() as a small text table: a line per (area, time) range,

@@ -4,7 +4,7 @@ taoamd_track_error_types) on the synthetic configurations of bench.py, with HIP
 events:
 
     python tools/time_error_types.py [--level image|track] [--config 3s] [--reps 20] [--warmup 3]
-                                     [--impact] [--association] [--confusion]
+                                     [--impact] [--association] [--occlusions] [--confusion]
 
 Times, on the image level's tables of that configuration, each alone on an idle
 stream: the fused match as a benchmark step runs it (the yardstick), the
@@ -23,11 +23,14 @@ nine variants (engine.stage_error_impact / engine.stage_track_error_impact),
 the kernels of both, and AP and dAP over all categories in range 0.  --level
 track --association times, instead of the breakdown, the per-frame followers
 (engine.stage_track_association) and the plan-less taoamd_track_iou over the
-same cells in the same process.  --confusion (both levels) adds the confusion
-table: the level's links pass, taoamd_confusion_count and taoamd_confusion_fill,
-each alone between HIP events in the same process, the whole stage with its
-read of the entry count, the kernels, and the number of entries beside the
-cells of the dense table.  Prints one JSON line."""
+same cells in the same process.  --level track --occlusions times the occlusion
+episodes (engine.stage_track_occlusion: count and fill each alone, the whole
+stage) beside the association pass they follow, in the same process.  --confusion
+(both levels) adds the confusion table: the level's links pass,
+taoamd_confusion_count and taoamd_confusion_fill, each alone between HIP events
+in the same process, the whole stage with its read of the entry count, the
+kernels, and the number of entries beside the cells of the dense table.  Prints
+one JSON line."""
 import argparse
 import json
 import os
@@ -109,6 +112,8 @@ def track_level(a, gt, dt, dev, V):
     res["track_iou_step"] = timed(lambda: engine.stage_track_iou(dp, ws))
     if a.association:
         return association(a, res, gt, fl, dp, ws, timed)
+    if a.occlusions:
+        return occlusions(a, res, gt, fl, dp, ws, timed)
     res["match_fused"] = timed(lambda: engine.stage_match(dp, ws))
     # the first call builds the per-video lists and runs the match for match_gt
     engine.stage_track_error_types(dp, ws, 0, a.bg_thr)
@@ -267,6 +272,62 @@ def association(a, res, gt, fl, dp, ws, timed):
     print(json.dumps(res))
 
 
+def occlusions(a, res, gt, fl, dp, ws, timed):
+    """--level track --occlusions: the occlusion episodes
+    (engine.stage_track_occlusion) at frame_thr 0.5, window [0, 0.1], recover 3
+    and the default length buckets, in the same process as the association pass
+    whose followers they read: that pass without windows, taoamd_track_occlusion_count
+    and taoamd_track_occlusion_fill each alone between HIP events, the whole stage
+    without and with the records (the latter reads the episode count), and the
+    kernels of both passes."""
+    import torch
+    from tao_amodal_amd import _lib, engine
+    lib = _lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    thr, lo, hi, recover, edges = 0.5, 0.0, 0.1, 3, (1, 3, 6, 11)
+    engine.set_frame_visibility(dp, np.asarray(gt.ann_vis)[fl.gt_frame_box.index])
+    # the first call allocates the buffers of both passes and the records
+    engine.stage_track_occlusion(dp, ws, thr, lo, hi, recover, edges, episodes=True)
+    torch.cuda.synchronize()
+    res["track_association_no_windows"] = timed(
+        lambda: engine.stage_track_association(dp, ws, thr, []))
+    t, n_gf = dp.t, int(dp.t["gt_frame_pos"].numel())
+    e = np.ascontiguousarray(edges, dtype=np.int32)
+    tables = (dp.n_gt, n_gf, dp.n_cat, len(e), recover, lo, hi, e.ctypes.data,
+              t["gt_cat"].data_ptr(), t["gt_flags"].data_ptr(), t["gt_frame_off"].data_ptr(),
+              t["gt_frame_vis"].data_ptr(), ws.assoc_best.data_ptr())
+
+    def count():
+        _lib.check(lib.taoamd_track_occlusion_count(
+            *tables, ws.occ_gt.data_ptr(), ws.occ_off.data_ptr(), ws.occ_counts.data_ptr(),
+            ws.occ_ws.data_ptr(), ws.occ_bytes, stream), "taoamd_track_occlusion_count")
+
+    def fill():
+        _lib.check(lib.taoamd_track_occlusion_fill(
+            *tables, ws.occ_off.data_ptr(), n_ep, ws.occ_episodes.data_ptr(),
+            ws.occ_ws.data_ptr(), ws.occ_bytes, stream), "taoamd_track_occlusion_fill")
+    n_ep = int(ws.occ_n)
+    res["occlusion_count"] = timed(count)
+    res["occlusion_fill"] = timed(fill)
+    res["occlusion_stage"] = timed(
+        lambda: engine.stage_track_occlusion(dp, ws, thr, lo, hi, recover, edges))
+    res["occlusion_stage_with_episodes"] = timed(
+        lambda: engine.stage_track_occlusion(dp, ws, thr, lo, hi, recover, edges, episodes=True))
+    _lib.kernel_timing(True)
+    for _ in range(a.reps):
+        engine.stage_track_association(dp, ws, thr, [])
+        count()
+        fill()
+    res["kernels_ms"] = {k: round(ms / n, 4) for k, (ms, n) in _lib.kernel_timings().items()}
+    _lib.kernel_timing(False)
+    res["occlusion_episodes"] = n_ep
+    res["occlusion_workspace_bytes"] = int(ws.occ_bytes)
+    res["occlusion_bytes_read"] = 12 * n_gf
+    res["occlusion_columns"] = list(_lib.OCC_COUNT_COLUMNS)
+    res["occlusion_counts_by_bucket"] = ws.occ_counts.sum(0).tolist()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--level", choices=("image", "track"), default="image")
@@ -279,10 +340,13 @@ def main():
     ap.add_argument("--bg-thr", type=float, default=0.1)
     ap.add_argument("--impact", action="store_true")
     ap.add_argument("--association", action="store_true")
+    ap.add_argument("--occlusions", action="store_true")
     ap.add_argument("--confusion", action="store_true")
     a = ap.parse_args()
     if a.association and a.level != "track":
         ap.error("--association is the track level's: --level track")
+    if a.occlusions and a.level != "track":
+        ap.error("--occlusions is the track level's: --level track")
     import torch
     from tao_amodal_amd import _lib, engine, flatten_dev
     from tao_amodal_amd.synth import synth
