@@ -1479,6 +1479,109 @@ int taoamd_track_occlusion_fill(int64_t n_gt, int64_t n_gt_frames, int32_t n_cat
                                 const int64_t *ep_off, int64_t cap, int32_t *episodes,
                                 void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- track-level identity: IDF1 / IDP / IDR (csrc/track_identity.hip) ----------------
+ * The association above is many-to-one: one detection track may be the primary
+ * of several ground-truth tracks, and a ground truth's covered frames may be
+ * spread over many ids.  The identity measures (Ristani et al., ECCV 2016) ask
+ * the global question: each ground-truth track may own ONE detection track and
+ * each detection track at most one ground truth -- how many frames can be
+ * explained?  A maximum-weight bipartite assignment per cell.  The reference has
+ * no counterpart; the definition is this library's.  Track level, boxes.
+ *
+ * Rows are those of the use_cats = 1 track table, as for
+ * taoamd_track_association.  A cell is (video, category) with D detection-track
+ * rows and G ground-truth rows; F_d and L_g are their frame counts.
+ *   share[cell_iou_off[cell] + d_local * G + g_local]  int32: the frames k of g
+ *               on which d has a frame at p_k and box_iou(d's box there, b_k) >=
+ *               frame_thr -- box_iou has the bits of taoamd_bb_iou (not crowd,
+ *               the detection first); a NaN is no overlap.  Counted for EVERY
+ *               pair of the cell, ignored ground truths included.  frame_thr: any
+ *               double in (0, 1].  Elementwise, share >= follow of the
+ *               association at the same threshold.
+ *   eligible    g whose gt_flags lacks TAOAMD_GT_IGNORE; other flags do not matter.
+ *   set aside   a detection track d is neither a candidate nor counted if
+ *               (a) its greatest share with an ignored ground truth of the cell
+ *                   is strictly greater than its greatest share with an eligible
+ *                   one (it follows something that is not evaluated), or
+ *               (b) dt_flags[d] has TAOAMD_DT_IGNORE_UNMATCHED and its share
+ *                   with every eligible ground truth is 0 (so also in a cell
+ *                   without ground truth).
+ *               Every other d is KEPT.  Both rules read share alone, never the
+ *               assignment: the counts below are unique.
+ *   assignment  a set of pairs (kept d, eligible g) of one cell, each d and each
+ *               g at most once, that maximises the sum of share.  IDTP(cell) is
+ *               that maximum, a unique integer.  Where several assignments
+ *               reach it ([[2, 1], [1, 0]]: 2 + 0 and 1 + 1), the one with the
+ *               most pairs of share > 0 is taken, so that their number is
+ *               unique too.
+ * Per category, cat_counts int64[n_cat][6]:
+ *   0 gt_tracks   the eligible ground-truth tracks
+ *   1 gt_frames   the sum of their L_g
+ *   2 dt_tracks   the kept detection tracks (category: the dt_cat column; cells
+ *                 without ground truth count too)
+ *   3 dt_frames   the sum of their F_d
+ *   4 idtp        the cells' IDTP summed
+ *   5 pairs       the assigned pairs with share > 0
+ * Rows with a category outside [0, n_cat) count nowhere.  IDFN = gt_frames -
+ * idtp, IDFP = dt_frames - idtp; the caller forms IDR = idtp / gt_frames, IDP =
+ * idtp / dt_frames, IDF1 = 2 idtp / (gt_frames + dt_frames).
+ * Per track: gt_ident int32[n_gt][2] = {the assigned detection row or -1, its
+ * share} -- {-1, 0} for an ignored or unassigned g, and a pair of share 0 is
+ * reported as unassigned --; dt_ident int32[n_dt][2] = {the assigned ground-truth
+ * row or -1, kept ? 1 : 0}.  Rows no cell lists hold {-1, 0}.  Under ties the
+ * optimal assignment is not unique; any optimal one is correct, and the one
+ * returned is a function of the input alone: one wavefront owns a cell, equal
+ * minima go to the lowest column, and no atomic decides anything -- the same from
+ * run to run.  Every output is an integer; share and cat_counts are integer adds,
+ * whose sum does not depend on the order of arrival.
+ *
+ * Two calls, so that each kernel can be driven alone.
+ * taoamd_track_identity_share zeroes and fills share from the cell tables and the
+ * CSR frame lists of taoamd_track_association: a lane per ground-truth frame
+ * walks its cell's detection tracks; no tile of the pair matrix, no limit on D, G
+ * or a track's length.
+ * taoamd_track_identity_assign reads share (any int32 table in that layout; a
+ * negative word reads as 0) and the columns, and writes cat_counts, gt_ident,
+ * dt_ident and one int32 *status (device): a wavefront per cell marks eligible
+ * and kept rows, keeps the rows and columns with a positive share, takes the
+ * smaller side as rows and runs the shortest-augmenting-path search (potentials
+ * in 64 bits; the state in LDS where the larger side is <= 256, else in the
+ * cell's slice of the workspace).  There is no size limit and no
+ * TAOAMD_ERR_TOO_LARGE.  Every loop has a bound known at entry; were one ever
+ * exhausted, the wavefront stores 1 to *status, leaves the cell's pairs at -1 and
+ * returns; nothing spins.  The potentials are sums of up to n weights share *
+ * (n + 1) + 1 (n: the smaller side of the cell after compaction), in 64 bits: a
+ * cell with n * (n + 1) * (its greatest share + 1) >= 2^62 is not solved but
+ * stores 2 to *status (a share of taoamd_track_identity_share is at most a
+ * track's frames: such tables are far inside).  *status is 0 otherwise.
+ * TAOAMD_ERR_ARG: frame_thr outside (0, 1] (a NaN included), a size below 0 or
+ * beyond int32, n_cat <= 0, a missing table; TAOAMD_ERR_WORKSPACE: fewer bytes
+ * than taoamd_track_identity_workspace(n_dt, n_gt, n_gt_frames), one size for both
+ * calls (the association's three descriptor tables and 40 bytes of search state
+ * per row; any base address, contents need not be initialised, and nothing is
+ * carried from one call to the other; the size function answers 0 to sizes it
+ * refuses).  Both are answered before the first device call.  Rows and frames
+ * named by the tables that lie outside them are skipped, never dereferenced. */
+size_t taoamd_track_identity_workspace(int64_t n_dt, int64_t n_gt, int64_t n_gt_frames);
+int taoamd_track_identity_share(int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou,
+                                int64_t n_dt_frames, int64_t n_gt_frames, double frame_thr,
+                                const int32_t *cell_dt_off, const int32_t *cell_gt_off,
+                                const int64_t *cell_iou_off, const int32_t *dt_frame_off,
+                                const int32_t *dt_frame_pos, const double *dt_frame_box,
+                                const int32_t *gt_frame_off, const int32_t *gt_frame_pos,
+                                const double *gt_frame_box, int32_t *share, void *workspace,
+                                size_t workspace_bytes, void *stream);
+int taoamd_track_identity_assign(int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou,
+                                 int64_t n_dt_frames, int64_t n_gt_frames, int32_t n_cat,
+                                 const int32_t *cell_dt_off, const int32_t *cell_gt_off,
+                                 const int64_t *cell_iou_off, const int32_t *gt_cat,
+                                 const uint8_t *gt_flags, const int32_t *dt_cat,
+                                 const uint8_t *dt_flags, const int32_t *dt_frame_off,
+                                 const int32_t *gt_frame_off, const int32_t *share,
+                                 int64_t *cat_counts, int32_t *gt_ident, int32_t *dt_ident,
+                                 int32_t *status, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+
 /* ---- multi-GPU result exchange (category-partitioned evaluation) -------------------
  * No reference counterpart (the reference is single-process); these carry the
  * tables of taoamd_accumulate_compact between ranks and end in the layout of

@@ -40,6 +40,7 @@ OCC_EPISODE_COLUMNS = ("gt", "a", "n", "outcome", "entry", "after", "gap", "cove
 OCC_TRACK_COLUMNS = ("episodes", "frames", "kept", "switched_lost")
 OCC_COUNT_COLUMNS = ("episodes", "frames", "covered", "held", "start", "unfollowed", "end",
                      "kept", "switched", "lost", "gap")
+IDENT_CAT_COLUMNS = ("gt_tracks", "gt_frames", "dt_tracks", "dt_frames", "idtp", "pairs")
 
 _vp, _i64, _i32, _sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
 
@@ -244,6 +245,9 @@ SIGNATURES = {
     "taoamd_track_occlusion_fill": (C.c_int, [_i64, _i64, _i32, _i32, _i32, C.c_double,
                                               C.c_double] + [_vp] * 7 + [_i64, _vp, _vp, _sz,
                                                                          _vp]),
+    "taoamd_track_identity_workspace": (_sz, [_i64, _i64, _i64]),
+    "taoamd_track_identity_share": (C.c_int, [_i64] * 6 + [C.c_double] + [_vp] * 11 + [_sz, _vp]),
+    "taoamd_track_identity_assign": (C.c_int, [_i64] * 6 + [_i32] + [_vp] * 15 + [_sz, _vp]),
 }
 
 _lib = None

@@ -48,6 +48,7 @@
 // box_iou is common.hpp's, compiled with -ffp-contract=off like every other use:
 // the bits of taoamd_bb_iou.  Everything else is an integer.
 #include "common.hpp"
+#include "track_frames.hpp"
 #include "workspace.hpp"
 
 using namespace taoamd;
@@ -85,43 +86,13 @@ struct AssocArgs {
     int32_t *trk_vis;                // [n_gt][8][3]: a track's counts per visibility window
 };
 
-__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi)
-{
-    return v < lo ? lo : (v > hi ? hi : v);
-}
+// (the three descriptor tables: track_frames.hpp, shared with the identity's share
+// pass)
+__global__ __launch_bounds__(256) void assoc_dt_meta_kernel(AssocArgs a) { frames_dt_meta(a); }
 
-__global__ __launch_bounds__(256) void assoc_dt_meta_kernel(AssocArgs a)
-{
-    const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (d >= a.n_dt) return;
-    // (offsets clamped to the table: a bad CSR reads wrong frames, never past an end)
-    const int64_t fs = clamp64(a.dfoff[d], 0, a.n_dt_frames);
-    const int64_t fe = clamp64(a.dfoff[d + 1], fs, a.n_dt_frames);
-    int4 m = make_int4((int32_t)fs, (int32_t)fe, 0, -1);
-    if (fe > fs) {
-        m.z = a.dfpos[fs];
-        m.w = a.dfpos[fe - 1];
-    }
-    a.dt_meta[d] = m;
-}
+__global__ __launch_bounds__(256) void assoc_cell_kernel(AssocArgs a) { frames_gt_cell(a); }
 
-__global__ __launch_bounds__(256) void assoc_cell_kernel(AssocArgs a)
-{
-    const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= a.n_cells) return;
-    const int64_t g0 = clamp64(a.cell_gt_off[c], 0, a.n_gt);
-    const int64_t g1 = clamp64(a.cell_gt_off[c + 1], g0, a.n_gt);
-    for (int64_t g = g0; g < g1; g++) a.gt_cell[g] = (int32_t)c;
-}
-
-__global__ __launch_bounds__(256) void assoc_frame_kernel(AssocArgs a)
-{
-    const int64_t g = (int64_t)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
-    if (g >= a.n_gt) return;
-    const int64_t s = clamp64(a.gfoff[g], 0, a.n_gt_frames);
-    const int64_t e = clamp64(a.gfoff[g + 1], s, a.n_gt_frames);
-    for (int64_t k = s + lane_id(); k < e; k += WAVE) a.frame_gt[k] = (int32_t)g;
-}
+__global__ __launch_bounds__(256) void assoc_frame_kernel(AssocArgs a) { frames_frame_gt(a); }
 
 __global__ __launch_bounds__(TA_TILE) void assoc_pair_kernel(AssocArgs a)
 {

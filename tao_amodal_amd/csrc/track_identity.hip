@@ -1,0 +1,535 @@
+// Track-level identity (gfx950): IDF1 / IDP / IDR from an optimal one-to-one
+// assignment of detection tracks to ground-truth tracks (Ristani et al., ECCV
+// 2016).  The reference has no such table; the definition is this library's,
+// stated in include/tao_amodal_hip.h and DESIGN.md section 8.
+//
+// Rows are those of the use_cats = 1 track table, cells and frame lists those of
+// the association (track_association.hip).  Two calls:
+//
+// taoamd_track_identity_share: share[cell_iou_off[cell] + d * G + g] = the frames
+// of ground-truth track g on which detection track d has a frame with box_iou >=
+// frame_thr -- per pair a COUNT, neither the 3D IoU's sum nor the association's
+// arg-max.
+//   ident_dt_meta_kernel / ident_cell_kernel / ident_frame_kernel  the three
+//                        descriptors of the association's pass (a detection
+//                        track's frame range and positions, the cell of a ground-
+//                        truth row, the track of a frame; track_frames.hpp), for
+//                        this call's workspace
+//   ident_share_kernel   lane = ground-truth frame, the whole table as one flat
+//                        list: the association's pair loop (a track without holes
+//                        is one probe, else a bisection between the two indices
+//                        its first and last position allow), but every candidate
+//                        with an overlap >= frame_thr counts, not the greatest:
+//                        an integer atomic add per (pair, wavefront) with a hit,
+//                        the lanes of one pair found by ballot.  No LDS, no limit
+//                        on a cell or a track.
+//
+// taoamd_track_identity_assign: a maximum-weight bipartite assignment per cell.
+//   ident_init_kernel    lane = row: {-1, 0} into gt_ident and dt_ident (rows no
+//                        cell lists stay so)
+//   ident_assign_kernel  workgroup = ONE wavefront = cell.
+//                        1  lane = detection track: its greatest share with an
+//                           eligible and with an ignored ground truth -> kept;
+//                           the kept ones with a positive share are compacted (a
+//                           ballot and a prefix popcount) into the cell's slice
+//                           of idx[]
+//                        2  lane = ground-truth track: the eligible ones with a
+//                           positive share in a compacted row are compacted
+//                        3  the smaller side becomes the rows (n <= m)
+//                        4  shortest augmenting paths (Hungarian in the Jonker-
+//                           Volgenant form, on cost = -weight): a row a time; a
+//                           step scans the free columns, lanes striding them
+//                           (ceil(m / 64) a lane), the minimum (value, column) by
+//                           a wavefront reduction -- the lowest column among
+//                           equal values, so the result is one function of the
+//                           input; potentials in 64 bits.  The search state (u,
+//                           v, minv, p, way, used, the two index lists) lives in
+//                           LDS where m <= TI_LDS, else in the cell's own slice
+//                           of workspace arrays of n_dt + n_gt entries.
+//                        Every loop has a bound known at entry: n rows, at most
+//                        m + 1 steps an augmentation, at most m + 1 edges of a
+//                        path.  A bound that runs out stores 1 to *status and
+//                        ends the cell with its pairs at -1; nothing spins.
+//                        A pair weighs share * (n + 1) + (share > 0): among equal
+//                        sums of shares the most pairs with a positive one, so
+//                        that `pairs` is unique as well.
+//                        The count tables are integer adds, one per (wavefront
+//                        step, category, column).
+// The wavefront is the workgroup, so __syncthreads() is the fence between its
+// lanes' stores and loads of the search state, in LDS and in global memory alike;
+// all control flow around it is uniform.
+// Registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950):
+//   ident_share_kernel 38 VGPRs, no LDS; ident_assign_kernel 54 VGPRs, 11 264 B
+//   of LDS (a workgroup is one wavefront: 14 cells a CU by LDS).
+#include "common.hpp"
+#include "track_frames.hpp"
+#include "workspace.hpp"
+
+using namespace taoamd;
+
+#define TI_TILE 64          // ground-truth frames per workgroup of the share kernel
+#define TI_LDS 256          // columns (and rows) of a cell whose search state is in LDS
+#define TI_NCAT 6
+#define TI_INF 0x1fffffffffffffffll
+
+struct IdentArgs {
+    int64_t n_dt, n_gt, n_cells, n_iou, n_dt_frames, n_gt_frames;
+    int32_t n_cat;
+    double thr;
+    const int32_t *cell_dt_off, *cell_gt_off;
+    const int64_t *cell_iou_off;
+    const int32_t *gt_cat, *dt_cat;
+    const uint8_t *gt_flags, *dt_flags;
+    const int32_t *dfoff, *dfpos;
+    const double4 *dfbox;
+    const int32_t *gfoff, *gfpos;
+    const double4 *gfbox;
+    int32_t *share;                  // [n_iou], the layout of the IoU matrix
+    unsigned long long *cat_counts;  // [n_cat][6]
+    int32_t *gt_ident, *dt_ident;    // [n_gt][2], [n_dt][2]
+    int32_t *status;
+    int4 *dt_meta;                   // [n_dt] {first frame, end, first position, last position}
+    int32_t *gt_cell;                // [n_gt], -1: in no cell
+    int32_t *frame_gt;               // [n_gt_frames], -1: of no track
+    // the search state of the cells that do not fit in LDS, n_dt + n_gt entries
+    // each: cell c owns [cell_dt_off[c] + cell_gt_off[c], the next cell's)
+    long long *su, *sv, *sminv;
+    int32_t *sp, *sway, *sused, *sidx;
+};
+
+// (the three descriptor tables and the probe of a frame list: track_frames.hpp,
+// shared with the association)
+__global__ __launch_bounds__(256) void ident_dt_meta_kernel(IdentArgs a) { frames_dt_meta(a); }
+
+__global__ __launch_bounds__(256) void ident_cell_kernel(IdentArgs a) { frames_gt_cell(a); }
+
+__global__ __launch_bounds__(256) void ident_frame_kernel(IdentArgs a) { frames_frame_gt(a); }
+
+__global__ __launch_bounds__(TI_TILE) void ident_share_kernel(IdentArgs a)
+{
+    const int64_t k = (int64_t)blockIdx.x * TI_TILE + threadIdx.x;
+    if (k >= a.n_gt_frames) return;
+    const int32_t g = a.frame_gt[k];
+    const int32_t cell = g >= 0 ? a.gt_cell[g] : -1;
+    if (cell < 0) return;
+    const int64_t d0 = clamp64(a.cell_dt_off[cell], 0, a.n_dt);
+    const int64_t d1 = clamp64(a.cell_dt_off[cell + 1], d0, a.n_dt);
+    const int64_t g0 = a.cell_gt_off[cell];
+    const int64_t G = (int64_t)a.cell_gt_off[cell + 1] - g0;
+    const int64_t col = a.cell_iou_off[cell] + (g - g0);
+    const int64_t p = a.gfpos[k];
+    const double4 B = a.gfbox[k];
+    for (int64_t d = d0; d < d1; d++) {
+        int64_t at = -1, lo;
+        if (frames_find(a.dfpos, a.dt_meta[d], p, lo)) {
+            const double4 D = a.dfbox[lo];
+            const double v = box_iou(D.x, D.y, D.z, D.w, B.x, B.y, B.z, B.w);
+            const int64_t i = col + (d - d0) * G;
+            // (a NaN compares false: no overlap)
+            if (v >= a.thr && i >= 0 && i < a.n_iou) at = i;
+        }
+        // One add per distinct pair among the lanes that are here together: a
+        // wavefront's lanes are consecutive frames, as a rule of one track, and then
+        // all its hits on d are one add.  (Lanes of other cells may be at another d
+        // or gone; whoever is here is grouped by address, so any grouping is right.)
+        uint64_t left = __ballot(at >= 0);
+        while (left) {
+            const int lead = __builtin_ctzll(left);
+            const int64_t to = __shfl(at, lead);
+            const uint64_t same = __ballot(at == to);
+            if (lane_id() == lead) atomicAdd(a.share + to, (int32_t)__popcll(same));
+            left &= ~same;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void ident_init_kernel(IdentArgs a)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.n_gt) reinterpret_cast<int2 *>(a.gt_ident)[i] = make_int2(-1, 0);
+    if (i < a.n_dt) reinterpret_cast<int2 *>(a.dt_ident)[i] = make_int2(-1, 0);
+}
+
+__device__ __forceinline__ long long ident_wave_sum(long long v)
+{
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// cat_counts[key][col0 + c] += the sum of v[c] over the wavefront's live lanes of
+// that key: one add per (distinct key, column with a sum), by the key's first lane
+__device__ __forceinline__ void ident_add(unsigned long long *cat_counts, bool live, int32_t key,
+                                          int col0, long long v0, long long v1)
+{
+    uint64_t left = __ballot(live);
+    while (left) {
+        const int lead = __builtin_ctzll(left);
+        const int32_t k = __builtin_amdgcn_readlane(key, lead);
+        const bool mine = live && key == k;
+        const uint64_t same = __ballot(mine);
+        const long long s0 = ident_wave_sum(mine ? v0 : 0ll);
+        const long long s1 = ident_wave_sum(mine ? v1 : 0ll);
+        if (lane_id() == lead) {
+            unsigned long long *row = cat_counts + (int64_t)k * TI_NCAT + col0;
+            if (s0) atomicAdd(row, (unsigned long long)s0);
+            if (s1) atomicAdd(row + 1, (unsigned long long)s1);
+        }
+        left &= ~same;
+    }
+}
+
+// A cell's share matrix: entry (d, g) in-cell, 0 outside the table; a share is a
+// count, so a negative word reads as 0 too
+struct CellShare {
+    const int32_t *share;
+    int64_t off, G, n_iou;
+    __device__ __forceinline__ int32_t at(int64_t d, int64_t g) const
+    {
+        const int64_t i = off + d * G + g;
+        const int32_t s = i >= 0 && i < n_iou ? share[i] : 0;
+        return s > 0 ? s : 0;
+    }
+};
+
+// The search state: column arrays of m entries, u of n, the index lists
+struct Search {
+    long long *u, *v, *minv;
+    int32_t *p, *way, *used;
+    const int32_t *ridx, *cidx;      // in-cell indices of row i / column j
+};
+
+// Rows 1 .. n, columns 1 .. m, n <= m; p[j - 1] = the row of column j, 0: free;
+// way[j - 1] = the column before j on the path, 0: the root (the new row).
+// The weight of a pair is share * (n + 1) + (share > 0): the sum of shares decides,
+// among equal sums the number of pairs with a positive share (fewer than n + 1),
+// so that both numbers are unique.  Returns false if a bound ran out (then p is
+// not an assignment).
+__device__ __forceinline__ bool ident_solve(const CellShare &S, const Search &s, int n, int m,
+                                            bool rows_are_dt)
+{
+    const long long scale = (long long)n + 1;
+    const int lane = lane_id();
+    for (int j = lane; j < m; j += WAVE) {
+        s.v[j] = 0;
+        s.p[j] = 0;
+    }
+    for (int i = lane; i < n; i += WAVE) s.u[i] = 0;
+    __syncthreads();
+    for (int i = 1; i <= n; i++) {
+        for (int j = lane; j < m; j += WAVE) {
+            s.minv[j] = TI_INF;
+            s.used[j] = 0;
+            s.way[j] = 0;
+        }
+        __syncthreads();
+        int j0 = 0, i0 = i;
+        bool found = false;
+        for (int step = 0; step <= m; step++) {
+            const long long ui = s.u[i0 - 1];
+            const int64_t r = s.ridx[i0 - 1];
+            long long best = TI_INF;
+            int bj = 0x7fffffff;
+            for (int j = lane; j < m; j += WAVE) {
+                if (s.used[j]) continue;
+                const int64_t c = s.cidx[j];
+                const long long w = rows_are_dt ? S.at(r, c) : S.at(c, r);
+                const long long cur = -(w * scale + (w > 0)) - ui - s.v[j];
+                long long mv = s.minv[j];
+                if (cur < mv) {
+                    mv = cur;
+                    s.minv[j] = cur;
+                    s.way[j] = j0;
+                }
+                if (mv < best) {             // (ascending j: the lowest among equal values)
+                    best = mv;
+                    bj = j;
+                }
+            }
+#pragma unroll
+            for (int o = WAVE / 2; o > 0; o >>= 1) {
+                const long long ob = __shfl_xor(best, o);
+                const int oj = __shfl_xor(bj, o);
+                if (ob < best || (ob == best && oj < bj)) {
+                    best = ob;
+                    bj = oj;
+                }
+            }
+            if (bj == 0x7fffffff) return false;     // no free column: n <= m rules it out
+            for (int j = lane; j < m; j += WAVE) {
+                if (s.used[j]) {
+                    s.u[s.p[j] - 1] += best;         // (distinct columns hold distinct rows)
+                    s.v[j] -= best;
+                } else {
+                    s.minv[j] -= best;
+                }
+            }
+            if (lane == 0) s.u[i - 1] += best;       // the root's row
+            if ((bj & (WAVE - 1)) == lane) s.used[bj] = 1;
+            __syncthreads();
+            j0 = bj + 1;
+            i0 = s.p[bj];
+            if (i0 == 0) {
+                found = true;
+                break;
+            }
+        }
+        if (!found) return false;
+        // the path back to the root; every lane walks it and stores the same words
+        for (int step = 0; step <= m && j0; step++) {
+            const int j1 = s.way[j0 - 1];
+            s.p[j0 - 1] = j1 ? s.p[j1 - 1] : i;
+            j0 = j1;
+        }
+        if (j0) return false;
+        __syncthreads();
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
+{
+    __shared__ long long l_u[TI_LDS], l_v[TI_LDS], l_minv[TI_LDS];
+    __shared__ int32_t l_p[TI_LDS], l_way[TI_LDS], l_used[TI_LDS], l_ridx[TI_LDS], l_cidx[TI_LDS];
+    const int64_t cell = blockIdx.x;
+    const int lane = lane_id();
+    const int64_t d0 = clamp64(a.cell_dt_off[cell], 0, a.n_dt);
+    const int64_t D = clamp64(a.cell_dt_off[cell + 1], d0, a.n_dt) - d0;
+    const int64_t g0 = clamp64(a.cell_gt_off[cell], 0, a.n_gt);
+    const int64_t G = clamp64(a.cell_gt_off[cell + 1], g0, a.n_gt) - g0;
+    if (D == 0 && G == 0) return;
+    CellShare S = {a.share, a.cell_iou_off[cell], G, a.n_iou};
+    const int64_t base = d0 + g0;                    // the cell's slice of the state arrays
+    int32_t *dlist = a.sidx + base, *glist = a.sidx + base + D;
+    const uint64_t below = (1ull << lane) - 1ull;
+
+    // 1: kept detection tracks; those with a positive share in an eligible row
+    int nd = 0;
+    int32_t top = 0;                                 // the greatest share that can be assigned
+    for (int64_t db = 0; db < D; db += WAVE) {
+        const int64_t d = db + lane;
+        const bool live = d < D;
+        int32_t me = 0, mi = 0;
+        if (live)
+            for (int64_t g = 0; g < G; g++) {
+                const int32_t v = S.at(d, g);
+                if (a.gt_flags[g0 + g] & TAOAMD_GT_IGNORE) mi = v > mi ? v : mi;
+                else me = v > me ? v : me;
+            }
+        bool kept = false;
+        int32_t cat = 0;
+        long long frames = 0;
+        if (live) {
+            kept = !(mi > me) && !((a.dt_flags[d0 + d] & TAOAMD_DT_IGNORE_UNMATCHED) && me == 0);
+            cat = a.dt_cat[d0 + d];
+            const int64_t fs = clamp64(a.dfoff[d0 + d], 0, a.n_dt_frames);
+            frames = clamp64(a.dfoff[d0 + d + 1], fs, a.n_dt_frames) - fs;
+            a.dt_ident[(d0 + d) * 2 + 1] = kept;
+        }
+        ident_add(a.cat_counts, kept && cat >= 0 && cat < a.n_cat, cat, 2, 1, frames);
+        const bool act = kept && me > 0;
+        top = act && me > top ? me : top;
+        const uint64_t m = __ballot(act);
+        if (act) dlist[nd + __popcll(m & below)] = (int32_t)d;
+        nd += __popcll(m);
+    }
+    __syncthreads();
+    // 2: eligible ground-truth tracks; those with a positive share in such a row
+    int ng = 0;
+    for (int64_t gb = 0; gb < G; gb += WAVE) {
+        const int64_t g = gb + lane;
+        const bool live = g < G;
+        const bool elig = live && !(a.gt_flags[g0 + g] & TAOAMD_GT_IGNORE);
+        bool act = false;
+        int32_t cat = 0;
+        long long frames = 0;
+        if (elig) {
+            for (int t = 0; t < nd && !act; t++) act = S.at(dlist[t], g) > 0;
+            cat = a.gt_cat[g0 + g];
+            const int64_t fs = clamp64(a.gfoff[g0 + g], 0, a.n_gt_frames);
+            frames = clamp64(a.gfoff[g0 + g + 1], fs, a.n_gt_frames) - fs;
+        }
+        ident_add(a.cat_counts, elig && cat >= 0 && cat < a.n_cat, cat, 0, 1, frames);
+        const uint64_t m = __ballot(act);
+        if (act) glist[ng + __popcll(m & below)] = (int32_t)g;
+        ng += __popcll(m);
+    }
+    __syncthreads();
+    if (nd == 0 || ng == 0) return;                  // (uniform)
+    // 3: the smaller side as rows
+    const bool rows_are_dt = nd <= ng;
+    const int n = rows_are_dt ? nd : ng, m = rows_are_dt ? ng : nd;
+    // a potential is a sum of at most n weights, each at most top * (n + 1) + 1: in
+    // 64 bits while n * (n + 1) * (top + 1) < 2^62.  A share of the share kernel is
+    // at most a track's frames, so real tables are far inside; a table that is not
+    // is refused, never solved wrongly
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) {
+        const int32_t t = __shfl_xor(top, o);
+        top = t > top ? t : top;
+    }
+    const unsigned long long nn = (unsigned long long)n * ((unsigned long long)n + 1);
+    const unsigned long long ww = (unsigned long long)top + 1;
+    if (__umul64hi(nn, ww) != 0 || nn * ww >= (1ull << 62)) {
+        if (lane == 0) *a.status = 2;
+        return;
+    }
+    const int32_t *rl = rows_are_dt ? dlist : glist, *cl = rows_are_dt ? glist : dlist;
+    // 4: the search, its state in LDS or in the cell's slice of the workspace
+    Search s;
+    bool ok;
+    if (m <= TI_LDS) {
+        for (int i = lane; i < n; i += WAVE) l_ridx[i] = rl[i];
+        for (int j = lane; j < m; j += WAVE) l_cidx[j] = cl[j];
+        s = {l_u, l_v, l_minv, l_p, l_way, l_used, l_ridx, l_cidx};
+        ok = ident_solve(S, s, n, m, rows_are_dt);
+    } else {
+        s = {a.su + base, a.sv + base, a.sminv + base, a.sp + base, a.sway + base,
+             a.sused + base, rl, cl};
+        ok = ident_solve(S, s, n, m, rows_are_dt);
+    }
+    if (!ok) {
+        if (lane == 0) *a.status = 1;
+        return;
+    }
+    // the pairs with a positive share
+    for (int jb = 0; jb < m; jb += WAVE) {
+        const int j = jb + lane;
+        const int i = j < m ? s.p[j] : 0;
+        int32_t w = 0, cat = 0;
+        if (i > 0) {
+            const int64_t r = s.ridx[i - 1], c = s.cidx[j];
+            const int64_t d = rows_are_dt ? r : c, g = rows_are_dt ? c : r;
+            w = S.at(d, g);
+            if (w > 0) {
+                reinterpret_cast<int2 *>(a.gt_ident)[g0 + g] = make_int2((int32_t)(d0 + d), w);
+                a.dt_ident[(d0 + d) * 2] = (int32_t)(g0 + g);
+                cat = a.gt_cat[g0 + g];
+            }
+        }
+        ident_add(a.cat_counts, w > 0 && cat >= 0 && cat < a.n_cat, cat, 4, w, 1);
+    }
+}
+
+// The tables of both calls, in buffer order: a function of (n_dt, n_gt, n_gt_frames)
+static void ident_layout(Carve &c, int64_t n_dt, int64_t n_gt, int64_t n_gt_frames, IdentArgs &a)
+{
+    const size_t n = (size_t)(n_dt + n_gt);
+    a.dt_meta = c.take<int4>((size_t)n_dt);
+    a.gt_cell = c.take<int32_t>((size_t)n_gt);
+    a.frame_gt = c.take<int32_t>((size_t)n_gt_frames);
+    a.su = c.take<long long>(n);
+    a.sv = c.take<long long>(n);
+    a.sminv = c.take<long long>(n);
+    a.sp = c.take<int32_t>(n);
+    a.sway = c.take<int32_t>(n);
+    a.sused = c.take<int32_t>(n);
+    a.sidx = c.take<int32_t>(n);
+}
+
+static bool ident_sizes_ok(int64_t n_dt, int64_t n_gt, int64_t n_gt_frames)
+{
+    return n_dt >= 0 && n_dt <= 0x7fffffff && n_gt >= 0 && n_gt <= 0x7fffffff &&
+           n_gt_frames >= 0 && n_gt_frames <= 0x7fffffff && n_dt + n_gt <= 0x7fffffff;
+}
+
+extern "C" size_t taoamd_track_identity_workspace(int64_t n_dt, int64_t n_gt, int64_t n_gt_frames)
+{
+    if (!ident_sizes_ok(n_dt, n_gt, n_gt_frames)) return 0;
+    IdentArgs a;
+    return measure([&](Carve &c) { ident_layout(c, n_dt, n_gt, n_gt_frames, a); });
+}
+
+extern "C" int taoamd_track_identity_share(
+    int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou, int64_t n_dt_frames,
+    int64_t n_gt_frames, double frame_thr, const int32_t *cell_dt_off, const int32_t *cell_gt_off,
+    const int64_t *cell_iou_off, const int32_t *dt_frame_off, const int32_t *dt_frame_pos,
+    const double *dt_frame_box, const int32_t *gt_frame_off, const int32_t *gt_frame_pos,
+    const double *gt_frame_box, int32_t *share, void *workspace, size_t workspace_bytes,
+    void *stream)
+{
+    if (!ident_sizes_ok(n_dt, n_gt, n_gt_frames) || n_cells < 0 || n_cells > 0x7fffffff ||
+        n_iou < 0 || n_dt_frames < 0 || n_dt_frames > 0x7fffffff)
+        return TAOAMD_ERR_ARG;
+    // (a NaN compares false both times)
+    if (!(frame_thr > 0) || !(frame_thr <= 1)) return TAOAMD_ERR_ARG;
+    if (!workspace) return TAOAMD_ERR_ARG;
+    if (n_cells > 0 && (!cell_dt_off || !cell_gt_off || !cell_iou_off)) return TAOAMD_ERR_ARG;
+    if (n_dt > 0 && !dt_frame_off) return TAOAMD_ERR_ARG;
+    if (n_dt_frames > 0 && (!dt_frame_pos || !dt_frame_box)) return TAOAMD_ERR_ARG;
+    if (n_gt > 0 && !gt_frame_off) return TAOAMD_ERR_ARG;
+    if (n_gt_frames > 0 && (!gt_frame_pos || !gt_frame_box)) return TAOAMD_ERR_ARG;
+    if (n_iou > 0 && !share) return TAOAMD_ERR_ARG;
+    Carve c(workspace);
+    IdentArgs a = {};
+    ident_layout(c, n_dt, n_gt, n_gt_frames, a);
+    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    a.n_dt = n_dt; a.n_gt = n_gt; a.n_cells = n_cells; a.n_iou = n_iou;
+    a.n_dt_frames = n_dt_frames; a.n_gt_frames = n_gt_frames; a.thr = frame_thr;
+    a.cell_dt_off = cell_dt_off; a.cell_gt_off = cell_gt_off; a.cell_iou_off = cell_iou_off;
+    a.dfoff = dt_frame_off; a.dfpos = dt_frame_pos;
+    a.dfbox = reinterpret_cast<const double4 *>(dt_frame_box);
+    a.gfoff = gt_frame_off; a.gfpos = gt_frame_pos;
+    a.gfbox = reinterpret_cast<const double4 *>(gt_frame_box);
+    a.share = share;
+    if (n_iou > 0) TAO_HIP(hipMemsetAsync(share, 0, (size_t)n_iou * sizeof(int32_t), s));
+    if (n_gt == 0 || n_gt_frames == 0 || n_dt == 0 || n_cells == 0) return TAOAMD_OK;
+    // (a ground-truth row no cell lists has no candidates, a frame no track lists counts nowhere)
+    TAO_HIP(hipMemsetAsync(a.gt_cell, 0xff, (size_t)n_gt * sizeof(int32_t), s));
+    TAO_HIP(hipMemsetAsync(a.frame_gt, 0xff, (size_t)n_gt_frames * sizeof(int32_t), s));
+    TAO_TIMED("ident_dt_meta_kernel", s,
+              ident_dt_meta_kernel<<<(unsigned)((n_dt + 255) / 256), 256, 0, s>>>(a));
+    TAO_TIMED("ident_cell_kernel", s,
+              ident_cell_kernel<<<(unsigned)((n_cells + 255) / 256), 256, 0, s>>>(a));
+    TAO_TIMED("ident_frame_kernel", s,
+              ident_frame_kernel<<<(unsigned)((n_gt + 256 / WAVE - 1) / (256 / WAVE)), 256, 0,
+                                   s>>>(a));
+    TAO_TIMED("ident_share_kernel", s,
+              ident_share_kernel<<<(unsigned)((n_gt_frames + TI_TILE - 1) / TI_TILE), TI_TILE, 0,
+                                   s>>>(a));
+    TAO_LAUNCH_CHECK();
+    return TAOAMD_OK;
+}
+
+extern "C" int taoamd_track_identity_assign(
+    int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou, int64_t n_dt_frames,
+    int64_t n_gt_frames, int32_t n_cat, const int32_t *cell_dt_off, const int32_t *cell_gt_off,
+    const int64_t *cell_iou_off, const int32_t *gt_cat, const uint8_t *gt_flags,
+    const int32_t *dt_cat, const uint8_t *dt_flags, const int32_t *dt_frame_off,
+    const int32_t *gt_frame_off, const int32_t *share, int64_t *cat_counts, int32_t *gt_ident,
+    int32_t *dt_ident, int32_t *status, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!ident_sizes_ok(n_dt, n_gt, n_gt_frames) || n_cells < 0 || n_cells > 0x7fffffff ||
+        n_iou < 0 || n_dt_frames < 0 || n_dt_frames > 0x7fffffff || n_cat <= 0)
+        return TAOAMD_ERR_ARG;
+    if (!cat_counts || !status || !workspace) return TAOAMD_ERR_ARG;
+    if (n_cells > 0 && (!cell_dt_off || !cell_gt_off || !cell_iou_off)) return TAOAMD_ERR_ARG;
+    if (n_dt > 0 && (!dt_cat || !dt_flags || !dt_frame_off || !dt_ident)) return TAOAMD_ERR_ARG;
+    if (n_gt > 0 && (!gt_cat || !gt_flags || !gt_frame_off || !gt_ident)) return TAOAMD_ERR_ARG;
+    if (n_iou > 0 && !share) return TAOAMD_ERR_ARG;
+    Carve c(workspace);
+    IdentArgs a = {};
+    ident_layout(c, n_dt, n_gt, n_gt_frames, a);
+    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    a.n_dt = n_dt; a.n_gt = n_gt; a.n_cells = n_cells; a.n_iou = n_iou;
+    a.n_dt_frames = n_dt_frames; a.n_gt_frames = n_gt_frames; a.n_cat = n_cat;
+    a.cell_dt_off = cell_dt_off; a.cell_gt_off = cell_gt_off; a.cell_iou_off = cell_iou_off;
+    a.gt_cat = gt_cat; a.gt_flags = gt_flags; a.dt_cat = dt_cat; a.dt_flags = dt_flags;
+    a.dfoff = dt_frame_off; a.gfoff = gt_frame_off;
+    a.share = const_cast<int32_t *>(share);
+    a.cat_counts = (unsigned long long *)cat_counts;
+    a.gt_ident = gt_ident; a.dt_ident = dt_ident; a.status = status;
+    TAO_HIP(hipMemsetAsync(cat_counts, 0, (size_t)n_cat * TI_NCAT * sizeof(int64_t), s));
+    TAO_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    const int64_t rows = n_dt > n_gt ? n_dt : n_gt;
+    if (rows > 0)
+        TAO_TIMED("ident_init_kernel", s,
+                  ident_init_kernel<<<(unsigned)((rows + 255) / 256), 256, 0, s>>>(a));
+    if (n_cells > 0)
+        TAO_TIMED("ident_assign_kernel", s,
+                  ident_assign_kernel<<<(unsigned)n_cells, WAVE, 0, s>>>(a));
+    TAO_LAUNCH_CHECK();
+    return TAOAMD_OK;
+}

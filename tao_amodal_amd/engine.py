@@ -592,6 +592,7 @@ class Workspace:
         self.assoc_gt = self.assoc_vis_counts = None
         self.assoc_frame_thr = None       # the frame_thr ws.assoc_best holds the followers of
         self.occ_ws = self.occ_gt = self.occ_off = self.occ_counts = self.occ_episodes = None
+        self.ident_ws = self.ident_share = self.ident_cat_counts = None
         self.occ_n = None                 # episodes of the last stage_track_occlusion that read them
         self.pairs_counted = False        # stage_track_iou counted the pairs' common frames
 
@@ -1460,6 +1461,55 @@ def stage_track_occlusion(dp, ws, frame_thr, vis_lo, vis_hi, recover, len_edges,
     _lib.check(lib.taoamd_track_occlusion_fill(
         *tables, _ptr(ws.occ_off), ws.occ_n, _ptr(ws.occ_episodes), _ptr(ws.occ_ws),
         ws.occ_bytes, s), "taoamd_track_occlusion_fill")
+
+
+def stage_track_identity(dp, ws, frame_thr):
+    """IDF1 / IDP / IDR from an optimal one-to-one assignment of detection tracks
+    to ground-truth tracks per cell (taoamd_track_identity_share,
+    taoamd_track_identity_assign; the definition is in include/tao_amodal_hip.h):
+    ws.ident_share int32[n_iou] in the layout of the IoU matrix -- per pair the
+    frames with a box IoU >= `frame_thr` in (0, 1] --, ws.ident_cat_counts
+    int64[n_cat, 6], ws.ident_gt int32[n_gt, 2] = {the assigned detection row or
+    -1, its share}, ws.ident_dt int32[n_dt, 2] = {the assigned ground-truth row or
+    -1, kept}.  On request only.  Reads the track tables alone, like
+    stage_track_association.  Raises if the assignment kernel reports a non-zero
+    status (an exhausted loop bound, weights beyond 64-bit potentials): one
+    synchronisation of the current stream.  Buffers are allocated
+    on the first call and kept with the workspace: 4 bytes per pair of a cell, 8
+    per track, and a workspace of 56 bytes per detection track, 44 per ground-
+    truth track and 4 per ground-truth frame."""
+    if dp.kind != "tao" or dp.mask_iou:
+        raise _lib.TaoAmdError("the track identity is the track level's, on boxes")
+    lib, t, dev, s = _lib.load(), dp.t, dp.device, _stream()
+    n_df, n_gf = int(t["dt_frame_pos"].numel()), int(t["gt_frame_pos"].numel())
+    if ws.ident_ws is None:
+        ws.ident_bytes = lib.taoamd_track_identity_workspace(dp.n_dt, dp.n_gt, n_gf)
+        ws.ident_ws = torch.empty(max(int(ws.ident_bytes), 256), dtype=torch.uint8, device=dev)
+        ws.ident_share = torch.empty(max(dp.n_iou, 1), dtype=torch.int32, device=dev)
+        ws.ident_cat_counts = torch.empty((dp.n_cat, len(_lib.IDENT_CAT_COLUMNS)),
+                                          dtype=torch.int64, device=dev)
+        ws.ident_gt = torch.empty((max(dp.n_gt, 1), 2), dtype=torch.int32, device=dev)
+        ws.ident_dt = torch.empty((max(dp.n_dt, 1), 2), dtype=torch.int32, device=dev)
+        ws.ident_status = torch.empty(1, dtype=torch.int32, device=dev)
+    sizes = (dp.n_dt, dp.n_gt, dp.n_cells, dp.n_iou, n_df, n_gf)
+    cells = (_ptr(t["cell_dt_off"]), _ptr(t["cell_gt_off"]), _ptr(t["cell_iou_off"]))
+    _lib.check(lib.taoamd_track_identity_share(
+        *sizes, float(frame_thr), *cells,
+        _ptr(t["dt_frame_off"]), _ptr(t["dt_frame_pos"]), _ptr(t["dt_frame_box"]),
+        _ptr(t["gt_frame_off"]), _ptr(t["gt_frame_pos"]), _ptr(t["gt_frame_box"]),
+        _ptr(ws.ident_share), _ptr(ws.ident_ws), ws.ident_bytes, s),
+        "taoamd_track_identity_share")
+    _lib.check(lib.taoamd_track_identity_assign(
+        *sizes, dp.n_cat, *cells, _ptr(t["gt_cat"]), _ptr(t["gt_flags"]), _ptr(t["dt_cat"]),
+        _ptr(t["dt_flags"]), _ptr(t["dt_frame_off"]), _ptr(t["gt_frame_off"]),
+        _ptr(ws.ident_share), _ptr(ws.ident_cat_counts), _ptr(ws.ident_gt), _ptr(ws.ident_dt),
+        _ptr(ws.ident_status), _ptr(ws.ident_ws), ws.ident_bytes, s),
+        "taoamd_track_identity_assign")
+    status = int(ws.ident_status.item())            # (synchronises)
+    if status:
+        raise _lib.TaoAmdError("taoamd_track_identity_assign: status %d (%s)" % (
+            status, "a search ran out of its loop bound" if status == 1 else
+            "a cell's weights exceed 64-bit potentials"))
 
 
 def stage_track_iou_guarded(dp, ws):

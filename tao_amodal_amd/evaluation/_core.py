@@ -369,9 +369,10 @@ class GpuRun:
         return rng.astype(np.int32), dt_cat, gt_cat, counts, K
 
     def _followers_at(self, what, ann_vis):
-        """What association_table() and occlusion_table() share: the refusals, in
-        the name `what` of the caller's method, and the frames' own visibility,
-        gathered from the annotations' column and uploaded on the first call."""
+        """What association_table(), occlusion_table() and identity_table()
+        share: the refusals, in the name `what` of the caller's method, and
+        (`ann_vis` not None) the frames' own visibility, gathered from the
+        annotations' column and uploaded on the first call."""
         if self.flat.kind != "tao":
             raise NotImplementedError(what + " is the track level's")
         if self.dp.mask_iou:
@@ -380,7 +381,7 @@ class GpuRun:
             raise NotImplementedError(
                 what + " with use_cats = 0: the candidates of a ground-truth track "
                 "are the detection tracks of its category")
-        if self.dp.t.get("gt_frame_vis") is None:
+        if ann_vis is not None and self.dp.t.get("gt_frame_vis") is None:
             with timed("upload+plan"):
                 rows = self.flat.gt_frame_box.index
                 self.engine.set_frame_visibility(
@@ -429,6 +430,22 @@ class GpuRun:
             return {"gt_occ": ws.occ_gt[:dp.n_gt].cpu().numpy(),
                     "counts": ws.occ_counts.cpu().numpy(),
                     "episodes": ws.occ_episodes[:ws.occ_n].cpu().numpy()}
+
+    def identity_table(self, frame_thr):
+        """The identity measures' tables (engine.stage_track_identity; the
+        definition is in include/tao_amodal_hip.h) at the per-frame threshold
+        `frame_thr`: dict(cat_counts int64[K, 6], gt_ident int32[n_gt, 2],
+        dt_ident int32[n_dt, 2], rows as table rows).  Reads the track tables
+        alone; refuses what association_table() refuses."""
+        self._followers_at("identity()", None)
+        dp, ws = self.dp, self.ws
+        with timed("kernels"):
+            self.engine.stage_track_identity(dp, ws, frame_thr)
+            self.torch.cuda.synchronize(self.device)
+        with timed("download"):
+            return {"cat_counts": ws.ident_cat_counts.cpu().numpy(),
+                    "gt_ident": ws.ident_gt[:dp.n_gt].cpu().numpy(),
+                    "dt_ident": ws.ident_dt[:dp.n_dt].cpu().numpy()}
 
     def pointer_tables(self):
         """What eval['dt_pointers'] is read from: the detections' ids and
@@ -849,6 +866,60 @@ def occlusion_lines(e):
                      + pct(c["kept"], out) + pct(c["switched"], out) + pct(c["lost"], out)
                      + pct(c["held"], c["frames"]))
     return lines
+
+
+def identity_ratios(idtp, gt_frames, dt_frames):
+    """(IDF1, IDP, IDR) as float64, NaN where the denominator is 0."""
+    idtp, gt_frames, dt_frames = (np.asarray(x, dtype=np.float64)
+                                  for x in (idtp, gt_frames, dt_frames))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (np.where(gt_frames + dt_frames > 0, 2 * idtp / (gt_frames + dt_frames), np.nan),
+                np.where(dt_frames > 0, idtp / dt_frames, np.nan),
+                np.where(gt_frames > 0, idtp / gt_frames, np.nan))
+
+
+def identity(ev, frame_thr):
+    """TaoEval.identity()'s whole result at `frame_thr` from the run's tables:
+    the category axis in the caller's order, rows as track ids."""
+    from .._lib import IDENT_CAT_COLUMNS
+    t = ev._run.identity_table(frame_thr)
+    flat = ev._run.flat
+    cat_counts = t["cat_counts"]
+    if ev._cat_pos is not None:
+        cat_counts = np.ascontiguousarray(cat_counts[ev._cat_pos])
+    idf1, idp, idr = identity_ratios(cat_counts[:, 4], cat_counts[:, 1], cat_counts[:, 3])
+    total = dict(zip(IDENT_CAT_COLUMNS, (int(x) for x in cat_counts.sum(0))))
+    total["idfn"] = total["gt_frames"] - total["idtp"]
+    total["idfp"] = total["dt_frames"] - total["idtp"]
+    for name, v in zip(("idf1", "idp", "idr"),
+                       identity_ratios(total["idtp"], total["gt_frames"], total["dt_frames"])):
+        total[name] = float(v)
+    dt_id, gt_id = np.asarray(flat.dt_id, dtype=np.int64), np.asarray(flat.gt_id, dtype=np.int64)
+
+    def ids(rows, table):
+        rows = rows.astype(np.int64)
+        return np.where(rows >= 0, table[np.maximum(rows, 0)], -1) if len(table) else \
+            np.full(len(rows), -1, dtype=np.int64)
+    gi, di = t["gt_ident"], t["dt_ident"]
+    tracks = np.stack([ids(gi[:, 0], dt_id), gi[:, 1].astype(np.int64),
+                       np.diff(np.asarray(flat.gt_frame_off, dtype=np.int64))], axis=1)
+    dt_tracks = np.stack([ids(di[:, 0], gt_id), di[:, 1].astype(np.int64),
+                          np.diff(np.asarray(flat.dt_frame_off, dtype=np.int64))], axis=1)
+    return {"columns": list(IDENT_CAT_COLUMNS), "cat_counts": cat_counts,
+            "idf1": idf1, "idp": idp, "idr": idr, "total": total, "frame_thr": frame_thr,
+            "tracks": (gt_id, tracks), "dt_tracks": (dt_id, dt_tracks)}
+
+
+def identity_lines(e):
+    """TaoEval.identity()'s result `e` as a small text table: the totals over
+    the categories."""
+    t = e["total"]
+
+    def pct(v):
+        return "{:.2f}".format(100.0 * v) if v == v else "-"
+    return [" track identity @[ frame IoU={:0.2f} ]".format(e["frame_thr"]),
+            " IDF1={}  IDP={}  IDR={}".format(pct(t["idf1"]), pct(t["idp"]), pct(t["idr"])),
+            " " + "  ".join("{}={}".format(c, t[c]) for c in list(e["columns"]) + ["idfn", "idfp"])]
 
 
 def now():

@@ -435,6 +435,9 @@ class DistRun:
     def occlusion_table(self, frame_thr, vis_rng, recover, len_edges, ann_vis):
         raise NotImplementedError("occlusions() in a multi-GPU run")
 
+    def identity_table(self, frame_thr):
+        raise NotImplementedError("identity() in a multi-GPU run")
+
     def pointer_tables(self):
         if self._pointers is None:
             raise NotImplementedError(

@@ -116,6 +116,7 @@ class TaoEval:
         self._confusion = {}
         self._association = {}
         self._occlusions = {}
+        self._identity = {}
         self._gt_columns = None
 
     # ------------------------------------------------------------ stages
@@ -175,6 +176,7 @@ class TaoEval:
         self._confusion = {}
         self._association = {}
         self._occlusions = {}
+        self._identity = {}
         self._gt_columns = gt_cols      # the annotation rows the tables' frames name
         self._run.evaluate()
         P = self.params
@@ -605,6 +607,62 @@ class TaoEval:
         shares of the episodes that have one of these three outcomes, and held /
         frames, in per cent.  Returned, not printed."""
         return _core.occlusion_lines(self.occlusions(frame_thr, vis_rng, recover, len_edges))
+
+    def identity(self, frame_thr=0.5, per_track=False):
+        """IDF1, IDP and IDR (Ristani et al., ECCV 2016; TrackEval's Identity):
+        the identity measure beside Track-AP.  association() is many-to-one --
+        one detection track may be the primary of several ground-truth tracks,
+        and a ground truth's covered frames may be spread over many ids; its
+        switches and fragments are the symptoms, this is the cost.  Each
+        ground-truth track may own ONE detection track and each detection track
+        at most one ground truth: under that rule, how many frames can be
+        explained?  A maximum-weight one-to-one assignment per (video, category),
+        solved on the device on request (csrc/track_identity.hip).  Callable
+        after evaluate(), cached per threshold.
+
+        Rows are the tracks that survived the max_dets cut and the federated
+        filter.  The weight of a pair of one video and category is its `share`:
+        the frames of the ground truth on which the detection track has a box
+        whose box IoU (pycocotools' bbIou, not crowd) with the ground truth's is
+        at least `frame_thr`, a double in (0, 1].  Ground-truth tracks marked
+        "ignore" take no part.  A detection track is set aside -- neither
+        assigned nor counted -- if its greatest share with an ignored ground
+        truth exceeds its greatest share with any other, or if it is marked
+        "ignore unmatched" (a category that is not exhaustively annotated or
+        absent in the video) and shares no frame with a ground truth that takes
+        part.  `idtp` is the greatest sum of shares an assignment reaches, `idfn`
+        = gt_frames - idtp, `idfp` = dt_frames - idtp; IDR = idtp / gt_frames,
+        IDP = idtp / dt_frames, IDF1 = 2 idtp / (gt_frames + dt_frames), NaN where
+        the denominator is 0.  The exact rules are in include/tao_amodal_hip.h,
+        section "track-level identity".
+
+        Returns {"columns": the names of cat_counts' columns, "cat_counts":
+        int64[K, 6] = gt_tracks, gt_frames, dt_tracks, dt_frames, idtp, pairs
+        with the category axis in the order of params.cat_ids, "idf1", "idp",
+        "idr": float64[K], "total": {the six sums, "idfn", "idfp", "idf1", "idp",
+        "idr"}, "frame_thr"}; with per_track=True "tracks": (ground-truth track
+        ids, int64[n_gt, 3] = the assigned detection track's id or -1, the
+        shared frames, the track's frames) and "dt_tracks": (detection track
+        ids, int64[n_dt, 3] = the assigned ground-truth track's id or -1, kept,
+        frames).  Every count is exact and the same from run to run; where
+        several assignments reach the optimum, the one reported is one of them.
+        Not available: iou_type="segm", use_cats = 0, multi-GPU runs."""
+        if self._run is None:
+            raise RuntimeError("Please run evaluate() first.")
+        frame_thr = float(frame_thr)
+        if not 0 < frame_thr <= 1:
+            raise ValueError("frame_thr: {} is not in (0, 1]".format(frame_thr))
+        hit = self._identity.get(frame_thr)
+        if hit is None:
+            hit = _core.identity(self, frame_thr)
+            self._identity[frame_thr] = hit
+        drop = () if per_track else ("tracks", "dt_tracks")
+        return {k: v for k, v in hit.items() if k not in drop}
+
+    def identity_lines(self, frame_thr=0.5):
+        """identity() as a small text table: the totals over the categories.
+        Returned, not printed."""
+        return _core.identity_lines(self.identity(frame_thr))
 
     def impact_lines(self, iou_thr=0.5, bg_thr=0.1):
         """error_impact() as a small text table: a line per (area, time) range,

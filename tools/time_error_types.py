@@ -4,7 +4,8 @@ taoamd_track_error_types) on the synthetic configurations of bench.py, with HIP
 events:
 
     python tools/time_error_types.py [--level image|track] [--config 3s] [--reps 20] [--warmup 3]
-                                     [--impact] [--association] [--occlusions] [--confusion]
+                                     [--impact] [--association] [--occlusions] [--identity]
+                                     [--confusion]
 
 Times, on the image level's tables of that configuration, each alone on an idle
 stream: the fused match as a benchmark step runs it (the yardstick), the
@@ -25,7 +26,11 @@ track --association times, instead of the breakdown, the per-frame followers
 (engine.stage_track_association) and the plan-less taoamd_track_iou over the
 same cells in the same process.  --level track --occlusions times the occlusion
 episodes (engine.stage_track_occlusion: count and fill each alone, the whole
-stage) beside the association pass they follow, in the same process.  --confusion
+stage) beside the association pass they follow, in the same process.  --level
+track --identity times the identity measures: taoamd_track_identity_share and
+taoamd_track_identity_assign each alone between HIP events and the whole stage
+(engine.stage_track_identity), beside the association pass without windows in
+the same process.  --confusion
 (both levels) adds the confusion table: the level's links pass,
 taoamd_confusion_count and taoamd_confusion_fill, each alone between HIP events
 in the same process, the whole stage with its read of the entry count, the
@@ -114,6 +119,8 @@ def track_level(a, gt, dt, dev, V):
         return association(a, res, gt, fl, dp, ws, timed)
     if a.occlusions:
         return occlusions(a, res, gt, fl, dp, ws, timed)
+    if a.identity:
+        return identity(a, res, dp, ws, timed)
     res["match_fused"] = timed(lambda: engine.stage_match(dp, ws))
     # the first call builds the per-video lists and runs the match for match_gt
     engine.stage_track_error_types(dp, ws, 0, a.bg_thr)
@@ -328,6 +335,81 @@ def occlusions(a, res, gt, fl, dp, ws, timed):
     print(json.dumps(res))
 
 
+def identity(a, res, dp, ws, timed):
+    """--level track --identity: the identity measures (engine.stage_track_identity)
+    at frame_thr 0.5: taoamd_track_identity_share and taoamd_track_identity_assign
+    each alone between HIP events, the whole stage (which reads the status word),
+    the association pass without windows in the same process, the kernels of the
+    three, and what the assignment met: the cells with a pair to assign, the
+    largest sides, the totals."""
+    import torch
+    from tao_amodal_amd import _lib, engine
+    lib = _lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    thr = 0.5
+    # the first calls allocate the buffers of both passes
+    engine.stage_track_identity(dp, ws, thr)
+    engine.stage_track_association(dp, ws, thr, [])
+    torch.cuda.synchronize()
+    t = dp.t
+    sizes = (dp.n_dt, dp.n_gt, dp.n_cells, dp.n_iou, int(t["dt_frame_pos"].numel()),
+             int(t["gt_frame_pos"].numel()))
+    cells = (t["cell_dt_off"].data_ptr(), t["cell_gt_off"].data_ptr(),
+             t["cell_iou_off"].data_ptr())
+
+    def share():
+        _lib.check(lib.taoamd_track_identity_share(
+            *sizes, thr, *cells, t["dt_frame_off"].data_ptr(), t["dt_frame_pos"].data_ptr(),
+            t["dt_frame_box"].data_ptr(), t["gt_frame_off"].data_ptr(),
+            t["gt_frame_pos"].data_ptr(), t["gt_frame_box"].data_ptr(),
+            ws.ident_share.data_ptr(), ws.ident_ws.data_ptr(), ws.ident_bytes, stream),
+            "taoamd_track_identity_share")
+
+    def assign():
+        _lib.check(lib.taoamd_track_identity_assign(
+            *sizes, dp.n_cat, *cells, t["gt_cat"].data_ptr(), t["gt_flags"].data_ptr(),
+            t["dt_cat"].data_ptr(), t["dt_flags"].data_ptr(), t["dt_frame_off"].data_ptr(),
+            t["gt_frame_off"].data_ptr(), ws.ident_share.data_ptr(),
+            ws.ident_cat_counts.data_ptr(), ws.ident_gt.data_ptr(), ws.ident_dt.data_ptr(),
+            ws.ident_status.data_ptr(), ws.ident_ws.data_ptr(), ws.ident_bytes, stream),
+            "taoamd_track_identity_assign")
+    res["track_association_no_windows"] = timed(
+        lambda: engine.stage_track_association(dp, ws, thr, []))
+    res["identity_share"] = timed(share)
+    res["identity_assign"] = timed(assign)
+    res["identity_stage"] = timed(lambda: engine.stage_track_identity(dp, ws, thr))
+    _lib.kernel_timing(True)
+    for _ in range(a.reps):
+        engine.stage_track_association(dp, ws, thr, [])
+        share()
+        assign()
+    res["kernels_ms"] = {k: round(ms / n, 4) for k, (ms, n) in _lib.kernel_timings().items()}
+    _lib.kernel_timing(False)
+    torch.cuda.synchronize()
+    # what the assignment met, from the share matrix (on the device, untimed)
+    sh = ws.ident_share[:dp.n_iou]
+    cell_of = torch.repeat_interleave(
+        torch.arange(dp.n_cells, device=sh.device),
+        (t["cell_iou_off"][1:] - t["cell_iou_off"][:-1]).long())
+    hit = torch.zeros(dp.n_cells, dtype=torch.int64, device=sh.device)
+    hit.index_add_(0, cell_of, (sh > 0).long())
+    res["identity_status"] = int(ws.ident_status.item())
+    res["identity_pairs_with_share"] = int((sh > 0).sum().item())
+    res["identity_cells_with_share"] = int((hit > 0).sum().item())
+    res["identity_most_pairs_with_share_in_a_cell"] = int(hit.max().item()) if dp.n_cells else 0
+    res["identity_share_max"] = int(sh.max().item()) if dp.n_iou else 0
+    res["identity_largest_cell"] = [
+        int((t["cell_dt_off"][1:] - t["cell_dt_off"][:-1]).max().item()),
+        int((t["cell_gt_off"][1:] - t["cell_gt_off"][:-1]).max().item())]
+    res["identity_workspace_bytes"] = int(ws.ident_bytes)
+    res["identity_share_bytes"] = 4 * dp.n_iou
+    res["identity_columns"] = list(_lib.IDENT_CAT_COLUMNS)
+    tot = ws.ident_cat_counts.sum(0).tolist()
+    res["identity_totals"] = tot
+    res["idf1"] = round(2 * tot[4] / max(tot[1] + tot[3], 1), 6)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--level", choices=("image", "track"), default="image")
@@ -341,12 +423,15 @@ def main():
     ap.add_argument("--impact", action="store_true")
     ap.add_argument("--association", action="store_true")
     ap.add_argument("--occlusions", action="store_true")
+    ap.add_argument("--identity", action="store_true")
     ap.add_argument("--confusion", action="store_true")
     a = ap.parse_args()
     if a.association and a.level != "track":
         ap.error("--association is the track level's: --level track")
     if a.occlusions and a.level != "track":
         ap.error("--occlusions is the track level's: --level track")
+    if a.identity and a.level != "track":
+        ap.error("--identity is the track level's: --level track")
     import torch
     from tao_amodal_amd import _lib, engine, flatten_dev
     from tao_amodal_amd.synth import synth
