@@ -1375,10 +1375,12 @@ int taoamd_track_error_types_links(int64_t n_dt, int64_t n_gt, int64_t n_cells, 
  * does not depend on the order of arrival; no float is ever added.
  * TAOAMD_ERR_ARG: frame_thr outside (0, 1] (a NaN included), n_vis outside
  * [0, 8], a size below 0; TAOAMD_ERR_WORKSPACE: fewer bytes than
- * taoamd_track_association_workspace(n_dt, n_gt, n_gt_frames) (a descriptor per
- * detection track, the cell of every ground-truth row, the track of every
- * ground-truth frame, a track's counts per window; any base address, contents
- * need not be initialised).  Both
+ * taoamd_track_association_workspace(n_dt, n_gt, n_gt_frames) (the frame index
+ * -- a descriptor per detection track, the cell of every ground-truth row, the
+ * track of every ground-truth frame: csrc/track_frames.hpp builds it, for this
+ * pass and for taoamd_track_identity_share alike, in the call's own workspace --
+ * and a track's counts per window; any base address, contents need not be
+ * initialised).  Both
  * are answered before the first device call.  Rows and frames named by the CSR
  * tables that lie outside the tables are skipped, never dereferenced: a ground-
  * truth row no cell lists has no candidates, a frame no track lists no follower. */
@@ -1557,8 +1559,8 @@ int taoamd_track_occlusion_fill(int64_t n_gt, int64_t n_gt_frames, int32_t n_cat
  * TAOAMD_ERR_ARG: frame_thr outside (0, 1] (a NaN included), a size below 0 or
  * beyond int32, n_cat <= 0, a missing table; TAOAMD_ERR_WORKSPACE: fewer bytes
  * than taoamd_track_identity_workspace(n_dt, n_gt, n_gt_frames), one size for both
- * calls (the association's three descriptor tables and 40 bytes of search state
- * per row; any base address, contents need not be initialised, and nothing is
+ * calls (the association's frame index, built by the same code of
+ * csrc/track_frames.hpp, and 40 bytes of search state per row; any base address, contents need not be initialised, and nothing is
  * carried from one call to the other; the size function answers 0 to sizes it
  * refuses).  Both are answered before the first device call.  Rows and frames
  * named by the tables that lie outside them are skipped, never dereferenced. */

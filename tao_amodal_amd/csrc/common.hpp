@@ -172,6 +172,54 @@ __device__ __forceinline__ void wave_count(T *base, bool live, int32_t key)
     }
 }
 
+// The sum / the greatest of v over all 64 lanes, in every lane
+template <typename T> __device__ __forceinline__ T wave_sum(T v)
+{
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+template <typename T> __device__ __forceinline__ T wave_max(T v)
+{
+#pragma unroll
+    for (int o = WAVE / 2; o > 0; o >>= 1) {
+        const T w = __shfl_xor(v, o);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+
+// wave_count with amounts instead of ones: base[key * stride + c] += the sum of
+// v[c] over the wavefront's live lanes of that key, one add per (distinct key,
+// column with a non-zero sum), by the key's first lane.  Integer adds: order-free.
+template <int N, typename T>
+__device__ __forceinline__ void wave_add(unsigned long long *base, int64_t stride, bool live,
+                                         int32_t key, const T (&v)[N])
+{
+    uint64_t left = __ballot(live);
+    while (left) {
+        const int lead = __builtin_ctzll(left);
+        const int32_t k = __builtin_amdgcn_readlane(key, lead);
+        const bool mine = live && key == k;
+        const uint64_t same = __ballot(mine);
+        long long s[N];
+#pragma unroll
+        for (int c = 0; c < N; c++) s[c] = wave_sum(mine ? (long long)v[c] : 0ll);
+        if (lane_id() == lead) {
+            unsigned long long *row = base + (int64_t)k * stride;
+#pragma unroll
+            for (int c = 0; c < N; c++)
+                if (s[c]) atomicAdd(row + c, (unsigned long long)s[c]);
+        }
+        left &= ~same;
+    }
+}
+
+__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi)
+{
+    return v < lo ? lo : (v > hi ? hi : v);
+}
+
 // The error types of the breakdowns (error_types.hip, track_error_types.hip)
 // and of the impact sweep that reads their type bytes (error_impact.hip): the
 // numbering of include/tao_amodal_hip.h ("0 TP" .. "6 BKG"), which is the

@@ -8,10 +8,10 @@
 // at p_k, g's box) where d has a frame at p_k, and best_k(g) = the candidate of
 // the greatest f >= frame_thr, the lowest row among equal values, -1 if none.
 //
-//   assoc_dt_meta_kernel  lane = detection track: {first frame, end, first and
-//                         last position} of its frame list, clamped to the tables
-//   assoc_cell_kernel     lane = cell: the cell of every ground-truth row
-//   assoc_frame_kernel    wavefront = ground-truth track: the track of every frame
+//   frames_build          the frame index (track_frames.hpp, shared with the
+//                         identity's share pass): a detection track's frame range
+//                         and positions, the cell of a ground-truth row, the track
+//                         of a ground-truth frame
 //   assoc_pair_kernel     THE HOT ONE.  lane = ground-truth frame, the whole table
 //                         as one flat list: a lane holds its frame's box and
 //                         position in registers and walks the cell's detection
@@ -22,10 +22,11 @@
 //                         found in its position list (strictly ascending integers)
 //                         between the two indices the track's first and last
 //                         position allow: a track without holes is ONE probe, else
-//                         a binary search between them.  Lanes of a wavefront are
-//                         consecutive frames, as a rule of one track: the
-//                         candidate's descriptor is one address for all of them,
-//                         the probes touch neighbouring entries.
+//                         a binary search between them (frames_find's lines,
+//                         written out: see track_frames.hpp).  Lanes of a
+//                         wavefront are consecutive frames, as a rule of one track:
+//                         the candidate's descriptor is one address for all of
+//                         them, the probes touch neighbouring entries.
 //   assoc_walk_kernel     wavefront = ground-truth track, lane = frame of a chunk of
 //                         64: best[] is read coalesced; covered, fragments and
 //                         switches are popcounts of ballots (the covered frame
@@ -41,10 +42,12 @@
 //                         which need the primary
 //   assoc_tally_kernel    lane = ground-truth track: its row into the two count
 //                         tables, integer adds, one per (wavefront, category,
-//                         column)
+//                         column) (wave_add of common.hpp)
 // (A lane per track that walks its own frames, the first form of the three, took
 // 0.63 ms at 20 000 tracks of 150 frames: 300 wavefronts, every load 64 cache
 // lines, two dependent walks.  See DESIGN.md section 8.)
+// Registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950):
+//   assoc_pair_kernel 36 VGPRs, 34 SGPRs, 8 waves/SIMD, no scratch, no LDS.
 // box_iou is common.hpp's, compiled with -ffp-contract=off like every other use:
 // the bits of taoamd_bb_iou.  Everything else is an integer.
 #include "common.hpp"
@@ -80,26 +83,16 @@ struct AssocArgs {
     unsigned long long *vis_counts;  // [n_vis][n_cat][3]
     int32_t *best;                   // [n_gt_frames]
     double *best_iou;                // [n_gt_frames] or null
-    int4 *dt_meta;                   // [n_dt] {first frame, end, first position, last position}
-    int32_t *gt_cell;                // [n_gt], -1: in no cell
-    int32_t *frame_gt;               // [n_gt_frames], -1: of no track
+    FrameTables ft;                  // the frame index (track_frames.hpp)
     int32_t *trk_vis;                // [n_gt][8][3]: a track's counts per visibility window
 };
-
-// (the three descriptor tables: track_frames.hpp, shared with the identity's share
-// pass)
-__global__ __launch_bounds__(256) void assoc_dt_meta_kernel(AssocArgs a) { frames_dt_meta(a); }
-
-__global__ __launch_bounds__(256) void assoc_cell_kernel(AssocArgs a) { frames_gt_cell(a); }
-
-__global__ __launch_bounds__(256) void assoc_frame_kernel(AssocArgs a) { frames_frame_gt(a); }
 
 __global__ __launch_bounds__(TA_TILE) void assoc_pair_kernel(AssocArgs a)
 {
     const int64_t k = (int64_t)blockIdx.x * TA_TILE + threadIdx.x;
     if (k >= a.n_gt_frames) return;
-    const int32_t g = a.frame_gt[k];
-    const int32_t cell = g >= 0 ? a.gt_cell[g] : -1;
+    const int32_t g = a.ft.frame_gt[k];
+    const int32_t cell = g >= 0 ? a.ft.gt_cell[g] : -1;
     int64_t d0 = 0, d1 = 0;
     if (cell >= 0) {
         d0 = clamp64(a.cell_dt_off[cell], 0, a.n_dt);
@@ -111,10 +104,9 @@ __global__ __launch_bounds__(TA_TILE) void assoc_pair_kernel(AssocArgs a)
         const int64_t p = a.gfpos[k];
         const double4 G = a.gfbox[k];
         for (int64_t d = d0; d < d1; d++) {
-            const int4 m = a.dt_meta[d];
+            // (frames_find of track_frames.hpp, written out: see the note there)
+            const int4 m = a.ft.dt_meta[d];
             if (p < m.z || p > m.w) continue;          // (a track without frames: z > w)
-            // positions ascend strictly: the frame at p, if any, lies no further from
-            // the list's first entry than p from its position, nor from its last
             int64_t lo = max((int64_t)m.x, (int64_t)m.y - 1 - ((int64_t)m.w - p));
             int64_t hi = min((int64_t)m.y - 1, (int64_t)m.x + (p - (int64_t)m.z));
             while (lo < hi) {
@@ -136,36 +128,6 @@ __global__ __launch_bounds__(TA_TILE) void assoc_pair_kernel(AssocArgs a)
     if (a.best_iou) a.best_iou[k] = top;
 }
 
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// base[key * N + c] += the sum of v[c] over the wavefront's live lanes of that
-// key: one add per (distinct key, column with a sum), by the key's first lane
-// (wave_count of common.hpp with amounts instead of ones).
-template <int N>
-__device__ __forceinline__ void assoc_add(unsigned long long *base, bool live, int32_t key,
-                                          const int32_t (&v)[N])
-{
-    uint64_t left = __ballot(live);
-    while (left) {
-        const int lead = __builtin_ctzll(left);
-        const int32_t k = __builtin_amdgcn_readlane(key, lead);
-        const bool mine = live && key == k;
-        const uint64_t same = __ballot(mine);
-#pragma unroll
-        for (int c = 0; c < N; c++) {
-            const long long s = wave_sum(mine ? (long long)v[c] : 0ll);
-            if (lane_id() == lead && s != 0)
-                atomicAdd(base + (int64_t)k * N + c, (unsigned long long)s);
-        }
-        left &= ~same;
-    }
-}
-
 // A wavefront's ground-truth track: its frames [s, e), its candidates [d0, d0 + D)
 // and its column of `follow` (entry d at col + d * G), clamped to the tables.
 struct OwnColumn {
@@ -175,7 +137,7 @@ struct OwnColumn {
         s = clamp64(a.gfoff[g], 0, a.n_gt_frames);
         e = clamp64(a.gfoff[g + 1], s, a.n_gt_frames);
         d0 = D = G = col = 0;
-        const int32_t cell = a.gt_cell[g];
+        const int32_t cell = a.ft.gt_cell[g];
         if (cell >= 0) {
             d0 = clamp64(a.cell_dt_off[cell], 0, a.n_dt);
             D = clamp64(a.cell_dt_off[cell + 1], d0, a.n_dt) - d0;
@@ -241,16 +203,6 @@ __global__ __launch_bounds__(256) void assoc_walk_kernel(AssocArgs a)
     }
 }
 
-__device__ __forceinline__ unsigned long long wave_max(unsigned long long v)
-{
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) {
-        const unsigned long long w = __shfl_xor(v, o);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
 // wavefront = ground-truth track, behind the walk (a kernel boundary: the column
 // is complete).  Lanes stride the column: ids, and the primary as the greatest
 // (count, ~index); then the frames once more, coalesced, for the visibility
@@ -271,7 +223,7 @@ __global__ __launch_bounds__(256) void assoc_column_kernel(AssocArgs a)
         ids += c > 0;
         top = c > 0 && key > top ? key : top;
     }
-    ids = (int32_t)wave_sum(ids);
+    ids = wave_sum(ids);
     top = wave_max(top);
     const int32_t prim = top ? (int32_t)~(uint32_t)top : -1;
     int32_t cnt[TA_VMAX][TA_NVIS];
@@ -324,7 +276,7 @@ __global__ __launch_bounds__(256) void assoc_tally_kernel(AssocArgs a)
     const int32_t row[TA_NCAT] = {1, frames, covered, ids, switches, fragments,
                                   5 * (int64_t)covered >= 4 * (int64_t)frames,
                                   5 * (int64_t)covered < (int64_t)frames};
-    assoc_add<TA_NCAT>(a.cat_counts, ok, cat, row);
+    wave_add(a.cat_counts, TA_NCAT, ok, cat, row);
 #pragma unroll
     for (int w = 0; w < TA_VMAX; w++) {
         if (w >= a.n_vis) continue;          // (uniform)
@@ -333,16 +285,14 @@ __global__ __launch_bounds__(256) void assoc_tally_kernel(AssocArgs a)
             const int32_t *v = a.trk_vis + g * (TA_VMAX * TA_NVIS) + w * TA_NVIS;
             cnt[0] = v[0]; cnt[1] = v[1]; cnt[2] = v[2];
         }
-        assoc_add<TA_NVIS>(a.vis_counts + (int64_t)w * a.n_cat * TA_NVIS, ok, cat, cnt);
+        wave_add(a.vis_counts + (int64_t)w * a.n_cat * TA_NVIS, TA_NVIS, ok, cat, cnt);
     }
 }
 
 // The tables of the pass, in buffer order: a function of (n_dt, n_gt, n_gt_frames)
 static void assoc_layout(Carve &c, int64_t n_dt, int64_t n_gt, int64_t n_gt_frames, AssocArgs &a)
 {
-    a.dt_meta = c.take<int4>((size_t)n_dt);
-    a.gt_cell = c.take<int32_t>((size_t)n_gt);
-    a.frame_gt = c.take<int32_t>((size_t)n_gt_frames);
+    frames_layout(c, n_dt, n_gt, n_gt_frames, a.ft);
     a.trk_vis = c.take<int32_t>((size_t)n_gt * TA_VMAX * TA_NVIS);
 }
 
@@ -406,24 +356,16 @@ extern "C" int taoamd_track_association(
         TAO_HIP(hipMemsetAsync(vis_counts, 0, (size_t)n_vis * n_cat * TA_NVIS * sizeof(int64_t), s));
     if (n_iou > 0) TAO_HIP(hipMemsetAsync(follow, 0, (size_t)n_iou * sizeof(int32_t), s));
     if (n_gt == 0) return TAOAMD_OK;
-    // (a ground-truth row no cell lists has no candidates, a frame no track lists no follower)
-    TAO_HIP(hipMemsetAsync(a.gt_cell, 0xff, (size_t)n_gt * sizeof(int32_t), s));
+    // (empty sides: the rule of track_frames.hpp.  A ground-truth row no cell lists has
+    // no candidates, a frame no track lists no follower)
+    const FrameSource src = {n_dt, n_gt, n_cells, n_dt_frames, n_gt_frames,
+                             cell_gt_off, dt_frame_off, dt_frame_pos, gt_frame_off};
+    const int st = frames_build(src, a.ft, s);
+    if (st != TAOAMD_OK) return st;
     if (n_gt_frames > 0)
-        TAO_HIP(hipMemsetAsync(a.frame_gt, 0xff, (size_t)n_gt_frames * sizeof(int32_t), s));
-    if (n_dt > 0)
-        TAO_TIMED("assoc_dt_meta_kernel", s,
-                  assoc_dt_meta_kernel<<<(unsigned)((n_dt + 255) / 256), 256, 0, s>>>(a));
-    if (n_cells > 0)
-        TAO_TIMED("assoc_cell_kernel", s,
-                  assoc_cell_kernel<<<(unsigned)((n_cells + 255) / 256), 256, 0, s>>>(a));
-    if (n_gt_frames > 0) {
-        TAO_TIMED("assoc_frame_kernel", s,
-                  assoc_frame_kernel<<<(unsigned)((n_gt + 256 / WAVE - 1) / (256 / WAVE)), 256, 0,
-                                       s>>>(a));
         TAO_TIMED("assoc_pair_kernel", s,
                   assoc_pair_kernel<<<(unsigned)((n_gt_frames + TA_TILE - 1) / TA_TILE), TA_TILE,
                                       0, s>>>(a));
-    }
     const int per = 256 / WAVE;
     const unsigned track_blocks = (unsigned)((n_gt + per - 1) / per);
     TAO_TIMED("assoc_walk_kernel", s, assoc_walk_kernel<<<track_blocks, 256, 0, s>>>(a));

@@ -1,23 +1,53 @@
-// What the passes over (ground-truth frame) x (the detection tracks of its cell)
-// share -- the association (track_association.hip) and the identity's share pass
-// (track_identity.hip): the three descriptor tables both build in their
-// workspace, and the probe of a detection track's frame list for a timeline
-// position (the association's pair kernel, written first, has the same lines in
-// its loop: moving them here changed its register allocation, so they stay).
-// Args is the pass's argument struct: n_dt, n_gt, n_cells, n_dt_frames,
-// n_gt_frames, cell_gt_off, dfoff, dfpos, gfoff, dt_meta, gt_cell, frame_gt.
+// The frame index of the passes over (ground-truth frame) x (the detection
+// tracks of its cell) -- the association (track_association.hip) and the
+// identity's share pass (track_identity.hip): three descriptor tables in the
+// pass's workspace, the one build of them, and the probe of a detection track's
+// frame list for a timeline position.  (assoc_pair_kernel has frames_find's lines
+// written out in its loop: calling it, or a form that takes the hit's body, cost
+// the kernel 38 VGPRs for 36 and, on an MI355X beside the written-out form in one
+// run, 0.351-0.354 ms for 0.347-0.349.  ident_share_kernel
+// calls it.)
+//
+//   frames_dt_meta_kernel   lane = detection track: {first frame, end, first and
+//                           last position} of its frame list, clamped to the tables
+//   frames_gt_cell_kernel   lane = cell: the cell of every ground-truth row
+//   frames_frame_gt_kernel  wavefront = ground-truth track: the track of every frame
+//
+// EMPTY SIDES, the one rule: frames_build leaves every table complete whatever
+// is empty -- a table without rows costs neither a memset nor a launch; a ground-
+// truth row no cell lists and a frame no track lists read -1, a detection track
+// without frames has first position > last, and the frame kernels then find no
+// candidate.  A pass returns before the build where it has no ground-truth track
+// (n_gt == 0: no row to write) and launches its frame kernel behind it where
+// there are ground-truth frames (n_gt_frames > 0).
 #pragma once
 #include "common.hpp"
+#include "workspace.hpp"
 
 namespace taoamd {
 
-__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi)
+struct FrameTables {
+    int4 *dt_meta;                   // [n_dt] {first frame, end, first position, last position}
+    int32_t *gt_cell;                // [n_gt], -1: in no cell
+    int32_t *frame_gt;               // [n_gt_frames], -1: of no track
+};
+
+// The tables come first in the workspace of either pass
+static inline void frames_layout(Carve &c, int64_t n_dt, int64_t n_gt, int64_t n_gt_frames,
+                                 FrameTables &t)
 {
-    return v < lo ? lo : (v > hi ? hi : v);
+    t.dt_meta = c.take<int4>((size_t)n_dt);
+    t.gt_cell = c.take<int32_t>((size_t)n_gt);
+    t.frame_gt = c.take<int32_t>((size_t)n_gt_frames);
 }
 
-// lane = detection track: {first frame, end, first and last position} of its frame list
-template <class Args> __device__ __forceinline__ void frames_dt_meta(const Args &a)
+// What the tables are built from
+struct FrameSource {
+    int64_t n_dt, n_gt, n_cells, n_dt_frames, n_gt_frames;
+    const int32_t *cell_gt_off, *dfoff, *dfpos, *gfoff;
+};
+
+static __global__ __launch_bounds__(256) void frames_dt_meta_kernel(FrameSource a, FrameTables t)
 {
     const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (d >= a.n_dt) return;
@@ -29,27 +59,45 @@ template <class Args> __device__ __forceinline__ void frames_dt_meta(const Args 
         m.z = a.dfpos[fs];
         m.w = a.dfpos[fe - 1];
     }
-    a.dt_meta[d] = m;
+    t.dt_meta[d] = m;
 }
 
-// lane = cell: the cell of every ground-truth row
-template <class Args> __device__ __forceinline__ void frames_gt_cell(const Args &a)
+static __global__ __launch_bounds__(256) void frames_gt_cell_kernel(FrameSource a, FrameTables t)
 {
     const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= a.n_cells) return;
     const int64_t g0 = clamp64(a.cell_gt_off[c], 0, a.n_gt);
     const int64_t g1 = clamp64(a.cell_gt_off[c + 1], g0, a.n_gt);
-    for (int64_t g = g0; g < g1; g++) a.gt_cell[g] = (int32_t)c;
+    for (int64_t g = g0; g < g1; g++) t.gt_cell[g] = (int32_t)c;
 }
 
-// wavefront = ground-truth track: the track of every frame
-template <class Args> __device__ __forceinline__ void frames_frame_gt(const Args &a)
+static __global__ __launch_bounds__(256) void frames_frame_gt_kernel(FrameSource a, FrameTables t)
 {
     const int64_t g = (int64_t)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
     if (g >= a.n_gt) return;
     const int64_t s = clamp64(a.gfoff[g], 0, a.n_gt_frames);
     const int64_t e = clamp64(a.gfoff[g + 1], s, a.n_gt_frames);
-    for (int64_t k = s + lane_id(); k < e; k += WAVE) a.frame_gt[k] = (int32_t)g;
+    for (int64_t k = s + lane_id(); k < e; k += WAVE) t.frame_gt[k] = (int32_t)g;
+}
+
+// The three tables on stream s, complete for any sizes (see EMPTY SIDES above)
+static inline int frames_build(const FrameSource &a, const FrameTables &t, hipStream_t s)
+{
+    if (a.n_gt > 0) TAO_HIP(hipMemsetAsync(t.gt_cell, 0xff, (size_t)a.n_gt * sizeof(int32_t), s));
+    if (a.n_gt_frames > 0)
+        TAO_HIP(hipMemsetAsync(t.frame_gt, 0xff, (size_t)a.n_gt_frames * sizeof(int32_t), s));
+    if (a.n_dt > 0)
+        TAO_TIMED("frames_dt_meta_kernel", s,
+                  frames_dt_meta_kernel<<<(unsigned)((a.n_dt + 255) / 256), 256, 0, s>>>(a, t));
+    if (a.n_cells > 0 && a.n_gt > 0)
+        TAO_TIMED("frames_gt_cell_kernel", s,
+                  frames_gt_cell_kernel<<<(unsigned)((a.n_cells + 255) / 256), 256, 0, s>>>(a, t));
+    if (a.n_gt > 0 && a.n_gt_frames > 0) {
+        const int per = 256 / WAVE;
+        TAO_TIMED("frames_frame_gt_kernel", s,
+                  frames_frame_gt_kernel<<<(unsigned)((a.n_gt + per - 1) / per), 256, 0, s>>>(a, t));
+    }
+    return TAOAMD_OK;
 }
 
 // Whether the list that m describes has a frame at position p, and its index: a

@@ -10,16 +10,14 @@
 // of ground-truth track g on which detection track d has a frame with box_iou >=
 // frame_thr -- per pair a COUNT, neither the 3D IoU's sum nor the association's
 // arg-max.
-//   ident_dt_meta_kernel / ident_cell_kernel / ident_frame_kernel  the three
-//                        descriptors of the association's pass (a detection
+//   frames_build         the frame index of the association's pass (a detection
 //                        track's frame range and positions, the cell of a ground-
-//                        truth row, the track of a frame; track_frames.hpp), for
-//                        this call's workspace
+//                        truth row, the track of a frame; track_frames.hpp), built
+//                        into this call's workspace
 //   ident_share_kernel   lane = ground-truth frame, the whole table as one flat
-//                        list: the association's pair loop (a track without holes
-//                        is one probe, else a bisection between the two indices
-//                        its first and last position allow), but every candidate
-//                        with an overlap >= frame_thr counts, not the greatest:
+//                        list: the association's pair loop and its probe
+//                        (frames_find), but every candidate with an overlap
+//                        >= frame_thr counts, not the greatest:
 //                        an integer atomic add per (pair, wavefront) with a hit,
 //                        the lanes of one pair found by ballot.  No LDS, no limit
 //                        on a cell or a track.
@@ -54,13 +52,14 @@
 //                        sums of shares the most pairs with a positive one, so
 //                        that `pairs` is unique as well.
 //                        The count tables are integer adds, one per (wavefront
-//                        step, category, column).
+//                        step, category, column) (wave_add of common.hpp).
 // The wavefront is the workgroup, so __syncthreads() is the fence between its
 // lanes' stores and loads of the search state, in LDS and in global memory alike;
 // all control flow around it is uniform.
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950):
-//   ident_share_kernel 38 VGPRs, no LDS; ident_assign_kernel 54 VGPRs, 11 264 B
-//   of LDS (a workgroup is one wavefront: 14 cells a CU by LDS).
+//   ident_share_kernel 38 VGPRs, 30 SGPRs, 8 waves/SIMD, no scratch, no LDS;
+//   ident_assign_kernel 54 VGPRs, 11 264 B of LDS (a workgroup is one wavefront:
+//   14 cells a CU by LDS).
 #include "common.hpp"
 #include "track_frames.hpp"
 #include "workspace.hpp"
@@ -88,29 +87,19 @@ struct IdentArgs {
     unsigned long long *cat_counts;  // [n_cat][6]
     int32_t *gt_ident, *dt_ident;    // [n_gt][2], [n_dt][2]
     int32_t *status;
-    int4 *dt_meta;                   // [n_dt] {first frame, end, first position, last position}
-    int32_t *gt_cell;                // [n_gt], -1: in no cell
-    int32_t *frame_gt;               // [n_gt_frames], -1: of no track
+    FrameTables ft;                  // the frame index (track_frames.hpp)
     // the search state of the cells that do not fit in LDS, n_dt + n_gt entries
     // each: cell c owns [cell_dt_off[c] + cell_gt_off[c], the next cell's)
     long long *su, *sv, *sminv;
     int32_t *sp, *sway, *sused, *sidx;
 };
 
-// (the three descriptor tables and the probe of a frame list: track_frames.hpp,
-// shared with the association)
-__global__ __launch_bounds__(256) void ident_dt_meta_kernel(IdentArgs a) { frames_dt_meta(a); }
-
-__global__ __launch_bounds__(256) void ident_cell_kernel(IdentArgs a) { frames_gt_cell(a); }
-
-__global__ __launch_bounds__(256) void ident_frame_kernel(IdentArgs a) { frames_frame_gt(a); }
-
 __global__ __launch_bounds__(TI_TILE) void ident_share_kernel(IdentArgs a)
 {
     const int64_t k = (int64_t)blockIdx.x * TI_TILE + threadIdx.x;
     if (k >= a.n_gt_frames) return;
-    const int32_t g = a.frame_gt[k];
-    const int32_t cell = g >= 0 ? a.gt_cell[g] : -1;
+    const int32_t g = a.ft.frame_gt[k];
+    const int32_t cell = g >= 0 ? a.ft.gt_cell[g] : -1;
     if (cell < 0) return;
     const int64_t d0 = clamp64(a.cell_dt_off[cell], 0, a.n_dt);
     const int64_t d1 = clamp64(a.cell_dt_off[cell + 1], d0, a.n_dt);
@@ -121,7 +110,7 @@ __global__ __launch_bounds__(TI_TILE) void ident_share_kernel(IdentArgs a)
     const double4 B = a.gfbox[k];
     for (int64_t d = d0; d < d1; d++) {
         int64_t at = -1, lo;
-        if (frames_find(a.dfpos, a.dt_meta[d], p, lo)) {
+        if (frames_find(a.dfpos, a.ft.dt_meta[d], p, lo)) {
             const double4 D = a.dfbox[lo];
             const double v = box_iou(D.x, D.y, D.z, D.w, B.x, B.y, B.z, B.w);
             const int64_t i = col + (d - d0) * G;
@@ -148,35 +137,6 @@ __global__ __launch_bounds__(256) void ident_init_kernel(IdentArgs a)
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < a.n_gt) reinterpret_cast<int2 *>(a.gt_ident)[i] = make_int2(-1, 0);
     if (i < a.n_dt) reinterpret_cast<int2 *>(a.dt_ident)[i] = make_int2(-1, 0);
-}
-
-__device__ __forceinline__ long long ident_wave_sum(long long v)
-{
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// cat_counts[key][col0 + c] += the sum of v[c] over the wavefront's live lanes of
-// that key: one add per (distinct key, column with a sum), by the key's first lane
-__device__ __forceinline__ void ident_add(unsigned long long *cat_counts, bool live, int32_t key,
-                                          int col0, long long v0, long long v1)
-{
-    uint64_t left = __ballot(live);
-    while (left) {
-        const int lead = __builtin_ctzll(left);
-        const int32_t k = __builtin_amdgcn_readlane(key, lead);
-        const bool mine = live && key == k;
-        const uint64_t same = __ballot(mine);
-        const long long s0 = ident_wave_sum(mine ? v0 : 0ll);
-        const long long s1 = ident_wave_sum(mine ? v1 : 0ll);
-        if (lane_id() == lead) {
-            unsigned long long *row = cat_counts + (int64_t)k * TI_NCAT + col0;
-            if (s0) atomicAdd(row, (unsigned long long)s0);
-            if (s1) atomicAdd(row + 1, (unsigned long long)s1);
-        }
-        left &= ~same;
-    }
 }
 
 // A cell's share matrix: entry (d, g) in-cell, 0 outside the table; a share is a
@@ -326,7 +286,8 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
             frames = clamp64(a.dfoff[d0 + d + 1], fs, a.n_dt_frames) - fs;
             a.dt_ident[(d0 + d) * 2 + 1] = kept;
         }
-        ident_add(a.cat_counts, kept && cat >= 0 && cat < a.n_cat, cat, 2, 1, frames);
+        const long long dt_cols[2] = {1, frames};                 // dt_tracks, dt_frames
+        wave_add(a.cat_counts + 2, TI_NCAT, kept && cat >= 0 && cat < a.n_cat, cat, dt_cols);
         const bool act = kept && me > 0;
         top = act && me > top ? me : top;
         const uint64_t m = __ballot(act);
@@ -349,7 +310,8 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
             const int64_t fs = clamp64(a.gfoff[g0 + g], 0, a.n_gt_frames);
             frames = clamp64(a.gfoff[g0 + g + 1], fs, a.n_gt_frames) - fs;
         }
-        ident_add(a.cat_counts, elig && cat >= 0 && cat < a.n_cat, cat, 0, 1, frames);
+        const long long gt_cols[2] = {1, frames};                 // gt_tracks, gt_frames
+        wave_add(a.cat_counts, TI_NCAT, elig && cat >= 0 && cat < a.n_cat, cat, gt_cols);
         const uint64_t m = __ballot(act);
         if (act) glist[ng + __popcll(m & below)] = (int32_t)g;
         ng += __popcll(m);
@@ -363,11 +325,7 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
     // 64 bits while n * (n + 1) * (top + 1) < 2^62.  A share of the share kernel is
     // at most a track's frames, so real tables are far inside; a table that is not
     // is refused, never solved wrongly
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) {
-        const int32_t t = __shfl_xor(top, o);
-        top = t > top ? t : top;
-    }
+    top = wave_max(top);
     const unsigned long long nn = (unsigned long long)n * ((unsigned long long)n + 1);
     const unsigned long long ww = (unsigned long long)top + 1;
     if (__umul64hi(nn, ww) != 0 || nn * ww >= (1ull << 62)) {
@@ -407,7 +365,8 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
                 cat = a.gt_cat[g0 + g];
             }
         }
-        ident_add(a.cat_counts, w > 0 && cat >= 0 && cat < a.n_cat, cat, 4, w, 1);
+        const int32_t pair_cols[2] = {w, 1};                      // idtp, pairs
+        wave_add(a.cat_counts + 4, TI_NCAT, w > 0 && cat >= 0 && cat < a.n_cat, cat, pair_cols);
     }
 }
 
@@ -415,9 +374,7 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
 static void ident_layout(Carve &c, int64_t n_dt, int64_t n_gt, int64_t n_gt_frames, IdentArgs &a)
 {
     const size_t n = (size_t)(n_dt + n_gt);
-    a.dt_meta = c.take<int4>((size_t)n_dt);
-    a.gt_cell = c.take<int32_t>((size_t)n_gt);
-    a.frame_gt = c.take<int32_t>((size_t)n_gt_frames);
+    frames_layout(c, n_dt, n_gt, n_gt_frames, a.ft);
     a.su = c.take<long long>(n);
     a.sv = c.take<long long>(n);
     a.sminv = c.take<long long>(n);
@@ -474,20 +431,17 @@ extern "C" int taoamd_track_identity_share(
     a.gfbox = reinterpret_cast<const double4 *>(gt_frame_box);
     a.share = share;
     if (n_iou > 0) TAO_HIP(hipMemsetAsync(share, 0, (size_t)n_iou * sizeof(int32_t), s));
-    if (n_gt == 0 || n_gt_frames == 0 || n_dt == 0 || n_cells == 0) return TAOAMD_OK;
-    // (a ground-truth row no cell lists has no candidates, a frame no track lists counts nowhere)
-    TAO_HIP(hipMemsetAsync(a.gt_cell, 0xff, (size_t)n_gt * sizeof(int32_t), s));
-    TAO_HIP(hipMemsetAsync(a.frame_gt, 0xff, (size_t)n_gt_frames * sizeof(int32_t), s));
-    TAO_TIMED("ident_dt_meta_kernel", s,
-              ident_dt_meta_kernel<<<(unsigned)((n_dt + 255) / 256), 256, 0, s>>>(a));
-    TAO_TIMED("ident_cell_kernel", s,
-              ident_cell_kernel<<<(unsigned)((n_cells + 255) / 256), 256, 0, s>>>(a));
-    TAO_TIMED("ident_frame_kernel", s,
-              ident_frame_kernel<<<(unsigned)((n_gt + 256 / WAVE - 1) / (256 / WAVE)), 256, 0,
-                                   s>>>(a));
-    TAO_TIMED("ident_share_kernel", s,
-              ident_share_kernel<<<(unsigned)((n_gt_frames + TI_TILE - 1) / TI_TILE), TI_TILE, 0,
-                                   s>>>(a));
+    if (n_gt == 0) return TAOAMD_OK;
+    // (empty sides: the rule of track_frames.hpp.  A ground-truth row no cell lists has
+    // no candidates, a frame no track lists counts nowhere: share stays 0)
+    const FrameSource src = {n_dt, n_gt, n_cells, n_dt_frames, n_gt_frames,
+                             cell_gt_off, dt_frame_off, dt_frame_pos, gt_frame_off};
+    const int st = frames_build(src, a.ft, s);
+    if (st != TAOAMD_OK) return st;
+    if (n_gt_frames > 0)
+        TAO_TIMED("ident_share_kernel", s,
+                  ident_share_kernel<<<(unsigned)((n_gt_frames + TI_TILE - 1) / TI_TILE), TI_TILE,
+                                       0, s>>>(a));
     TAO_LAUNCH_CHECK();
     return TAOAMD_OK;
 }

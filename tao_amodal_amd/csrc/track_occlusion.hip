@@ -64,11 +64,6 @@ struct OccArgs {
     int32_t *episodes;                       // [cap][9]
 };
 
-__device__ __forceinline__ int64_t occ_clamp(int64_t v, int64_t lo, int64_t hi)
-{
-    return v < lo ? lo : (v > hi ? hi : v);
-}
-
 // One chunk: the lane's follower (-1 behind the track's end) and the ballots
 struct OccChunk {
     int32_t b;
@@ -102,8 +97,8 @@ __global__ __launch_bounds__(256) void occ_walk_kernel(OccArgs a)
     if (g >= a.n_gt) return;                 // (whole wavefronts)
     const int lane = lane_id();
     // (offsets clamped to the table: a bad CSR reads wrong frames, never past an end)
-    const int64_t s = occ_clamp(a.gfoff[g], 0, a.n_gt_frames);
-    const int64_t e = occ_clamp(a.gfoff[g + 1], s, a.n_gt_frames);
+    const int64_t s = clamp64(a.gfoff[g], 0, a.n_gt_frames);
+    const int64_t e = clamp64(a.gfoff[g + 1], s, a.n_gt_frames);
     const int32_t L = (int32_t)(e - s);
     int64_t row0 = 0, row1 = 0;
     if (FILL) {

@@ -1350,6 +1350,22 @@ def set_frame_visibility(dp, vis):
     dp.t["gt_frame_vis"] = torch.from_numpy(vis if len(vis) else np.zeros(1)).to(dp.device)
 
 
+def _track_tables(dp, what):
+    """What the stages of the three track analyses share: the refusal, in the
+    stage's own words `what`, and the argument groups of their entry points --
+    the sizes (n_dt, n_gt, n_cells, n_iou, n_dt_frames, n_gt_frames), the cells'
+    three offset tables, the six frame tables (detections first)."""
+    if dp.kind != "tao" or dp.mask_iou:
+        raise _lib.TaoAmdError("the track %s the track level's, on boxes" % what)
+    t = dp.t
+    sizes = (dp.n_dt, dp.n_gt, dp.n_cells, dp.n_iou,
+             int(t["dt_frame_pos"].numel()), int(t["gt_frame_pos"].numel()))
+    cells = (_ptr(t["cell_dt_off"]), _ptr(t["cell_gt_off"]), _ptr(t["cell_iou_off"]))
+    frames = (_ptr(t["dt_frame_off"]), _ptr(t["dt_frame_pos"]), _ptr(t["dt_frame_box"]),
+              _ptr(t["gt_frame_off"]), _ptr(t["gt_frame_pos"]), _ptr(t["gt_frame_box"]))
+    return sizes, cells, frames
+
+
 def stage_track_association(dp, ws, frame_thr, vis_rng):
     """Per-frame followers of the ground-truth tracks (taoamd_track_association;
     the definition is in include/tao_amodal_hip.h): ws.assoc_follow[n_iou] in the
@@ -1361,8 +1377,7 @@ def stage_track_association(dp, ws, frame_thr, vis_rng):
     track tables alone -- never ws.iou, never the match --, so it depends on
     neither the metric, the thresholds nor the ranges.  Buffers are allocated on
     the first call and kept with the workspace."""
-    if dp.kind != "tao" or dp.mask_iou:
-        raise _lib.TaoAmdError("the track association is the track level's, on boxes")
+    sizes, cells, frames = _track_tables(dp, "association is")
     lib, t, dev = _lib.load(), dp.t, dp.device
     vis_rng = np.ascontiguousarray(vis_rng if vis_rng is not None else [],
                                    dtype=np.float64).reshape(-1, 2)
@@ -1373,7 +1388,7 @@ def stage_track_association(dp, ws, frame_thr, vis_rng):
     if n_vis and t.get("gt_frame_vis") is None:
         raise _lib.TaoAmdError("visibility windows need the frames' visibility "
                                "(engine.set_frame_visibility)")
-    n_df, n_gf = int(t["dt_frame_pos"].numel()), int(t["gt_frame_pos"].numel())
+    n_gf = sizes[5]
     if ws.assoc_gt is None:
         ws.assoc_bytes = lib.taoamd_track_association_workspace(dp.n_dt, dp.n_gt, n_gf)
         ws.assoc_ws = torch.empty(max(int(ws.assoc_bytes), 256), dtype=torch.uint8, device=dev)
@@ -1392,12 +1407,8 @@ def stage_track_association(dp, ws, frame_thr, vis_rng):
         ws.assoc_vis_counts = None
     rng_t = torch.from_numpy(vis_rng).to(dev) if n_vis else None
     _lib.check(lib.taoamd_track_association(
-        dp.n_dt, dp.n_gt, dp.n_cells, dp.n_iou, n_df, n_gf, dp.n_cat, n_vis, float(frame_thr),
-        _ptr(t["cell_dt_off"]), _ptr(t["cell_gt_off"]), _ptr(t["cell_iou_off"]),
-        _ptr(t["gt_cat"]), _ptr(t["gt_flags"]),
-        _ptr(t["dt_frame_off"]), _ptr(t["dt_frame_pos"]), _ptr(t["dt_frame_box"]),
-        _ptr(t["gt_frame_off"]), _ptr(t["gt_frame_pos"]), _ptr(t["gt_frame_box"]),
-        _ptr(t["gt_frame_vis"]) if n_vis else None, _ptr(rng_t),
+        *sizes, dp.n_cat, n_vis, float(frame_thr), *cells, _ptr(t["gt_cat"]), _ptr(t["gt_flags"]),
+        *frames, _ptr(t["gt_frame_vis"]) if n_vis else None, _ptr(rng_t),
         _ptr(ws.assoc_follow), _ptr(ws.assoc_gt), _ptr(ws.assoc_cat_counts),
         _ptr(ws.assoc_vis_counts), _ptr(ws.assoc_best), _ptr(ws.assoc_best_iou),
         _ptr(ws.assoc_ws), ws.assoc_bytes, _stream()), "taoamd_track_association")
@@ -1421,8 +1432,8 @@ def stage_track_occlusion(dp, ws, frame_thr, vis_lo, vis_hi, recover, len_edges,
     only.  Buffers are allocated on the first call and kept with the workspace:
     4 bytes per ground-truth track of workspace, 24 per track and 88 per
     (category, bucket) of results, 36 per episode, regrown where a call finds more."""
-    if dp.kind != "tao" or dp.mask_iou:
-        raise _lib.TaoAmdError("the track occlusions are the track level's, on boxes")
+    sizes, _, frames = _track_tables(dp, "occlusions are")
+    n_gf = sizes[5]
     lib, t, dev, s = _lib.load(), dp.t, dp.device, _stream()
     if t.get("gt_frame_vis") is None:
         raise _lib.TaoAmdError("the occlusion episodes need the frames' visibility "
@@ -1435,7 +1446,6 @@ def stage_track_occlusion(dp, ws, frame_thr, vis_lo, vis_hi, recover, len_edges,
     frame_thr = float(frame_thr)
     if ws.assoc_gt is None or ws.assoc_frame_thr != frame_thr:
         stage_track_association(dp, ws, frame_thr, [])
-    n_gf = int(t["gt_frame_pos"].numel())
     if ws.occ_ws is None:
         ws.occ_bytes = lib.taoamd_track_occlusion_workspace(dp.n_gt, n_gf, n_len)
         ws.occ_ws = torch.empty(max(int(ws.occ_bytes), 256), dtype=torch.uint8, device=dev)
@@ -1447,7 +1457,7 @@ def stage_track_occlusion(dp, ws, frame_thr, vis_lo, vis_hi, recover, len_edges,
                                     dtype=torch.int64, device=dev)
     tables = (dp.n_gt, n_gf, dp.n_cat, n_len, int(recover), float(vis_lo), float(vis_hi),
               edges.ctypes.data, _ptr(t["gt_cat"]), _ptr(t["gt_flags"]),
-              _ptr(t["gt_frame_off"]), _ptr(t["gt_frame_vis"]), _ptr(ws.assoc_best))
+              frames[3], _ptr(t["gt_frame_vis"]), _ptr(ws.assoc_best))
     _lib.check(lib.taoamd_track_occlusion_count(
         *tables, _ptr(ws.occ_gt), _ptr(ws.occ_off), _ptr(ws.occ_counts), _ptr(ws.occ_ws),
         ws.occ_bytes, s), "taoamd_track_occlusion_count")
@@ -1478,12 +1488,10 @@ def stage_track_identity(dp, ws, frame_thr):
     on the first call and kept with the workspace: 4 bytes per pair of a cell, 8
     per track, and a workspace of 56 bytes per detection track, 44 per ground-
     truth track and 4 per ground-truth frame."""
-    if dp.kind != "tao" or dp.mask_iou:
-        raise _lib.TaoAmdError("the track identity is the track level's, on boxes")
+    sizes, cells, frames = _track_tables(dp, "identity is")
     lib, t, dev, s = _lib.load(), dp.t, dp.device, _stream()
-    n_df, n_gf = int(t["dt_frame_pos"].numel()), int(t["gt_frame_pos"].numel())
     if ws.ident_ws is None:
-        ws.ident_bytes = lib.taoamd_track_identity_workspace(dp.n_dt, dp.n_gt, n_gf)
+        ws.ident_bytes = lib.taoamd_track_identity_workspace(dp.n_dt, dp.n_gt, sizes[5])
         ws.ident_ws = torch.empty(max(int(ws.ident_bytes), 256), dtype=torch.uint8, device=dev)
         ws.ident_share = torch.empty(max(dp.n_iou, 1), dtype=torch.int32, device=dev)
         ws.ident_cat_counts = torch.empty((dp.n_cat, len(_lib.IDENT_CAT_COLUMNS)),
@@ -1491,17 +1499,13 @@ def stage_track_identity(dp, ws, frame_thr):
         ws.ident_gt = torch.empty((max(dp.n_gt, 1), 2), dtype=torch.int32, device=dev)
         ws.ident_dt = torch.empty((max(dp.n_dt, 1), 2), dtype=torch.int32, device=dev)
         ws.ident_status = torch.empty(1, dtype=torch.int32, device=dev)
-    sizes = (dp.n_dt, dp.n_gt, dp.n_cells, dp.n_iou, n_df, n_gf)
-    cells = (_ptr(t["cell_dt_off"]), _ptr(t["cell_gt_off"]), _ptr(t["cell_iou_off"]))
     _lib.check(lib.taoamd_track_identity_share(
-        *sizes, float(frame_thr), *cells,
-        _ptr(t["dt_frame_off"]), _ptr(t["dt_frame_pos"]), _ptr(t["dt_frame_box"]),
-        _ptr(t["gt_frame_off"]), _ptr(t["gt_frame_pos"]), _ptr(t["gt_frame_box"]),
+        *sizes, float(frame_thr), *cells, *frames,
         _ptr(ws.ident_share), _ptr(ws.ident_ws), ws.ident_bytes, s),
         "taoamd_track_identity_share")
     _lib.check(lib.taoamd_track_identity_assign(
         *sizes, dp.n_cat, *cells, _ptr(t["gt_cat"]), _ptr(t["gt_flags"]), _ptr(t["dt_cat"]),
-        _ptr(t["dt_flags"]), _ptr(t["dt_frame_off"]), _ptr(t["gt_frame_off"]),
+        _ptr(t["dt_flags"]), frames[0], frames[3],
         _ptr(ws.ident_share), _ptr(ws.ident_cat_counts), _ptr(ws.ident_gt), _ptr(ws.ident_dt),
         _ptr(ws.ident_status), _ptr(ws.ident_ws), ws.ident_bytes, s),
         "taoamd_track_identity_assign")

@@ -847,81 +847,6 @@ def confusion_lines(ev, iou_thr, bg_thr, rng, top):
     return lines
 
 
-def occlusion_lines(e):
-    """TaoEval.occlusions()'s result `e` as a small text table, the totals over
-    the categories: a line per length bucket."""
-    cols = e["columns"]["counts"]
-
-    def pct(n, d):
-        return "{:>10.2f}".format(100.0 * float(n) / float(d)) if d else "{:>10s}".format("-")
-    w = max([len(x) for x in e["len_lbl"]] + [len("length")])
-    lines = [" track occlusions @[ frame IoU={:0.2f} | vis=[{:g}, {:g}] | recover={} ]".format(
-                 e["frame_thr"], e["vis_rng"][0], e["vis_rng"][1], e["recover"]),
-             " " + "length".ljust(w) + "".join(
-                 c.rjust(10) for c in ("episodes", "kept%", "switched%", "lost%", "held%"))]
-    for name, v in zip(e["len_lbl"], e["counts"].sum(0).tolist()):
-        c = dict(zip(cols, v))
-        out = c["kept"] + c["switched"] + c["lost"]
-        lines.append(" " + name.ljust(w) + "{:>10d}".format(c["episodes"])
-                     + pct(c["kept"], out) + pct(c["switched"], out) + pct(c["lost"], out)
-                     + pct(c["held"], c["frames"]))
-    return lines
-
-
-def identity_ratios(idtp, gt_frames, dt_frames):
-    """(IDF1, IDP, IDR) as float64, NaN where the denominator is 0."""
-    idtp, gt_frames, dt_frames = (np.asarray(x, dtype=np.float64)
-                                  for x in (idtp, gt_frames, dt_frames))
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return (np.where(gt_frames + dt_frames > 0, 2 * idtp / (gt_frames + dt_frames), np.nan),
-                np.where(dt_frames > 0, idtp / dt_frames, np.nan),
-                np.where(gt_frames > 0, idtp / gt_frames, np.nan))
-
-
-def identity(ev, frame_thr):
-    """TaoEval.identity()'s whole result at `frame_thr` from the run's tables:
-    the category axis in the caller's order, rows as track ids."""
-    from .._lib import IDENT_CAT_COLUMNS
-    t = ev._run.identity_table(frame_thr)
-    flat = ev._run.flat
-    cat_counts = t["cat_counts"]
-    if ev._cat_pos is not None:
-        cat_counts = np.ascontiguousarray(cat_counts[ev._cat_pos])
-    idf1, idp, idr = identity_ratios(cat_counts[:, 4], cat_counts[:, 1], cat_counts[:, 3])
-    total = dict(zip(IDENT_CAT_COLUMNS, (int(x) for x in cat_counts.sum(0))))
-    total["idfn"] = total["gt_frames"] - total["idtp"]
-    total["idfp"] = total["dt_frames"] - total["idtp"]
-    for name, v in zip(("idf1", "idp", "idr"),
-                       identity_ratios(total["idtp"], total["gt_frames"], total["dt_frames"])):
-        total[name] = float(v)
-    dt_id, gt_id = np.asarray(flat.dt_id, dtype=np.int64), np.asarray(flat.gt_id, dtype=np.int64)
-
-    def ids(rows, table):
-        rows = rows.astype(np.int64)
-        return np.where(rows >= 0, table[np.maximum(rows, 0)], -1) if len(table) else \
-            np.full(len(rows), -1, dtype=np.int64)
-    gi, di = t["gt_ident"], t["dt_ident"]
-    tracks = np.stack([ids(gi[:, 0], dt_id), gi[:, 1].astype(np.int64),
-                       np.diff(np.asarray(flat.gt_frame_off, dtype=np.int64))], axis=1)
-    dt_tracks = np.stack([ids(di[:, 0], gt_id), di[:, 1].astype(np.int64),
-                          np.diff(np.asarray(flat.dt_frame_off, dtype=np.int64))], axis=1)
-    return {"columns": list(IDENT_CAT_COLUMNS), "cat_counts": cat_counts,
-            "idf1": idf1, "idp": idp, "idr": idr, "total": total, "frame_thr": frame_thr,
-            "tracks": (gt_id, tracks), "dt_tracks": (dt_id, dt_tracks)}
-
-
-def identity_lines(e):
-    """TaoEval.identity()'s result `e` as a small text table: the totals over
-    the categories."""
-    t = e["total"]
-
-    def pct(v):
-        return "{:.2f}".format(100.0 * v) if v == v else "-"
-    return [" track identity @[ frame IoU={:0.2f} ]".format(e["frame_thr"]),
-            " IDF1={}  IDP={}  IDR={}".format(pct(t["idf1"]), pct(t["idp"]), pct(t["idr"])),
-            " " + "  ".join("{}={}".format(c, t[c]) for c in list(e["columns"]) + ["idfn", "idfp"])]
-
-
 def now():
     return datetime.datetime.now().strftime("%Y-%m-%d %H:%M:%S")
 

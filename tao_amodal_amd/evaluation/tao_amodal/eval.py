@@ -15,6 +15,7 @@ from collections.abc import Mapping
 import numpy as np
 
 from .. import _core
+from . import followers
 from .._core import (N_REC, N_THR, CellView, GpuRun, LazyIous, LazyPointers,
                      EvalConstants,
                      masked_mean, now, operating_points, summaries, timed)
@@ -111,13 +112,13 @@ class TaoEval:
         self.flat = self.tao_dt.flat
         self._run = None
         self._cat_pos = None
-        self._error_types = {}
-        self._error_impact = {}
-        self._confusion = {}
-        self._association = {}
-        self._occlusions = {}
-        self._identity = {}
+        self._reset_analyses()
         self._gt_columns = None
+
+    def _reset_analyses(self):
+        """The caches of the analyses on request: they hold results of one evaluate()."""
+        self._error_types, self._error_impact, self._confusion = {}, {}, {}
+        self._association, self._occlusions, self._identity = {}, {}, {}
 
     # ------------------------------------------------------------ stages
     def evaluate(self, show_progress=False):
@@ -171,12 +172,7 @@ class TaoEval:
         else:
             self._run = GpuRun(flat, self.device, self.params.iou_3d_type,
                                constants=constants)
-        self._error_types = {}
-        self._error_impact = {}
-        self._confusion = {}
-        self._association = {}
-        self._occlusions = {}
-        self._identity = {}
+        self._reset_analyses()
         self._gt_columns = gt_cols      # the annotation rows the tables' frames name
         self._run.evaluate()
         P = self.params
@@ -424,95 +420,13 @@ class TaoEval:
         .. frame_off[i + 1].  It reads the track tables alone: the result does
         not depend on iou_3d_type, params.iou_thrs or the ranges.  Not available:
         iou_type="segm", use_cats = 0, multi-GPU runs."""
-        if self._run is None:
-            raise RuntimeError("Please run evaluate() first.")
-        frame_thr = float(frame_thr)
-        if not 0 < frame_thr <= 1:
-            raise ValueError("frame_thr: {} is not in (0, 1]".format(frame_thr))
-        if vis_rng is None:
-            from ..lvis_amodal.eval import Params as LvisParams
-            lp = LvisParams(self.params.iou_type)
-            vis_rng = lp.visibility_rng[:5]
-            if vis_lbl is None:
-                vis_lbl = lp.visibility_rng_lbl[:5]
-        rng = np.asarray(vis_rng, dtype=np.float64).reshape(-1, 2)
-        if len(rng) > 8:
-            raise ValueError("vis_rng: up to 8 visibility windows")
-        if vis_lbl is None:
-            vis_lbl = ["[{:g}, {:g}]".format(lo, hi) for lo, hi in rng.tolist()]
-        vis_lbl = [str(x) for x in vis_lbl]
-        if len(vis_lbl) != len(rng):
-            raise ValueError("vis_lbl: {} labels for {} windows".format(len(vis_lbl), len(rng)))
-        key = (frame_thr, rng.tobytes(), tuple(vis_lbl))
-        hit = self._association.get(key)
-        if hit is None:
-            from ..._lib import ASSOC_CAT_COLUMNS, ASSOC_TRACK_COLUMNS, ASSOC_VIS_COLUMNS
-            t = self._run.association_table(frame_thr, rng, self._gt_columns.ann_vis)
-            flat = self._run.flat
-            cat_counts, vis_counts = t["cat_counts"], t["vis_counts"]
-            if self._cat_pos is not None:
-                cat_counts = np.ascontiguousarray(cat_counts[self._cat_pos])
-                vis_counts = np.ascontiguousarray(vis_counts[:, self._cat_pos])
-            dt_id = np.asarray(flat.dt_id, dtype=np.int64)
-            tracks = t["gt_assoc"].astype(np.int64)
-            prim = tracks[:, 5]
-            tracks[:, 5] = np.where(prim >= 0, dt_id[np.maximum(prim, 0)], -1) if len(dt_id) \
-                else -1
-            # frames: the image at (video, timeline position), the follower's id
-            foff, cell, img = self._gt_frame_tables()
-            best_id = self._follower_ids(cell, t["best"])
-            hit = {"columns": {"tracks": list(ASSOC_TRACK_COLUMNS),
-                               "cat_counts": list(ASSOC_CAT_COLUMNS),
-                               "vis_counts": list(ASSOC_VIS_COLUMNS)},
-                   "cat_counts": cat_counts, "vis_counts": vis_counts,
-                   "vis_rng": rng.tolist(), "vis_lbl": list(vis_lbl), "frame_thr": frame_thr,
-                   "tracks": (np.asarray(flat.gt_id), tracks),
-                   "frames": (foff, np.asarray(img), best_id, t["best_iou"])}
-            self._association[key] = hit
-        drop = [k for k, on in (("tracks", per_track), ("frames", per_frame)) if not on]
-        return {k: v for k, v in hit.items() if k not in drop}
+        return followers.association(self, frame_thr, vis_rng, vis_lbl, per_track, per_frame)
 
     def association_lines(self, frame_thr=0.5, vis_rng=None, vis_lbl=None):
         """association() as a small text table: the totals over the categories,
         then a line per visibility window with its frames, the covered ones and
         those the primary follower covers, in per cent.  Returned, not printed."""
-        a = self.association(frame_thr, vis_rng, vis_lbl)
-        tot = a["cat_counts"].sum(0)
-        cols = a["columns"]["cat_counts"]
-
-        def pct(n, d):
-            return "{:>9.2f}".format(100.0 * float(n) / float(d)) if d else "{:>9s}".format("-")
-        w = max([len(x) for x in a["vis_lbl"]] + [10])
-        lines = [" track association @[ frame IoU={:0.2f} ]".format(a["frame_thr"]),
-                 " " + "  ".join("{}={}".format(c, int(v)) for c, v in zip(cols, tot))
-                 + "  coverage={}".format(pct(tot[2], tot[1]).strip())]
-        for name, v in zip(a["vis_lbl"], a["vis_counts"].sum(1)):
-            lines.append(" " + name.ljust(w) + "{:>11d}".format(int(v[0]))
-                         + pct(v[1], v[0]) + pct(v[2], v[0]))
-        return lines
-
-    def _gt_frame_tables(self):
-        """(frame_off int64[n_gt + 1], the cell and the image id of every
-        ground-truth frame): the image at (video, timeline position)."""
-        flat = self._run.flat
-        foff = np.asarray(flat.gt_frame_off, dtype=np.int64)
-        g_of = np.repeat(np.arange(len(foff) - 1), np.diff(foff))
-        cell = np.asarray(flat.gt_cell, dtype=np.int64)[g_of]
-        vid = np.asarray(flat.cell_unit, dtype=np.int64)[cell]
-        img = np.asarray(flat.tl_image_id)[np.asarray(flat.tl_vid_start, dtype=np.int64)[vid]
-                                           + np.asarray(flat.gt_frame_pos, dtype=np.int64)]
-        return foff, cell, img
-
-    def _follower_ids(self, cell, best):
-        """In-cell followers `best` of the cells `cell` as detection track ids, -1
-        for none."""
-        flat = self._run.flat
-        dt_id = np.asarray(flat.dt_id, dtype=np.int64)
-        best = np.asarray(best).astype(np.int64)
-        if not len(dt_id):
-            return np.full(len(best), -1, dtype=np.int64)
-        row = np.asarray(flat.cell_dt_off, dtype=np.int64)[cell] + best
-        return np.where(best >= 0, dt_id[np.where(best >= 0, row, 0)], -1)
+        return followers.association_lines(self.association(frame_thr, vis_rng, vis_lbl))
 
     def occlusions(self, frame_thr=0.5, vis_rng=(0.0, 0.1), recover=3, len_edges=(1, 3, 6, 11),
                    per_track=False, per_episode=False):
@@ -554,51 +468,8 @@ class TaoEval:
         covered, held with entry and after as detection track ids, -1 for none),
         by ascending (row, a).  Not available: iou_type="segm", use_cats = 0,
         multi-GPU runs."""
-        if self._run is None:
-            raise RuntimeError("Please run evaluate() first.")
-        frame_thr = float(frame_thr)
-        if not 0 < frame_thr <= 1:
-            raise ValueError("frame_thr: {} is not in (0, 1]".format(frame_thr))
-        rng = np.asarray(vis_rng, dtype=np.float64).reshape(-1)
-        if len(rng) != 2 or not rng[0] <= rng[1]:
-            raise ValueError("vis_rng: {} is not one window lo <= hi".format(vis_rng))
-        if int(recover) != recover or not 1 <= recover <= 64:
-            raise ValueError("recover: {} is not an integer in [1, 64]".format(recover))
-        edges = [int(x) for x in np.asarray(len_edges).reshape(-1).tolist()]
-        if not 1 <= len(edges) <= 8 or edges[0] != 1 \
-                or any(a >= b for a, b in zip(edges, edges[1:])) \
-                or edges != np.asarray(len_edges).reshape(-1).tolist():
-            raise ValueError("len_edges: {} is not 1 to 8 ascending integers that start at 1"
-                             .format(len_edges))
-        key = (frame_thr, float(rng[0]), float(rng[1]), int(recover), tuple(edges))
-        hit = self._occlusions.get(key)
-        if hit is None:
-            from ..._lib import (OCC_COUNT_COLUMNS, OCC_EPISODE_COLUMNS, OCC_OUTCOMES,
-                                 OCC_TRACK_COLUMNS)
-            t = self._run.occlusion_table(frame_thr, key[1:3], key[3], edges,
-                                          self._gt_columns.ann_vis)
-            counts = t["counts"]
-            if self._cat_pos is not None:
-                counts = np.ascontiguousarray(counts[self._cat_pos])
-            gt_id = np.asarray(self._run.flat.gt_id)
-            foff, cell, img = self._gt_frame_tables()
-            ep = t["episodes"].astype(np.int64)
-            first = foff[ep[:, 0]] + ep[:, 1]
-            for col in (4, 5):
-                ep[:, col] = self._follower_ids(cell[first], ep[:, col])
-            lbl = ["{}-{}".format(a, b - 1) if b - 1 > a else str(a)
-                   for a, b in zip(edges, edges[1:])] + ["{}+".format(edges[-1])]
-            hit = {"columns": {"counts": list(OCC_COUNT_COLUMNS), "tracks": list(OCC_TRACK_COLUMNS),
-                               "episodes": list(OCC_EPISODE_COLUMNS),
-                               "outcomes": list(OCC_OUTCOMES)},
-                   "counts": counts, "len_edges": edges, "len_lbl": lbl,
-                   "vis_rng": [key[1], key[2]], "frame_thr": frame_thr, "recover": key[3],
-                   "tracks": (gt_id, t["gt_occ"].astype(np.int64)),
-                   "episodes": (gt_id[ep[:, 0]], np.asarray(img)[first],
-                                np.asarray(img)[first + ep[:, 2] - 1], ep)}
-            self._occlusions[key] = hit
-        drop = [k for k, on in (("tracks", per_track), ("episodes", per_episode)) if not on]
-        return {k: v for k, v in hit.items() if k not in drop}
+        return followers.occlusions(self, frame_thr, vis_rng, recover, len_edges, per_track,
+                                    per_episode)
 
     def occlusion_lines(self, frame_thr=0.5, vis_rng=(0.0, 0.1), recover=3,
                         len_edges=(1, 3, 6, 11)):
@@ -606,7 +477,7 @@ class TaoEval:
         line per length bucket with its episodes, the kept / switched / lost
         shares of the episodes that have one of these three outcomes, and held /
         frames, in per cent.  Returned, not printed."""
-        return _core.occlusion_lines(self.occlusions(frame_thr, vis_rng, recover, len_edges))
+        return followers.occlusion_lines(self.occlusions(frame_thr, vis_rng, recover, len_edges))
 
     def identity(self, frame_thr=0.5, per_track=False):
         """IDF1, IDP and IDR (Ristani et al., ECCV 2016; TrackEval's Identity):
@@ -647,22 +518,12 @@ class TaoEval:
         frames).  Every count is exact and the same from run to run; where
         several assignments reach the optimum, the one reported is one of them.
         Not available: iou_type="segm", use_cats = 0, multi-GPU runs."""
-        if self._run is None:
-            raise RuntimeError("Please run evaluate() first.")
-        frame_thr = float(frame_thr)
-        if not 0 < frame_thr <= 1:
-            raise ValueError("frame_thr: {} is not in (0, 1]".format(frame_thr))
-        hit = self._identity.get(frame_thr)
-        if hit is None:
-            hit = _core.identity(self, frame_thr)
-            self._identity[frame_thr] = hit
-        drop = () if per_track else ("tracks", "dt_tracks")
-        return {k: v for k, v in hit.items() if k not in drop}
+        return followers.identity(self, frame_thr, per_track)
 
     def identity_lines(self, frame_thr=0.5):
         """identity() as a small text table: the totals over the categories.
         Returned, not printed."""
-        return _core.identity_lines(self.identity(frame_thr))
+        return followers.identity_lines(self.identity(frame_thr))
 
     def impact_lines(self, iou_thr=0.5, bg_thr=0.1):
         """error_impact() as a small text table: a line per (area, time) range,

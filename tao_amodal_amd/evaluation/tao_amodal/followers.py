@@ -1,0 +1,217 @@
+"""The analyses of TaoEval that read the track tables alone -- association(),
+occlusions(), identity() -- and their text tables: the class layer over
+GpuRun.association_table / occlusion_table / identity_table.  The track
+level's alone; the methods of TaoEval carry the documentation and call in here
+with the evaluator `ev`."""
+import numpy as np
+
+from .._core import _params_cats
+
+
+def _frame_thr(ev, frame_thr):
+    """The per-frame threshold as a float in (0, 1], behind evaluate()."""
+    if ev._run is None:
+        raise RuntimeError("Please run evaluate() first.")
+    frame_thr = float(frame_thr)
+    if not 0 < frame_thr <= 1:
+        raise ValueError("frame_thr: {} is not in (0, 1]".format(frame_thr))
+    return frame_thr
+
+
+def _cached(cache, key, make, optional):
+    """make() once per key; the (key, asked) of `optional` that are not asked
+    for -- the per-track tables -- are left out of what is returned."""
+    hit = cache.get(key)
+    if hit is None:
+        hit = cache[key] = make()
+    drop = [k for k, on in optional if not on]
+    return {k: v for k, v in hit.items() if k not in drop}
+
+
+def _track_ids(rows, ids):
+    """Table rows as the track ids `ids` of that table, -1 for none."""
+    rows, ids = np.asarray(rows).astype(np.int64), np.asarray(ids, dtype=np.int64)
+    if not len(ids):
+        return np.full(len(rows), -1, dtype=np.int64)
+    return np.where(rows >= 0, ids[np.maximum(rows, 0)], -1)
+
+
+def _follower_ids(flat, cell, best):
+    """In-cell followers `best` of the cells `cell` as detection track ids, -1
+    for none."""
+    best = np.asarray(best).astype(np.int64)
+    row = np.asarray(flat.cell_dt_off, dtype=np.int64)[cell] + best
+    return _track_ids(np.where(best >= 0, row, -1), flat.dt_id)
+
+
+def _gt_frame_tables(flat):
+    """(frame_off int64[n_gt + 1], the cell and the image id of every
+    ground-truth frame): the image at (video, timeline position)."""
+    foff = np.asarray(flat.gt_frame_off, dtype=np.int64)
+    g_of = np.repeat(np.arange(len(foff) - 1), np.diff(foff))
+    cell = np.asarray(flat.gt_cell, dtype=np.int64)[g_of]
+    vid = np.asarray(flat.cell_unit, dtype=np.int64)[cell]
+    img = np.asarray(flat.tl_image_id)[np.asarray(flat.tl_vid_start, dtype=np.int64)[vid]
+                                       + np.asarray(flat.gt_frame_pos, dtype=np.int64)]
+    return foff, cell, np.asarray(img)
+
+
+def _pct(n, d=1.0, width=0):
+    """n / d in per cent, "-" without a denominator or for a NaN."""
+    text = "{:.2f}".format(100.0 * float(n) / float(d)) if d and n == n else "-"
+    return text.rjust(width)
+
+
+def association(ev, frame_thr, vis_rng, vis_lbl, per_track, per_frame):
+    frame_thr = _frame_thr(ev, frame_thr)
+    if vis_rng is None:
+        from ..lvis_amodal.eval import Params as LvisParams
+        lp = LvisParams(ev.params.iou_type)
+        vis_rng = lp.visibility_rng[:5]
+        if vis_lbl is None:
+            vis_lbl = lp.visibility_rng_lbl[:5]
+    rng = np.asarray(vis_rng, dtype=np.float64).reshape(-1, 2)
+    if len(rng) > 8:
+        raise ValueError("vis_rng: up to 8 visibility windows")
+    if vis_lbl is None:
+        vis_lbl = ["[{:g}, {:g}]".format(lo, hi) for lo, hi in rng.tolist()]
+    vis_lbl = [str(x) for x in vis_lbl]
+    if len(vis_lbl) != len(rng):
+        raise ValueError("vis_lbl: {} labels for {} windows".format(len(vis_lbl), len(rng)))
+
+    def make():
+        from ..._lib import ASSOC_CAT_COLUMNS, ASSOC_TRACK_COLUMNS, ASSOC_VIS_COLUMNS
+        t = ev._run.association_table(frame_thr, rng, ev._gt_columns.ann_vis)
+        flat = ev._run.flat
+        tracks = t["gt_assoc"].astype(np.int64)
+        tracks[:, 5] = _track_ids(tracks[:, 5], flat.dt_id)
+        # frames: the image at (video, timeline position), the follower's id
+        foff, cell, img = _gt_frame_tables(flat)
+        return {"columns": {"tracks": list(ASSOC_TRACK_COLUMNS),
+                            "cat_counts": list(ASSOC_CAT_COLUMNS),
+                            "vis_counts": list(ASSOC_VIS_COLUMNS)},
+                "cat_counts": _params_cats(ev, t["cat_counts"], 0),
+                "vis_counts": _params_cats(ev, t["vis_counts"], 1),
+                "vis_rng": rng.tolist(), "vis_lbl": list(vis_lbl), "frame_thr": frame_thr,
+                "tracks": (np.asarray(flat.gt_id), tracks),
+                "frames": (foff, img, _follower_ids(flat, cell, t["best"]), t["best_iou"])}
+    return _cached(ev._association, (frame_thr, rng.tobytes(), tuple(vis_lbl)), make,
+                   (("tracks", per_track), ("frames", per_frame)))
+
+
+def association_lines(a):
+    """TaoEval.association()'s result `a` as a small text table."""
+    tot = a["cat_counts"].sum(0)
+    w = max([len(x) for x in a["vis_lbl"]] + [10])
+    lines = [" track association @[ frame IoU={:0.2f} ]".format(a["frame_thr"]),
+             " " + "  ".join("{}={}".format(c, int(v))
+                             for c, v in zip(a["columns"]["cat_counts"], tot))
+             + "  coverage={}".format(_pct(tot[2], tot[1]))]
+    for name, v in zip(a["vis_lbl"], a["vis_counts"].sum(1)):
+        lines.append(" " + name.ljust(w) + "{:>11d}".format(int(v[0]))
+                     + _pct(v[1], v[0], 9) + _pct(v[2], v[0], 9))
+    return lines
+
+
+def occlusions(ev, frame_thr, vis_rng, recover, len_edges, per_track, per_episode):
+    frame_thr = _frame_thr(ev, frame_thr)
+    rng = np.asarray(vis_rng, dtype=np.float64).reshape(-1)
+    if len(rng) != 2 or not rng[0] <= rng[1]:
+        raise ValueError("vis_rng: {} is not one window lo <= hi".format(vis_rng))
+    if int(recover) != recover or not 1 <= recover <= 64:
+        raise ValueError("recover: {} is not an integer in [1, 64]".format(recover))
+    edges = [int(x) for x in np.asarray(len_edges).reshape(-1).tolist()]
+    if not 1 <= len(edges) <= 8 or edges[0] != 1 \
+            or any(a >= b for a, b in zip(edges, edges[1:])) \
+            or edges != np.asarray(len_edges).reshape(-1).tolist():
+        raise ValueError("len_edges: {} is not 1 to 8 ascending integers that start at 1"
+                         .format(len_edges))
+    key = (frame_thr, float(rng[0]), float(rng[1]), int(recover), tuple(edges))
+
+    def make():
+        from ..._lib import (OCC_COUNT_COLUMNS, OCC_EPISODE_COLUMNS, OCC_OUTCOMES,
+                             OCC_TRACK_COLUMNS)
+        t = ev._run.occlusion_table(frame_thr, key[1:3], key[3], edges, ev._gt_columns.ann_vis)
+        flat = ev._run.flat
+        gt_id = np.asarray(flat.gt_id)
+        foff, cell, img = _gt_frame_tables(flat)
+        ep = t["episodes"].astype(np.int64)
+        first = foff[ep[:, 0]] + ep[:, 1]
+        for col in (4, 5):
+            ep[:, col] = _follower_ids(flat, cell[first], ep[:, col])
+        lbl = ["{}-{}".format(a, b - 1) if b - 1 > a else str(a)
+               for a, b in zip(edges, edges[1:])] + ["{}+".format(edges[-1])]
+        return {"columns": {"counts": list(OCC_COUNT_COLUMNS), "tracks": list(OCC_TRACK_COLUMNS),
+                            "episodes": list(OCC_EPISODE_COLUMNS),
+                            "outcomes": list(OCC_OUTCOMES)},
+                "counts": _params_cats(ev, t["counts"], 0), "len_edges": edges, "len_lbl": lbl,
+                "vis_rng": [key[1], key[2]], "frame_thr": frame_thr, "recover": key[3],
+                "tracks": (gt_id, t["gt_occ"].astype(np.int64)),
+                "episodes": (gt_id[ep[:, 0]], img[first], img[first + ep[:, 2] - 1], ep)}
+    return _cached(ev._occlusions, key, make,
+                   (("tracks", per_track), ("episodes", per_episode)))
+
+
+def occlusion_lines(e):
+    """TaoEval.occlusions()'s result `e` as a small text table, the totals over
+    the categories: a line per length bucket."""
+    cols = e["columns"]["counts"]
+    w = max([len(x) for x in e["len_lbl"]] + [len("length")])
+    lines = [" track occlusions @[ frame IoU={:0.2f} | vis=[{:g}, {:g}] | recover={} ]".format(
+                 e["frame_thr"], e["vis_rng"][0], e["vis_rng"][1], e["recover"]),
+             " " + "length".ljust(w) + "".join(
+                 c.rjust(10) for c in ("episodes", "kept%", "switched%", "lost%", "held%"))]
+    for name, v in zip(e["len_lbl"], e["counts"].sum(0).tolist()):
+        c = dict(zip(cols, v))
+        out = c["kept"] + c["switched"] + c["lost"]
+        lines.append(" " + name.ljust(w) + "{:>10d}".format(c["episodes"])
+                     + "".join(_pct(c[k], out, 10) for k in ("kept", "switched", "lost"))
+                     + _pct(c["held"], c["frames"], 10))
+    return lines
+
+
+def identity_ratios(idtp, gt_frames, dt_frames):
+    """(IDF1, IDP, IDR) as float64, NaN where the denominator is 0."""
+    idtp, gt_frames, dt_frames = (np.asarray(x, dtype=np.float64)
+                                  for x in (idtp, gt_frames, dt_frames))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return (np.where(gt_frames + dt_frames > 0, 2 * idtp / (gt_frames + dt_frames), np.nan),
+                np.where(dt_frames > 0, idtp / dt_frames, np.nan),
+                np.where(gt_frames > 0, idtp / gt_frames, np.nan))
+
+
+def identity(ev, frame_thr, per_track):
+    frame_thr = _frame_thr(ev, frame_thr)
+
+    def make():
+        from ..._lib import IDENT_CAT_COLUMNS
+        t = ev._run.identity_table(frame_thr)
+        flat = ev._run.flat
+        cat_counts = _params_cats(ev, t["cat_counts"], 0)
+        idf1, idp, idr = identity_ratios(cat_counts[:, 4], cat_counts[:, 1], cat_counts[:, 3])
+        total = dict(zip(IDENT_CAT_COLUMNS, (int(x) for x in cat_counts.sum(0))))
+        total["idfn"] = total["gt_frames"] - total["idtp"]
+        total["idfp"] = total["dt_frames"] - total["idtp"]
+        for name, v in zip(("idf1", "idp", "idr"),
+                           identity_ratios(total["idtp"], total["gt_frames"], total["dt_frames"])):
+            total[name] = float(v)
+        dt_id, gt_id = (np.asarray(x, dtype=np.int64) for x in (flat.dt_id, flat.gt_id))
+        gi, di = t["gt_ident"], t["dt_ident"]
+        tracks = np.stack([_track_ids(gi[:, 0], dt_id), gi[:, 1].astype(np.int64),
+                           np.diff(np.asarray(flat.gt_frame_off, dtype=np.int64))], axis=1)
+        dt_tracks = np.stack([_track_ids(di[:, 0], gt_id), di[:, 1].astype(np.int64),
+                              np.diff(np.asarray(flat.dt_frame_off, dtype=np.int64))], axis=1)
+        return {"columns": list(IDENT_CAT_COLUMNS), "cat_counts": cat_counts,
+                "idf1": idf1, "idp": idp, "idr": idr, "total": total, "frame_thr": frame_thr,
+                "tracks": (gt_id, tracks), "dt_tracks": (dt_id, dt_tracks)}
+    return _cached(ev._identity, frame_thr, make,
+                   (("tracks", per_track), ("dt_tracks", per_track)))
+
+
+def identity_lines(e):
+    """TaoEval.identity()'s result `e` as a small text table: the totals over
+    the categories."""
+    t = e["total"]
+    return [" track identity @[ frame IoU={:0.2f} ]".format(e["frame_thr"]),
+            " IDF1={}  IDP={}  IDR={}".format(_pct(t["idf1"]), _pct(t["idp"]), _pct(t["idr"])),
+            " " + "  ".join("{}={}".format(c, t[c]) for c in list(e["columns"]) + ["idfn", "idfp"])]

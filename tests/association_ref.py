@@ -162,3 +162,84 @@ def hand_flat():
     """(flat, dt_at, gt_at, vis)."""
     f, dt_at, gt_at = make_track_flat(4, 2, HAND_DETS, HAND_GTS)
     return f, dt_at, gt_at, frame_vis(f, gt_at, HAND_VIS)
+
+
+# ---------------------------------------------------------------------------
+# The empty sides: tables of two categories and at most three cells for the
+# association and the identity's share pass, which build one frame index.
+# ---------------------------------------------------------------------------
+def side_table(cells, dts, gts, first=(0, 0), loose=0):
+    """A table written row by row, so that it can hold what no flatten makes.
+    cells: (detection tracks, ground-truth tracks) per cell, dts: {position:
+    box} per detection row, gts: (category, flags, {position: box}) per ground-
+    truth row; first = (detection rows, ground-truth rows) before the first
+    cell's -- rows no cell lists; loose: ground-truth frames behind the last
+    track's -- frames no track lists.  Returns (table, vis)."""
+    from types import SimpleNamespace
+
+    def frames(tracks, extra=0):
+        pos = [p for fr in tracks for p in sorted(fr)] + list(range(extra))
+        box = [fr[p] for fr in tracks for p in sorted(fr)] + [BOX] * extra
+        return (np.cumsum([0] + [len(fr) for fr in tracks]).astype(np.int32),
+                np.array(pos, np.int32), np.array(box, np.float64).reshape(-1, 4))
+    D = np.array([c[0] for c in cells], np.int64)
+    G = np.array([c[1] for c in cells], np.int64)
+    f = SimpleNamespace(n_cells=len(cells), cat_ids=np.arange(2, dtype=np.int64))
+    f.cell_dt_off = (first[0] + np.r_[0, np.cumsum(D)]).astype(np.int32)
+    f.cell_gt_off = (first[1] + np.r_[0, np.cumsum(G)]).astype(np.int32)
+    f.cell_iou_off = np.r_[0, np.cumsum(D * G)].astype(np.int64)
+    assert f.cell_dt_off[-1] == len(dts) and f.cell_gt_off[-1] == len(gts)
+    f.gt_cat = np.array([g[0] for g in gts], np.int32)
+    f.gt_flags = np.array([g[1] for g in gts], np.uint8)
+    f.dt_frame_off, f.dt_frame_pos, f.dt_frame_box = frames(dts)
+    f.gt_frame_off, f.gt_frame_pos, f.gt_frame_box = frames([g[2] for g in gts], loose)
+    # (a visibility per frame that lies in some windows of VIS_RNG and not in others)
+    return f, np.resize([0.05, 0.5, 0.9, 1.0], len(f.gt_frame_pos))
+
+
+def _run(positions, box=BOX):
+    return {p: box for p in positions}
+
+
+def empty_sides():
+    """{case: (table, vis)}.  A ground-truth row no cell lists is marked "ignore":
+    the restatement walks the cells and never sees it, so it may count nowhere."""
+    one, long_ = _run(range(1)), _run(range(65))
+    some = [_run(range(3)), _run(range(2, 70)), _run((0, 64))]
+    out = {
+        # (a) no detection tracks at all, ground-truth tracks of 1 and 65 frames
+        "no_detection_tracks": side_table([(0, 1), (0, 1)], [], [(0, 0, one), (1, 0, long_)]),
+        # (b) no ground-truth tracks
+        "no_ground_truth": side_table([(2, 0), (1, 0)], some, []),
+        # (c) no cells, rows on both sides
+        "no_cells": side_table([], some, [(0, GT_IGNORE, one), (1, GT_IGNORE, long_)],
+                               first=(3, 2)),
+        # (d) detection tracks that all have no frames
+        "no_detection_frames": side_table([(2, 1), (1, 1)], [{}, {}, {}],
+                                          [(0, 0, one), (1, 0, long_)]),
+    }
+    # (e) ground-truth row 0 is in no cell, the last two ground-truth frames in no
+    # track; of the first cell's detection tracks the middle one has no frames and
+    # the last a hole at position 10 between its ends 0 and 20, where the ground
+    # truth has a frame: the probe bisects.  HALF overlaps at exactly 0.5.
+    holed = {**_run(range(10), HALF), **_run(range(11, 21), HALF)}
+    out["mixed"] = side_table(
+        [(3, 1), (1, 1)], [_run(range(10)), {}, holed, _run((6, 7, 8))],
+        [(0, GT_IGNORE, _run(range(2))), (0, 0, long_), (1, 0, _run((5, 6, 7)))],
+        first=(0, 1), loose=2)
+    return out
+
+
+def association_of_table(f, vis, frame_thr):
+    """association() for a table of side_table(): a ground-truth row no cell lists
+    is not the restatement's to visit; its row of gt_assoc is the header's "no
+    candidates" -- its frames, nothing covered, no primary."""
+    want = association(f, vis, frame_thr)
+    g_off = np.asarray(f.cell_gt_off, np.int64)
+    listed = np.zeros(int(g_off[-1]), bool)
+    for c in range(f.n_cells):
+        listed[g_off[c]:g_off[c + 1]] = True
+    for g in np.flatnonzero(~listed):
+        assert f.gt_flags[g] & GT_IGNORE
+        want["gt_assoc"][g] = [f.gt_frame_off[g + 1] - f.gt_frame_off[g], 0, 0, 0, 0, -1, 0]
+    return want

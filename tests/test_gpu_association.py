@@ -276,6 +276,22 @@ def test_abi_on_boxes_that_are_any_double():
     _same(got, want)
 
 
+@pytest.mark.parametrize("case", ["no_detection_tracks", "no_ground_truth", "no_cells",
+                                  "no_detection_frames", "mixed"])
+def test_abi_on_empty_sides(case):
+    """A side without rows, cells or frames, and rows and frames that nothing
+    lists (association_ref.empty_sides): the frame index is complete whatever is
+    empty, and every output is the restatement's."""
+    f, vis = ref.empty_sides()[case]
+    want = ref.association_of_table(f, vis, 0.5)
+    if case == "mixed":
+        # the hole is probed, both followers of the long track are found
+        assert want["gt_assoc"][1].tolist() == [65, 20, 2, 1, 2, 0, 10]
+        assert want["best"][2:2 + 21].tolist() == [0] * 10 + [-1] + [2] * 10
+        assert want["gt_assoc"][0].tolist() == [2, 0, 0, 0, 0, -1, 0]
+    _same(_device_association(f, vis, 0.5), want)
+
+
 def test_abi_error_paths():
     f, _, _, vis = ref.hand_flat()
     lib = _lib.load()

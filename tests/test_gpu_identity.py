@@ -314,6 +314,33 @@ def test_share_on_boxes_that_are_any_double():
     assert np.array_equal(_device_share(f, 0.3), want)
 
 
+@pytest.mark.parametrize("case", ["no_detection_tracks", "no_ground_truth", "no_cells",
+                                  "no_detection_frames", "mixed"])
+def test_share_on_empty_sides(case):
+    """A side without rows, cells or frames, and rows and frames that nothing
+    lists (association_ref.empty_sides): share is the restatement's whatever is
+    empty, over the frame index the association builds as well."""
+    import association_ref
+    f, vis = association_ref.empty_sides()[case]
+    want = ref.share(f, 0.5)
+    got = _device_share(f, 0.5)
+    assert got.dtype == np.int32 and np.array_equal(got, want)
+    if case != "mixed":
+        assert not want.any()
+        return
+    # [the whole track, none, the holed one] x [the long ground truth]; the other cell
+    assert want.tolist() == [10, 0, 20, 2]
+    # the two passes read one index: a follower shares the frame it follows, and a
+    # covered frame is shared by someone
+    a = _device_association(f, vis, 0.5)
+    assert (a["follow"] <= got).all()
+    for c in range(f.n_cells):
+        D = f.cell_dt_off[c + 1] - f.cell_dt_off[c]
+        g0, g1 = f.cell_gt_off[c], f.cell_gt_off[c + 1]
+        column = got[f.cell_iou_off[c]:f.cell_iou_off[c + 1]].reshape(D, g1 - g0).sum(0)
+        assert (a["gt_assoc"][g0:g1, 1] <= column).all() and a["gt_assoc"][g0:g1, 1].all()
+
+
 def test_both_calls_on_the_hand_written_table():
     f, dt_at, gt_at = ref.hand_flat()
     for thr, cell1, gi_want, counts in (

@@ -88,10 +88,10 @@ def test_abi_on_the_hand_written_table():
     assert got["ep_off"].tolist() == ref.HAND_EP_OFF
     assert got["counts"].tolist() == ref.HAND_COUNTS
     _same(got, want)
-    from tao_amodal_amd.evaluation import _core
+    from tao_amodal_amd.evaluation.tao_amodal import followers
     e = {"columns": {"counts": list(_lib.OCC_COUNT_COLUMNS)}, "counts": got["counts"],
          "len_lbl": ["1", "2", "3+"], "frame_thr": 0.5, "vis_rng": [0.0, 0.1], "recover": 2}
-    assert _core.occlusion_lines(e) == ref.HAND_LINES
+    assert followers.occlusion_lines(e) == ref.HAND_LINES
     one = _device(t, 2, ref.HAND_WINDOW, 1, ref.HAND_EDGES)
     assert tuple(one["episodes"][2].tolist()) == ref.HAND_EPISODE2_RECOVER1
     assert one["counts"][0, 0].tolist() == ref.HAND_COUNTS00_RECOVER1
