@@ -1,40 +1,124 @@
-"""ctypes binding of the C ABI declared in include/tao_amodal_hip.h.
+"""ctypes binding of the C ABI declared in include/tao_amodal_hip.h and
+include/tao_amodal_ingest.h.
 
-The shared library is built in-tree by ``tao_amodal_amd/csrc/build.sh`` (or
-``__graft_entry__.build()``).  There is NO fallback: if the library is missing
-or fails to load, importing the product path raises -- results never come
-from a CPU path.
+The two headers are the only declaration: ``SIGNATURES`` / ``INGEST_SIGNATURES``
+and the constants below are read from them when this module is imported (plain
+``re``, nothing but the standard library -- the module is importable without
+torch and without either library).  A new entry point is declared in the
+header, defined in csrc/ and called; nothing is typed in here.
+
+The shared libraries are built in-tree by ``tao_amodal_amd/csrc/build.sh`` (or
+``__graft_entry__.build()``).  There is NO fallback for the device library: if
+it is missing or fails to load, importing the product path raises -- results
+never come from a CPU path.
 """
 import ctypes as C
 import os
+import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 # TAOAMD_LIBRARY: another build of the same C ABI (A/B timing of kernel
 # variants on one GPU box); the default is the in-tree library
 SO_PATH = os.environ.get("TAOAMD_LIBRARY") or os.path.join(HERE, "libtao_amodal_hip.so")
+INGEST_SO_PATH = os.path.join(HERE, "libtao_amodal_ingest.so")
 
-OK = 0
-ERR_HIP, ERR_ARG, JSON_FALLBACK = 1, 2, 16
-N_THR, N_REC = 10, 101
-LVIS_RNG, TAO_RNG = 6, 20
-MAX_GT_PER_CELL = 3072
-SEGMENT_TILE = 2816
-ERROR_TYPES_TILE = 256
-TRACK_ERROR_TYPES_TILE = 16
+
+class TaoAmdError(RuntimeError):
+    pass
+
+
+# ---- the header reader
+# Scalars by name; `void` is a return type only; `const char *` is c_char_p and
+# every other pointer c_void_p (which takes ints, None, ctypes arrays and byref).
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64,
+            "uint32_t": C.c_uint32, "size_t": C.c_size_t, "double": C.c_double}
+_PROTOTYPE = re.compile(r"([\w\s*]+?)\b(taoamd_\w+)\s*\(([^()]*)\)\s*;")
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(TAOAMD_\w+)[ \t]+(-?\d+)[ \t]*$", re.M)
+
+
+def _ctype(decl, prototype):
+    """ctypes type of a return type or of one parameter with its name."""
+    if "*" in decl:
+        words = decl.replace("*", " * ").split()
+        return C.c_char_p if words[:3] == ["const", "char", "*"] and len(words) <= 4 \
+            else C.c_void_p
+    words = [w for w in decl.split() if w != "const"]
+    if words == ["void"]:
+        return None
+    if not words or words[0] not in _SCALARS or len(words) > 2 \
+            or not re.fullmatch(r"\w+", words[-1]):        # (`double box[4]` is no scalar)
+        raise TaoAmdError("unknown type '%s' in the prototype of %s" % (decl.strip(), prototype))
+    return _SCALARS[words[0]]
+
+
+def parse_header(text):
+    """({name: (restype, argtypes)}, {TAOAMD_X: int}) of a header's text: every
+    ``ret taoamd_name(args);`` and every ``#define TAOAMD_X <integer literal>``
+    outside the comments (a #define of anything else is skipped)."""
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    defines = {name: int(value) for name, value in _DEFINE.findall(text)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    signatures = {}
+    for ret, name, args in _PROTOTYPE.findall(text):
+        args = [a for a in args.split(",") if a.strip() not in ("", "void")]
+        signatures[name] = (_ctype(ret, name), [_ctype(a, name) for a in args])
+    return signatures, defines
+
+
+def read_header(name):
+    path = os.path.join(INCLUDE, name)
+    try:
+        with open(path) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise TaoAmdError("the C ABI is declared in %s, which cannot be read (%s); "
+                          "there is no second copy of it" % (path, e))
+
+
+# Once per process: the device header here, since the constants below come from
+# it; the ingest header, which defines none, when INGEST_SIGNATURES is first asked for.
+SIGNATURES, DEFINES = read_header("tao_amodal_hip.h")
+
+
+def _ingest_signatures():
+    if "INGEST_SIGNATURES" not in globals():
+        globals()["INGEST_SIGNATURES"] = read_header("tao_amodal_ingest.h")[0]
+    return globals()["INGEST_SIGNATURES"]
+
+
+def __getattr__(name):
+    if name == "INGEST_SIGNATURES":
+        return _ingest_signatures()
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
+def _define(name):
+    return DEFINES["TAOAMD_" + name]
+
+
+OK = _define("OK")
+ERR_HIP, ERR_ARG, JSON_FALLBACK = _define("ERR_HIP"), _define("ERR_ARG"), _define("JSON_FALLBACK")
+N_THR, N_REC = _define("N_THR"), _define("N_REC")
+LVIS_RNG, TAO_RNG = _define("LVIS_RNG"), _define("TAO_RNG")
+MAX_GT_PER_CELL = _define("MAX_GT_PER_CELL")
+SEGMENT_TILE = _define("SEGMENT_TILE")
+ERROR_TYPES_TILE = _define("ERROR_TYPES_TILE")
+TRACK_ERROR_TYPES_TILE = _define("TRACK_ERROR_TYPES_TILE")
 ERROR_TYPES = ("TP", "IGNORED", "DUP", "LOC", "CLS", "BOTH", "BKG")
-ERROR_IMPACT_CHUNK = 256
+ERROR_IMPACT_CHUNK = _define("ERROR_IMPACT_CHUNK")
 ERROR_FIXES = ("BASE", "CLS", "LOC", "BOTH", "DUP", "BKG", "MISS", "FP", "FN")
-CONFUSION_TILE = 2048
+CONFUSION_TILE = _define("CONFUSION_TILE")
 CONFUSION_COLUMNS = ("cls", "both", "unheld", "adopted")
-TRACK_ASSOCIATION_TILE = 64
-TRACK_ASSOCIATION_VIS = 8
+TRACK_ASSOCIATION_TILE = _define("TRACK_ASSOCIATION_TILE")
+TRACK_ASSOCIATION_VIS = _define("TRACK_ASSOCIATION_VIS")
 ASSOC_TRACK_COLUMNS = ("frames", "covered", "ids", "switches", "fragments", "primary",
                        "primary_frames")
 ASSOC_CAT_COLUMNS = ("tracks", "frames", "covered", "ids", "switches", "fragments",
                      "mostly_tracked", "mostly_lost")
 ASSOC_VIS_COLUMNS = ("frames", "covered", "primary")
-TRACK_OCCLUSION_LEN = 8
-TRACK_OCCLUSION_RECOVER = 64
+TRACK_OCCLUSION_LEN = _define("TRACK_OCCLUSION_LEN")
+TRACK_OCCLUSION_RECOVER = _define("TRACK_OCCLUSION_RECOVER")
 OCC_OUTCOMES = ("START", "UNFOLLOWED", "END", "KEPT", "SWITCHED", "LOST")
 OCC_EPISODE_COLUMNS = ("gt", "a", "n", "outcome", "entry", "after", "gap", "covered", "held")
 OCC_TRACK_COLUMNS = ("episodes", "frames", "kept", "switched_lost")
@@ -42,219 +126,26 @@ OCC_COUNT_COLUMNS = ("episodes", "frames", "covered", "held", "start", "unfollow
                      "kept", "switched", "lost", "gap")
 IDENT_CAT_COLUMNS = ("gt_tracks", "gt_frames", "dt_tracks", "dt_frames", "idtp", "pairs")
 
-_vp, _i64, _i32, _sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
 
-SIGNATURES = {
-    "taoamd_strerror": (C.c_char_p, [C.c_int]),
-    "taoamd_last_error": (C.c_char_p, []),
-    "taoamd_version": (C.c_int, []),
-    "taoamd_thresholds_host": (C.c_int, [_vp, _vp]),
-    "taoamd_set_thresholds": (C.c_int, [_vp, _vp]),
-    "taoamd_set_ranges": (C.c_int, [_vp, _vp, _vp]),
-    "taoamd_kernel_timing_enable": (C.c_int, [C.c_int]),
-    "taoamd_kernel_timing_label": (C.c_int, [C.c_char_p]),
-    "taoamd_kernel_timing_collect": (C.c_int, [_vp, _sz, _vp, _vp, _i32, _vp]),
-    "taoamd_bb_iou": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _vp, _vp]),
-    "taoamd_bb_iou_host": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _vp]),
-    "taoamd_lvis_ranges": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _i64, _vp,
-                                     _i32, _vp, _vp, _vp, _vp]),
-    "taoamd_tao_ranges": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
-                                    _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
-    "taoamd_sort_segments_workspace": (_sz, [_i64]),
-    "taoamd_sort_segments": (C.c_int, [_i64, _i32, _vp, _vp, _i32, _i32, _vp,
-                                       _vp, _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_sort_plan_host": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "taoamd_sort_sampled_workspace": (_sz, [_i64, _i64, _i32]),
-    "taoamd_sort_sampled_cap_limit": (C.c_int, [_i32]),
-    "taoamd_sort_sampled_notify": (C.c_int, [_vp]),
-    "taoamd_event_create": (C.c_int, [_vp]),
-    "taoamd_event_destroy": (C.c_int, [_vp]),
-    "taoamd_stream_wait_event": (C.c_int, [_vp, _vp]),
-    "taoamd_sort_sampled": (C.c_int, [_i64, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _vp,
-                                      _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp,
-                                      _sz, _vp]),
-    "taoamd_track_iou": (C.c_int, [_i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
-                                   _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
-    "taoamd_track_iou_single": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
-                                          _vp, _vp, _vp]),
-    "taoamd_track_iou_planned": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                           _i32, _vp, _vp, _i64, _vp, _vp]),
-    "taoamd_track_stream": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "taoamd_json_pred_workspace": (_sz, [_sz]),
-    "taoamd_json_pred_open": (_vp, [C.c_char_p, _vp, _sz, _vp, C.c_char_p, _sz, _vp]),
-    "taoamd_json_pred_count": (_i64, [_vp]),
-    "taoamd_json_pred_read": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                        _i32, _vp]),
-    "taoamd_json_pred_convert": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                           _i32, _vp]),
-    "taoamd_json_pred_close": (None, [_vp]),
-    "taoamd_track_pad": (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64,
-                                   _vp, _vp, _vp]),
-    "taoamd_track_iou_near": (C.c_int, [_i64, _vp, _vp, _i64, _vp, _i32, _i32,
-                                        _vp, _vp, _vp]),
-    "taoamd_track_iou_setorder_table": (_i64, [_i64, _i64]),
-    "taoamd_track_iou_setorder": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                            _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32,
-                                            _vp, _vp, _vp, _i64, _i64, _vp, _vp]),
-    "taoamd_set_order_iou_host": (C.c_int, [_vp, _i32, _vp, _vp, _i32, _vp, _vp,
-                                            _i32, _vp]),
-    "taoamd_pyset_union_order_host": (C.c_int, [_i64, _vp, _i64, _vp, _vp, _vp]),
-    "taoamd_track_iou_plan_host": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp,
-                                             _vp, _vp, _vp, _vp]),
-    "taoamd_track_iou_plan_spans_host": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp,
-                                                   _vp, _vp, _vp, _vp, _vp]),
-    "taoamd_flat_map": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp,
-                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "taoamd_flat_count_bad": (C.c_int, [_i64, _vp, _vp, _vp, _vp]),
-    "taoamd_flat_ordscore": (C.c_int, [_i64, _vp, _vp, _vp, _i32, _vp, _vp]),
-    "taoamd_flat_ordinal": (C.c_int, [_i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp]),
-    "taoamd_flat_merge_cat": (C.c_int, [_i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp,
-                                        _vp, _vp]),
-    "taoamd_flat_split64": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp]),
-    "taoamd_flat_compose": (C.c_int, [_i64, _vp, _vp, _vp, _vp]),
-    "taoamd_flat_gather_cols": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                          _vp]),
-    "taoamd_flat_track_of": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "taoamd_flat_keys": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                   _vp, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp,
-                                   _vp, _vp]),
-    "taoamd_flat_track_kept": (C.c_int, [_i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
-                                         _vp, _vp, _vp]),
-    "taoamd_flat_track_sel": (C.c_int, [_i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
-                                        _vp, _vp, _vp, _vp, _vp]),
-    "taoamd_flat_track_filter": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                           _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
-                                           _vp, _vp, _vp, _vp, _vp, _vp]),
-    "taoamd_flat_frames": (C.c_int, [_i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp,
-                                     _vp, _vp, _vp, _vp, _vp]),
-    "taoamd_flat_scan": (C.c_int, [_i64, _vp, _vp, _vp, _vp]),
-    "taoamd_flat_runs_by": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
-                                      _vp]),
-    "taoamd_flat_runs64_by": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                        _sz, _vp]),
-    "taoamd_flat_rank_drop": (C.c_int, [_i64, _vp, _vp, _vp, _i32, _vp, _vp]),
-    "taoamd_flat_filter": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _i32, _i64,
-                                     _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
-                                     _vp, _vp]),
-    "taoamd_flat_gather": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp,
-                                     _vp, _vp, _vp, _vp, _vp, _vp]),
-    "taoamd_flat_runs_workspace": (_sz, [_i64]),
-    "taoamd_flat_runs": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_flat_remap": (C.c_int, [_i64, _vp, _vp, _vp, _vp]),
-    "taoamd_match_plan_host": (C.c_int, [_i64, _vp, _vp, _i32, _i32, _i32, _vp,
-                                         _vp, _vp]),
-    "taoamd_match": (C.c_int, [_i64, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32,
-                               _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
-                               _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp]),
-    "taoamd_match_compact": (C.c_int, [_i64, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp,
-                                       _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp]),
-    "taoamd_expand_rows": (C.c_int, [_i64, _i32, _vp, _vp, _vp]),
-    "taoamd_gather_rows": (C.c_int, [_i64, _i32, _vp, _vp, _i64, _vp, _vp,
-                                     _vp, _vp]),
-    "taoamd_compact_elems": (_sz, [_i32, _i32]),
-    "taoamd_accumulate_compact": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp,
-                                            _vp, _i32, _i32, _i32, _vp, _vp,
-                                            _vp, _sz, _vp]),
-    "taoamd_rle_iou_workspace": (_sz, [_i64, _i64, _i64, _i64]),
-    "taoamd_rle_iou": (C.c_int, [_i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp,
-                                 _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
-                                 _sz, _vp]),
-    "taoamd_track_mask_iou_workspace": (_sz, [_i64, _i64, _i64, _i64]),
-    "taoamd_track_mask_iou": (C.c_int, [_i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i64,
-                                        _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp,
-                                        _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_finalize": (C.c_int, [_i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "taoamd_exchange_chunk_bytes": (_sz, [_i32, _i32, _i64]),
-    "taoamd_exchange_workspace": (_sz, [_i32, _i32, _i32]),
-    "taoamd_exchange_sizes": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_exchange_pack": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp,
-                                       _vp, _vp, _i64, _vp, _vp, _sz, _i32, _vp]),
-    "taoamd_exchange_unpack": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _i64, _vp,
-                                         _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
-    "taoamd_exchange_scores": (C.c_int, [_i64, _vp, _vp, _vp, _vp]),
-    "taoamd_exchange_positions": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp,
-                                            _vp, _vp, _vp]),
-    "taoamd_exchange_place": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp,
-                                        _vp]),
-    "taoamd_sort_workspace": (_sz, [_i64]),
-    "taoamd_sort_by_cat_score": (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _sz,
-                                           _vp]),
-    "taoamd_accumulate_workspace": (_sz, [_i64, _i32, _i32]),
-    "taoamd_accumulate": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32,
-                                    _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_accumulate_error": (C.c_int, [_vp, _vp, _vp]),
-    "taoamd_accumulate_chunked": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32,
-                                            _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_accumulate_compact_chunked": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp,
-                                                    _vp, _i32, _i32, _i32, _vp, _vp,
-                                                    _vp, _sz, _vp]),
-    "taoamd_accumulate_sweep_mode": (C.c_int, [_i32]),
-    "taoamd_accumulate_plan_kind": (C.c_int, [_i64, _i32, _i32]),
-    "taoamd_accumulate_spin_limit": (C.c_int, [_i32]),
-    "taoamd_accumulate_giveup_counter": (C.c_int, [_vp]),
-    "taoamd_accumulate_prepare": (C.c_int, [_i64, _i32, _i32, _vp, _i32, _vp, _sz, _vp]),
-    "taoamd_accumulate_prepared": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _i32,
-                                    _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_accumulate_by_order": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp,
-                                             _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_accumulate_by_order_prepared": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp,
-                                             _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_accumulate_by_order_chunked": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp,
-                                             _vp, _i32, _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_accumulate_by_order_compact": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp,
-                                                     _vp, _i32, _vp, _vp, _vp, _sz, _i32,
-                                                     _vp]),
-    "taoamd_score_at_recall_workspace": (_sz, [_i64, _i32, _i32]),
-    "taoamd_score_at_recall": (C.c_int, [_i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
-                                         _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_error_types_workspace": (_sz, [_i64, _i64, _i32]),
-    "taoamd_error_types": (C.c_int, [_i64, _i64, _i32, _i32, _i32, _i32, C.c_double,
-                                     _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
-                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_error_types_links": (C.c_int, [_i64, _i64, _i32, _i32, _i32, _i32, C.c_double,
-                                           _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
-                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                           _sz, _vp]),
-    "taoamd_error_impact_workspace": (_sz, [_i64, _i64, _i32, _i32]),
-    "taoamd_error_impact": (C.c_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
-                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_track_error_types_workspace": (_sz, [_i64, _i64, _i32]),
-    "taoamd_track_error_types": (C.c_int, [_i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
-                                           C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
-                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_track_error_types_links": (C.c_int, [_i64, _i64, _i64, _i64, _i32, _i32, _i32,
-                                                 _i32, C.c_double, _vp, _vp, _vp, _vp, _vp,
-                                                 _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                 _vp, _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_track_error_impact_workspace": (_sz, [_i64, _i64, _i32, _i32]),
-    "taoamd_track_error_impact": (C.c_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
-                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_confusion_workspace": (_sz, [_i64, _i64, _i32, _i32]),
-    "taoamd_confusion_count": (C.c_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
-                                         _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_confusion_fill": (C.c_int, [_i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
-                                        _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
-    "taoamd_track_association_workspace":(_sz, [_i64, _i64, _i64]),
-    "taoamd_track_association": (C.c_int, [_i64, _i64, _i64, _i64, _i64, _i64, _i32, _i32,
-                                           C.c_double] + [_vp] * 20 + [_sz, _vp]),
-    "taoamd_track_occlusion_workspace": (_sz, [_i64, _i64, _i32]),
-    "taoamd_track_occlusion_count": (C.c_int, [_i64, _i64, _i32, _i32, _i32, C.c_double,
-                                               C.c_double] + [_vp] * 10 + [_sz, _vp]),
-    "taoamd_track_occlusion_fill": (C.c_int, [_i64, _i64, _i32, _i32, _i32, C.c_double,
-                                              C.c_double] + [_vp] * 7 + [_i64, _vp, _vp, _sz,
-                                                                         _vp]),
-    "taoamd_track_identity_workspace": (_sz, [_i64, _i64, _i64]),
-    "taoamd_track_identity_share": (C.c_int, [_i64] * 6 + [C.c_double] + [_vp] * 11 + [_sz, _vp]),
-    "taoamd_track_identity_assign": (C.c_int, [_i64] * 6 + [_i32] + [_vp] * 15 + [_sz, _vp]),
-}
+# ---- the two libraries
+def bind(cdll, table, names=None):
+    """Set restype and argtypes of the functions `names` (default: all) of
+    `table` on `cdll`.  A symbol the library lacks -- a build older than the
+    header -- raises AttributeError naming it, and nothing is bound.  Binding
+    twice sets the same values: harmless from two threads at once."""
+    names = list(table) if names is None else names
+    missing = [name for name in names if not hasattr(cdll, name)]
+    if missing:
+        raise AttributeError("%s lacks %s: it is older than its header (run "
+                             "tao_amodal_amd/csrc/build.sh)" % (cdll._name, ", ".join(missing)))
+    for name in names:
+        fn = getattr(cdll, name)
+        fn.restype, fn.argtypes = table[name]
+    return cdll
+
 
 _lib = None
-
-
-class TaoAmdError(RuntimeError):
-    pass
+_ingest = None
 
 
 def load():
@@ -272,13 +163,34 @@ def load():
             "HIP extension not built: %s is missing.  Run "
             "tao_amodal_amd/csrc/build.sh (or __graft_entry__.build()).  "
             "There is no CPU fallback." % SO_PATH)
-    lib = C.CDLL(SO_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)     # AttributeError if a symbol is missing
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+    _lib = bind(C.CDLL(SO_PATH), SIGNATURES)
+    return _lib
+
+
+def load_ingest(required=False):
+    """libtao_amodal_ingest.so (the host-only readers, writers, masks and
+    vector helpers) with every function of its header bound, opened once; None
+    when it is not built -- the file absent, one that does not load, or a build
+    that lacks a declared symbol.  ``required``: raise instead (callers without
+    a Python statement of what they ask the library for)."""
+    global _ingest
+    lib = _ingest
+    if lib is None:
+        # (the answer is published when it is complete: a thread that arrives
+        # meanwhile opens and binds a handle of its own, which is harmless, and
+        # is never told "not built" by a half-made one)
+        lib = False
+        if os.path.exists(INGEST_SO_PATH):
+            try:
+                lib = bind(C.CDLL(INGEST_SO_PATH), _ingest_signatures())
+            except (OSError, AttributeError):
+                pass
+        _ingest = lib
+    if required and not lib:
+        raise TaoAmdError(
+            "native host library not built: %s is missing or older than its header (run "
+            "tao_amodal_amd/csrc/build.sh); this call has no Python fallback" % INGEST_SO_PATH)
+    return lib or None
 
 
 TIMING = False     # kernel_timing(True): engine passes label their launches

@@ -30,16 +30,6 @@ FREQ_MISSING, FREQ_OTHER = ord("?"), 0xFF
 EARLY_HIP = {}
 
 
-def _ingest_lib():
-    import ctypes as C
-    so = os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                      "libtao_amodal_ingest.so")
-    lib = C.CDLL(so)
-    lib.taoamd_pred_write.argtypes = [C.c_char_p, C.c_int64] + [C.c_void_p] * 6
-    lib.taoamd_gt_write.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int32]
-    return lib
-
-
 def _freq_byte(cat):
     if "frequency" not in cat:
         return FREQ_MISSING
@@ -85,21 +75,10 @@ class GTColumns:
         parallel); returns None when that library is not built.  Errors are
         those ``json.load`` + ``from_json`` would raise."""
         import ctypes as C
-        import os
-        so = os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                          "libtao_amodal_ingest.so")
-        if not os.path.exists(so):
+        from . import _lib
+        lib = _lib.load_ingest()
+        if lib is None:
             return None
-        lib = C.CDLL(so)
-        if not hasattr(lib, "taoamd_gt_parse"):
-            return None
-        lib.taoamd_gt_parse.restype = C.c_void_p
-        lib.taoamd_gt_parse.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
-        lib.taoamd_gt_array.argtypes = [C.c_void_p, C.c_char_p,
-                                        C.POINTER(C.c_void_p),
-                                        C.POINTER(C.c_int64), C.POINTER(C.c_int)]
-        lib.taoamd_gt_free.argtypes = [C.c_void_p]
-        lib.taoamd_gt_copy.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p]
         err = C.create_string_buffer(512)
         h = lib.taoamd_gt_parse(os.fsencode(path), err, 512)
         if not h:
@@ -223,7 +202,8 @@ class GTColumns:
         jsonwrite.cpp): what ``json.dump(self.to_json())`` holds, without the
         dicts -- for sets of millions of annotations."""
         import ctypes as C
-        lib = _ingest_lib()
+        from . import _lib
+        lib = _lib.load_ingest(required=True)
         arrs = [np.ascontiguousarray(getattr(self, f)) for f in self.FIELDS]
         want = {"cat_freq": np.uint8, "trk_ignore": np.uint8, "ann_oof": np.uint8,
                 "ann_ignore": np.uint8, "img_frame": np.float64,
@@ -382,22 +362,14 @@ class DTColumns:
         CLI) -- the result then carries ``first`` (position of its first record
         in the file) and ``total`` (records in the file)."""
         import ctypes as C
-        import os
-        so = os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                          "libtao_amodal_ingest.so")
-        if not os.path.exists(so):
+        from . import _lib
+        lib = _lib.load_ingest()
+        if lib is None:
             return None
-        lib = C.CDLL(so)
         if n_parts == 1:
             out = cls._from_file_device(path, lib)
             if out is not None:
                 return out
-        lib.taoamd_pred_scan.restype = C.c_void_p
-        lib.taoamd_pred_scan.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.c_char_p,
-                                         C.c_size_t]
-        lib.taoamd_pred_scan_info.argtypes = [C.c_void_p] * 4
-        lib.taoamd_pred_convert.argtypes = [C.c_void_p] * 7 + [C.c_char_p, C.c_size_t]
-        lib.taoamd_pred_scan_free.argtypes = [C.c_void_p]
         err = C.create_string_buffer(512)
 
         def refuse(msg):
@@ -485,13 +457,9 @@ class DTColumns:
             ev.wait()
             if not EARLY_HIP.get("ok") or not os.path.exists(_lib.SO_PATH):
                 return None
-            hip = C.CDLL(_lib.SO_PATH)
-            for name in ("taoamd_json_pred_open", "taoamd_json_pred_workspace",
-                         "taoamd_json_pred_count",
-                         "taoamd_json_pred_read", "taoamd_json_pred_close",
-                         "taoamd_last_error"):
-                fn = getattr(hip, name)
-                fn.restype, fn.argtypes = _lib.SIGNATURES[name]
+            hip = _lib.bind(C.CDLL(_lib.SO_PATH), _lib.SIGNATURES, (
+                "taoamd_json_pred_open", "taoamd_json_pred_workspace", "taoamd_json_pred_count",
+                "taoamd_json_pred_read", "taoamd_json_pred_close", "taoamd_last_error"))
         else:
             try:
                 hip = _lib.load()
@@ -589,8 +557,9 @@ class DTColumns:
         order = np.argsort(flag[:k], kind="stable")
         idx = np.ascontiguousarray(flag[:k][order])
         at = np.ascontiguousarray(flag_at[:k][order])
-        host_lib.taoamd_pred_patch.argtypes = [C.c_char_p, C.c_int64] + [C.c_void_p] * 8 \
-            + [C.c_char_p, C.c_size_t]
+        # (host_lib is the caller's handle, not necessarily the loader's: without
+        # argtypes the pointers below would be passed as C ints)
+        _lib.bind(host_lib, _lib.INGEST_SIGNATURES, ("taoamd_pred_patch",))
         rc = host_lib.taoamd_pred_patch(
             os.fsencode(path), k, idx.ctypes.data, at.ctypes.data,
             out.image_id.ctypes.data, out.category_id.ctypes.data, out.bbox.ctypes.data,
@@ -650,7 +619,8 @@ class DTColumns:
     def write_json(self, path):
         """The prediction list written by the native writer (csrc/
         jsonwrite.cpp)."""
-        lib = _ingest_lib()
+        from . import _lib
+        lib = _lib.load_ingest(required=True)
         i64 = lambda a: np.ascontiguousarray(a, dtype=np.int64)
         cols = [i64(self.image_id), i64(self.category_id),
                 np.ascontiguousarray(self.bbox, dtype=np.float64),

@@ -18,17 +18,13 @@ from .lvis import LVIS
 def _all_known(sorted_ids, values):
     """every value is one of sorted_ids (native: 30 M image ids on all
     threads; numpy when the reader library is not built)"""
-    from ...columns import _ingest_lib
-    try:
-        lib = _ingest_lib()
-    except OSError:
+    from ... import _lib
+    lib = _lib.load_ingest()
+    if lib is None:
         from ...flatten import _lookup
         return bool((_lookup(sorted_ids, values) >= 0).all())
-    import ctypes as C
     k = np.ascontiguousarray(sorted_ids, dtype=np.int64)
     v = np.ascontiguousarray(values, dtype=np.int64)
-    lib.taoamd_host_all_in_sorted.restype = C.c_int
-    lib.taoamd_host_all_in_sorted.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     rc = lib.taoamd_host_all_in_sorted(len(k), k.ctypes.data, len(v), v.ctypes.data)
     assert rc >= 0
     return rc == 1

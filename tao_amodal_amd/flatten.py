@@ -40,6 +40,7 @@ import sys
 
 import numpy as np
 
+from . import _lib
 from .columns import DTColumns, GTColumns, array_key
 
 MAX_DETS = 300
@@ -53,40 +54,11 @@ DT_IGNORE_UNMATCHED = 1   # unmatched detection is ignored (not exhaustive...)
 DT_NO_CONSUME = 2         # id <= 0: a match does not mark the GT as taken
 
 
-_HOST_LIB = None
-
-
 def _host_lib():
-    """libtao_amodal_ingest.so (native host helpers) or False when not built."""
-    global _HOST_LIB
-    if _HOST_LIB is None:
-        import ctypes as C
-        import os
-        so = os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                          "libtao_amodal_ingest.so")
-        _HOST_LIB = False
-        if os.path.exists(so):
-            lib = C.CDLL(so)
-            vp, i64 = C.c_void_p, C.c_int64
-            sigs = {
-                "taoamd_host_sort_key_score": [i64, vp, vp, vp],
-                "taoamd_host_lookup": [i64, vp, i64, vp, vp],
-                "taoamd_host_take": [C.c_int32, i64, vp, i64, vp, vp],
-                "taoamd_host_seq_mean": [i64, vp, vp, vp],
-                "taoamd_host_pyset_self_and": [i64, vp, vp, vp],
-                "taoamd_host_track_clash": [i64, vp, vp, vp],
-                "taoamd_host_count_bad_boxes": [i64, vp, vp],
-                "taoamd_host_threads": [],
-                "taoamd_host_thread_cap": [C.c_int32],
-            }
-            # (a library of another build -- a symbol missing -- is not used at
-            # all: the numpy statements of these helpers are the fallback)
-            if all(hasattr(lib, name) for name in sigs):
-                for name, args in sigs.items():
-                    getattr(lib, name).argtypes = args
-                    getattr(lib, name).restype = C.c_int
-                _HOST_LIB = lib
-    return _HOST_LIB
+    """libtao_amodal_ingest.so (native host helpers) or False when not built
+    (a library of another build -- a symbol missing -- is not used at all: the
+    numpy statements of these helpers are the fallback)."""
+    return _lib.load_ingest() or False
 
 
 _NATIVE_MIN = 50000       # elements from which a call into the host library pays

@@ -10,45 +10,10 @@ form); ``arrays()`` returns the back-to-back run lengths the device kernel
 library has to be built (csrc/build.sh).
 """
 import ctypes as C
-import os
 
 import numpy as np
 
-_SO = os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                   "libtao_amodal_ingest.so")
-_lib = None
-
-
-def _load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(_SO):
-            raise RuntimeError(
-                "native host library not built: %s is missing (run "
-                "tao_amodal_amd/csrc/build.sh); run-length masks have no "
-                "Python fallback" % _SO)
-        lib = C.CDLL(_SO)
-        vp, i64 = C.c_void_p, C.c_int64
-        lib.taoamd_rle_new.restype = vp
-        lib.taoamd_rle_free.argtypes = [vp]
-        lib.taoamd_rle_count.restype = i64
-        lib.taoamd_rle_count.argtypes = [vp]
-        lib.taoamd_rle_total.restype = i64
-        lib.taoamd_rle_total.argtypes = [vp]
-        lib.taoamd_rle_add_polygons.restype = i64
-        lib.taoamd_rle_add_polygons.argtypes = [vp, C.c_int32, vp, vp, i64, i64]
-        lib.taoamd_rle_add_polygon_batch.restype = i64
-        lib.taoamd_rle_add_polygon_batch.argtypes = [vp, i64, vp, vp, vp, vp]
-        lib.taoamd_rle_add_counts.restype = i64
-        lib.taoamd_rle_add_counts.argtypes = [vp, vp, i64, i64, i64]
-        lib.taoamd_rle_add_string.restype = i64
-        lib.taoamd_rle_add_string.argtypes = [vp, C.c_char_p, i64, i64]
-        lib.taoamd_rle_copy.restype = C.c_int
-        lib.taoamd_rle_copy.argtypes = [vp, vp, vp, vp, vp, vp]
-        lib.taoamd_rle_string.restype = i64
-        lib.taoamd_rle_string.argtypes = [vp, i64, vp, i64]
-        _lib = lib
-    return _lib
+from . import _lib
 
 
 class MaskArrays:
@@ -77,7 +42,7 @@ class MaskArrays:
 
 class MaskBatch:
     def __init__(self):
-        self.lib = _load()
+        self.lib = _lib.load_ingest(required=True)
         self.h = self.lib.taoamd_rle_new()
 
     def close(self):

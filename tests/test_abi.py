@@ -22,14 +22,14 @@ def test_header_symbols_are_exported_and_bound():
 
 
 def test_ingest_header_symbols_are_exported():
-    import ctypes
     text = open(os.path.join(ROOT, "include", "tao_amodal_ingest.h")).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     declared = set(re.findall(r"\b(taoamd_[a-z_0-9]+)\s*\(", text))
     assert len(declared) == 37, declared
-    lib = ctypes.CDLL(os.path.join(ROOT, "tao_amodal_amd", "libtao_amodal_ingest.so"))
+    lib = _lib.load_ingest(required=True)
     for name in sorted(declared):
         assert hasattr(lib, name), name
+    assert declared == set(_lib.INGEST_SIGNATURES), declared ^ set(_lib.INGEST_SIGNATURES)
 
 
 def test_thresholds_are_numpy_linspace_bit_for_bit():
@@ -78,11 +78,7 @@ def test_sort_plan_covers_every_category():
 
 
 def test_all_in_sorted_is_the_membership_test():
-    import ctypes as C
-    from tao_amodal_amd.columns import _ingest_lib
-    lib = _ingest_lib()
-    lib.taoamd_host_all_in_sorted.restype = C.c_int
-    lib.taoamd_host_all_in_sorted.argtypes = [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    lib = _lib.load_ingest(required=True)
     rng = np.random.default_rng(3)
 
     def ask(keys, values):
@@ -260,3 +256,123 @@ def test_entry_points_refuse_a_workspace_below_the_reported_size():
     calls.append(("taoamd_flat_runs64_by", (n, p, p, p, p, p, p, p, nb, None)))
     for name, args in calls:
         assert getattr(lib, name)(*args) == 4, name
+
+
+# ---- the binding is read from the headers (_lib.parse_header)
+_FORMS = """
+/* a comment with code in it: int taoamd_fake(int x); (and, commas) */
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define TAOAMD_PLAIN 7   /* a trailing comment */
+#define TAOAMD_PRODUCT (16 * 2816)
+const char *taoamd_text(int status);
+int taoamd_nothing(void);
+void taoamd_close(void *handle);   /* a trailing comment */
+size_t taoamd_bytes(
+    int64_t n, int32_t k, uint32_t u, double x, size_t s);
+int taoamd_many(const char *path, const void *const *arrays, const void **ptr,
+                void **event, int *elem, char *err,
+                const int64_t *counts, const unsigned char *flags);
+void *taoamd_open(const int64_t n);
+"""
+
+
+def test_reader_handles_every_prototype_form():
+    import ctypes as C
+    vp = C.c_void_p
+    sigs, defines = _lib.parse_header(_FORMS)
+    assert sigs == {
+        "taoamd_text": (C.c_char_p, [C.c_int]),
+        "taoamd_nothing": (C.c_int, []),
+        "taoamd_close": (None, [vp]),
+        "taoamd_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_uint32, C.c_double, C.c_size_t]),
+        "taoamd_many": (C.c_int, [C.c_char_p, vp, vp, vp, vp, vp, vp, vp]),
+        "taoamd_open": (vp, [C.c_int64]),
+    }
+    assert "taoamd_fake" not in sigs
+    assert defines == {"TAOAMD_PLAIN": 7}
+
+
+def test_reader_refuses_an_unknown_type():
+    import pytest
+    for text in ("int taoamd_x(float v);", "float taoamd_x(int v);",
+                 "int taoamd_x(unsigned int v);", "int taoamd_x(double box[4]);"):
+        with pytest.raises(_lib.TaoAmdError, match="taoamd_x"):
+            _lib.parse_header(text)
+
+
+def test_constants_come_from_the_header():
+    sigs, defines = _lib.read_header("tao_amodal_hip.h")
+    assert defines["TAOAMD_N_THR"] == 10 == _lib.N_THR
+    assert "TAOAMD_SORT_CHUNK" not in defines
+    assert sigs == _lib.SIGNATURES
+    import pytest
+    with pytest.raises(_lib.TaoAmdError, match="no_such_header.h"):
+        _lib.read_header("no_such_header.h")
+
+
+def test_every_declared_function_is_bound():
+    import pytest
+    for lib, table in ((_lib.load(), _lib.SIGNATURES),
+                       (_lib.load_ingest(required=True), _lib.INGEST_SIGNATURES)):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(lib, name)
+            assert fn.restype is restype, name
+            assert list(fn.argtypes) == argtypes, name
+            if argtypes:
+                with pytest.raises(TypeError):      # (refused before the call: nothing runs)
+                    fn()
+
+
+def test_a_stale_library_is_reported_and_not_bound(monkeypatch):
+    import ctypes as C
+    import pytest
+    table = dict(_lib.INGEST_SIGNATURES, taoamd_not_in_this_build=(C.c_int, [C.c_int64]))
+    lib = C.CDLL(_lib.INGEST_SO_PATH)
+    with pytest.raises(AttributeError, match="taoamd_not_in_this_build"):
+        _lib.bind(lib, table)
+    assert lib.taoamd_host_lookup.argtypes is None      # nothing was bound
+    assert _lib.bind(lib, table, ("taoamd_host_lookup",)) is lib
+    assert len(lib.taoamd_host_lookup.argtypes) == 5
+    # the loader: such a build counts as not built
+    monkeypatch.setattr(_lib, "_ingest", None)
+    monkeypatch.setattr(_lib, "INGEST_SIGNATURES", table)
+    assert _lib.load_ingest() is None
+    with pytest.raises(_lib.TaoAmdError, match="build.sh"):
+        _lib.load_ingest(required=True)
+
+
+def test_two_threads_loading_the_ingest_library_at_once_both_get_it(monkeypatch):
+    """The CLI's two readers call the loader side by side: neither may be told
+    "not built" while the other is still opening and binding the library."""
+    import threading
+    for _ in range(200):
+        monkeypatch.setattr(_lib, "_ingest", None)
+        barrier, got = threading.Barrier(2), []
+
+        def ask():
+            barrier.wait()
+            got.append(_lib.load_ingest())
+        threads = [threading.Thread(target=ask) for _ in range(2)]
+        for t in threads:
+            t.start()
+        for t in threads:
+            t.join()
+        assert len(got) == 2 and None not in got
+        assert all(len(lib.taoamd_pred_patch.argtypes) == 12 for lib in got)
+
+
+def test_a_library_that_does_not_load_counts_as_not_built(monkeypatch, tmp_path):
+    bad = tmp_path / "libtao_amodal_ingest.so"
+    bad.write_bytes(b"not an ELF file")
+    monkeypatch.setattr(_lib, "_ingest", None)
+    monkeypatch.setattr(_lib, "INGEST_SO_PATH", str(bad))
+    assert _lib.load_ingest() is None
+
+
+def test_the_ingest_library_is_opened_once():
+    lib = _lib.load_ingest()
+    assert lib is not None and _lib.load_ingest() is lib
+    from tao_amodal_amd import flatten
+    assert flatten._host_lib() is lib

@@ -195,7 +195,7 @@ def test_flatten_is_the_same_with_and_without_the_native_sort(monkeypatch):
     ids, _ = flatten.make_track_ids_unique(dt)
     dt.track_id = ids
     a_t = flatten.flatten_tao(gt, dt)
-    monkeypatch.setattr(flatten, "_HOST_LIB", False)
+    monkeypatch.setattr(flatten, "_host_lib", lambda: False)
     flatten_dev.forget_columns(dt)
     b_l = flatten.flatten_lvis(gt, dt)
     b_t = flatten.flatten_tao(gt, dt)
@@ -416,7 +416,7 @@ def test_rows_patched_for_the_device_reader(tmp_path):
     json_ingest.hip) leaves to this one, read at their byte offsets into their
     rows -- the same values as the whole-file read, the same error text."""
     import ctypes as C
-    from tao_amodal_amd import columns
+    from tao_amodal_amd import _lib
     base = '{"image_id": %d, "category_id": 3, "bbox": [1, 2.5, 3e1, 4], "score": %s, "track_id": %s}'
     objs = [base % (k, "0.5", str(k)) for k in range(200)]
     objs[7] = base % (7, "NaN", "7")
@@ -427,10 +427,7 @@ def test_rows_patched_for_the_device_reader(tmp_path):
     with open(p, "w") as f:
         f.write(text)
     whole = DTColumns.from_file_native(p)
-    lib = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(columns.__file__)),
-                              "libtao_amodal_ingest.so"))
-    lib.taoamd_pred_patch.argtypes = [C.c_char_p, C.c_int64] + [C.c_void_p] * 8 + [C.c_char_p,
-                                                                                   C.c_size_t]
+    lib = _lib.load_ingest(required=True)
     n = len(objs)
     cols = DTColumns(image_id=np.zeros(n, np.int64), category_id=np.zeros(n, np.int64),
                      bbox=np.zeros((n, 4)), score=np.zeros(n), track_id=np.zeros(n, np.int64),

@@ -458,7 +458,7 @@ def main(argv=None):
                 for the rest of it, the import included."""
                 from tao_amodal_amd import flatten as fl
                 lib = fl._host_lib() if team else False
-                if not lib or not hasattr(lib, "taoamd_host_thread_cap"):
+                if not lib:
                     return fn(*a)
                 lib.taoamd_host_thread_cap(team)
                 try:

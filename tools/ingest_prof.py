@@ -4,12 +4,12 @@ validation scale (development aid): three device reads and one host read of a
     TAOAMD_INGEST_TIMING=1 python tools/ingest_prof.py        (on an MI355X box)
     rocprofv3 --kernel-trace --stats -- python tools/ingest_prof.py   (the js_* kernels)
 """
-import os, sys, time, ctypes as C
+import os, sys, time
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 import numpy as np
 import torch
 from tao_amodal_amd.columns import DTColumns
-from tao_amodal_amd import columns
+from tao_amodal_amd import _lib
 from tao_amodal_amd.synth import synth
 path = '/tmp/_pred_prof.json'
 if not os.path.exists(path):
@@ -17,7 +17,7 @@ if not os.path.exists(path):
     dt.write_json(path)
     del gt, dt
 print('file MB', os.path.getsize(path) / 1e6)
-lib = C.CDLL(os.path.join(os.path.dirname(os.path.abspath(columns.__file__)), "libtao_amodal_ingest.so"))
+lib = _lib.load_ingest(required=True)
 torch.zeros(1, device='cuda')
 for rep in range(3):
     t = time.perf_counter()
