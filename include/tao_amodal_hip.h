@@ -701,17 +701,6 @@ int taoamd_sort_plan_host(int32_t n_cat, const int32_t *cat_off_host, int64_t *s
                           int32_t *bucket_chunk);
 size_t taoamd_sort_sampled_workspace(int64_t n, int64_t n_buckets, int32_t merge);
 int taoamd_sort_sampled_cap_limit(int32_t limit);
-/* Ordering other streams around the splitter kernel INSIDE taoamd_sort_sampled:
- * `event` (from taoamd_event_create) is recorded on the sort's stream right
- * behind the splitter kernel of the calling thread's NEXT taoamd_sort_sampled
- * (NULL = none; the request is consumed by that call).  The image level's
- * splitters are 0.06 ms of latency at the head of the step's critical chain;
- * work started beside the sort (the track level's 3D IoU) waits for them with
- * taoamd_stream_wait_event instead of starving their workgroups of wave slots. */
-int taoamd_sort_sampled_notify(void *event);
-int taoamd_event_create(void **event);
-int taoamd_event_destroy(void *event);
-int taoamd_stream_wait_event(void *stream, void *event);
 int taoamd_sort_sampled(int64_t n, int32_t n_cat, const int32_t *cat_off,
                         const int32_t *tile_off, int32_t n_tiles, int32_t max_segment,
                         const double *dt_score, int32_t n_chunks, const int32_t *chunks,
@@ -820,7 +809,6 @@ int taoamd_accumulate_compact_chunked(int64_t n_dt, int32_t n_cat, int32_t n_rng
                               double *val, double *rec, void *workspace,
                               size_t workspace_bytes, void *stream);
 /* Which sweep long categories take, for the process: -1 automatic (the
- * environment's TAOAMD_SWEEP=chunked|lookback|twopass if set, else the
  * one-pass look-back sweep from 6 M rows up), 0 the chunked kernels, 1 the
  * one-pass sweep with the look-back, 2 the one-pass sweep behind a counting
  * pass.  An explicit 1 / 2 also takes the short categories the fused

@@ -56,12 +56,8 @@
 
 using namespace taoamd;
 
-#ifndef ACC_CH
 #define ACC_CH 256
-#endif
-#ifndef ACC_INLINE_CHUNKS
 #define ACC_INLINE_CHUNKS 64    // categories up to 16384 rows scan their chunks inline
-#endif
 
 struct AccArgs {
     int64_t n_dt;
@@ -1164,23 +1160,19 @@ __global__ __launch_bounds__(FW * WAVE) void acc_fused_kernel(AccArgs a, RecThr 
 //
 // The walk itself (emit_block) is the chunked path's, statement by statement.
 // ===========================================================================
-// -DSW_ABLATE=<bits> (timing experiments, results wrong): 1 no walk, 2 no
-// transposes, 4 no look-back, 8 leave behind the rows' counts, 16 leave behind
-// the counts of the earlier chunks.  Round 6, 21.4 M rows, one box: whole kernel
-// 0.260 ms; rows fetched and counted without transposes 0.069 (5.0 TB/s), with
+// Measured with builds that left the kernel at five points (results wrong,
+// timing only).  Round 6, 21.4 M rows, one box: whole kernel 0.260 ms; rows fetched and counted without transposes 0.069 (5.0 TB/s), with
 // them 0.103; up to the earlier chunks' counts 0.113; everything but the walk
 // 0.160 (0.159 without the transposes too: behind the first barrier they are
 // hidden); without the look-back 0.245.  So the walk is 0.10 ms of the kernel
 // and the bookkeeping between the counts and the walk's end 0.05.
 #define SC_SPIN_LIMIT (1 << 18)     // a fraction of a second of polling
 #define SWEEP_NB 8                   // blocks of 64 rows per wavefront of the one-pass sweep
-#ifndef SWEEP_SW
 #define SWEEP_SW 4                   // wavefronts (chunks) per super-chunk: 16 and 8 were
                                      // measured slower (big workgroups hold their CU's wave
                                      // slots until the slowest wavefront is done); round 5,
                                      // -DSWEEP_SW=2 / 3 / 6 at 21 M rows: 0.287 / 0.270 /
                                      // 0.297 against 0.264 ms
-#endif
 #define SC_FLAG_AGG 1ull
 #define SC_FLAG_PRE 2ull
 __device__ __forceinline__ uint64_t sc_status(uint32_t gen, uint64_t flag, uint32_t v)
@@ -1302,13 +1294,8 @@ void acc_sweep_kernel(AccArgs a, RecThr rec)
             if (GATHER == 2)
                 crow_rows<NB>(a, start, len, lane, blk, cw[blk], s_crow, nall_lo, nall_hi,
                               tpw[blk], vw[blk]);
-#if defined(SW_ABLATE) && (SW_ABLATE & 2)     // (timing experiment: no transposes)
-            t_ = tpw[blk];
-            v_ = vw[blk];
-#else
             t_ = transpose64(tpw[blk], lane);
             v_ = transpose64(vw[blk], lane);
-#endif
         }
         T[blk] = t_;
         TF[blk] = v_;
@@ -1316,10 +1303,6 @@ void acc_sweep_kernel(AccArgs a, RecThr rec)
         n_own += (uint32_t)__popcll(v_);
     }
     const uint32_t fp_own = n_own - tp_own;       // (TP and FP rows are disjoint)
-#if defined(SW_ABLATE) && (SW_ABLATE & 8)     // (timing experiment: rows fetched and counted, nothing else)
-    if (tp_own + n_own == (uint32_t)a.sc_spin) a.sc_max[0] = n_own;
-    return;
-#endif
     s_tp[wave][lane] = tp_own;
     s_fp[wave][lane] = fp_own;
     __syncthreads();
@@ -1349,9 +1332,6 @@ void acc_sweep_kernel(AccArgs a, RecThr rec)
             // prefix.  A pair is usable when both words are of this call and of
             // one kind (the publisher replaces AGG by PRE word by word)
             bool open = jsc > 0;
-#if defined(SW_ABLATE) && (SW_ABLATE & 4)     // (timing experiment: no look-back)
-            open = false;
-#endif
             const int64_t stride = 2 * (int64_t)a.n_words * WAVE;
             const uint64_t *p = st - stride;
             for (int32_t jj = jsc - 1; jj >= 0 && __ballot(open) != 0; jj--, p -= stride) {
@@ -1396,10 +1376,6 @@ void acc_sweep_kernel(AccArgs a, RecThr rec)
     __syncthreads();
     tp0 += s_pre[0][lane];
     fp0 += s_pre[1][lane];
-#if defined(SW_ABLATE) && (SW_ABLATE & 16)    // (timing experiment: ... and the counts before the chunk)
-    if (tp0 + fp0 == (uint32_t)a.sc_spin) a.sc_max[0] = T[0] ^ TF[NB - 1];
-    return;
-#endif
     // ---- my lane's combo
     const int combo = word * WAVE + lane;
     const bool active = combo < a.n_rng * N_THR;
@@ -1442,11 +1418,7 @@ void acc_sweep_kernel(AccArgs a, RecThr rec)
 #pragma unroll
     for (int blk = NB - 1; blk >= 0; blk--) {
         if (blk * WAVE >= len) continue;
-#if defined(SW_ABLATE) && (SW_ABLATE & 1)     // (timing experiment: no walk)
-        run ^= T[blk] + TF[blk];
-#else
         emit_block<1>(live ? T[blk] : 0, live ? TF[blk] : 0, tp, n, run, jcur, cnext, out, cj);
-#endif
     }
     if (live && is_first && jcur > 0 && len > 0) {
         const uint64_t v = run;
@@ -1866,8 +1838,8 @@ static int32_t max_chunks(int64_t n_dt, int32_t n_cat)
 //   "chunked"  the six chunked kernels;  "lookback"  acc_sweep_kernel in one
 //   pass;  "twopass"  acc_sweep_kernel behind a counting pass.
 // taoamd_accumulate_sweep_mode() sets it for the process (the tests run every
-// parity case under each); unset, the environment's TAOAMD_SWEEP (read once);
-// without either: the one-pass sweep from SWEEP_ONEPASS_MIN rows up.  At
+// parity case under each); unset: the one-pass sweep from SWEEP_ONEPASS_MIN
+// rows up.  At
 // 21 M rows (2000 videos) it takes 0.39 ms against 0.52 for the chunked kernels
 // (rows read once instead of three times plus a transposed copy); at 2 M rows
 // (Config 2) everything is latency and the chunked kernels' three short
@@ -1879,16 +1851,8 @@ static std::atomic<int> g_sweep_spin{0};       // 0: SC_SPIN_LIMIT
 static std::atomic<uint32_t *> g_sweep_giveups{nullptr};   // taoamd_accumulate_giveup_counter
 static int sweep_mode(int64_t n_dt)
 {
-    static const int env = [] {
-        const char *e = getenv("TAOAMD_SWEEP");
-        if (e && !strcmp(e, "lookback")) return (int)SWEEP_LOOKBACK;
-        if (e && !strcmp(e, "twopass")) return (int)SWEEP_TWOPASS;
-        if (e && !strcmp(e, "chunked")) return (int)SWEEP_CHUNKED;
-        return (int)SWEEP_AUTO;
-    }();
     const int set = g_sweep_set.load(std::memory_order_relaxed);
-    const int m = set != SWEEP_AUTO ? set : env;
-    if (m != SWEEP_AUTO) return m;
+    if (set != SWEEP_AUTO) return set;
     return n_dt >= SWEEP_ONEPASS_MIN ? (int)SWEEP_LOOKBACK : (int)SWEEP_CHUNKED;
 }
 
@@ -1899,15 +1863,13 @@ extern "C" int taoamd_accumulate_sweep_mode(int32_t mode)
     return TAOAMD_OK;
 }
 
-// an explicit one-pass mode (setter or environment) also takes the categories
+// an explicit one-pass mode also takes the categories
 // the fused single-workgroup sweep would have taken: the parity tests drive the
 // small reference fixtures through the look-back that way
 static bool sweep_mode_explicit_onepass()
 {
     const int set = g_sweep_set.load(std::memory_order_relaxed);
-    const char *e = set == SWEEP_AUTO ? getenv("TAOAMD_SWEEP") : nullptr;
-    return set == SWEEP_LOOKBACK || set == SWEEP_TWOPASS ||
-           (e && (!strcmp(e, "lookback") || !strcmp(e, "twopass")));
+    return set == SWEEP_LOOKBACK || set == SWEEP_TWOPASS;
 }
 
 // Which kind of plan taoamd_accumulate_prepare builds for these sizes under

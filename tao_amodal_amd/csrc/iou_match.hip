@@ -421,11 +421,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         const int32_t d = d0 + min(lane, nD - 1);
         const int32_t g = g0 + min(lane, max(nG, 1) - 1);
         const uint32_t mt = a.dt_meta[d];
-#ifdef TAOAMD_ABLATE_SCATTER     // (timing experiment: rows stored in detection order)
-        const int32_t row = SCATTER ? d + (a.dst[d] & 0) : d;
-#else
         const int32_t row = SCATTER ? a.dst[d] : d;
-#endif
         const double4 box = reinterpret_cast<const double4 *>(a.dt_box)[d];
         uint32_t gr = 0xffffffffu;
         uint8_t gf = 0;
@@ -983,8 +979,7 @@ static int match_launch(int64_t n_cells, const int32_t *cell_dt_off,
     a.dt_meta = fused && ious_out == nullptr ? dt_meta : nullptr;
     a.dt_group = dt_group; a.groups = groups; a.n_groups = planned ? n_groups : 0;
     a.singles = planned ? singles : nullptr; a.n_singles = planned ? n_singles : 0;
-    static const int xcd_env = getenv("TAOAMD_XCD") ? atoi(getenv("TAOAMD_XCD")) : 1;
-    a.xcd = xcd_env;
+    a.xcd = 1;
     a.compact = compact;
     // compact rows: the fast cell-order instance on dense 16-byte pairs, nothing else
     if (compact != nullptr &&

@@ -641,9 +641,7 @@ __device__ __forceinline__ int32_t rank_in(const uint64_t *__restrict__ key,
 // binary search per tile, unique (key, input position) order) -- that sum is
 // its final place.  Longer categories take log2(tiles) pairwise merge-path
 // passes (seg_mpass_kernel; measured: equal at 5 tiles, 20 % faster at 6).
-#ifndef SEG_KMERGE_TILES
 #define SEG_KMERGE_TILES 5      // longest category (in tiles) finished by seg_kmerge_kernel
-#endif
 
 __global__ __launch_bounds__(256) void seg_kmerge_kernel(SegArgs a)
 {
@@ -1013,11 +1011,9 @@ extern "C" int taoamd_sort_segments(int64_t n, int32_t n_cat,
 // ===========================================================================
 #define SS_CAP 1024
 #define SS_FAST 512                    // most elements the one-word network takes
-#ifndef SS_TARGET                      // (build.sh -DSS_TARGET=.. -DSS_CHUNK_TILES=..: experiments)
 #define SS_TARGET 352
 #define SS_CHUNK_TILES 16
 #define SS_FIRST_MERGE_PASS 4          // log2(SS_CHUNK / SEG_TILE)
-#endif
 #define SS_OVER 32
 #define SS_DIRECT 1024
 #define SS_CHUNK (SS_CHUNK_TILES * SEG_TILE)   // 45056 = SS_MAXB * SS_TARGET
@@ -1046,16 +1042,7 @@ struct SsArgs {
     int32_t *order, *dst;
     int32_t *redo;                     // buckets left to ss_redo_kernel, redo[-1] = their number
     int32_t n_buckets, n_stiles, cap_limit;
-    int32_t dbg;                       // ablation switches (TAOAMD_SS_DBG, timing experiments)
 };
-// Ablation switches for timing experiments (results are wrong with any bit
-// set): compiled in only by `bash build.sh -DTAOAMD_ABLATE`, constant 0 in the
-// library that ships.
-#ifdef TAOAMD_ABLATE
-#define SS_DBG(a, bit) ((a).dbg & (bit))
-#else
-#define SS_DBG(a, bit) 0
-#endif
 
 static int g_ss_cap_limit = SS_CAP;
 
@@ -1120,7 +1107,6 @@ __device__ __forceinline__ double ss_dpp_f64(double v)
 }
 __device__ __forceinline__ double ss_shfl_xor_f64(double v, int m)
 {
-#ifndef SS_NO_DPP
     switch (m) {
     case 1: return ss_dpp_f64<0xB1>(v);           // quad_perm [1, 0, 3, 2]
     case 2: return ss_dpp_f64<0x4E>(v);           // quad_perm [2, 3, 0, 1]
@@ -1131,7 +1117,6 @@ __device__ __forceinline__ double ss_shfl_xor_f64(double v, int m)
     case 15: return ss_dpp_f64<0x140>(v);         // row_mirror
     default: break;
     }
-#endif
     const int lo = __shfl_xor(__double2loint(v), m, WAVE);
     const int hi = __shfl_xor(__double2hiint(v), m, WAVE);
     return __hiloint2double(hi, lo);
@@ -1261,7 +1246,7 @@ __device__ __forceinline__ uint64_t ss_wave_max_u64(uint64_t v)
     return v;
 }
 
-#define SS_SPLIT_KEY_BITS 45              // ss_split_chunk: key part | position in the chunk
+#define SS_SPLIT_KEY_BITS 45              // ss_split_chunk4: key part | position in the chunk
 #define SS_IDX_BITS 16
 #define SS_PAD 0x3fffffffffffffffull       // sorts last; still a normal fp64
 __device__ __forceinline__ double ss_pack(uint64_t key, uint64_t lo, int shift, int32_t rel)
@@ -1270,43 +1255,13 @@ __device__ __forceinline__ double ss_pack(uint64_t key, uint64_t lo, int shift, 
                                             (uint64_t)rel));
 }
 
-// Splitters of one chunk: its samples sorted by ONE wavefront in registers.
-// The samples only have to be ordered well enough to cut the chunk evenly: key
-// parts that tie after the shift are not repaired here (the scatter kernel
-// checks that the splitters ascend and hands the chunk to the counting path if
-// not -- scores that differ in their last 19 bits only).
-template <int R>
-__device__ __forceinline__ void ss_split_chunk(const SsArgs &a, const SsChunk &c, int lane)
-{
-    const int32_t S = ss_over(c.n), B = c.n_buckets, m = S * B;
-    const int32_t stride = c.n / m;
-    // (the top 45 key bits -- sign, exponent, 33 bits of mantissa -- are plenty
-    // to cut a chunk evenly; no pass over the samples for their range)
-    double p[R];
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int j = lane * R + r;               // samples in ascending position
-        p[r] = __longlong_as_double((long long)SS_PAD);
-        if (j < m) {
-            const int32_t rel = j * stride +
-                (int32_t)(ss_mix((uint32_t)j * 0x9e3779b9u ^ (uint32_t)c.begin) % (uint32_t)stride);
-            p[r] = ss_pack(desc_key(a.score[c.begin + rel]), 0, 64 - SS_SPLIT_KEY_BITS, rel);
-        }
-    }
-    ss_bitonic_packed<R>(p, lane);
-    // splitter b = the sample of rank b * S - 1 (b = 1 .. B - 1)
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int q = lane * R + r + 1;
-        if (q % S == 0 && q / S < B) {
-            const int32_t at = c.begin + (int32_t)((uint64_t)__double_as_longlong(p[r]) &
-                                                   ((1u << SS_IDX_BITS) - 1));
-            a.spl_key[c.bucket0 + q / S] = desc_key(a.score[at]);
-            a.spl_idx[c.bucket0 + q / S] = at;
-        }
-    }
-}
-
+// Splitters of one chunk: its samples sorted by their top 45 key bits (sign,
+// exponent, 33 bits of mantissa: plenty to cut a chunk evenly; no pass over the
+// samples for their range).  The samples only have to be ordered well enough
+// for that: key parts that tie after the shift are not repaired here (the
+// scatter kernel checks that the splitters ascend and hands the chunk to the
+// counting path if not -- scores that differ in their last 19 bits only).
+//
 // Round 4: the splitters of one chunk by a WORKGROUP.  One wavefront sorting a
 // chunk's 1000-2000 samples in 16-32 registers per lane was 0.09 ms of pure
 // latency at the head of the step's critical chain (1300 wavefronts on 1024
@@ -1341,7 +1296,6 @@ __device__ __forceinline__ void ss_split_chunk4(const SsArgs &a, const SsChunk &
     // mostly were: 32 of them)
     int32_t rel[R];
     double sc[R];
-#ifndef SS_SAMPLE_SCATTERED
     // Round 5: the samples are taken as WHOLE 64-byte lines -- eight consecutive
     // scores at a jittered, line-aligned place of every window of 8 * stride
     // elements, eight neighbouring lanes a line -- instead of one score out of
@@ -1369,24 +1323,11 @@ __device__ __forceinline__ void ss_split_chunk4(const SsArgs &a, const SsChunk &
             : g * win;
         rel[r] = j < m ? at + e : 0;
     }
-#else
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const int j = (lane * R + r) * 4 + wave;  // my quarter: samples j = wave (mod 4)
-        rel[r] = j < m ? j * stride + (int32_t)(ss_mix((uint32_t)j * 0x9e3779b9u ^
-                                                       (uint32_t)c.begin) % (uint32_t)stride)
-                       : 0;
-    }
-#endif
 #pragma unroll
     for (int r = 0; r < R; r++) sc[r] = a.score[c.begin + rel[r]];
 #pragma unroll
     for (int r = 0; r < R; r++) {
-#ifndef SS_SAMPLE_SCATTERED
         const int j = (r * 4 + wave) * WAVE + lane;
-#else
-        const int j = (lane * R + r) * 4 + wave;
-#endif
         p[r] = j < m ? ss_pack(desc_key(sc[r]), 0, 64 - SS_SPLIT_KEY_BITS, rel[r])
                      : __longlong_as_double((long long)SS_PAD);
     }
@@ -1465,20 +1406,6 @@ __global__ __launch_bounds__(256) void ss_split4_kernel(SsArgs a, int32_t n_spli
     else ss_split_chunk4<8>(a, c, lane, wave, run);
 }
 
-__global__ __launch_bounds__(256) void ss_split_kernel(SsArgs a, int32_t n_split)
-{
-    const int lane = lane_id();
-    const int32_t w = (int32_t)blockIdx.x * 4 + (int32_t)(threadIdx.x >> 6);
-    if (w >= n_split) return;
-    const SsChunk c = a.chunks[a.split_list[w]];
-    const int32_t m = ss_over(c.n) * c.n_buckets;  // <= 2048 samples
-    if (m <= 128) ss_split_chunk<2>(a, c, lane);
-    else if (m <= 256) ss_split_chunk<4>(a, c, lane);
-    else if (m <= 512) ss_split_chunk<8>(a, c, lane);
-    else if (m <= 1024) ss_split_chunk<16>(a, c, lane);
-    else ss_split_chunk<32>(a, c, lane);
-}
-
 __global__ __launch_bounds__(SEG_THREADS) void ss_scatter_kernel(SsArgs a)
 {
     __shared__ uint64_t s_key[SS_MAXB];
@@ -1499,7 +1426,7 @@ __global__ __launch_bounds__(SEG_THREADS) void ss_scatter_kernel(SsArgs a)
         s_idx[b] = real ? a.spl_idx[c.bucket0 + b] : INT32_MAX;
     }
     __syncthreads();
-    // the splitters must ascend (ss_split_chunk sorts the samples by a shortened
+    // the splitters must ascend (ss_split_chunk4 sorts the samples by a shortened
     // key): if two are out of order the chunk goes to the counting path
     if (threadIdx.x >= 1 && (int)threadIdx.x + 1 < B) {
         const int b = threadIdx.x;
@@ -1535,7 +1462,7 @@ __global__ __launch_bounds__(SEG_THREADS) void ss_scatter_kernel(SsArgs a)
                 if (before) lo = mid + 1; else hi = mid;
             }
             br[r] = lo - 1;
-            rr[r] = SS_DBG(a, 32) ? (int32_t)threadIdx.x >> 4 : atomicAdd(&s_cnt[lo - 1], 1);
+            rr[r] = atomicAdd(&s_cnt[lo - 1], 1);
         }
     }
     __syncthreads();
@@ -1548,7 +1475,7 @@ __global__ __launch_bounds__(SEG_THREADS) void ss_scatter_kernel(SsArgs a)
     for (int r = 0; r < SEG_ROUNDS; r++) {
         if (br[r] >= 0) {
             const int32_t at = s_base[br[r]] + rr[r];
-            if (at < SS_CAP && !SS_DBG(a, 16)) {
+            if (at < SS_CAP) {
                 const int64_t s = (int64_t)(c.bucket0 + br[r]) * SS_CAP + at;
                 a.slot_key[s] = kr[r];
                 a.slot_idx[s] = t0 + r * SEG_THREADS + (int32_t)threadIdx.x;
@@ -1638,7 +1565,7 @@ __device__ __forceinline__ bool ss_sort_bucket(const SsArgs &a, const SsChunk &c
                   ((uint64_t)(x[r] - c.begin) << SS_E_BITS) | (uint64_t)e))
             : pad;
     }
-    if (!SS_DBG(a, 1)) ss_bitonic_packed<R>(p, lane);
+    ss_bitonic_packed<R>(p, lane);
     // (the wavefront's own LDS writes are complete before its reads: one
     // wavefront, program order; the waitcnt is the compiler's)
     bool bad = false;
@@ -1650,12 +1577,10 @@ __device__ __forceinline__ bool ss_sort_bucket(const SsArgs &a, const SsChunk &c
         k[r] = ok ? full[bits & ((1u << SS_E_BITS) - 1) & (WAVE * R - 1)] : ~0ull;
         if (r > 0) bad |= k[r] < k[r - 1];
     }
-    if (!SS_DBG(a, 2)) {
-        const uint64_t up = ss_shfl_up64(k[R - 1]);
-        bad |= lane > 0 && k[0] < up;
-        if (__ballot(bad) != 0) return false;
-    }
-    if (lane * R + R <= count && c.final && a.order && !SS_DBG(a, 8)) {
+    const uint64_t up = ss_shfl_up64(k[R - 1]);
+    bad |= lane > 0 && k[0] < up;
+    if (__ballot(bad) != 0) return false;
+    if (lane * R + R <= count && c.final && a.order) {
         int32_t *o = a.order + out0 + lane * R;
         if (R == 2) *(ss_i2 *)o = ss_i2{x[0], x[1]};
 #pragma unroll
@@ -1669,8 +1594,8 @@ __device__ __forceinline__ bool ss_sort_bucket(const SsArgs &a, const SsChunk &c
         if (e < count) {
             const int32_t pp = out0 + e;
             if (c.final) {
-                if (a.order && !SS_DBG(a, 8) && lane * R + R > count) a.order[pp] = x[r];
-                if (a.dst && !SS_DBG(a, 4)) a.dst[x[r]] = pp;
+                if (a.order && lane * R + R > count) a.order[pp] = x[r];
+                if (a.dst) a.dst[x[r]] = pp;
             } else {
                 a.key_out[pp] = k[r];
                 a.idx_out[pp] = x[r];
@@ -1895,21 +1820,6 @@ extern "C" size_t taoamd_sort_sampled_workspace(int64_t n, int64_t n_buckets, in
     return measure([&](Carve &c) { ss_layout(c, n, n_buckets, merge, a, m); });
 }
 
-// The splitter kernel is 0.06 ms of latency at the head of the image level's
-// chain; a caller that starts other work beside the sort (the track level's 3D
-// IoU: 11 k workgroups that take every wave slot they find) wants that work to
-// wait for the splitters, not for the whole sort -- in a kernel trace of the
-// step the splitters' workgroups, 139 VGPRs each, took 347 us to get their turn
-// beside it.  `event` (a hipEvent_t) is recorded on the sort's stream right
-// behind the splitter kernel of the calling thread's NEXT taoamd_sort_sampled;
-// NULL = none.
-static thread_local hipEvent_t g_ss_notify = nullptr;
-extern "C" int taoamd_sort_sampled_notify(void *event)
-{
-    g_ss_notify = (hipEvent_t)event;
-    return TAOAMD_OK;
-}
-
 extern "C" int taoamd_sort_sampled_cap_limit(int32_t limit)
 {
     g_ss_cap_limit = limit > 0 && limit < SS_CAP ? limit : SS_CAP;
@@ -1943,12 +1853,6 @@ extern "C" int taoamd_sort_sampled(int64_t n, int32_t n_cat, const int32_t *cat_
     a.stile_chunk = stile_chunk; a.bucket_chunk = bucket_chunk;
     a.order = order; a.dst = dst; a.n_buckets = n_buckets; a.n_stiles = n_stiles;
     a.cap_limit = g_ss_cap_limit;
-#ifdef TAOAMD_ABLATE
-    static const int dbg_env = getenv("TAOAMD_SS_DBG") ? atoi(getenv("TAOAMD_SS_DBG")) : 0;
-    a.dbg = dbg_env;
-#else
-    a.dbg = 0;
-#endif
     m.cat_off = cat_off; m.tile_off = tile_off; m.cat = nullptr; m.score = dt_score;
     m.order = order; m.dst = dst; m.n = n; m.n_cat = n_cat; m.n_tiles = n_tiles;
     // (merge buffers: null without merge passes)
@@ -1956,18 +1860,9 @@ extern "C" int taoamd_sort_sampled(int64_t n, int32_t n_cat, const int32_t *cat_
     a.idx_out = m.idx[SS_FIRST_MERGE_PASS & 1];
     TAO_HIP(hipMemsetAsync(a.cursor, 0, cursor_ints * 4, s));
     if (n_split > 0) {
-        // (TAOAMD_SS_SPLIT=1: one wavefront per chunk, the round-3 kernel, for A/B timing)
-        static const bool one_wave = getenv("TAOAMD_SS_SPLIT") && atoi(getenv("TAOAMD_SS_SPLIT")) == 1;
-        if (one_wave)
-            TAO_TIMED("ss_split_kernel", s, ss_split_kernel<<<(unsigned)((n_split + 3) / 4), 256, 0, s>>>(a, n_split));
-        else
-            TAO_TIMED("ss_split_kernel", s, ss_split4_kernel<<<(unsigned)n_split, 256, 0, s>>>(a, n_split));
-        if (g_ss_notify) TAO_HIP(hipEventRecord(g_ss_notify, s));
+        TAO_TIMED("ss_split_kernel", s, ss_split4_kernel<<<(unsigned)n_split, 256, 0, s>>>(a, n_split));
         TAO_TIMED("ss_scatter_kernel", s, ss_scatter_kernel<<<(unsigned)n_stiles, SEG_THREADS, 0, s>>>(a));
-    } else if (g_ss_notify) {
-        TAO_HIP(hipEventRecord(g_ss_notify, s));
     }
-    g_ss_notify = nullptr;
     TAO_TIMED("ss_sort_kernel", s, ss_sort_kernel<<<(unsigned)((n_buckets + 3) / 4), 256, 0, s>>>(a));
     TAO_TIMED("ss_redo_kernel", s, ss_redo_kernel<<<(unsigned)std::min<int64_t>(1024, (n_buckets + 3) / 4), 256, 0, s>>>(a));
     if (merge) {

@@ -324,14 +324,7 @@ __device__ __forceinline__ void tt_stager(
             // stretch -- the stream ends in a margin: what it loads is never
             // parked, and no select is spent on it)
             const uint32_t off = cur + ((uint32_t)__popc(pm & (bit[i] - 1u)) << 8) + joff;
-#ifdef TT_ABLATE_LOADS     // (timing experiment: every load hits the stretch's first bytes)
-            Bx[i] = *reinterpret_cast<const double4 *>(tbase + (off & 0u));
-#elif defined(TT_ABLATE_CACHED)   // (timing experiment: the same requests inside 1 MB)
-            Bx[i] = *reinterpret_cast<const double4 *>(
-                reinterpret_cast<const char *>(frames) + (((uint32_t)(sbase * 32) + off) & 0xfffe0u));
-#else
             Bx[i] = *reinterpret_cast<const double4 *>(tbase + off);
-#endif
         }
         cur += (uint32_t)__popc(pm) << 8;
     };
@@ -474,9 +467,6 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(MODE == 2 ?
     double u = 0.0, i = 0.0;
     unsigned long long common = 0;
     auto add = [&](int b, int32_t pc) {
-#ifdef TT_ABLATE_ADDER     // (timing experiment: the adder only keeps the barriers)
-        return;
-#endif
         // Round 6: the stagers park a row exactly where its span first .. last
         // reaches into the chunk, and the adder branches on the same test --
         // from four registers, where it used to wait for two LDS round trips
@@ -489,9 +479,6 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(MODE == 2 ?
         const bool dp = Fd < pc + TT_P && Ld >= pc;
         const bool gp = Fg < pc + TT_P && Lg >= pc;
         if (__ballot(dp || gp) == 0) return;
-#ifdef TT_ABLATE_ADD_BODY  // (timing experiment: 1 = no area-only step, 2 = no general step, 3 = neither)
-        if (TT_ABLATE_ADD_BODY == 3) return;
-#endif
         // (row offsets in two registers; the buffer's base folds into the LDS
         // instructions' immediate offsets)
         const char *rbase = reinterpret_cast<const char *>(rows[b]);
@@ -503,11 +490,7 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(MODE == 2 ?
             // far boxes (x = 1e300, area 0) the general formula gives i_ = 0
             // and u_ = (a + 0) - 0 = a, the same bits.  Lanes branch: fewer
             // lanes, fewer LDS reads (round 4).
-#ifdef TT_ABLATE_ADD_BODY
-            if (dp != gp && !(TT_ABLATE_ADD_BODY & 1)) {
-#else
             if (dp != gp) {
-#endif
                 const double2 *__restrict__ a2 =
                     reinterpret_cast<const double2 *>(rbase + (dp ? offd : offg) + 4 * TT_P * 8);
 #pragma unroll
@@ -516,11 +499,7 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(MODE == 2 ?
                     u += ar.x;
                     u += ar.y;
                 }
-#ifdef TT_ABLATE_ADD_BODY
-            } else if (dp && gp && !(TT_ABLATE_ADD_BODY & 2)) {
-#else
             } else if (dp) {
-#endif
                 // two positions per 16-byte LDS read of every field
                 const double2 *__restrict__ d2 = reinterpret_cast<const double2 *>(dr);
                 const double2 *__restrict__ g2 = reinterpret_cast<const double2 *>(gr);
@@ -841,18 +820,15 @@ extern "C" int taoamd_track_iou_planned(int64_t n_tasks, const int32_t *tasks,
     const unsigned zero_wgs = (unsigned)std::min<int64_t>(
         (n_zero + 192 * TT_ZERO_PER - 1) / (192 * TT_ZERO_PER), 4096);
     const unsigned grid = (unsigned)n_tasks + zero_wgs;
-    // (TAOAMD_TT_LDS_PAD: unused dynamic LDS per task, i.e. fewer tasks per CU --
-    // a schedule experiment: room for the other level's workgroups beside this kernel)
-    static const unsigned lds_pad = getenv("TAOAMD_TT_LDS_PAD") ? (unsigned)atoi(getenv("TAOAMD_TT_LDS_PAD")) : 0u;
 #define TT_LAUNCH(M)                                                           \
     TAO_TIMED("track_iou_task_kernel", s,                                      \
-              track_iou_task_kernel<M><<<grid, 192, lds_pad, s>>>(             \
+              track_iou_task_kernel<M><<<grid, 192, 0, s>>>(             \
                   (const int4 *)tasks, task_rows, task_pairs, task_out,        \
                   (const double4 *)frames, task_base, (const int4 *)trk_meta, iou, pf, \
                   (int32_t)n_tasks, n_zero, zero_out))
     if (mode == 0 && pf == nullptr)
         TAO_TIMED("track_iou_task_kernel", s,
-                  (track_iou_task_kernel<0, false><<<grid, 192, lds_pad, s>>>(
+                  (track_iou_task_kernel<0, false><<<grid, 192, 0, s>>>(
                       (const int4 *)tasks, task_rows, task_pairs, task_out,
                       (const double4 *)frames, task_base, (const int4 *)trk_meta, iou, pf,
                       (int32_t)n_tasks, n_zero, zero_out)));

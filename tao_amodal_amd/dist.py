@@ -99,8 +99,6 @@ class HipBackend:
         # are its own, so are the pairs to recompute -- on the device, no host
         # round trip (the host half only for ids Python hashes differently)
         self.engine.stage_track_iou_guarded(dp, ws)
-        if dp.guard_flat is not None:
-            ws.guarded_pairs = self.engine.apply_iou_guard(dp, ws)
 
     def scores_at_place(self, dp, ws, out):
         """out[sorted place of detection i] = bits of its score: the first

@@ -502,7 +502,7 @@ class Workspace:
         # nothing else, the rows stay where the detections are and dst[] is the
         # identity, written once (dst_identity: it still is).
         self.order_buf = torch.empty(max(dp.n_dt, 1), dtype=torch.int32, device=dev) \
-            if (detail or keep_order or self.gather or SORT_ASIDE) else None
+            if (detail or keep_order or self.gather) else None
         self._n_dt = dp.n_dt
         self.dst = torch.empty(max(dp.n_dt, 1), dtype=torch.int32, device=dev)
         self.dst_identity = False
@@ -650,7 +650,6 @@ def stage_ranges(dp, ws):
             "taoamd_tao_ranges")
 
 
-import os as _os0
 # Which segment sort a pass takes.  The sample sort (taoamd_sort_sampled: one
 # scatter pass + one register sort per bucket) wins where categories span many
 # LDS tiles -- 2000 videos, 21 M detections: 0.62 against 0.79 ms -- but is four
@@ -659,9 +658,10 @@ import os as _os0
 # bucket sort's exchanges became DPP moves the threshold was 6 M -- Config 2,
 # 2.1 M detections: 107 against 130 us; since then the sample sort takes 80 us
 # there against 102, and 67 against 77 at the 3 M rows of the stress stand-in.)
-# TAOAMD_SORT=sampled / segments forces one.
+# _SORT_FORCE "sampled" / "segments" forces one (the tests' way onto the sample
+# sort with small inputs).
 SORT_SAMPLED_MIN = 1_500_000
-_SORT_FORCE = _os0.environ.get("TAOAMD_SORT", "")
+_SORT_FORCE = ""
 
 
 def sort_is_sampled(dp):
@@ -671,25 +671,19 @@ def sort_is_sampled(dp):
 
 
 # Image level, Overlap's chain: where the match leaves its rows (run_forked).
-# TAOAMD_SORT_ASIDE unset: cell order + gathering sweep where gathers_rows() says
-# so; =0: the scatter form everywhere; =1: cell order wherever the chain can
-# (A/B timing from one build).  Measured on one MI355X at 21.4 M rows, three runs
-# each: scatter form 1.356-1.361 ms a step, cell order 1.290-1.304 (the sort
+# Cell order + gathering sweep where gathers_rows() says so, the scatter form
+# everywhere else.  Measured on one MI355X at 21.4 M rows, three runs each:
+# scatter form 1.356-1.361 ms a step, cell order 1.290-1.304 (the sort
 # stores no dst[], the match reads none, stores whole-wavefront runs and runs
 # beside the sort; the one-pass sweep's gathered loader pays part of it back).
 # The round-2 form of the same idea -- generic loader, unprepared plan, the slow
 # match kernel -- was and is a loss: 1.364-1.371 ms.
-_ASIDE_ENV = _os0.environ.get("TAOAMD_SORT_ASIDE", "")
-SORT_ASIDE = None if _ASIDE_ENV == "" else _ASIDE_ENV != "0"
-
 
 def gathers_rows(dp):
     """Whether Overlap's image-level chain leaves the match's rows in cell
     order on this problem: box IoU, grouped plan, the sample sort (it can store
     order[] alone) and the one-pass sweep (it reads every row once: the 6 M-row
     rule of taoamd_accumulate_plan_kind) on one GPU."""
-    if SORT_ASIDE is not None:
-        return False          # (forced either way: run_forked is told by its caller)
     return (dp.kind == "lvis" and not dp.mask_iou and dp.grouped and dp.n_dt > 0
             and dp.device.type == "cuda" and sort_is_sampled(dp)
             and _plan_key(dp)[1] in (2, 3))
@@ -1519,6 +1513,10 @@ def stage_track_identity(dp, ws, frame_thr):
 def stage_track_iou_guarded(dp, ws):
     stage_track_iou(dp, ws)
     stage_iou_guard(dp, ws)
+    if dp.guard_flat is not None:
+        # host half of the guard (ids Python does not hash to themselves):
+        # one synchronisation, the listed pairs patched before the match
+        ws.guarded_pairs = apply_iou_guard(dp, ws)
 
 
 STAGES = (("ranges", stage_ranges), ("sort", stage_sort),
@@ -1533,23 +1531,6 @@ def run(dp, ws):
         _lib.kernel_timing_label(dp.kind)
     for name, fn in STAGES:
         fn(dp, ws)
-        if name == "track_iou" and dp.guard_flat is not None:
-            ws.guarded_pairs = apply_iou_guard(dp, ws)
-
-
-import os as _os
-# A/B: the 3D IoU (the longest kernel) alone ahead of the image level instead of beside it
-TRACK_FIRST = _os.environ.get("TAOAMD_TRACK_FIRST", "0") != "0"
-TRACK_AFTER_SORT = _os.environ.get("TAOAMD_TRACK_AFTER_SORT", "0") != "0"
-# ... or when its splitter kernel is done (taoamd_sort_sampled_notify): the
-# splitters then take 0.08 instead of 0.35 ms, but the 3D IoU runs beside the
-# scatter and the bucket sort instead and slows those down: 1.54 against 1.52
-# ms.  The step is bound by the sum of its kernels' work, not by the chain.
-TRACK_AFTER_SPLIT = _os.environ.get("TAOAMD_TRACK_AFTER_SPLIT", "0") != "0"
-# ... or when the image level's MATCH is done: the 3D IoU (bound by the LDS
-# array) then runs beside the sweep (bound by VALU issue, no LDS to speak of) --
-# the one pairing of the step's long kernels that does not share its bound
-TRACK_AFTER_MATCH = _os.environ.get("TAOAMD_TRACK_AFTER_MATCH", "0") != "0"
 
 
 class Overlap:
@@ -1563,22 +1544,8 @@ class Overlap:
     events, so the caller's barrier + synchronize bracketing stays valid."""
 
     def __init__(self, device, n=4):
-        import ctypes as C
         self.device = torch.device(device)
         self.streams = [torch.cuda.Stream(self.device) for _ in range(n)]
-        # recorded behind the image level's splitter kernel: what the track
-        # level waits for (run_pair)
-        self.split_done = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.load().taoamd_event_create(C.byref(self.split_done)),
-                       "taoamd_event_create")
-
-    def __del__(self):
-        try:
-            if self.split_done:
-                _lib.load().taoamd_event_destroy(self.split_done)
-        except Exception:
-            pass
 
     def _fork(self, k):
         s = self.streams[k]
@@ -1593,47 +1560,8 @@ class Overlap:
         # pass is forked and joined.
         cur = torch.cuda.current_stream(self.device)
         s_aux_l, s_aux_t = self.streams[2], self.streams[3]   # forked by run_forked
-        if TRACK_FIRST and dpt.kind == "tao":
-            # A/B schedule: the track level's head (range masks, sort, 3D IoU)
-            # ahead of everything, the rest of it beside the image level
-            run_forked(dpt, wst, s_aux_t, head_only=True, no_match=True)
-            st = self._fork(1)
-            run_forked(dpl, wsl, s_aux_l, sort_aside=SORT_ASIDE)
-            with torch.cuda.stream(st):
-                _probed("match", stage_match, dpt, wst)
-                stage_accumulate(dpt, wst)
-            cur.wait_stream(st)
-            return
         st = self._fork(1)
-        if TRACK_AFTER_SPLIT and dpl.kind == "lvis" and sort_is_sampled(dpl) and dpl.grouped \
-                and dpl.n_dt and not SORT_ASIDE:
-            # The track level starts when the image level's SPLITTERS are done.
-            # Those are 0.06 ms of latency at the head of the step's critical
-            # chain, 1200 workgroups of 139 VGPRs; started together, the 3D
-            # IoU's 11 k small workgroups took every wave slot that came free
-            # and the splitters ran for 0.35 ms (kernel trace of round 4).
-            lib = _lib.load()
-            lib.taoamd_sort_sampled_notify(self.split_done)
-            run_forked(dpl, wsl, s_aux_l)
-            _lib.check(lib.taoamd_stream_wait_event(st.cuda_stream, self.split_done),
-                       "taoamd_stream_wait_event")
-            _lib.check(lib.taoamd_stream_wait_event(s_aux_t.cuda_stream, self.split_done),
-                       "taoamd_stream_wait_event")
-        elif TRACK_AFTER_MATCH:
-            ev = torch.cuda.Event()
-            run_forked(dpl, wsl, s_aux_l, sort_aside=SORT_ASIDE, match_done=ev)
-            # (the image level's sweep is launched by run_forked right behind the
-            # event: the track level's kernels queue beside it)
-            st.wait_event(ev)
-        elif TRACK_AFTER_SORT:
-            # A/B schedule: the track level starts when the image level's sort is
-            # done -- its 3D IoU then runs beside the match and the sweep instead
-            # of holding the wave slots the sort's short kernels wait for
-            ev = torch.cuda.Event()
-            run_forked(dpl, wsl, s_aux_l, sort_aside=SORT_ASIDE, sort_done=ev)
-            st.wait_event(ev)
-        else:
-            run_forked(dpl, wsl, s_aux_l, sort_aside=SORT_ASIDE)
+        run_forked(dpl, wsl, s_aux_l)
         with torch.cuda.stream(st):
             run_forked(dpt, wst, s_aux_t)
         cur.wait_stream(st)
@@ -1671,8 +1599,7 @@ def _probed(name, fn, dp, ws):
         PROBE.wrap(dp.kind + ":" + name, fn, dp, ws)
 
 
-def run_forked(dp, ws, aux, head_only=False, sort_aside=None, no_match=False,
-               sort_done=None, match_done=None):
+def run_forked(dp, ws, aux, head_only=False, sort_aside=None):
     """One evaluator pass on the current stream, its independent head stages
     on the stream `aux` (forked from and joined to the current stream):
     image level  ranges || sort -> match -> accumulate,
@@ -1688,7 +1615,7 @@ def run_forked(dp, ws, aux, head_only=False, sort_aside=None, no_match=False,
     if sort_aside is None:
         sort_aside = ws.gather and _plan_key(dp)[1] in (2, 3)
     if sort_aside and dp.kind == "lvis" and not dp.mask_iou and not head_only \
-            and not no_match and dp.grouped and dp.n_dt:
+            and dp.grouped and dp.n_dt:
         order_only = sort_is_sampled(dp) and ws.order_buf is not None
         if order_only and not ws.dst_identity:
             # nobody stores sorted places: dst[] says where the rows are
@@ -1698,12 +1625,8 @@ def run_forked(dp, ws, aux, head_only=False, sort_aside=None, no_match=False,
         # 1.290-1.304 against 1.327-1.335 ms a step at 21 M rows (parent 1.356-1.361)
         with torch.cuda.stream(aux):
             stage_sort(dp, ws, order_only=order_only)
-            if sort_done is not None:
-                sort_done.record(aux)
         stage_ranges(dp, ws)
         _probed("match", lambda d, w: stage_match(d, w, scatter=False), dp, ws)
-        if match_done is not None:
-            match_done.record(cur)
         cur.wait_stream(aux)
         stage_accumulate_by_order(dp, ws)
         return
@@ -1712,23 +1635,13 @@ def run_forked(dp, ws, aux, head_only=False, sort_aside=None, no_match=False,
             stage_ranges(dp, ws)
             stage_mask_iou(dp, ws)
         stage_sort(dp, ws)
-        if sort_done is not None:
-            sort_done.record(cur)
     else:
         with torch.cuda.stream(aux):
             stage_ranges(dp, ws)
             stage_sort(dp, ws)
         _probed("track_iou", stage_track_iou_guarded, dp, ws)
-        if dp.guard_flat is not None:
-            # host half of the guard (ids Python does not hash to themselves):
-            # one synchronisation, the listed pairs patched before the match
-            ws.guarded_pairs = apply_iou_guard(dp, ws)
     cur.wait_stream(aux)
-    if no_match:
-        return
     _probed("match", stage_match, dp, ws)
-    if match_done is not None:
-        match_done.record(cur)
     if not head_only:
         stage_accumulate(dp, ws)
 
