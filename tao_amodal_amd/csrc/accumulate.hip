@@ -403,6 +403,47 @@ __device__ __forceinline__ void crow_rows(const AccArgs &a, int64_t start, int l
     if (!full && blk * WAVE + lane >= len) { tpw = 0; vw = 0; }
 }
 
+// Round 12, the plane form of a FULL chunk's blocks without an escaped word: a
+// compact word says everything in 18 bits, and for combo lane (a, t) the
+// transposed words are products of the words' bit planes over a block's rows,
+//     T  = P_t & ~(G_a | H)                          TP
+//     TF = (P_t & ~(G_a | (H & U))) | (~P_t & ~U)    valid
+// with P_t, G_a, U, H the 64-row planes of bits t, 10 + a, 16 and 17 (equal to
+// matched & ~ignored and ~ignored of crow_expand for every word: the n_rng
+// ranges' lanes; the lanes above them hold T = 0 and a TF nobody reads).  Three
+// blocks' 18 bits fit one 64-bit word a lane, and ONE transpose64 of it leaves
+// the plane of bit p of block j in lane 18 j + p: a combo lane fetches P_t and
+// G_a with two ds_bpermute_b32 each (the block's 72 bytes go into the offset
+// field) and U and H are wave-uniform (v_readlane).
+#define CROW_BITS 18
+__device__ __forceinline__ uint64_t crow_pack(uint32_t w0, uint32_t w1, uint32_t w2)
+{
+    constexpr uint32_t M = (1u << CROW_BITS) - 1;        // (bits 18-30 may hold anything)
+    const uint32_t lo = (w0 & M) | w1 << CROW_BITS;
+    const uint32_t hi = (w1 & M) >> (32 - CROW_BITS) | (w2 & M) << (2 * CROW_BITS - 32);
+    return (uint64_t)hi << 32 | lo;
+}
+__device__ __forceinline__ uint64_t bpermute_u64(int addr, uint64_t v)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)(uint32_t)(v >> 32));
+    return (uint64_t)hi << 32 | lo;
+}
+// block J of a group from the group's transposed word X; addr_p / addr_g: four
+// times the lanes of my P_t and G_a of block 0; dead: ~0 in a lane above the
+// ranges' combos
+__device__ __forceinline__ void crow_planes(uint64_t X, int J, int addr_p, int addr_g,
+                                            uint32_t dead, uint64_t &T, uint64_t &TF)
+{
+    const uint64_t P = bpermute_u64(addr_p + J * CROW_BITS * 4, X);
+    const uint64_t G = bpermute_u64(addr_g + J * CROW_BITS * 4, X);
+    const uint64_t U = readlane_u64(X, J * CROW_BITS + 16);
+    const uint64_t H = readlane_u64(X, J * CROW_BITS + 17);
+    const uint64_t D = (uint64_t)dead << 32 | dead;
+    T = P & ~(G | H | D);
+    TF = (P & ~(G | (H & U))) | (~P & ~U);
+}
+
 template <int ACC_BLK_N, int GATHER = 0>
 __device__ __forceinline__ void load_chunk_tv(const AccArgs &a, int64_t start, int word, int len,
                                               int lane, uint64_t (&tpw)[ACC_BLK_N],
@@ -1284,23 +1325,60 @@ void acc_sweep_kernel(AccArgs a, RecThr rec)
     }
     uint64_t T[NB], TF[NB];
     uint32_t tp_own = 0, n_own = 0;
+    if (GATHER == 2 && len == NB * WAVE) {
+        // a full chunk of compact rows (all but a category's last): the blocks'
+        // bit planes, three blocks to a transpose (crow_planes; NB = 8: 3 + 3 + 2,
+        // last block first as below).  A block with an escaped word takes
+        // crow_rows and its two transposes -- that block alone, the group's
+        // transpose still serves the others
+        const int addr_p = (lane % N_THR) * 4, addr_g = (N_THR + lane / N_THR) * 4;
+        uint32_t dead = lane >= a.n_rng * N_THR ? ~0u : 0u;
+        asm volatile("" : "+v"(dead));      // (a register, not a select a block)
 #pragma unroll
-    for (int b_ = 0; b_ < NB; b_++) {
-        // (compact rows: last block first, the order the walk below uses them in --
-        // the block that is walked last is not carried through all the others)
-        const int blk = GATHER == 2 ? NB - 1 - b_ : b_;
-        uint64_t t_ = 0, v_ = 0;
-        if (blk * WAVE < len) {
-            if (GATHER == 2)
-                crow_rows<NB>(a, start, len, lane, blk, cw[blk], s_crow, nall_lo, nall_hi,
-                              tpw[blk], vw[blk]);
-            t_ = transpose64(tpw[blk], lane);
-            v_ = transpose64(vw[blk], lane);
+        for (int top = NB; top > 0; top -= 3) {
+            const uint64_t X = transpose64(crow_pack(cw[top - 1], top >= 2 ? cw[top - 2] : 0u,
+                                                     top >= 3 ? cw[top - 3] : 0u), lane);
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                const int blk = top - 1 - j;
+                if (blk < 0) continue;
+                uint64_t t_, v_;
+                if (__builtin_expect(__ballot((int32_t)cw[blk] < 0) != 0, 0)) {   // (uniform: CROW_ESCAPE)
+                    crow_rows<NB>(a, start, len, lane, blk, cw[blk], s_crow, nall_lo, nall_hi,
+                                  tpw[blk], vw[blk]);
+                    t_ = transpose64(tpw[blk], lane);
+                    v_ = transpose64(vw[blk], lane);
+                } else {
+                    crow_planes(X, j, addr_p, addr_g, dead, t_, v_);
+                }
+                T[blk] = t_;
+                TF[blk] = v_;
+                tp_own += (uint32_t)__popcll(t_);
+                n_own += (uint32_t)__popcll(v_);
+                // (counted here: the compiler otherwise moves all the popcounts
+                // behind the join with the other path and spills to hold them)
+                asm volatile("" : "+v"(tp_own), "+v"(n_own));
+            }
         }
-        T[blk] = t_;
-        TF[blk] = v_;
-        tp_own += (uint32_t)__popcll(t_);
-        n_own += (uint32_t)__popcll(v_);
+    } else {
+#pragma unroll
+        for (int b_ = 0; b_ < NB; b_++) {
+            // (compact rows: last block first, the order the walk below uses them in --
+            // the block that is walked last is not carried through all the others)
+            const int blk = GATHER == 2 ? NB - 1 - b_ : b_;
+            uint64_t t_ = 0, v_ = 0;
+            if (blk * WAVE < len) {
+                if (GATHER == 2)
+                    crow_rows<NB>(a, start, len, lane, blk, cw[blk], s_crow, nall_lo, nall_hi,
+                                  tpw[blk], vw[blk]);
+                t_ = transpose64(tpw[blk], lane);
+                v_ = transpose64(vw[blk], lane);
+            }
+            T[blk] = t_;
+            TF[blk] = v_;
+            tp_own += (uint32_t)__popcll(t_);
+            n_own += (uint32_t)__popcll(v_);
+        }
     }
     const uint32_t fp_own = n_own - tp_own;       // (TP and FP rows are disjoint)
     s_tp[wave][lane] = tp_own;
