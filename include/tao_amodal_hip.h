@@ -1572,6 +1572,119 @@ int taoamd_track_identity_assign(int64_t n_dt, int64_t n_gt, int64_t n_cells, in
                                  int32_t *status, void *workspace, size_t workspace_bytes,
                                  void *stream);
 
+/* ---- track-level HOTA: HOTA / DetA / AssA (csrc/track_hota.hip) ----------------------
+ * The association is a per-frame arg-max (many-to-one), the identity one
+ * assignment per cell over whole tracks.  HOTA (Luiten et al., IJCV 2021) asks
+ * for a ONE-TO-ONE assignment per FRAME, weighted by how well each pair of tracks
+ * aligns over the whole video, and then for an association score per matched
+ * pair.  The reference has no counterpart; the definition is this library's,
+ * after TrackEval's HOTA class.  Track level, boxes.
+ *
+ * Every device output is an integer (match_iou: one box_iou value) and identical
+ * from run to run; no float is ever added atomically.  HOTA's sums are
+ * fractional, so they are carried in fixed point: ONE = 2^30 (TAOAMD_HOTA_ONE),
+ * q(x) = (int64) rint(x * ONE) for x in [0, 1].
+ *
+ * Rows and cells are those of taoamd_track_association; L_g and F_d are the
+ * tracks' frame counts.
+ *   eligible    g whose gt_flags lacks TAOAMD_GT_IGNORE: the ground truths that
+ *               take part.
+ *   kept        d with dt_keep[d] != 0 (uint8[n_dt]; NULL: every d): the detection
+ *               tracks that take part.  The class layer passes the `kept` column
+ *               of taoamd_track_identity_assign, so HOTA and IDF1 are computed
+ *               over the same tracks and the set-aside rules are stated once.
+ *   frame group (cell, timeline position p): Gp = the eligible ground truths of
+ *               the cell with a frame at p, Dp = the kept detection tracks of the
+ *               cell with a frame at p, both in ascending row.
+ *   s, c(s)     s = box_iou(d's box at p, g's box at p), the bits of taoamd_bb_iou;
+ *               c(s) = 0 unless s > 0 (a NaN is 0), else min(s, 1).
+ * ALIGN.  In double, each sum added in ascending row from 0.0 (so whichever lane
+ * forms it gets the same bits): rowsum_g = the sum of c(s) over d in Dp, colsum_d
+ * = the sum of c(s) over g in Gp, den = (rowsum_g + colsum_d) - c(s), a = den >
+ * 2^-52 ? min(c(s) / den, 1) : 0.  pot[cell_iou_off[cell] + d_local * G + g_local]
+ * int64 = the sum over the group's positions of q(a): only the integer q(a) is
+ * accumulated across frames.  0 for every pair of an ignored g or a d not kept.
+ * GLOBAL ALIGNMENT.  P = (double) pot / ONE; gas = pot > 0 ? P / ((L_g + F_d) - P)
+ * : 0, read as 0 where it is not positive and as 1 above 1 (no table of the align
+ * call gives either).
+ * MATCH, per frame group.  w(g, d) = q(gas * c(s)) <= 2^30.  Rows and columns
+ * without a positive w drop out; the smaller side becomes the solver's rows (the
+ * ground truths when equal); the assignment maximises the sum of w, a unique
+ * integer; a pair with w = 0 is unassigned.  Equal minima go to the lowest column,
+ * as in the identity's solver (the same code): the assignment returned is a
+ * function of the input alone.  It is made ONCE per frame, not once per alpha.
+ *   alphas      double[n_alpha] (HOST memory), strictly ascending, 1 <= n_alpha <=
+ *               TAOAMD_TRACK_HOTA_ALPHAS; the caller has subtracted TrackEval's eps.
+ *   mc, lc      for an assigned pair and every a with c(s) >= alphas[a]:
+ *               mc[a][pair] += 1 (int32[n_alpha][n_iou]), lc[a][pair] += q(c(s))
+ *               (int64[n_alpha][n_iou]).
+ *   match       int32[n_gt_frames]: the in-cell index of the assigned d, or -1;
+ *               match_iou double[n_gt_frames] (may be NULL): its s, or 0.0.
+ *   status      int32 (device): 0; 1 if a loop bound of the solver ran out (then
+ *               that group's frames stay at -1).  Weights of at most 2^30 and fewer
+ *               than 2^31 rows cannot overflow 64-bit potentials.
+ * REDUCE, per category (gt_cat) and alpha over the pairs of eligible g with m =
+ * mc[a][pair] > 0: tp += m; loc += lc[a][pair]; ass[0] += q'(m * r(m, (L_g + F_d)
+ * - m)); ass[1] += q'(m * r(m, L_g)); ass[2] += q'(m * r(m, F_d)), with r(m, x) =
+ * x > 0 ? min(m / x, 1) : 0 and q'(x) = (int64) rint(x * ONE).  tp int64[n_cat]
+ * [n_alpha], loc int64[n_cat][n_alpha], ass int64[n_cat][n_alpha][3]; categories
+ * outside [0, n_cat) count nowhere.  With all sizes inside int32, a category's m
+ * add up to fewer than 2^31 frames and every term is at most m * ONE: every sum
+ * stays below 2^62.
+ * The caller forms the ratios: FN = gt_frames - tp, FP = dt_frames - tp (the frame
+ * counts of taoamd_track_identity_assign's cat_counts); DetA = tp / max(1, tp + FN
+ * + FP), DetRe = tp / max(1, tp + FN), DetPr = tp / max(1, tp + FP); AssA = ass[0]
+ * / ONE / max(1, tp), AssRe and AssPr from ass[1] and ass[2]; LocA = loc / ONE /
+ * tp; HOTA = sqrt(DetA * AssA).
+ *
+ * Three calls, so that each kernel can be driven alone; one workspace size
+ * (taoamd_track_hota_workspace answers 0 to sizes it refuses; any base address,
+ * contents need not be initialised, nothing is carried from call to call).
+ * taoamd_track_hota_align zeroes and fills pot.  taoamd_track_hota_match reads pot
+ * (any int64 table in that layout; a negative word reads 0) and zeroes / fills
+ * mc, lc, match, match_iou and status.  taoamd_track_hota_reduce reads mc and lc
+ * (any tables in that layout; mc words <= 0 are skipped) and zeroes / fills tp,
+ * loc and ass.  There is no size limit and no TAOAMD_ERR_TOO_LARGE; every loop
+ * has a bound known at entry; nothing spins.
+ * TAOAMD_ERR_ARG: a size below 0 or beyond int32, n_cat <= 0, n_alpha outside [1,
+ * 32], alphas that do not strictly ascend or hold a NaN, a missing table;
+ * TAOAMD_ERR_WORKSPACE: fewer bytes than the size reported.  Both are answered
+ * before the first device call.  Rows and frames named by the tables that lie
+ * outside them are skipped, never dereferenced; n_gt == 0 returns after the
+ * zeroing. */
+#define TAOAMD_HOTA_ONE 1073741824          /* 2^30: the fixed point of the HOTA sums */
+#define TAOAMD_TRACK_HOTA_ALPHAS 32         /* localisation thresholds, at most */
+size_t taoamd_track_hota_workspace(int64_t n_dt, int64_t n_gt, int64_t n_gt_frames);
+int taoamd_track_hota_align(int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou,
+                            int64_t n_dt_frames, int64_t n_gt_frames,
+                            const int32_t *cell_dt_off, const int32_t *cell_gt_off,
+                            const int64_t *cell_iou_off, const uint8_t *gt_flags,
+                            const uint8_t *dt_keep, const int32_t *dt_frame_off,
+                            const int32_t *dt_frame_pos, const double *dt_frame_box,
+                            const int32_t *gt_frame_off, const int32_t *gt_frame_pos,
+                            const double *gt_frame_box, int64_t *pot, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int taoamd_track_hota_match(int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou,
+                            int64_t n_dt_frames, int64_t n_gt_frames, int32_t n_alpha,
+                            const double *alphas, const int32_t *cell_dt_off,
+                            const int32_t *cell_gt_off, const int64_t *cell_iou_off,
+                            const uint8_t *gt_flags, const uint8_t *dt_keep,
+                            const int32_t *dt_frame_off, const int32_t *dt_frame_pos,
+                            const double *dt_frame_box, const int32_t *gt_frame_off,
+                            const int32_t *gt_frame_pos, const double *gt_frame_box,
+                            const int64_t *pot, int32_t *mc, int64_t *lc, int32_t *match,
+                            double *match_iou, int32_t *status, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int taoamd_track_hota_reduce(int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou,
+                             int64_t n_dt_frames, int64_t n_gt_frames, int32_t n_cat,
+                             int32_t n_alpha, const int32_t *cell_dt_off,
+                             const int32_t *cell_gt_off, const int64_t *cell_iou_off,
+                             const int32_t *gt_cat, const uint8_t *gt_flags,
+                             const int32_t *dt_frame_off, const int32_t *gt_frame_off,
+                             const int32_t *mc, const int64_t *lc, int64_t *tp, int64_t *loc,
+                             int64_t *ass, void *workspace, size_t workspace_bytes,
+                             void *stream);
+
 /* ---- multi-GPU result exchange (category-partitioned evaluation) -------------------
  * No reference counterpart (the reference is single-process); these carry the
  * tables of taoamd_accumulate_compact between ranks and end in the layout of

@@ -12,6 +12,9 @@
 //                           last position} of its frame list, clamped to the tables
 //   frames_gt_cell_kernel   lane = cell: the cell of every ground-truth row
 //   frames_frame_gt_kernel  wavefront = ground-truth track: the track of every frame
+// HOTA (track_hota.hip) builds the same three and, beside them, a fourth table of
+// its own, the twin of dt_meta for the ground-truth tracks:
+//   frames_gt_meta_kernel   lane = ground-truth track (frames_build_gt_meta)
 //
 // EMPTY SIDES, the one rule: frames_build leaves every table complete whatever
 // is empty -- a table without rows costs neither a memset nor a launch; a ground-
@@ -97,6 +100,38 @@ static inline int frames_build(const FrameSource &a, const FrameTables &t, hipSt
         TAO_TIMED("frames_frame_gt_kernel", s,
                   frames_frame_gt_kernel<<<(unsigned)((a.n_gt + per - 1) / per), 256, 0, s>>>(a, t));
     }
+    return TAOAMD_OK;
+}
+
+// The twin of dt_meta for the ground-truth tracks, for the pass that also asks
+// which OTHER ground truths of a cell have a frame at a position (track_hota.hip):
+// gt_meta[n_gt] = {first frame, end, first and last position}, a table of the
+// pass's own beside the three above, probed by frames_find like dt_meta.
+static __global__ __launch_bounds__(256) void frames_gt_meta_kernel(int64_t n_gt,
+                                                                    int64_t n_gt_frames,
+                                                                    const int32_t *gfoff,
+                                                                    const int32_t *gfpos,
+                                                                    int4 *gt_meta)
+{
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_gt) return;
+    const int64_t fs = clamp64(gfoff[g], 0, n_gt_frames);
+    const int64_t fe = clamp64(gfoff[g + 1], fs, n_gt_frames);
+    int4 m = make_int4((int32_t)fs, (int32_t)fe, 0, -1);
+    if (fe > fs) {
+        m.z = gfpos[fs];
+        m.w = gfpos[fe - 1];
+    }
+    gt_meta[g] = m;
+}
+
+static inline int frames_build_gt_meta(int64_t n_gt, int64_t n_gt_frames, const int32_t *gfoff,
+                                       const int32_t *gfpos, int4 *gt_meta, hipStream_t s)
+{
+    if (n_gt > 0)
+        TAO_TIMED("frames_gt_meta_kernel", s,
+                  frames_gt_meta_kernel<<<(unsigned)((n_gt + 255) / 256), 256, 0, s>>>(
+                      n_gt, n_gt_frames, gfoff, gfpos, gt_meta));
     return TAOAMD_OK;
 }
 

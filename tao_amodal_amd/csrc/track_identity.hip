@@ -35,7 +35,8 @@
 //                           positive share in a compacted row are compacted
 //                        3  the smaller side becomes the rows (n <= m)
 //                        4  shortest augmenting paths (Hungarian in the Jonker-
-//                           Volgenant form, on cost = -weight): a row a time; a
+//                           Volgenant form, on cost = -weight; assign_solve.hpp,
+//                           shared with track_hota.hip): a row a time; a
 //                           step scans the free columns, lanes striding them
 //                           (ceil(m / 64) a lane), the minimum (value, column) by
 //                           a wavefront reduction -- the lowest column among
@@ -60,6 +61,7 @@
 //   ident_share_kernel 38 VGPRs, 30 SGPRs, 8 waves/SIMD, no scratch, no LDS;
 //   ident_assign_kernel 54 VGPRs, 11 264 B of LDS (a workgroup is one wavefront:
 //   14 cells a CU by LDS).
+#include "assign_solve.hpp"
 #include "common.hpp"
 #include "track_frames.hpp"
 #include "workspace.hpp"
@@ -69,7 +71,6 @@ using namespace taoamd;
 #define TI_TILE 64          // ground-truth frames per workgroup of the share kernel
 #define TI_LDS 256          // columns (and rows) of a cell whose search state is in LDS
 #define TI_NCAT 6
-#define TI_INF 0x1fffffffffffffffll
 
 struct IdentArgs {
     int64_t n_dt, n_gt, n_cells, n_iou, n_dt_frames, n_gt_frames;
@@ -152,100 +153,19 @@ struct CellShare {
     }
 };
 
-// The search state: column arrays of m entries, u of n, the index lists
-struct Search {
-    long long *u, *v, *minv;
-    int32_t *p, *way, *used;
-    const int32_t *ridx, *cidx;      // in-cell indices of row i / column j
+// The weight of a pair for the shared solver (assign_solve.hpp): share * (n + 1) +
+// (share > 0) -- the sum of shares decides, among equal sums the number of pairs
+// with a positive share (fewer than n + 1), so that both numbers are unique.
+struct IdentWeight {
+    CellShare S;
+    long long scale;                 // n + 1
+    bool rows_are_dt;
+    __device__ __forceinline__ long long operator()(int64_t r, int64_t c) const
+    {
+        const long long w = rows_are_dt ? S.at(r, c) : S.at(c, r);
+        return w * scale + (w > 0);
+    }
 };
-
-// Rows 1 .. n, columns 1 .. m, n <= m; p[j - 1] = the row of column j, 0: free;
-// way[j - 1] = the column before j on the path, 0: the root (the new row).
-// The weight of a pair is share * (n + 1) + (share > 0): the sum of shares decides,
-// among equal sums the number of pairs with a positive share (fewer than n + 1),
-// so that both numbers are unique.  Returns false if a bound ran out (then p is
-// not an assignment).
-__device__ __forceinline__ bool ident_solve(const CellShare &S, const Search &s, int n, int m,
-                                            bool rows_are_dt)
-{
-    const long long scale = (long long)n + 1;
-    const int lane = lane_id();
-    for (int j = lane; j < m; j += WAVE) {
-        s.v[j] = 0;
-        s.p[j] = 0;
-    }
-    for (int i = lane; i < n; i += WAVE) s.u[i] = 0;
-    __syncthreads();
-    for (int i = 1; i <= n; i++) {
-        for (int j = lane; j < m; j += WAVE) {
-            s.minv[j] = TI_INF;
-            s.used[j] = 0;
-            s.way[j] = 0;
-        }
-        __syncthreads();
-        int j0 = 0, i0 = i;
-        bool found = false;
-        for (int step = 0; step <= m; step++) {
-            const long long ui = s.u[i0 - 1];
-            const int64_t r = s.ridx[i0 - 1];
-            long long best = TI_INF;
-            int bj = 0x7fffffff;
-            for (int j = lane; j < m; j += WAVE) {
-                if (s.used[j]) continue;
-                const int64_t c = s.cidx[j];
-                const long long w = rows_are_dt ? S.at(r, c) : S.at(c, r);
-                const long long cur = -(w * scale + (w > 0)) - ui - s.v[j];
-                long long mv = s.minv[j];
-                if (cur < mv) {
-                    mv = cur;
-                    s.minv[j] = cur;
-                    s.way[j] = j0;
-                }
-                if (mv < best) {             // (ascending j: the lowest among equal values)
-                    best = mv;
-                    bj = j;
-                }
-            }
-#pragma unroll
-            for (int o = WAVE / 2; o > 0; o >>= 1) {
-                const long long ob = __shfl_xor(best, o);
-                const int oj = __shfl_xor(bj, o);
-                if (ob < best || (ob == best && oj < bj)) {
-                    best = ob;
-                    bj = oj;
-                }
-            }
-            if (bj == 0x7fffffff) return false;     // no free column: n <= m rules it out
-            for (int j = lane; j < m; j += WAVE) {
-                if (s.used[j]) {
-                    s.u[s.p[j] - 1] += best;         // (distinct columns hold distinct rows)
-                    s.v[j] -= best;
-                } else {
-                    s.minv[j] -= best;
-                }
-            }
-            if (lane == 0) s.u[i - 1] += best;       // the root's row
-            if ((bj & (WAVE - 1)) == lane) s.used[bj] = 1;
-            __syncthreads();
-            j0 = bj + 1;
-            i0 = s.p[bj];
-            if (i0 == 0) {
-                found = true;
-                break;
-            }
-        }
-        if (!found) return false;
-        // the path back to the root; every lane walks it and stores the same words
-        for (int step = 0; step <= m && j0; step++) {
-            const int j1 = s.way[j0 - 1];
-            s.p[j0 - 1] = j1 ? s.p[j1 - 1] : i;
-            j0 = j1;
-        }
-        if (j0) return false;
-        __syncthreads();
-    }
-    return true;
-}
 
 __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
 {
@@ -334,17 +254,18 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
     }
     const int32_t *rl = rows_are_dt ? dlist : glist, *cl = rows_are_dt ? glist : dlist;
     // 4: the search, its state in LDS or in the cell's slice of the workspace
+    const IdentWeight W = {S, (long long)n + 1, rows_are_dt};
     Search s;
     bool ok;
     if (m <= TI_LDS) {
         for (int i = lane; i < n; i += WAVE) l_ridx[i] = rl[i];
         for (int j = lane; j < m; j += WAVE) l_cidx[j] = cl[j];
         s = {l_u, l_v, l_minv, l_p, l_way, l_used, l_ridx, l_cidx};
-        ok = ident_solve(S, s, n, m, rows_are_dt);
+        ok = assign_solve(W, s, n, m);
     } else {
         s = {a.su + base, a.sv + base, a.sminv + base, a.sp + base, a.sway + base,
              a.sused + base, rl, cl};
-        ok = ident_solve(S, s, n, m, rows_are_dt);
+        ok = assign_solve(W, s, n, m);
     }
     if (!ok) {
         if (lane == 0) *a.status = 1;

@@ -593,7 +593,9 @@ class Workspace:
         self.assoc_frame_thr = None       # the frame_thr ws.assoc_best holds the followers of
         self.occ_ws = self.occ_gt = self.occ_off = self.occ_counts = self.occ_episodes = None
         self.ident_ws = self.ident_share = self.ident_cat_counts = None
-        self.occ_n = None                 # episodes of the last stage_track_occlusion that read them
+        self.ident_frame_thr = None       # the frame_thr ws.ident_dt holds the kept tracks of
+        self.hota_ws = self.hota_mc = self.hota_lc = None
+        self.occ_n = None                # episodes of the last stage_track_occlusion that read them
         self.pairs_counted = False        # stage_track_iou counted the pairs' common frames
 
 
@@ -1504,10 +1506,74 @@ def stage_track_identity(dp, ws, frame_thr):
         _ptr(ws.ident_status), _ptr(ws.ident_ws), ws.ident_bytes, s),
         "taoamd_track_identity_assign")
     status = int(ws.ident_status.item())            # (synchronises)
+    ws.ident_frame_thr = None
     if status:
         raise _lib.TaoAmdError("taoamd_track_identity_assign: status %d (%s)" % (
             status, "a search ran out of its loop bound" if status == 1 else
             "a cell's weights exceed 64-bit potentials"))
+    ws.ident_frame_thr = float(frame_thr)
+
+
+def stage_track_hota(dp, ws, alphas, frame_thr):
+    """HOTA's integer tables from a one-to-one assignment per frame
+    (taoamd_track_hota_align, taoamd_track_hota_match, taoamd_track_hota_reduce;
+    the definition is in include/tao_amodal_hip.h): ws.hota_tp and ws.hota_loc
+    int64[n_cat, n_alpha], ws.hota_ass int64[n_cat, n_alpha, 3] in fixed point
+    (_lib.HOTA_ONE), ws.hota_match int32[n_gt_frames] (the in-cell index of the
+    frame's detection track or -1) and ws.hota_match_iou, at the ascending
+    localisation thresholds `alphas` (1 to 32 doubles, TrackEval's eps already
+    subtracted).  The detection tracks that take part are the identity's kept
+    ones at `frame_thr`: stage_track_identity runs first unless the workspace
+    holds it for that threshold (ws.ident_frame_thr).  On request only.  Raises
+    if the match reports a non-zero status (an exhausted loop bound): one
+    synchronisation of the current stream.  Buffers are allocated on the first
+    call and kept with the workspace: 8 bytes per pair of a cell for pot and 12
+    per (alpha, pair) for mc and lc, regrown where a call brings more alphas, 12
+    per ground-truth frame, 1 per detection track, and a workspace of 64 bytes
+    per detection track, 68 per ground-truth track and 4 per ground-truth frame."""
+    sizes, cells, frames = _track_tables(dp, "HOTA is")
+    lib, t, dev, s = _lib.load(), dp.t, dp.device, _stream()
+    alphas = np.ascontiguousarray(alphas, dtype=np.float64).reshape(-1)
+    n_alpha = len(alphas)
+    if not 1 <= n_alpha <= _lib.TRACK_HOTA_ALPHAS:
+        raise _lib.TaoAmdError("%d alphas; the kernels take 1 to %d"
+                               % (n_alpha, _lib.TRACK_HOTA_ALPHAS))
+    frame_thr = float(frame_thr)
+    if ws.ident_ws is None or ws.ident_frame_thr != frame_thr:
+        stage_track_identity(dp, ws, frame_thr)
+    n_gf = sizes[5]
+    if ws.hota_ws is None:
+        ws.hota_bytes = lib.taoamd_track_hota_workspace(dp.n_dt, dp.n_gt, n_gf)
+        ws.hota_ws = torch.empty(max(int(ws.hota_bytes), 256), dtype=torch.uint8, device=dev)
+        ws.hota_pot = torch.empty(max(dp.n_iou, 1), dtype=torch.int64, device=dev)
+        ws.hota_keep = torch.empty(max(dp.n_dt, 1), dtype=torch.uint8, device=dev)
+        ws.hota_match = torch.empty(max(n_gf, 1), dtype=torch.int32, device=dev)
+        ws.hota_match_iou = torch.empty(max(n_gf, 1), dtype=torch.float64, device=dev)
+        ws.hota_status = torch.empty(1, dtype=torch.int32, device=dev)
+        ws.hota_mc = None
+    if ws.hota_mc is None or ws.hota_mc.shape[0] < n_alpha:
+        ws.hota_mc = torch.empty((n_alpha, max(dp.n_iou, 1)), dtype=torch.int32, device=dev)
+        ws.hota_lc = torch.empty((n_alpha, max(dp.n_iou, 1)), dtype=torch.int64, device=dev)
+    ws.hota_tp = torch.empty((dp.n_cat, n_alpha), dtype=torch.int64, device=dev)
+    ws.hota_loc = torch.empty((dp.n_cat, n_alpha), dtype=torch.int64, device=dev)
+    ws.hota_ass = torch.empty((dp.n_cat, n_alpha, 3), dtype=torch.int64, device=dev)
+    ws.hota_keep.copy_(ws.ident_dt[:, 1])
+    tables = (*cells, _ptr(t["gt_flags"]), _ptr(ws.hota_keep), *frames)
+    _lib.check(lib.taoamd_track_hota_align(
+        *sizes, *tables, _ptr(ws.hota_pot), _ptr(ws.hota_ws), ws.hota_bytes, s),
+        "taoamd_track_hota_align")
+    _lib.check(lib.taoamd_track_hota_match(
+        *sizes, n_alpha, alphas.ctypes.data, *tables, _ptr(ws.hota_pot), _ptr(ws.hota_mc),
+        _ptr(ws.hota_lc), _ptr(ws.hota_match), _ptr(ws.hota_match_iou), _ptr(ws.hota_status),
+        _ptr(ws.hota_ws), ws.hota_bytes, s), "taoamd_track_hota_match")
+    _lib.check(lib.taoamd_track_hota_reduce(
+        *sizes, dp.n_cat, n_alpha, *cells, _ptr(t["gt_cat"]), _ptr(t["gt_flags"]), frames[0],
+        frames[3], _ptr(ws.hota_mc), _ptr(ws.hota_lc), _ptr(ws.hota_tp), _ptr(ws.hota_loc),
+        _ptr(ws.hota_ass), _ptr(ws.hota_ws), ws.hota_bytes, s), "taoamd_track_hota_reduce")
+    status = int(ws.hota_status.item())             # (synchronises)
+    if status:
+        raise _lib.TaoAmdError("taoamd_track_hota_match: status %d (a search ran out of its "
+                               "loop bound)" % status)
 
 
 def stage_track_iou_guarded(dp, ws):

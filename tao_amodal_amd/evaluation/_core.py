@@ -369,8 +369,8 @@ class GpuRun:
         return rng.astype(np.int32), dt_cat, gt_cat, counts, K
 
     def _followers_at(self, what, ann_vis):
-        """What association_table(), occlusion_table() and identity_table()
-        share: the refusals, in the name `what` of the caller's method, and
+        """What association_table(), occlusion_table(), identity_table() and
+        hota_table() share: the refusals, in the name `what` of the caller's method, and
         (`ann_vis` not None) the frames' own visibility, gathered from the
         annotations' column and uploaded on the first call."""
         if self.flat.kind != "tao":
@@ -446,6 +446,26 @@ class GpuRun:
             return {"cat_counts": ws.ident_cat_counts.cpu().numpy(),
                     "gt_ident": ws.ident_gt[:dp.n_gt].cpu().numpy(),
                     "dt_ident": ws.ident_dt[:dp.n_dt].cpu().numpy()}
+
+    def hota_table(self, alphas, frame_thr):
+        """HOTA's integer tables (engine.stage_track_hota; the definition is in
+        include/tao_amodal_hip.h) at the localisation thresholds `alphas` (eps
+        already subtracted) over the tracks identity_table(frame_thr) keeps:
+        dict(cat_counts int64[K, 6] of the identity, tp and loc int64[K, A], ass
+        int64[K, A, 3], match int32[n_gt_frames] as in-cell indices, match_iou).
+        Reads the track tables alone; refuses what identity_table() refuses."""
+        self._followers_at("hota()", None)
+        dp, ws = self.dp, self.ws
+        with timed("kernels"):
+            self.engine.stage_track_hota(dp, ws, alphas, frame_thr)
+            self.torch.cuda.synchronize(self.device)
+        with timed("download"):
+            n_gf = int(dp.t["gt_frame_pos"].numel())
+            return {"cat_counts": ws.ident_cat_counts.cpu().numpy(),
+                    "tp": ws.hota_tp.cpu().numpy(), "loc": ws.hota_loc.cpu().numpy(),
+                    "ass": ws.hota_ass.cpu().numpy(),
+                    "match": ws.hota_match[:n_gf].cpu().numpy(),
+                    "match_iou": ws.hota_match_iou[:n_gf].cpu().numpy()}
 
     def pointer_tables(self):
         """What eval['dt_pointers'] is read from: the detections' ids and

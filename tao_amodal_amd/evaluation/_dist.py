@@ -438,6 +438,9 @@ class DistRun:
     def identity_table(self, frame_thr):
         raise NotImplementedError("identity() in a multi-GPU run")
 
+    def hota_table(self, alphas, frame_thr):
+        raise NotImplementedError("hota() in a multi-GPU run")
+
     def pointer_tables(self):
         if self._pointers is None:
             raise NotImplementedError(

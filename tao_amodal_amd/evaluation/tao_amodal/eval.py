@@ -119,6 +119,7 @@ class TaoEval:
         """The caches of the analyses on request: they hold results of one evaluate()."""
         self._error_types, self._error_impact, self._confusion = {}, {}, {}
         self._association, self._occlusions, self._identity = {}, {}, {}
+        self._hota = {}
 
     # ------------------------------------------------------------ stages
     def evaluate(self, show_progress=False):
@@ -524,6 +525,55 @@ class TaoEval:
         """identity() as a small text table: the totals over the categories.
         Returned, not printed."""
         return followers.identity_lines(self.identity(frame_thr))
+
+    def hota(self, alphas=None, frame_thr=0.5, per_frame=False):
+        """HOTA, DetA and AssA (Luiten et al., IJCV 2021; TrackEval's HOTA): the
+        measure tracking papers print beside Track-AP and IDF1.  association()
+        is a per-frame arg-max and identity() one assignment over whole tracks;
+        HOTA makes a ONE-TO-ONE assignment in every frame, weighted by how well
+        each pair of tracks aligns over the whole video, and scores every
+        matched frame by the share of its two tracks' frames that are matched
+        to each other.  Solved on the device on request (csrc/track_hota.hip).
+        Callable after evaluate(), cached per (alphas, frame_thr).
+
+        Rows are the tracks that survived the max_dets cut and the federated
+        filter; a frame's candidates are the boxes of its video and category.
+        The tracks that take part are identity(frame_thr)'s: ground-truth tracks
+        marked "ignore" are left out, and so are the detection tracks it sets
+        aside, so HOTA and IDF1 are computed over the same tracks.  `alphas`:
+        the localisation thresholds, 1 to 32 strictly ascending values in (0, 1]
+        (ValueError otherwise); None is TrackEval's np.arange(0.05, 0.99, 0.05).
+        A matched frame counts at alpha where its box IoU >= alpha - eps.  The
+        assignment is made once per frame, not once per alpha.  Every sum is
+        carried as an integer in fixed point (2^30): the tables are exact and the
+        same from run to run.  The exact rules are in include/tao_amodal_hip.h,
+        section "track-level HOTA"; what differs from TrackEval's TAO
+        preprocessing is in DESIGN.md section 8.
+
+        Returns {"alphas", "frame_thr", "cat_counts": int64[K, 4] = gt_tracks,
+        gt_frames, dt_tracks, dt_frames with the category axis in the order of
+        params.cat_ids, the integers "tp", "fn", "fp", "loc": int64[K, A] and
+        "ass": int64[K, A, 3] (loc and ass times 2^30), float64[K, A] "hota",
+        "deta", "assa", "detre", "detpr", "assre", "asspr", "loca" with
+        TrackEval's max(1, .) denominators (LocA is 1 without a match), NaN where
+        the category has neither ground-truth nor detection frames, "total":
+        the sums over the categories, their per-alpha ratios under the same
+        names and the means over alpha "HOTA", "DetA", "AssA", "DetRe", "DetPr",
+        "AssRe", "AssPr", "LocA" with "HOTA(0)", "LocA(0)", "HOTALocA(0)" at the
+        first alpha (TrackEval's detection-averaged combination), "mean": those
+        scalars averaged over the categories that have frames (its class-
+        averaged combination)}; with per_frame=True "frames": per ground-truth
+        frame (the ground-truth track id, the image id, the matched detection
+        track's id or -1, its box IoU or 0).
+        Not available: iou_type="segm", use_cats = 0, multi-GPU runs, the
+        command line; a per-visibility breakdown of DetRe is not computed (the
+        per-frame output carries what it needs)."""
+        return followers.hota(self, alphas, frame_thr, per_frame)
+
+    def hota_lines(self, alphas=None, frame_thr=0.5):
+        """hota() as a small text table in per cent, in TrackEval's column order:
+        the total and the class mean.  Returned, not printed."""
+        return followers.hota_lines(self.hota(alphas, frame_thr))
 
     def impact_lines(self, iou_thr=0.5, bg_thr=0.1):
         """error_impact() as a small text table: a line per (area, time) range,

@@ -1,6 +1,6 @@
 """The analyses of TaoEval that read the track tables alone -- association(),
-occlusions(), identity() -- and their text tables: the class layer over
-GpuRun.association_table / occlusion_table / identity_table.  The track
+occlusions(), identity(), hota() -- and their text tables: the class layer over
+GpuRun.association_table / occlusion_table / identity_table / hota_table.  The track
 level's alone; the methods of TaoEval carry the documentation and call in here
 with the evaluator `ev`."""
 import numpy as np
@@ -206,6 +206,102 @@ def identity(ev, frame_thr, per_track):
                 "tracks": (gt_id, tracks), "dt_tracks": (dt_id, dt_tracks)}
     return _cached(ev._identity, frame_thr, make,
                    (("tracks", per_track), ("dt_tracks", per_track)))
+
+
+HOTA_SCALARS = ("HOTA", "DetA", "AssA", "DetRe", "DetPr", "AssRe", "AssPr", "LocA")
+
+
+def hota_alphas(alphas):
+    """The localisation thresholds as float64: TrackEval's 19 for None, else 1 to
+    32 strictly ascending values in (0, 1]."""
+    if alphas is None:
+        return np.arange(0.05, 0.99, 0.05)
+    a = np.asarray(alphas, dtype=np.float64).reshape(-1)
+    if not 1 <= len(a) <= 32:
+        raise ValueError("alphas: {} values; 1 to 32".format(len(a)))
+    if not ((a > 0) & (a <= 1)).all():
+        raise ValueError("alphas: {} are not all in (0, 1]".format(a.tolist()))
+    if (np.diff(a) <= 0).any():
+        raise ValueError("alphas: {} do not strictly ascend".format(a.tolist()))
+    return a
+
+
+def hota_ratios(tp, loc, ass, gt_frames, dt_frames):
+    """The eight ratios of HOTA's integer tables as float64 in the shape of tp,
+    with TrackEval's max(1, .) denominators: tp, loc [.., A] and ass [.., A, 3] in
+    fixed point, the frame counts broadcast against tp.  LocA is 1 where tp is 0,
+    as in TrackEval."""
+    from ..._lib import HOTA_ONE
+    tp = np.asarray(tp, dtype=np.int64)
+    fn = np.asarray(gt_frames, dtype=np.int64) - tp
+    fp = np.asarray(dt_frames, dtype=np.int64) - tp
+    tpf, one = tp.astype(np.float64), np.maximum(1, tp).astype(np.float64)
+    ass = np.asarray(ass, dtype=np.int64).astype(np.float64) / HOTA_ONE
+    loc = np.asarray(loc, dtype=np.int64).astype(np.float64) / HOTA_ONE
+    out = {"deta": tpf / np.maximum(1, tp + fn + fp), "detre": tpf / np.maximum(1, tp + fn),
+           "detpr": tpf / np.maximum(1, tp + fp), "assa": ass[..., 0] / one,
+           "assre": ass[..., 1] / one, "asspr": ass[..., 2] / one,
+           "loca": np.where(tp > 0, loc / one, 1.0)}
+    out["hota"] = np.sqrt(out["deta"] * out["assa"])
+    return out
+
+
+def hota_scalars(r):
+    """The means over alpha of the ratios `r` (last axis) under TrackEval's
+    names, and HOTA(0), LocA(0), HOTALocA(0) at the first alpha."""
+    out = {name: r[name.lower()].mean(-1) for name in HOTA_SCALARS}
+    out["HOTA(0)"], out["LocA(0)"] = r["hota"][..., 0], r["loca"][..., 0]
+    out["HOTALocA(0)"] = out["HOTA(0)"] * out["LocA(0)"]
+    return out
+
+
+def hota(ev, alphas, frame_thr, per_frame):
+    frame_thr = _frame_thr(ev, frame_thr)
+    alphas = hota_alphas(alphas)
+
+    def make():
+        from ..._lib import HOTA_RATIOS
+        t = ev._run.hota_table(alphas - np.finfo(float).eps, frame_thr)
+        flat = ev._run.flat
+        counts = _params_cats(ev, t["cat_counts"], 0)[:, :4]
+        tp, loc, ass = (_params_cats(ev, t[k], 0) for k in ("tp", "loc", "ass"))
+        gt_frames, dt_frames = counts[:, 1:2], counts[:, 3:4]
+        out = {"alphas": alphas, "frame_thr": frame_thr, "cat_counts": counts, "tp": tp,
+               "fn": gt_frames - tp, "fp": dt_frames - tp, "loc": loc, "ass": ass}
+        r = hota_ratios(tp, loc, ass, gt_frames, dt_frames)
+        has = (counts[:, 1] + counts[:, 3]) > 0
+        for k in HOTA_RATIOS:
+            out[k] = np.where(has[:, None], r[k], np.nan)
+        tot = counts.sum(0)
+        total = dict(zip(("gt_tracks", "gt_frames", "dt_tracks", "dt_frames"),
+                         (int(x) for x in tot)))
+        total.update(tp=tp.sum(0), fn=tot[1] - tp.sum(0), fp=tot[3] - tp.sum(0), loc=loc.sum(0),
+                     ass=ass.sum(0))
+        rt = hota_ratios(total["tp"], total["loc"], total["ass"], tot[1], tot[3])
+        total.update(rt)
+        total.update({k: float(v) for k, v in hota_scalars(rt).items()})
+        per_cat = hota_scalars(r)
+        mean = {k: float(v[has].mean()) if has.any() else float("nan")
+                for k, v in per_cat.items()}
+        out["total"], out["mean"] = total, mean
+        foff, cell, img = _gt_frame_tables(flat)
+        g_of = np.repeat(np.arange(len(foff) - 1), np.diff(foff))
+        out["frames"] = (np.asarray(flat.gt_id, dtype=np.int64)[g_of], img,
+                         _follower_ids(flat, cell, t["match"]), t["match_iou"])
+        return out
+    return _cached(ev._hota, (alphas.tobytes(), frame_thr), make, (("frames", per_frame),))
+
+
+def hota_lines(e):
+    """TaoEval.hota()'s result `e` as a small text table, in per cent and in
+    TrackEval's column order: the detection-averaged total and the class mean."""
+    names = list(HOTA_SCALARS) + ["HOTA(0)", "LocA(0)", "HOTALocA(0)"]
+    lines = [" track HOTA @[ alphas={:0.2f}:{:0.2f} ({}) | frame IoU={:0.2f} ]".format(
+                 float(e["alphas"][0]), float(e["alphas"][-1]), len(e["alphas"]), e["frame_thr"]),
+             " " + "".ljust(10) + "".join(n.rjust(12) for n in names)]
+    for label, row in (("total", e["total"]), ("class mean", e["mean"])):
+        lines.append(" " + label.ljust(10) + "".join(_pct(row[n], width=12) for n in names))
+    return lines
 
 
 def identity_lines(e):

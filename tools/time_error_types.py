@@ -5,7 +5,7 @@ events:
 
     python tools/time_error_types.py [--level image|track] [--config 3s] [--reps 20] [--warmup 3]
                                      [--impact] [--association] [--occlusions] [--identity]
-                                     [--confusion]
+                                     [--hota] [--confusion]
 
 Times, on the image level's tables of that configuration, each alone on an idle
 stream: the fused match as a benchmark step runs it (the yardstick), the
@@ -30,7 +30,11 @@ stage) beside the association pass they follow, in the same process.  --level
 track --identity times the identity measures: taoamd_track_identity_share and
 taoamd_track_identity_assign each alone between HIP events and the whole stage
 (engine.stage_track_identity), beside the association pass without windows in
-the same process.  --confusion
+the same process.  --level track --hota times HOTA: taoamd_track_hota_align,
+taoamd_track_hota_match and taoamd_track_hota_reduce each alone between HIP
+events and the whole stage (engine.stage_track_hota) beside the identity stage
+in the same process, and reports the sizes of mc and lc and the share of frame
+groups with more than one ground truth.  --confusion
 (both levels) adds the confusion table: the level's links pass,
 taoamd_confusion_count and taoamd_confusion_fill, each alone between HIP events
 in the same process, the whole stage with its read of the entry count, the
@@ -121,6 +125,8 @@ def track_level(a, gt, dt, dev, V):
         return occlusions(a, res, gt, fl, dp, ws, timed)
     if a.identity:
         return identity(a, res, dp, ws, timed)
+    if a.hota:
+        return hota(a, res, dp, ws, timed)
     res["match_fused"] = timed(lambda: engine.stage_match(dp, ws))
     # the first call builds the per-video lists and runs the match for match_gt
     engine.stage_track_error_types(dp, ws, 0, a.bg_thr)
@@ -410,6 +416,96 @@ def identity(a, res, dp, ws, timed):
     print(json.dumps(res))
 
 
+def hota(a, res, dp, ws, timed):
+    """--level track --hota: HOTA (engine.stage_track_hota) at TrackEval's 19
+    alphas over the identity's kept tracks at frame_thr 0.5: the three calls each
+    alone between HIP events, the whole stage (which reads the status word), the
+    identity stage in the same process, the kernels, the sizes of the tables and
+    the share of frame groups with more than one ground truth."""
+    import torch
+    from tao_amodal_amd import _lib, engine
+    lib = _lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    thr = 0.5
+    alphas = np.ascontiguousarray(np.arange(0.05, 0.99, 0.05) - np.finfo(float).eps)
+    n_alpha = len(alphas)
+    # the first call allocates the buffers of both stages
+    engine.stage_track_hota(dp, ws, alphas, thr)
+    torch.cuda.synchronize()
+    t = dp.t
+    sizes = (dp.n_dt, dp.n_gt, dp.n_cells, dp.n_iou, int(t["dt_frame_pos"].numel()),
+             int(t["gt_frame_pos"].numel()))
+    cells = (t["cell_dt_off"].data_ptr(), t["cell_gt_off"].data_ptr(),
+             t["cell_iou_off"].data_ptr())
+    tables = (*cells, t["gt_flags"].data_ptr(), ws.hota_keep.data_ptr(),
+              t["dt_frame_off"].data_ptr(), t["dt_frame_pos"].data_ptr(),
+              t["dt_frame_box"].data_ptr(), t["gt_frame_off"].data_ptr(),
+              t["gt_frame_pos"].data_ptr(), t["gt_frame_box"].data_ptr())
+
+    def align():
+        _lib.check(lib.taoamd_track_hota_align(
+            *sizes, *tables, ws.hota_pot.data_ptr(), ws.hota_ws.data_ptr(), ws.hota_bytes,
+            stream), "taoamd_track_hota_align")
+
+    def match():
+        _lib.check(lib.taoamd_track_hota_match(
+            *sizes, n_alpha, alphas.ctypes.data, *tables, ws.hota_pot.data_ptr(),
+            ws.hota_mc.data_ptr(), ws.hota_lc.data_ptr(), ws.hota_match.data_ptr(),
+            ws.hota_match_iou.data_ptr(), ws.hota_status.data_ptr(), ws.hota_ws.data_ptr(),
+            ws.hota_bytes, stream), "taoamd_track_hota_match")
+
+    def reduce():
+        _lib.check(lib.taoamd_track_hota_reduce(
+            *sizes, dp.n_cat, n_alpha, *cells, t["gt_cat"].data_ptr(), t["gt_flags"].data_ptr(),
+            t["dt_frame_off"].data_ptr(), t["gt_frame_off"].data_ptr(), ws.hota_mc.data_ptr(),
+            ws.hota_lc.data_ptr(), ws.hota_tp.data_ptr(), ws.hota_loc.data_ptr(),
+            ws.hota_ass.data_ptr(), ws.hota_ws.data_ptr(), ws.hota_bytes, stream),
+            "taoamd_track_hota_reduce")
+    res["identity_stage"] = timed(lambda: engine.stage_track_identity(dp, ws, thr))
+    res["hota_align"] = timed(align)
+    res["hota_match"] = timed(match)
+    res["hota_reduce"] = timed(reduce)
+    res["hota_stage"] = timed(lambda: engine.stage_track_hota(dp, ws, alphas, thr))
+    _lib.kernel_timing(True)
+    for _ in range(a.reps):
+        align()
+        match()
+        reduce()
+    res["kernels_ms"] = {k: round(ms / n, 4) for k, (ms, n) in _lib.kernel_timings().items()}
+    _lib.kernel_timing(False)
+    torch.cuda.synchronize()
+    # what the match met (on the device, untimed): a frame group is (cell, position);
+    # its ground truths are the eligible ones with a frame there
+    n_gf = sizes[5]
+    foff = t["gt_frame_off"].long()
+    g_of = torch.repeat_interleave(torch.arange(dp.n_gt, device=foff.device), foff[1:] - foff[:-1])
+    g_cell = torch.repeat_interleave(
+        torch.arange(dp.n_cells, device=foff.device),
+        (t["cell_gt_off"][1:] - t["cell_gt_off"][:-1]).long())
+    elig = (t["gt_flags"][:dp.n_gt][g_of] & 1) == 0
+    top = int(t["gt_frame_pos"].max().item()) + 1 if n_gf else 1
+    key = g_cell[g_of].long() * top + t["gt_frame_pos"].long()
+    _, per_group = torch.unique(key[elig], return_counts=True)
+    res["hota_status"] = int(ws.hota_status.item())
+    res["hota_alphas"] = n_alpha
+    res["hota_frame_groups"] = int(per_group.numel())
+    res["hota_frame_groups_with_several_ground_truths"] = int((per_group > 1).sum().item())
+    res["hota_largest_frame_group"] = int(per_group.max().item()) if per_group.numel() else 0
+    res["hota_matched_frames"] = int((ws.hota_match[:n_gf] >= 0).sum().item())
+    res["hota_workspace_bytes"] = int(ws.hota_bytes)
+    res["hota_pot_bytes"] = 8 * dp.n_iou
+    res["hota_mc_bytes"] = 4 * n_alpha * dp.n_iou
+    res["hota_lc_bytes"] = 8 * n_alpha * dp.n_iou
+    tp = ws.hota_tp.sum(0).double()
+    ass = ws.hota_ass.sum(0).double()[:, 0] / _lib.HOTA_ONE
+    cc = ws.ident_cat_counts.sum(0).tolist()
+    deta = tp / torch.clamp(cc[1] + cc[3] - tp, min=1)
+    assa = ass / torch.clamp(tp, min=1)
+    res["hota_totals"] = {"gt_frames": cc[1], "dt_frames": cc[3], "tp": [int(x) for x in tp.tolist()]}
+    res["hota"] = round(float(torch.sqrt(deta * assa).mean().item()), 6)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--level", choices=("image", "track"), default="image")
@@ -424,6 +520,7 @@ def main():
     ap.add_argument("--association", action="store_true")
     ap.add_argument("--occlusions", action="store_true")
     ap.add_argument("--identity", action="store_true")
+    ap.add_argument("--hota", action="store_true")
     ap.add_argument("--confusion", action="store_true")
     a = ap.parse_args()
     if a.association and a.level != "track":
@@ -432,6 +529,8 @@ def main():
         ap.error("--occlusions is the track level's: --level track")
     if a.identity and a.level != "track":
         ap.error("--identity is the track level's: --level track")
+    if a.hota and a.level != "track":
+        ap.error("--hota is the track level's: --level track")
     import torch
     from tao_amodal_amd import _lib, engine, flatten_dev
     from tao_amodal_amd.synth import synth
