@@ -1685,6 +1685,141 @@ int taoamd_track_hota_reduce(int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_
                              int64_t *ass, void *workspace, size_t workspace_bytes,
                              void *stream);
 
+/* ---- track-level CLEAR: MOTA / MOTP / IDSW (csrc/track_clear.hip) --------------------
+ * The third of the measures printed beside Track-AP (Bernardin & Stiefelhagen,
+ * 2008): a ONE-TO-ONE assignment per frame, as HOTA's, but each frame's weights
+ * depend on the frame before -- the pair matched a step ago gets a bonus -- and an
+ * ID switch is scored against the last match however long ago it was.  The
+ * frames of a cell are a serial chain.  The reference has no counterpart; the
+ * definition is this library's, after TrackEval's CLEAR class; it is not
+ * TrackEval's TAO number, for the reasons given for HOTA (no preprocessing of the
+ * TAO kind).  Track level, boxes.
+ *
+ * Rows, cells, frame lists, `eligible`, `kept` (dt_keep, NULL: every d), s, c(s)
+ * and q are those of track-level HOTA above: MOTA, IDF1 and HOTA are computed over
+ * the same tracks and the same gt_frames / dt_frames.
+ *   candidate   at a timeline position p the pair (eligible g, kept d) of one cell,
+ *               both with a frame at p, with s >= frame_thr and q(c(s)) > 0.  A NaN
+ *               is no candidate.  frame_thr: any double in (0, 1].
+ *   step        a position of a cell at which at least one eligible ground truth
+ *               AND at least one kept detection track of the cell have a frame
+ *               (candidates are not required).  A cell's steps are taken in
+ *               ascending position.  A position that is no step changes no state
+ *               (TrackEval `continue`s there before it touches anything): a track
+ *               with holes, or a position without any detection frame of the
+ *               cell, does not reset continuity.
+ *   state       per eligible g of the cell, both none at first: prev[g], its match
+ *               at the cell's previous step; last[g], its most recent match at
+ *               any earlier step.
+ * A STEP.  w(g, d) = q(c(s)) + (d == prev[g] ? 1000 * 2^30 : 0) for a candidate, 0
+ * (no edge) otherwise; a weight is below 2^41.  The step's match is the one-to-one
+ * set of pairs with w > 0 that maximises the sum of w, a unique integer.  Among
+ * equal sums the solver's choice holds, a function of the input alone, and it
+ * feeds later steps, so it is stated: the ROWS are the ground truths of the step
+ * with at least one candidate, in ascending row; the COLUMNS are the detection
+ * rows those candidates name, in ascending row; the smaller side becomes the
+ * solver's rows (the ground truths when equal); shortest augmenting paths, a row
+ * at a time in that order, equal minima to the lowest column (assign_solve.hpp,
+ * the code of the identity and HOTA).  One row needs no solver: the candidate
+ * equal to prev if there is one, else the greatest q, the first of the list among
+ * equals -- which is what the solver returns for it.
+ * For a matched (g, d): an ID switch is counted (and sw set at the frame) if
+ * last[g] is not none and last[g] != d; then last[g] = d.  For EVERY eligible g of
+ * the cell, present at the step or not, prev[g] becomes its match at this step or
+ * none; started[g] is incremented where prev[g] was none and now is not.
+ * Per ground-truth track, gt_clear int32[n_gt][4] = {present, matched, idsw,
+ * started}: present = its frames (all of them, steps or not), matched = its
+ * matched frames; zeros for an ignored row.  frag = max(started - 1, 0); mostly
+ * tracked iff 5 * matched > 4 * present, partly tracked iff not mostly tracked and
+ * 5 * matched >= present, mostly lost otherwise (TrackEval's > 0.8 and >= 0.2).
+ * Per category (gt_cat), cat_counts int64[n_cat][7] = {tp, idsw, frag, mt, pt, ml,
+ * motp_sum} over the eligible tracks: tp = the matched frames, motp_sum = the sum
+ * of q(c(s)) over the matches.  The caller forms fn = gt_frames - tp, fp =
+ * dt_frames - tp (the frame counts of taoamd_track_identity_assign's cat_counts;
+ * positions without a ground truth need no visit), MOTA = (tp - fp - idsw) /
+ * max(1, tp + fn), MOTP = motp_sum / 2^30 / max(1, tp).
+ * By visibility, vis_counts int64[n_vis][n_cat][4] = {frames, matched, idsw,
+ * q sum}: the association's windows -- n_vis <= 8 closed windows vis_rng
+ * double[n_vis][2] (device), they may overlap, a NaN visibility lies in none --
+ * over the eligible tracks' frames: the frames in the window, the matched ones,
+ * those with sw set, the q of those matches.  Categories outside [0, n_cat)
+ * count nowhere.
+ *
+ * Three stages, each of which can be driven alone; one workspace size
+ * (taoamd_track_clear_workspace answers 0 to sizes it refuses; any base address,
+ * contents need not be initialised, nothing is carried from call to call).
+ * CANDIDATES, in parallel, count then fill.  taoamd_track_clear_count fills the
+ * whole of cand_off int64[n_gt_frames + 1], the exclusive prefix sum of the
+ * frames' candidate counts (cand_off[n_gt_frames] = n_cand), and step
+ * uint8[n_gt_frames]: 1 where some kept detection track of the cell has a frame
+ * at the position of the (eligible track's) frame -- the step bit; a frame of an
+ * ignored track has no candidates and no bit.  taoamd_track_clear_fill, with the
+ * same tables, stores per candidate, at the frame's place and in ascending row,
+ * cand_row int32 (the in-cell detection row), cand_q int32 (q(c(s)), in (0, 2^30])
+ * and, if not NULL, cand_iou double (s); nothing at or beyond entry n_cand.
+ * WALK.  taoamd_track_clear_walk reads the cell tables, the ground-truth frame
+ * lists' offsets and positions, the step bits and the candidate store (any tables
+ * in that layout: a row outside the cell or a q <= 0 is no candidate, a q above
+ * 2^30 reads 2^30; lists are taken to ascend in row), never a box.  It fills
+ * match int32[n_gt_frames] (the in-cell detection row or -1), match_iou
+ * double[n_gt_frames] (may be NULL; the cand_iou of the match, 0.0 where
+ * unmatched or cand_iou is NULL), sw uint8[n_gt_frames], gt_clear and one int32
+ * *status (device): 0; 1 if a loop bound of the solver ran out (that step is
+ * left unmatched); 2 if a cell's smaller side exceeds
+ * TAOAMD_TRACK_CLEAR_NMAX = 2^18 -- below it the 64-bit potentials, sums of at
+ * most n weights below 2^41 of which the search adds three, stay under 2^61 --:
+ * such a cell is not walked, nothing else is computed in its place.
+ * REDUCE.  taoamd_track_clear_reduce reads gt_clear (tp, idsw, frag, mt / pt /
+ * ml), match, sw, the frames' visibility and the store (motp_sum and the windows'
+ * q: the q of the list entry whose row is the match) and zeroes / fills
+ * cat_counts and vis_counts.  n_vis = 0 with vis_rng, gt_frame_vis and vis_counts
+ * NULL is allowed.  Integer adds only.
+ * Every output is zeroed / filled by its call; every loop has a bound known at
+ * entry; nothing spins.  TAOAMD_ERR_ARG: frame_thr outside (0, 1] (a NaN
+ * included), n_vis outside [0, 8], windows without visibilities, a size below 0
+ * or beyond int32, n_cat <= 0, a missing table; TAOAMD_ERR_WORKSPACE: fewer bytes
+ * than the size reported.  Both are answered before the first device call and
+ * leave every output untouched.  Rows, frames and candidates named by the
+ * tables that lie outside them are skipped, never dereferenced. */
+#define TAOAMD_TRACK_CLEAR_BONUS 1000       /* times 2^30: the weight of continuity */
+#define TAOAMD_TRACK_CLEAR_NMAX 262144      /* 2^18: the smaller side of a cell, at most */
+size_t taoamd_track_clear_workspace(int64_t n_dt, int64_t n_gt, int64_t n_gt_frames);
+int taoamd_track_clear_count(int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_dt_frames,
+                             int64_t n_gt_frames, double frame_thr, const int32_t *cell_dt_off,
+                             const int32_t *cell_gt_off, const uint8_t *gt_flags,
+                             const uint8_t *dt_keep, const int32_t *dt_frame_off,
+                             const int32_t *dt_frame_pos, const double *dt_frame_box,
+                             const int32_t *gt_frame_off, const int32_t *gt_frame_pos,
+                             const double *gt_frame_box, int64_t *cand_off, uint8_t *step,
+                             void *workspace, size_t workspace_bytes, void *stream);
+int taoamd_track_clear_fill(int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_dt_frames,
+                            int64_t n_gt_frames, double frame_thr, const int32_t *cell_dt_off,
+                            const int32_t *cell_gt_off, const uint8_t *gt_flags,
+                            const uint8_t *dt_keep, const int32_t *dt_frame_off,
+                            const int32_t *dt_frame_pos, const double *dt_frame_box,
+                            const int32_t *gt_frame_off, const int32_t *gt_frame_pos,
+                            const double *gt_frame_box, const int64_t *cand_off, int64_t n_cand,
+                            int32_t *cand_row, int32_t *cand_q, double *cand_iou,
+                            void *workspace, size_t workspace_bytes, void *stream);
+int taoamd_track_clear_walk(int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_gt_frames,
+                            int64_t n_cand, const int32_t *cell_dt_off,
+                            const int32_t *cell_gt_off, const uint8_t *gt_flags,
+                            const int32_t *gt_frame_off, const int32_t *gt_frame_pos,
+                            const int64_t *cand_off, const int32_t *cand_row,
+                            const int32_t *cand_q, const double *cand_iou, const uint8_t *step,
+                            int32_t *match, double *match_iou, uint8_t *sw, int32_t *gt_clear,
+                            int32_t *status, void *workspace, size_t workspace_bytes,
+                            void *stream);
+int taoamd_track_clear_reduce(int64_t n_dt, int64_t n_gt, int64_t n_gt_frames, int64_t n_cand,
+                              int32_t n_cat, int32_t n_vis, const int32_t *gt_cat,
+                              const uint8_t *gt_flags, const int32_t *gt_frame_off,
+                              const double *gt_frame_vis, const double *vis_rng,
+                              const int64_t *cand_off, const int32_t *cand_row,
+                              const int32_t *cand_q, const int32_t *match, const uint8_t *sw,
+                              const int32_t *gt_clear, int64_t *cat_counts,
+                              int64_t *vis_counts, void *workspace, size_t workspace_bytes,
+                              void *stream);
+
 /* ---- multi-GPU result exchange (category-partitioned evaluation) -------------------
  * No reference counterpart (the reference is single-process); these carry the
  * tables of taoamd_accumulate_compact between ranks and end in the layout of

@@ -128,6 +128,13 @@ IDENT_CAT_COLUMNS = ("gt_tracks", "gt_frames", "dt_tracks", "dt_frames", "idtp",
 HOTA_ONE = _define("HOTA_ONE")
 TRACK_HOTA_ALPHAS = _define("TRACK_HOTA_ALPHAS")
 HOTA_RATIOS = ("hota", "deta", "assa", "detre", "detpr", "assre", "asspr", "loca")
+TRACK_CLEAR_BONUS = _define("TRACK_CLEAR_BONUS")
+TRACK_CLEAR_NMAX = _define("TRACK_CLEAR_NMAX")
+CLEAR_TRACK_COLUMNS = ("present", "matched", "idsw", "started")
+CLEAR_CAT_COLUMNS = ("tp", "idsw", "frag", "mt", "pt", "ml", "motp_sum")
+CLEAR_VIS_COLUMNS = ("frames", "matched", "idsw", "q_sum")
+CLEAR_RATIOS = ("mota", "motp", "moda", "smota", "clr_re", "clr_pr", "clr_f1", "mtr", "ptr",
+                "mlr")
 
 
 # ---- the two libraries

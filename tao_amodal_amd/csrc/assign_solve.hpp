@@ -1,9 +1,10 @@
 // The wavefront assignment solver of the track analyses: a maximum-weight
 // bipartite assignment by shortest augmenting paths (Hungarian in the Jonker-
 // Volgenant form, on cost = -weight), one wavefront a problem.  The identity
-// (track_identity.hip: a cell's tracks, weight share * (n + 1) + (share > 0)) and
-// HOTA (track_hota.hip: a frame's boxes, weight w) share it; the weight is a
-// functor, computed on the fly, so no matrix is stored.
+// (track_identity.hip: a cell's tracks, weight share * (n + 1) + (share > 0)),
+// HOTA (track_hota.hip: a frame's boxes, weight w) and CLEAR (track_clear.hip: a
+// step's stored candidates, weight q + the bonus of continuity) share it; the
+// weight is a functor, computed on the fly, so no matrix is stored.
 //
 // A row a time; a step scans the free columns, lanes striding them (ceil(m / 64)
 // a lane), the minimum (value, column) by a wavefront reduction -- the lowest

@@ -11,7 +11,7 @@ OBJ=../../build/obj
 mkdir -p $OBJ
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -Wall -Wno-unused-result"
 pids=()
-for f in api iou_match track_iou flatten sort accumulate score_at_recall error_types error_impact confusion track_error_types track_association track_occlusion track_identity track_hota exchange rle_iou track_mask_iou json_ingest; do
+for f in api iou_match track_iou flatten sort accumulate score_at_recall error_types error_impact confusion track_error_types track_association track_occlusion track_identity track_hota track_clear exchange rle_iou track_mask_iou json_ingest; do
     extra=""
     # sort.hip: the register bitonic networks are unrolled in full (up to 66
     # layers x 32 registers), beyond the default size limit of #pragma unroll
@@ -21,7 +21,7 @@ for f in api iou_match track_iou flatten sort accumulate score_at_recall error_t
 done
 for p in "${pids[@]}"; do wait $p; done
 $HIPCC --offload-arch=gfx950 -fPIC -shared $OBJ/api.o $OBJ/iou_match.o $OBJ/track_iou.o $OBJ/flatten.o \
-    $OBJ/sort.o $OBJ/accumulate.o $OBJ/score_at_recall.o $OBJ/error_types.o $OBJ/error_impact.o $OBJ/confusion.o $OBJ/track_error_types.o $OBJ/track_association.o $OBJ/track_occlusion.o $OBJ/track_identity.o $OBJ/track_hota.o $OBJ/exchange.o $OBJ/rle_iou.o $OBJ/track_mask_iou.o $OBJ/json_ingest.o -o $OUT
+    $OBJ/sort.o $OBJ/accumulate.o $OBJ/score_at_recall.o $OBJ/error_types.o $OBJ/error_impact.o $OBJ/confusion.o $OBJ/track_error_types.o $OBJ/track_association.o $OBJ/track_occlusion.o $OBJ/track_identity.o $OBJ/track_hota.o $OBJ/track_clear.o $OBJ/exchange.o $OBJ/rle_iou.o $OBJ/track_mask_iou.o $OBJ/json_ingest.o -o $OUT
 echo "built $(realpath $OUT)"
 # host-only: columnar JSON ingest + writer, run-length masks (no GPU code)
 g++ -O3 -std=c++17 -fPIC -shared -fopenmp -Wall -ffp-contract=off ingest.cpp rle.cpp jsonwrite.cpp -o ../libtao_amodal_ingest.so

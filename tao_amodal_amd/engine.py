@@ -595,6 +595,7 @@ class Workspace:
         self.ident_ws = self.ident_share = self.ident_cat_counts = None
         self.ident_frame_thr = None       # the frame_thr ws.ident_dt holds the kept tracks of
         self.hota_ws = self.hota_mc = self.hota_lc = None
+        self.clear_ws = self.clear_cand = self.clear_vis_counts = None
         self.occ_n = None                # episodes of the last stage_track_occlusion that read them
         self.pairs_counted = False        # stage_track_iou counted the pairs' common frames
 
@@ -1574,6 +1575,94 @@ def stage_track_hota(dp, ws, alphas, frame_thr):
     if status:
         raise _lib.TaoAmdError("taoamd_track_hota_match: status %d (a search ran out of its "
                                "loop bound)" % status)
+
+
+def stage_track_clear(dp, ws, frame_thr, vis_rng):
+    """CLEAR MOT's integer tables from a one-to-one assignment per step that
+    depends on the step before (taoamd_track_clear_count, _fill, _walk, _reduce;
+    the definition is in include/tao_amodal_hip.h): ws.clear_cat_counts
+    int64[n_cat, 7] (motp_sum in fixed point, _lib.HOTA_ONE), ws.clear_vis_counts
+    int64[n_vis, n_cat, 4] (None without windows), ws.clear_gt int32[n_gt, 4],
+    ws.clear_match int32[n_gt_frames] (the in-cell index of the frame's detection
+    track or -1), ws.clear_match_iou and ws.clear_sw uint8[n_gt_frames], at the
+    per-frame threshold `frame_thr` in (0, 1] and the closed visibility windows
+    `vis_rng` (up to 8 {lo, hi} pairs; they need set_frame_visibility).  The
+    detection tracks that take part are the identity's kept ones at `frame_thr`:
+    stage_track_identity runs first unless the workspace holds it for that
+    threshold (ws.ident_frame_thr).  On request only.  The number of candidates is
+    read between count and fill, the status word at the end: two synchronisations
+    of the current stream; a non-zero status raises.  Buffers are allocated on the
+    first call and kept with the workspace: 22 bytes per ground-truth frame, 16
+    per candidate (regrown where a call finds more), 16 per ground-truth track, 1
+    per detection track, and a workspace of 144 bytes per detection track, 132 per
+    ground-truth track and 8 per ground-truth frame."""
+    sizes, cells, frames = _track_tables(dp, "CLEAR is")
+    lib, t, dev, s = _lib.load(), dp.t, dp.device, _stream()
+    vis_rng = np.ascontiguousarray(vis_rng if vis_rng is not None else [],
+                                   dtype=np.float64).reshape(-1, 2)
+    n_vis = len(vis_rng)
+    if n_vis > _lib.TRACK_ASSOCIATION_VIS:
+        raise _lib.TaoAmdError("%d visibility windows; the kernels take up to %d"
+                               % (n_vis, _lib.TRACK_ASSOCIATION_VIS))
+    if n_vis and t.get("gt_frame_vis") is None:
+        raise _lib.TaoAmdError("visibility windows need the frames' visibility "
+                               "(engine.set_frame_visibility)")
+    frame_thr = float(frame_thr)
+    if ws.ident_ws is None or ws.ident_frame_thr != frame_thr:
+        stage_track_identity(dp, ws, frame_thr)
+    n_dt, n_gt, n_cells, _, n_df, n_gf = sizes
+    if ws.clear_ws is None:
+        ws.clear_bytes = lib.taoamd_track_clear_workspace(n_dt, n_gt, n_gf)
+        ws.clear_ws = torch.empty(max(int(ws.clear_bytes), 256), dtype=torch.uint8, device=dev)
+        ws.clear_keep = torch.empty(max(n_dt, 1), dtype=torch.uint8, device=dev)
+        ws.clear_off = torch.empty(n_gf + 1, dtype=torch.int64, device=dev)
+        ws.clear_step = torch.empty(max(n_gf, 1), dtype=torch.uint8, device=dev)
+        ws.clear_match = torch.empty(max(n_gf, 1), dtype=torch.int32, device=dev)
+        ws.clear_match_iou = torch.empty(max(n_gf, 1), dtype=torch.float64, device=dev)
+        ws.clear_sw = torch.empty(max(n_gf, 1), dtype=torch.uint8, device=dev)
+        ws.clear_gt = torch.empty((max(n_gt, 1), len(_lib.CLEAR_TRACK_COLUMNS)),
+                                  dtype=torch.int32, device=dev)
+        ws.clear_cat_counts = torch.empty((dp.n_cat, len(_lib.CLEAR_CAT_COLUMNS)),
+                                          dtype=torch.int64, device=dev)
+        ws.clear_status = torch.empty(1, dtype=torch.int32, device=dev)
+    if n_vis and (ws.clear_vis_counts is None or ws.clear_vis_counts.shape[0] != n_vis):
+        ws.clear_vis_counts = torch.empty((n_vis, dp.n_cat, len(_lib.CLEAR_VIS_COLUMNS)),
+                                          dtype=torch.int64, device=dev)
+    if not n_vis:
+        ws.clear_vis_counts = None
+    ws.clear_keep.copy_(ws.ident_dt[:, 1])
+    tables = (n_dt, n_gt, n_cells, n_df, n_gf, frame_thr, cells[0], cells[1],
+              _ptr(t["gt_flags"]), _ptr(ws.clear_keep), *frames)
+    _lib.check(lib.taoamd_track_clear_count(
+        *tables, _ptr(ws.clear_off), _ptr(ws.clear_step), _ptr(ws.clear_ws), ws.clear_bytes, s),
+        "taoamd_track_clear_count")
+    ws.clear_n = int(ws.clear_off[-1].item())       # (synchronises)
+    if ws.clear_cand is None or ws.clear_cand[0].numel() < ws.clear_n:
+        ws.clear_cand = (torch.empty(max(ws.clear_n, 1), dtype=torch.int32, device=dev),
+                         torch.empty(max(ws.clear_n, 1), dtype=torch.int32, device=dev),
+                         torch.empty(max(ws.clear_n, 1), dtype=torch.float64, device=dev))
+    row, q, iou = ws.clear_cand
+    _lib.check(lib.taoamd_track_clear_fill(
+        *tables, _ptr(ws.clear_off), ws.clear_n, _ptr(row), _ptr(q), _ptr(iou), _ptr(ws.clear_ws),
+        ws.clear_bytes, s), "taoamd_track_clear_fill")
+    store = (_ptr(ws.clear_off), _ptr(row), _ptr(q))
+    _lib.check(lib.taoamd_track_clear_walk(
+        n_dt, n_gt, n_cells, n_gf, ws.clear_n, cells[0], cells[1], _ptr(t["gt_flags"]),
+        frames[3], frames[4], *store, _ptr(iou), _ptr(ws.clear_step), _ptr(ws.clear_match),
+        _ptr(ws.clear_match_iou), _ptr(ws.clear_sw), _ptr(ws.clear_gt), _ptr(ws.clear_status),
+        _ptr(ws.clear_ws), ws.clear_bytes, s), "taoamd_track_clear_walk")
+    rng_t = torch.from_numpy(vis_rng).to(dev) if n_vis else None
+    _lib.check(lib.taoamd_track_clear_reduce(
+        n_dt, n_gt, n_gf, ws.clear_n, dp.n_cat, n_vis, _ptr(t["gt_cat"]), _ptr(t["gt_flags"]),
+        frames[3], _ptr(t["gt_frame_vis"]) if n_vis else None, _ptr(rng_t), *store,
+        _ptr(ws.clear_match), _ptr(ws.clear_sw), _ptr(ws.clear_gt), _ptr(ws.clear_cat_counts),
+        _ptr(ws.clear_vis_counts), _ptr(ws.clear_ws), ws.clear_bytes, s),
+        "taoamd_track_clear_reduce")
+    status = int(ws.clear_status.item())            # (synchronises; the windows were read)
+    if status:
+        raise _lib.TaoAmdError("taoamd_track_clear_walk: status %d (%s)" % (
+            status, "a search ran out of its loop bound" if status == 1 else
+            "a cell's smaller side exceeds %d" % _lib.TRACK_CLEAR_NMAX))
 
 
 def stage_track_iou_guarded(dp, ws):

@@ -467,6 +467,30 @@ class GpuRun:
                     "match": ws.hota_match[:n_gf].cpu().numpy(),
                     "match_iou": ws.hota_match_iou[:n_gf].cpu().numpy()}
 
+    def clear_table(self, frame_thr, vis_rng, ann_vis):
+        """CLEAR MOT's integer tables (engine.stage_track_clear; the definition is
+        in include/tao_amodal_hip.h) at the per-frame threshold `frame_thr` and the
+        visibility windows `vis_rng`, over the tracks identity_table(frame_thr)
+        keeps: dict(ident_counts int64[K, 6] of the identity, cat_counts int64[K,
+        7], vis_counts int64[n_vis, K, 4], gt_clear int32[n_gt, 4], match
+        int32[n_gt_frames] as in-cell indices, match_iou, sw uint8).  `ann_vis` as
+        for association_table(); refuses what it refuses."""
+        self._followers_at("clear()", ann_vis)
+        dp, ws = self.dp, self.ws
+        with timed("kernels"):
+            self.engine.stage_track_clear(dp, ws, frame_thr, vis_rng)
+            self.torch.cuda.synchronize(self.device)
+        with timed("download"):
+            n_gf = int(dp.t["gt_frame_pos"].numel())
+            return {"ident_counts": ws.ident_cat_counts.cpu().numpy(),
+                    "cat_counts": ws.clear_cat_counts.cpu().numpy(),
+                    "vis_counts": ws.clear_vis_counts.cpu().numpy() if len(vis_rng) else
+                    np.zeros((0, dp.n_cat, 4), dtype=np.int64),
+                    "gt_clear": ws.clear_gt[:dp.n_gt].cpu().numpy(),
+                    "match": ws.clear_match[:n_gf].cpu().numpy(),
+                    "match_iou": ws.clear_match_iou[:n_gf].cpu().numpy(),
+                    "sw": ws.clear_sw[:n_gf].cpu().numpy()}
+
     def pointer_tables(self):
         """What eval['dt_pointers'] is read from: the detections' ids and
         (matched, ignored) words in the sweep's order (category-major, stable

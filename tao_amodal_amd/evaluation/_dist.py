@@ -441,6 +441,9 @@ class DistRun:
     def hota_table(self, alphas, frame_thr):
         raise NotImplementedError("hota() in a multi-GPU run")
 
+    def clear_table(self, frame_thr, vis_rng, ann_vis):
+        raise NotImplementedError("clear() in a multi-GPU run")
+
     def pointer_tables(self):
         if self._pointers is None:
             raise NotImplementedError(

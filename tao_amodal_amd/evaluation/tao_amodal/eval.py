@@ -120,6 +120,7 @@ class TaoEval:
         self._error_types, self._error_impact, self._confusion = {}, {}, {}
         self._association, self._occlusions, self._identity = {}, {}, {}
         self._hota = {}
+        self._clear = {}
 
     # ------------------------------------------------------------ stages
     def evaluate(self, show_progress=False):
@@ -566,14 +567,67 @@ class TaoEval:
         frame (the ground-truth track id, the image id, the matched detection
         track's id or -1, its box IoU or 0).
         Not available: iou_type="segm", use_cats = 0, multi-GPU runs, the
-        command line; a per-visibility breakdown of DetRe is not computed (the
-        per-frame output carries what it needs)."""
+        command line; recall per visibility window is clear()'s "vis_re" (the
+        per-frame output here carries what a breakdown of DetRe needs)."""
         return followers.hota(self, alphas, frame_thr, per_frame)
 
     def hota_lines(self, alphas=None, frame_thr=0.5):
         """hota() as a small text table in per cent, in TrackEval's column order:
         the total and the class mean.  Returned, not printed."""
         return followers.hota_lines(self.hota(alphas, frame_thr))
+
+    def clear(self, frame_thr=0.5, vis_rng=None, vis_lbl=None, per_track=False,
+              per_frame=False):
+        """CLEAR MOT (Bernardin & Stiefelhagen, 2008; TrackEval's CLEAR): MOTA,
+        MOTP, ID switches, fragmentations, mostly tracked / mostly lost -- the
+        third of the measures printed beside Track-AP, with IDF1 (identity())
+        and HOTA (hota()).  A ONE-TO-ONE assignment in every frame, as HOTA's,
+        but each frame's weights depend on the frame before: the pair matched a
+        step ago gets a bonus of 1000 over its box IoU, and an ID switch is
+        scored against the ground truth's last match however long ago.  The
+        frames of a (video, category) are a serial chain, walked on the device
+        on request (csrc/track_clear.hip).  Callable after evaluate(), cached
+        per (frame_thr, windows).
+
+        Rows are the tracks that survived the max_dets cut and the federated
+        filter.  The tracks that take part are identity(frame_thr)'s, as for
+        hota(): MOTA, IDF1 and HOTA are computed over the same tracks and the
+        same frame counts.  A pair is a candidate where its box IoU >=
+        `frame_thr`; positions at which the cell has no ground-truth or no
+        detection frame change no state.  `vis_rng`: up to 8 closed visibility
+        windows (ValueError otherwise), by default association()'s, with
+        `vis_lbl` their labels: how much of the recall and how many of the ID
+        switches fall on occluded frames.  Every sum is an integer (MOTP's in
+        fixed point, 2^30): the tables are exact and the same from run to run.
+        The exact rules are in include/tao_amodal_hip.h, section "track-level
+        CLEAR"; what differs from TrackEval is in DESIGN.md section 8.
+
+        Returns {"frame_thr", "columns", "cat_counts": int64[K, 11] = gt_tracks,
+        gt_frames, dt_tracks, dt_frames (identity()'s four), tp, idsw, frag, mt,
+        pt, ml, motp_sum (times 2^30) with the category axis in the order of
+        params.cat_ids, "fn", "fp": int64[K], float64[K] "mota" = (tp - fp - idsw)
+        / max(1, tp + fn), "motp" = motp_sum / 2^30 / max(1, tp), "moda", "smota",
+        "clr_re", "clr_pr", "clr_f1", "mtr", "ptr", "mlr" (over max(1,
+        gt_tracks)), NaN where the category has neither ground-truth nor
+        detection frames, "vis_counts": int64[n_vis, K, 4] = frames, matched,
+        idsw, q_sum, "vis_rng", "vis_lbl", "vis_re": float64[n_vis, K] = matched /
+        frames (NaN without frames), "total": the sums over the categories and
+        the ratios of the sums, "mean": the ratios averaged over the categories
+        that have frames}; with per_track=True "tracks": (the ground-truth track
+        ids, int64[n_gt, 5] = present, matched, idsw, frag, 0 / 1 / 2 for mostly
+        lost / partly / mostly tracked; zeros for an ignored track); with
+        per_frame=True "frames": per ground-truth frame (the ground-truth track
+        id, the image id, the matched detection track's id or -1, its box IoU
+        or 0, the switch flag).
+        Not available: iou_type="segm", use_cats = 0, multi-GPU runs, the
+        command line; FP per frame (no table holds a video's frame count)."""
+        return followers.clear(self, frame_thr, vis_rng, vis_lbl, per_track, per_frame)
+
+    def clear_lines(self, frame_thr=0.5, vis_rng=None, vis_lbl=None):
+        """clear() as a small text table in per cent, in TrackEval's CLEAR column
+        order: the total and the class mean, then a line per visibility window
+        with CLR_Re and IDSW.  Returned, not printed."""
+        return followers.clear_lines(self.clear(frame_thr, vis_rng, vis_lbl))
 
     def impact_lines(self, iou_thr=0.5, bg_thr=0.1):
         """error_impact() as a small text table: a line per (area, time) range,

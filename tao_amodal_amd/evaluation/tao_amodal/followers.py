@@ -1,6 +1,7 @@
 """The analyses of TaoEval that read the track tables alone -- association(),
-occlusions(), identity(), hota() -- and their text tables: the class layer over
-GpuRun.association_table / occlusion_table / identity_table / hota_table.  The track
+occlusions(), identity(), hota(), clear() -- and their text tables: the class layer
+over GpuRun.association_table / occlusion_table / identity_table / hota_table /
+clear_table.  The track
 level's alone; the methods of TaoEval carry the documentation and call in here
 with the evaluator `ev`."""
 import numpy as np
@@ -62,8 +63,8 @@ def _pct(n, d=1.0, width=0):
     return text.rjust(width)
 
 
-def association(ev, frame_thr, vis_rng, vis_lbl, per_track, per_frame):
-    frame_thr = _frame_thr(ev, frame_thr)
+def _windows(ev, vis_rng, vis_lbl):
+    """(windows float64[n, 2], their labels): association()'s defaults for None."""
     if vis_rng is None:
         from ..lvis_amodal.eval import Params as LvisParams
         lp = LvisParams(ev.params.iou_type)
@@ -78,6 +79,12 @@ def association(ev, frame_thr, vis_rng, vis_lbl, per_track, per_frame):
     vis_lbl = [str(x) for x in vis_lbl]
     if len(vis_lbl) != len(rng):
         raise ValueError("vis_lbl: {} labels for {} windows".format(len(vis_lbl), len(rng)))
+    return rng, vis_lbl
+
+
+def association(ev, frame_thr, vis_rng, vis_lbl, per_track, per_frame):
+    frame_thr = _frame_thr(ev, frame_thr)
+    rng, vis_lbl = _windows(ev, vis_rng, vis_lbl)
 
     def make():
         from ..._lib import ASSOC_CAT_COLUMNS, ASSOC_TRACK_COLUMNS, ASSOC_VIS_COLUMNS
@@ -301,6 +308,99 @@ def hota_lines(e):
              " " + "".ljust(10) + "".join(n.rjust(12) for n in names)]
     for label, row in (("total", e["total"]), ("class mean", e["mean"])):
         lines.append(" " + label.ljust(10) + "".join(_pct(row[n], width=12) for n in names))
+    return lines
+
+
+CLEAR_SCALARS = ("MOTA", "MOTP", "MODA", "CLR_Re", "CLR_Pr", "MTR", "PTR", "MLR", "sMOTA",
+                 "CLR_F1")
+CLEAR_INTEGERS = ("CLR_TP", "CLR_FN", "CLR_FP", "IDSW", "MT", "PT", "ML", "Frag")
+
+
+def clear_ratios(cat_counts):
+    """The ten ratios of clear()'s int64[..., 11] table as float64 in the shape of
+    its leading axes, with TrackEval's max(1, .) denominators."""
+    from ..._lib import HOTA_ONE
+    cc = np.asarray(cat_counts, dtype=np.int64)
+    gt_tracks, gt_frames, dt_frames = cc[..., 0], cc[..., 1], cc[..., 3]
+    tp, idsw = cc[..., 4], cc[..., 5]
+    motp = cc[..., 10].astype(np.float64) / HOTA_ONE
+    fn, fp = gt_frames - tp, dt_frames - tp
+    g = np.maximum(1, tp + fn).astype(np.float64)
+    tr = np.maximum(1, gt_tracks).astype(np.float64)
+    return {"mota": (tp - fp - idsw) / g, "motp": motp / np.maximum(1, tp),
+            "moda": (tp - fp) / g, "smota": (motp - fp - idsw) / g, "clr_re": tp / g,
+            "clr_pr": tp / np.maximum(1, tp + fp).astype(np.float64),
+            "clr_f1": tp / np.maximum(1, 2 * tp + fn + fp).astype(np.float64) * 2,
+            "mtr": cc[..., 7] / tr, "ptr": cc[..., 8] / tr, "mlr": cc[..., 9] / tr}
+
+
+def clear(ev, frame_thr, vis_rng, vis_lbl, per_track, per_frame):
+    frame_thr = _frame_thr(ev, frame_thr)
+    rng, vis_lbl = _windows(ev, vis_rng, vis_lbl)
+
+    def make():
+        from ..._lib import (CLEAR_CAT_COLUMNS, CLEAR_RATIOS, CLEAR_VIS_COLUMNS,
+                             IDENT_CAT_COLUMNS)
+        t = ev._run.clear_table(frame_thr, rng, ev._gt_columns.ann_vis)
+        flat = ev._run.flat
+        cc = np.concatenate([_params_cats(ev, t["ident_counts"], 0)[:, :4],
+                             _params_cats(ev, t["cat_counts"], 0)], axis=1)
+        vis = _params_cats(ev, t["vis_counts"], 1)
+        columns = list(IDENT_CAT_COLUMNS[:4]) + list(CLEAR_CAT_COLUMNS)
+        out = {"frame_thr": frame_thr, "cat_counts": cc, "fn": cc[:, 1] - cc[:, 4],
+               "fp": cc[:, 3] - cc[:, 4], "vis_counts": vis, "vis_rng": rng.tolist(),
+               "vis_lbl": list(vis_lbl),
+               "columns": {"cat_counts": columns, "vis_counts": list(CLEAR_VIS_COLUMNS),
+                           "tracks": ["present", "matched", "idsw", "frag", "tracked"]}}
+        r = clear_ratios(cc)
+        has = (cc[:, 1] + cc[:, 3]) > 0
+        for k in CLEAR_RATIOS:
+            out[k] = np.where(has, r[k], np.nan)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["vis_re"] = np.where(vis[..., 0] > 0, vis[..., 1] / vis[..., 0].astype(np.float64),
+                                     np.nan)
+        tot = cc.sum(0)
+        total = dict(zip(columns, (int(x) for x in tot)))
+        total.update(fn=int(tot[1] - tot[4]), fp=int(tot[3] - tot[4]))
+        total.update({k: float(v) for k, v in clear_ratios(tot).items()})
+        total["vis_counts"] = vis.sum(1)
+        out["total"] = total
+        out["mean"] = {k: float(r[k][has].mean()) if has.any() else float("nan")
+                       for k in CLEAR_RATIOS}
+        gc = t["gt_clear"].astype(np.int64)
+        mt = 5 * gc[:, 1] > 4 * gc[:, 0]
+        pt = ~mt & (5 * gc[:, 1] >= gc[:, 0])
+        live = (np.asarray(flat.gt_flags)[:len(gc)] & 1) == 0
+        tracks = np.stack([gc[:, 0], gc[:, 1], gc[:, 2], np.maximum(gc[:, 3] - 1, 0),
+                           np.where(live, 2 * mt + pt, 0)], axis=1)
+        out["tracks"] = (np.asarray(flat.gt_id, dtype=np.int64), tracks)
+        foff, cell, img = _gt_frame_tables(flat)
+        g_of = np.repeat(np.arange(len(foff) - 1), np.diff(foff))
+        out["frames"] = (np.asarray(flat.gt_id, dtype=np.int64)[g_of], img,
+                         _follower_ids(flat, cell, t["match"]), t["match_iou"], t["sw"])
+        return out
+    return _cached(ev._clear, (frame_thr, rng.tobytes(), tuple(vis_lbl)), make,
+                   (("tracks", per_track), ("frames", per_frame)))
+
+
+def clear_lines(e):
+    """TaoEval.clear()'s result `e` as a small text table in TrackEval's CLEAR
+    column order: the ratios in per cent and the integers for the total, the
+    ratios for the class mean, then CLR_Re and IDSW per visibility window."""
+    tot = e["total"]
+    ints = {"CLR_TP": tot["tp"], "CLR_FN": tot["fn"], "CLR_FP": tot["fp"], "IDSW": tot["idsw"],
+            "MT": tot["mt"], "PT": tot["pt"], "ML": tot["ml"], "Frag": tot["frag"]}
+    lines = [" track CLEAR @[ frame IoU={:0.2f} ]".format(e["frame_thr"]),
+             " " + "".ljust(10) + "".join(n.rjust(9) for n in CLEAR_SCALARS + CLEAR_INTEGERS),
+             " " + "total".ljust(10)
+             + "".join(_pct(tot[n.lower()], width=9) for n in CLEAR_SCALARS)
+             + "".join("{:>9d}".format(int(ints[n])) for n in CLEAR_INTEGERS),
+             " " + "class mean".ljust(10)
+             + "".join(_pct(e["mean"][n.lower()], width=9) for n in CLEAR_SCALARS)]
+    w = max([len(x) for x in e["vis_lbl"]] + [10])
+    for name, v in zip(e["vis_lbl"], tot["vis_counts"]):
+        lines.append(" " + name.ljust(w) + "{:>11d}".format(int(v[0]))
+                     + _pct(v[1], v[0], 9) + "{:>9d}".format(int(v[2])))
     return lines
 
 

@@ -5,7 +5,7 @@ events:
 
     python tools/time_error_types.py [--level image|track] [--config 3s] [--reps 20] [--warmup 3]
                                      [--impact] [--association] [--occlusions] [--identity]
-                                     [--hota] [--confusion]
+                                     [--hota] [--clear] [--confusion]
 
 Times, on the image level's tables of that configuration, each alone on an idle
 stream: the fused match as a benchmark step runs it (the yardstick), the
@@ -34,7 +34,13 @@ the same process.  --level track --hota times HOTA: taoamd_track_hota_align,
 taoamd_track_hota_match and taoamd_track_hota_reduce each alone between HIP
 events and the whole stage (engine.stage_track_hota) beside the identity stage
 in the same process, and reports the sizes of mc and lc and the share of frame
-groups with more than one ground truth.  --confusion
+groups with more than one ground truth.  --level track --clear times CLEAR MOT:
+the candidates (taoamd_track_clear_count and _fill), taoamd_track_clear_walk and
+taoamd_track_clear_reduce each alone between HIP events and the whole stage
+(engine.stage_track_clear) beside the identity and the HOTA stage in the same
+process, and reports the number of candidates, the share of steps with more than
+one ground truth and the sizes of the candidate store and the workspace.
+--confusion
 (both levels) adds the confusion table: the level's links pass,
 taoamd_confusion_count and taoamd_confusion_fill, each alone between HIP events
 in the same process, the whole stage with its read of the entry count, the
@@ -127,6 +133,8 @@ def track_level(a, gt, dt, dev, V):
         return identity(a, res, dp, ws, timed)
     if a.hota:
         return hota(a, res, dp, ws, timed)
+    if a.clear:
+        return clear(a, res, gt, fl, dp, ws, timed)
     res["match_fused"] = timed(lambda: engine.stage_match(dp, ws))
     # the first call builds the per-video lists and runs the match for match_gt
     engine.stage_track_error_types(dp, ws, 0, a.bg_thr)
@@ -506,6 +514,114 @@ def hota(a, res, dp, ws, timed):
     print(json.dumps(res))
 
 
+def clear(a, res, gt, fl, dp, ws, timed):
+    """--level track --clear: CLEAR MOT (engine.stage_track_clear) over the
+    identity's kept tracks at frame_thr 0.5 with the association's five windows:
+    the candidates (count and fill), the walk and the reduction each alone between
+    HIP events, the whole stage (which reads the candidate count and the status
+    word), the identity and the HOTA stage in the same process, the kernels, the
+    number of candidates, the share of steps with more than one ground truth and
+    the sizes of the candidate store and the workspace."""
+    import torch
+    from tao_amodal_amd import _lib, engine
+    lib = _lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    thr = 0.5
+    windows = np.array([[0, 1.0], [0, 0.1], [0.1, 0.8], [0.8, 1.0], [0, 0.8]])
+    alphas = np.ascontiguousarray(np.arange(0.05, 0.99, 0.05) - np.finfo(float).eps)
+    engine.set_frame_visibility(dp, np.asarray(gt.ann_vis)[fl.gt_frame_box.index])
+    # the first calls allocate the buffers of the three stages
+    engine.stage_track_hota(dp, ws, alphas, thr)
+    engine.stage_track_clear(dp, ws, thr, windows)
+    torch.cuda.synchronize()
+    t = dp.t
+    n_df, n_gf = int(t["dt_frame_pos"].numel()), int(t["gt_frame_pos"].numel())
+    n_cand = int(ws.clear_n)
+    row, q, iou = ws.clear_cand
+    rng_t = torch.from_numpy(windows).to(dp.device)
+    tables = (dp.n_dt, dp.n_gt, dp.n_cells, n_df, n_gf, thr, t["cell_dt_off"].data_ptr(),
+              t["cell_gt_off"].data_ptr(), t["gt_flags"].data_ptr(), ws.clear_keep.data_ptr(),
+              t["dt_frame_off"].data_ptr(), t["dt_frame_pos"].data_ptr(),
+              t["dt_frame_box"].data_ptr(), t["gt_frame_off"].data_ptr(),
+              t["gt_frame_pos"].data_ptr(), t["gt_frame_box"].data_ptr())
+    store = (ws.clear_off.data_ptr(), row.data_ptr(), q.data_ptr())
+    work = (ws.clear_ws.data_ptr(), ws.clear_bytes, stream)
+
+    def count():
+        _lib.check(lib.taoamd_track_clear_count(
+            *tables, ws.clear_off.data_ptr(), ws.clear_step.data_ptr(), *work),
+            "taoamd_track_clear_count")
+
+    def fill():
+        _lib.check(lib.taoamd_track_clear_fill(
+            *tables, ws.clear_off.data_ptr(), n_cand, row.data_ptr(), q.data_ptr(),
+            iou.data_ptr(), *work), "taoamd_track_clear_fill")
+
+    def walk():
+        _lib.check(lib.taoamd_track_clear_walk(
+            dp.n_dt, dp.n_gt, dp.n_cells, n_gf, n_cand, t["cell_dt_off"].data_ptr(),
+            t["cell_gt_off"].data_ptr(), t["gt_flags"].data_ptr(), t["gt_frame_off"].data_ptr(),
+            t["gt_frame_pos"].data_ptr(), *store, iou.data_ptr(), ws.clear_step.data_ptr(),
+            ws.clear_match.data_ptr(), ws.clear_match_iou.data_ptr(), ws.clear_sw.data_ptr(),
+            ws.clear_gt.data_ptr(), ws.clear_status.data_ptr(), *work), "taoamd_track_clear_walk")
+
+    def reduce():
+        _lib.check(lib.taoamd_track_clear_reduce(
+            dp.n_dt, dp.n_gt, n_gf, n_cand, dp.n_cat, len(windows), t["gt_cat"].data_ptr(),
+            t["gt_flags"].data_ptr(), t["gt_frame_off"].data_ptr(), t["gt_frame_vis"].data_ptr(),
+            rng_t.data_ptr(), *store, ws.clear_match.data_ptr(), ws.clear_sw.data_ptr(),
+            ws.clear_gt.data_ptr(), ws.clear_cat_counts.data_ptr(),
+            ws.clear_vis_counts.data_ptr(), *work), "taoamd_track_clear_reduce")
+    res["identity_stage"] = timed(lambda: engine.stage_track_identity(dp, ws, thr))
+    res["hota_stage"] = timed(lambda: engine.stage_track_hota(dp, ws, alphas, thr))
+    res["clear_count"] = timed(count)
+    res["clear_fill"] = timed(fill)
+    res["clear_walk"] = timed(walk)
+    res["clear_reduce"] = timed(reduce)
+    res["clear_stage"] = timed(lambda: engine.stage_track_clear(dp, ws, thr, windows))
+    _lib.kernel_timing(True)
+    for _ in range(a.reps):
+        engine.stage_track_hota(dp, ws, alphas, thr)
+        count()
+        fill()
+        walk()
+        reduce()
+    res["kernels_ms"] = {k: round(ms / n, 4) for k, (ms, n) in _lib.kernel_timings().items()}
+    _lib.kernel_timing(False)
+    torch.cuda.synchronize()
+    # what the walk met (on the device, untimed): a step is a (cell, position) with
+    # the step bit; its ground truths are the eligible ones with a frame there
+    foff = t["gt_frame_off"].long()
+    g_of = torch.repeat_interleave(torch.arange(dp.n_gt, device=foff.device), foff[1:] - foff[:-1])
+    g_cnt = (t["cell_gt_off"][1:] - t["cell_gt_off"][:-1]).long()
+    g_cell = torch.repeat_interleave(torch.arange(dp.n_cells, device=foff.device), g_cnt)
+    on = ws.clear_step[:n_gf] != 0
+    top = int(t["gt_frame_pos"].max().item()) + 1 if n_gf else 1
+    key = g_cell[g_of].long() * top + t["gt_frame_pos"].long()
+    _, per_step = torch.unique(key[on], return_counts=True)
+    elig = (t["gt_flags"][:dp.n_gt] & 1) == 0
+    per_cell = torch.zeros(dp.n_cells, dtype=torch.int64, device=foff.device)
+    per_cell.index_add_(0, g_cell, elig.long())
+    n_per = (ws.clear_off[1:] - ws.clear_off[:-1])
+    res["clear_status"] = int(ws.clear_status.item())
+    res["clear_candidates"] = n_cand
+    res["clear_most_candidates_of_a_frame"] = int(n_per.max().item()) if n_gf else 0
+    res["clear_steps"] = int(per_step.numel())
+    res["clear_steps_with_several_ground_truths"] = int((per_step > 1).sum().item())
+    res["clear_cells_with_one_eligible_ground_truth"] = int((per_cell == 1).sum().item())
+    res["clear_cells_with_several"] = int((per_cell > 1).sum().item())
+    res["clear_store_bytes"] = 8 * (n_gf + 1) + n_gf + 16 * n_cand
+    res["clear_workspace_bytes"] = int(ws.clear_bytes)
+    cc = ws.ident_cat_counts.sum(0).tolist()
+    tot = ws.clear_cat_counts.sum(0).tolist()
+    res["clear_columns"] = list(_lib.CLEAR_CAT_COLUMNS)
+    res["clear_totals"] = {"gt_frames": cc[1], "dt_frames": cc[3], "counts": tot,
+                           "vis_counts": ws.clear_vis_counts.sum(1).tolist()}
+    res["mota"] = round((tot[0] - (cc[3] - tot[0]) - tot[1]) / max(cc[1], 1), 6)
+    res["motp"] = round(tot[6] / _lib.HOTA_ONE / max(tot[0], 1), 6)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--level", choices=("image", "track"), default="image")
@@ -521,6 +637,7 @@ def main():
     ap.add_argument("--occlusions", action="store_true")
     ap.add_argument("--identity", action="store_true")
     ap.add_argument("--hota", action="store_true")
+    ap.add_argument("--clear", action="store_true")
     ap.add_argument("--confusion", action="store_true")
     a = ap.parse_args()
     if a.association and a.level != "track":
@@ -531,6 +648,8 @@ def main():
         ap.error("--identity is the track level's: --level track")
     if a.hota and a.level != "track":
         ap.error("--hota is the track level's: --level track")
+    if a.clear and a.level != "track":
+        ap.error("--clear is the track level's: --level track")
     import torch
     from tao_amodal_amd import _lib, engine, flatten_dev
     from tao_amodal_amd.synth import synth
