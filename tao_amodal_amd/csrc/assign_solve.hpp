@@ -15,8 +15,14 @@
 // The wavefront is the workgroup, so __syncthreads() is the fence between its
 // lanes' stores and loads of the search state, in LDS and in global memory alike;
 // all control flow around it is uniform.
+//
+// Around the solver, what its three users share: where the search state lives
+// (SearchLds in LDS, SearchStore in the workspace), which side becomes the rows
+// (assign_sides) and the walk over the assigned pairs (assign_pairs).  The weight
+// functors and what becomes of a pair are each kernel's own.
 #pragma once
 #include "common.hpp"
+#include "workspace.hpp"
 
 namespace taoamd {
 
@@ -28,6 +34,60 @@ struct Search {
     int32_t *p, *way, *used;
     const int32_t *ridx, *cidx;      // what the weight functor is told of row i / column j
 };
+
+// The state of a cell (a tile) whose sides are at most N, declared __shared__ by
+// the kernel, and two index lists beside it
+template <int N> struct SearchLds {
+    long long u[N], v[N], minv[N];
+    int32_t p[N], way[N], used[N], idx0[N], idx1[N];
+    __device__ __forceinline__ Search search()
+    {
+        return {u, v, minv, p, way, used, nullptr, nullptr};
+    }
+};
+
+// The state of the cells beyond LDS: six workspace arrays of n = n_dt + n_gt
+// entries; cell c owns [base, the next cell's), base = cell_dt_off[c] +
+// cell_gt_off[c], and one wavefront walks it
+struct SearchStore {
+    long long *u, *v, *minv;
+    int32_t *p, *way, *used;
+    void layout(Carve &c, size_t n)
+    {
+        u = c.take<long long>(n);
+        v = c.take<long long>(n);
+        minv = c.take<long long>(n);
+        p = c.take<int32_t>(n);
+        way = c.take<int32_t>(n);
+        used = c.take<int32_t>(n);
+    }
+    __device__ __forceinline__ Search at(int64_t base) const
+    {
+        return {u + base, v + base, minv + base, p + base, way + base, used + base, nullptr,
+                nullptr};
+    }
+};
+
+// The smaller of two sides becomes the rows (n <= m), the FIRST where they are
+// equal.  The solver breaks ties by the lowest column, so that choice is part of
+// the result: HOTA and CLEAR pass the ground truths first.  (The identity takes
+// the detections when equal; its kernel has the choice written out.)
+struct Sides {
+    bool first;                      // the rows are the first side's entries
+    int n, m;
+    const int32_t *rows, *cols;      // the two lists, for Search::ridx and cidx
+};
+__device__ __forceinline__ Sides assign_sides(const int32_t *first, int n_first,
+                                              const int32_t *second, int n_second)
+{
+    Sides r;
+    r.first = n_first <= n_second;
+    r.n = r.first ? n_first : n_second;
+    r.m = r.first ? n_second : n_first;
+    r.rows = r.first ? first : second;
+    r.cols = r.first ? second : first;
+    return r;
+}
 
 // Rows 1 .. n, columns 1 .. m, n <= m; p[j - 1] = the row of column j, 0: free;
 // way[j - 1] = the column before j on the path, 0: the root (the new row).
@@ -111,6 +171,25 @@ __device__ __forceinline__ bool assign_solve(const Weight &weight, const Search 
         __syncthreads();
     }
     return true;
+}
+
+// The assigned pairs of a solved search, a lane a column: take(has, a, b) with
+// the pair's entry of the first and of the second side.  Every lane of the
+// wavefront calls take in every pass (has = false: no pair), so take may hold
+// wavefront operations.
+template <class Take>
+__device__ __forceinline__ void assign_pairs(const Search &s, const Sides &sd, Take take)
+{
+    for (int jb = 0; jb < sd.m; jb += WAVE) {
+        const int j = jb + lane_id();
+        const int i = j < sd.m ? s.p[j] : 0;
+        int64_t r = 0, c = 0;
+        if (i > 0) {
+            r = s.ridx[i - 1];
+            c = s.cidx[j];
+        }
+        take(i > 0, sd.first ? r : c, sd.first ? c : r);
+    }
 }
 
 }  // namespace taoamd

@@ -189,6 +189,17 @@ template <typename T> __device__ __forceinline__ T wave_max(T v)
     return v;
 }
 
+// The sum of v over the lanes up to and including this one
+__device__ __forceinline__ long long wave_prefix(long long v)
+{
+#pragma unroll
+    for (int o = 1; o < WAVE; o <<= 1) {
+        const long long u = __shfl_up(v, o, WAVE);
+        if (lane_id() >= o) v += u;
+    }
+    return v;
+}
+
 // wave_count with amounts instead of ones: base[key * stride + c] += the sum of
 // v[c] over the wavefront's live lanes of that key, one add per (distinct key,
 // column with a non-zero sum), by the key's first lane.  Integer adds: order-free.

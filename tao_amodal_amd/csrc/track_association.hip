@@ -8,10 +8,8 @@
 // at p_k, g's box) where d has a frame at p_k, and best_k(g) = the candidate of
 // the greatest f >= frame_thr, the lowest row among equal values, -1 if none.
 //
-//   frames_build          the frame index (track_frames.hpp, shared with the
-//                         identity's share pass): a detection track's frame range
-//                         and positions, the cell of a ground-truth row, the track
-//                         of a ground-truth frame
+//   track_index           the frame index (track_frames.hpp); the entry point's
+//                         common part is track_tables.hpp's
 //   assoc_pair_kernel     THE HOT ONE.  lane = ground-truth frame, the whole table
 //                         as one flat list: a lane holds its frame's box and
 //                         position in registers and walks the cell's detection
@@ -50,9 +48,7 @@
 //   assoc_pair_kernel 36 VGPRs, 34 SGPRs, 8 waves/SIMD, no scratch, no LDS.
 // box_iou is common.hpp's, compiled with -ffp-contract=off like every other use:
 // the bits of taoamd_bb_iou.  Everything else is an integer.
-#include "common.hpp"
-#include "track_frames.hpp"
-#include "workspace.hpp"
+#include "track_tables.hpp"
 
 using namespace taoamd;
 
@@ -64,6 +60,13 @@ using namespace taoamd;
 
 static_assert(TA_TILE % WAVE == 0, "whole wavefronts");
 
+// The kernels' argument block is this file's own, the common fields where they
+// were (track_fill sets them): over { TrackTables t; ... } assoc_pair_kernel
+// compiled to the same 36 VGPRs and the same loop, its argument loads scheduled
+// otherwise, and measured 0.3499-0.3516 ms beside 0.3445-0.3457 of the parent,
+// whose code this form compiles to, five runs each in turn on one MI355X (a run
+// of its own: other runs lie up to 1 % apart as a whole) -- the sensitivity the
+// note in track_frames.hpp records.
 struct AssocArgs {
     int64_t n_dt, n_gt, n_cells, n_iou, n_dt_frames, n_gt_frames;
     int32_t n_cat, n_vis;
@@ -134,16 +137,17 @@ struct OwnColumn {
     int64_t s, e, d0, D, G, col;
     __device__ __forceinline__ void init(const AssocArgs &a, int64_t g)
     {
-        s = clamp64(a.gfoff[g], 0, a.n_gt_frames);
-        e = clamp64(a.gfoff[g + 1], s, a.n_gt_frames);
+        const TrackSpan f = track_span(a.gfoff, g, a.n_gt_frames);
+        s = f.first;
+        e = f.end;
         d0 = D = G = col = 0;
         const int32_t cell = a.ft.gt_cell[g];
         if (cell >= 0) {
-            d0 = clamp64(a.cell_dt_off[cell], 0, a.n_dt);
-            D = clamp64(a.cell_dt_off[cell + 1], d0, a.n_dt) - d0;
-            const int64_t g0 = a.cell_gt_off[cell];
-            G = (int64_t)a.cell_gt_off[cell + 1] - g0;
-            col = a.cell_iou_off[cell] + (g - g0);
+            const TrackCell c = track_cell(a, cell);
+            d0 = c.d0;
+            D = c.D;
+            G = c.G;
+            col = c.off + (g - c.g0);
         }
     }
     // where the count of in-cell index d lies, -1: nowhere
@@ -267,7 +271,7 @@ __global__ __launch_bounds__(256) void assoc_tally_kernel(AssocArgs a)
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = g < a.n_gt;
     const int32_t cat = valid ? a.gt_cat[g] : 0;
-    const bool ok = valid && !(a.gt_flags[g] & TAOAMD_GT_IGNORE) && cat >= 0 && cat < a.n_cat;
+    const bool ok = valid && track_eligible(a, g) && cat >= 0 && cat < a.n_cat;
     int32_t frames = 0, covered = 0, ids = 0, switches = 0, fragments = 0;
     if (ok) {
         const int32_t *in = a.gt_assoc + g * TA_NASSOC;
@@ -290,20 +294,19 @@ __global__ __launch_bounds__(256) void assoc_tally_kernel(AssocArgs a)
 }
 
 // The tables of the pass, in buffer order: a function of (n_dt, n_gt, n_gt_frames)
-static void assoc_layout(Carve &c, int64_t n_dt, int64_t n_gt, int64_t n_gt_frames, AssocArgs &a)
+static void assoc_layout(Carve &c, int64_t n_dt, int64_t n_gt, int64_t n_gt_frames,
+                         FrameTables &ft, AssocArgs &a)
 {
-    frames_layout(c, n_dt, n_gt, n_gt_frames, a.ft);
+    frames_layout(c, n_dt, n_gt, n_gt_frames, ft);
     a.trk_vis = c.take<int32_t>((size_t)n_gt * TA_VMAX * TA_NVIS);
 }
 
 extern "C" size_t taoamd_track_association_workspace(int64_t n_dt, int64_t n_gt,
                                                      int64_t n_gt_frames)
 {
-    if (n_dt < 0 || n_dt > 0x7fffffff || n_gt < 0 || n_gt > 0x7fffffff || n_gt_frames < 0 ||
-        n_gt_frames > 0x7fffffff)
-        return 0;
+    if (!track_sizes_ok(n_dt, n_gt, n_gt_frames, 0)) return 0;
     AssocArgs a;
-    return measure([&](Carve &c) { assoc_layout(c, n_dt, n_gt, n_gt_frames, a); });
+    return measure([&](Carve &c) { assoc_layout(c, n_dt, n_gt, n_gt_frames, a.ft, a); });
 }
 
 extern "C" int taoamd_track_association(
@@ -317,35 +320,25 @@ extern "C" int taoamd_track_association(
     int64_t *vis_counts, int32_t *best, double *best_iou, void *workspace,
     size_t workspace_bytes, void *stream)
 {
-    if (n_dt < 0 || n_dt > 0x7fffffff || n_gt < 0 || n_gt > 0x7fffffff || n_cells < 0 ||
-        n_cells > 0x7fffffff || n_iou < 0 || n_dt_frames < 0 || n_dt_frames > 0x7fffffff ||
-        n_gt_frames < 0 || n_gt_frames > 0x7fffffff || n_cat <= 0 || n_vis < 0 || n_vis > TA_VMAX)
-        return TAOAMD_ERR_ARG;
+    TrackTables t = {n_dt, n_gt, n_cells, n_iou, n_dt_frames, n_gt_frames, cell_dt_off,
+                     cell_gt_off, cell_iou_off, gt_cat, gt_flags, dt_frame_off, dt_frame_pos,
+                     track_boxes(dt_frame_box), gt_frame_off, gt_frame_pos,
+                     track_boxes(gt_frame_box)};
+    if (n_cat <= 0 || n_vis < 0 || n_vis > TA_VMAX) return TAOAMD_ERR_ARG;
     // (a NaN compares false both times)
     if (!(frame_thr > 0) || !(frame_thr <= 1)) return TAOAMD_ERR_ARG;
-    if (!cat_counts || !workspace) return TAOAMD_ERR_ARG;
+    if (!cat_counts || (n_gt > 0 && !gt_assoc) || (n_gt_frames > 0 && !best)) return TAOAMD_ERR_ARG;
     if (n_vis > 0 && (!vis_rng || !vis_counts || (n_gt_frames > 0 && !gt_frame_vis)))
         return TAOAMD_ERR_ARG;
-    if (n_cells > 0 && (!cell_dt_off || !cell_gt_off || !cell_iou_off)) return TAOAMD_ERR_ARG;
-    if (n_dt > 0 && !dt_frame_off) return TAOAMD_ERR_ARG;
-    if (n_dt_frames > 0 && (!dt_frame_pos || !dt_frame_box)) return TAOAMD_ERR_ARG;
-    if (n_gt > 0 && (!gt_cat || !gt_flags || !gt_frame_off || !gt_assoc)) return TAOAMD_ERR_ARG;
-    if (n_gt_frames > 0 && (!gt_frame_pos || !gt_frame_box || !best)) return TAOAMD_ERR_ARG;
     if (n_iou > 0 && !follow) return TAOAMD_ERR_ARG;
-    Carve c(workspace);
     AssocArgs a;
-    assoc_layout(c, n_dt, n_gt, n_gt_frames, a);
-    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
+    const int st = track_args(t, TT_IOU | TT_GT_CAT | TT_GT_FLAGS | TT_BOXES, workspace,
+                              workspace_bytes,
+                              [&](Carve &c) { assoc_layout(c, n_dt, n_gt, n_gt_frames, t.ft, a); });
+    if (st != TAOAMD_OK) return st;
+    track_fill(a, t);
     hipStream_t s = (hipStream_t)stream;
-    a.n_dt = n_dt; a.n_gt = n_gt; a.n_cells = n_cells; a.n_iou = n_iou;
-    a.n_dt_frames = n_dt_frames; a.n_gt_frames = n_gt_frames;
     a.n_cat = n_cat; a.n_vis = n_vis; a.thr = frame_thr;
-    a.cell_dt_off = cell_dt_off; a.cell_gt_off = cell_gt_off; a.cell_iou_off = cell_iou_off;
-    a.gt_cat = gt_cat; a.gt_flags = gt_flags;
-    a.dfoff = dt_frame_off; a.dfpos = dt_frame_pos;
-    a.dfbox = reinterpret_cast<const double4 *>(dt_frame_box);
-    a.gfoff = gt_frame_off; a.gfpos = gt_frame_pos;
-    a.gfbox = reinterpret_cast<const double4 *>(gt_frame_box);
     a.gfvis = gt_frame_vis; a.vis_rng = vis_rng;
     a.follow = follow; a.gt_assoc = gt_assoc;
     a.cat_counts = (unsigned long long *)cat_counts;
@@ -358,10 +351,8 @@ extern "C" int taoamd_track_association(
     if (n_gt == 0) return TAOAMD_OK;
     // (empty sides: the rule of track_frames.hpp.  A ground-truth row no cell lists has
     // no candidates, a frame no track lists no follower)
-    const FrameSource src = {n_dt, n_gt, n_cells, n_dt_frames, n_gt_frames,
-                             cell_gt_off, dt_frame_off, dt_frame_pos, gt_frame_off};
-    const int st = frames_build(src, a.ft, s);
-    if (st != TAOAMD_OK) return st;
+    const int si = track_index(t, s);
+    if (si != TAOAMD_OK) return si;
     if (n_gt_frames > 0)
         TAO_TIMED("assoc_pair_kernel", s,
                   assoc_pair_kernel<<<(unsigned)((n_gt_frames + TA_TILE - 1) / TA_TILE), TA_TILE,

@@ -6,12 +6,14 @@
 // table; the definition is this library's, after TrackEval's CLEAR class, stated
 // in include/tao_amodal_hip.h ("track-level CLEAR") and DESIGN.md section 8.
 //
-// Rows, cells and frame lists are those of the association, the identity and
-// HOTA; q and c(s) are HOTA's (ONE = 2^30): every output is an integer
-// (match_iou: one box_iou value) and the same from run to run.  Three stages:
+// Rows, cells, frame lists and the entry points' common part are those of every
+// track analysis (track_tables.hpp, track_frames.hpp; CLEAR has no per-pair table,
+// so its cells come without `off`); q and c(s) are HOTA's (ONE = 2^30): every
+// output is an integer (match_iou: one box_iou value) and the same from run to
+// run.  Three stages:
 //
 // taoamd_track_clear_count / _fill: the candidates, in parallel.
-//   frames_build          the frame index (track_frames.hpp)
+//   track_index           the frame index (track_frames.hpp)
 //   clear_cand_kernel     lane = ground-truth frame of an eligible track: walks the
 //                         cell's kept detection tracks in ascending row
 //                         (frames_find); a track with a frame at the position sets
@@ -49,8 +51,8 @@
 //                         {cursor, end, the position under the cursor, last, the
 //                         step of last, matched, idsw, started} and the solver's lie
 //                         in LDS where both sides of the cell are <= TC_LDS = 64,
-//                         else in the cell's slice of the workspace (n_dt + n_gt
-//                         entries an array; one wavefront owns it).  prev[g] is
+//                         else in the cell's slice of the workspace (the search
+//                         store of assign_solve.hpp and arrays like it).  prev[g] is
 //                         last[g] where its step is the step before: "every ground
 //                         truth of the cell loses prev unless matched" costs
 //                         nothing.  An iteration: the least position under the
@@ -68,9 +70,10 @@
 //                         no search runs.  Else the columns are the rows' candidates
 //                         (marked in a cell-wide table, compacted in ascending
 //                         row), the smaller side becomes the solver's rows (the
-//                         ground truths when equal), assign_solve with a weight
-//                         functor that finds the pair in the frame's list -- staged
-//                         or in the store -- by bisection and adds the bonus.
+//                         ground truths when equal: assign_sides), assign_solve
+//                         with a weight functor that finds the pair in the
+//                         frame's list -- staged or in the store -- by bisection
+//                         and adds the bonus.
 //                         Iterations are bounded by the eligible tracks' frames,
 //                         counted at entry.
 //                         A cell whose smaller side exceeds TC_NMAX = 2^18 stores 2
@@ -98,11 +101,9 @@
 //   62 VGPRs, clear_scan_top_kernel 60, 128 B of LDS each;  clear_scan_add_kernel 4;
 //   clear_walk1_kernel 40 VGPRs, no LDS;  clear_walk_kernel 107 VGPRs, 8 720 B of LDS
 //   (a workgroup is one wavefront: 16 cells a CU by registers, 18 by LDS);
-//   clear_reduce_kernel 62 VGPRs, no LDS.
+//   clear_reduce_kernel 59 VGPRs, no LDS.
 #include "assign_solve.hpp"
-#include "common.hpp"
-#include "track_frames.hpp"
-#include "workspace.hpp"
+#include "track_tables.hpp"
 
 using namespace taoamd;
 
@@ -121,6 +122,12 @@ using namespace taoamd;
 
 static_assert(TC_LDS <= WAVE, "a step's rows of a cell in LDS are one pass of the wavefront");
 
+// The kernels' argument block is this file's own, the common fields where they
+// were (track_fill<false> sets them; no cell_iou_off: track_cell<false>): over
+// { TrackTables t; ... } clear_cand_kernel<COUNT>, the same lines, measured
+// 0.4149-0.4170 ms beside 0.4119-0.4129 of the parent, whose code this form
+// compiles to, five runs each in turn on one MI355X (a run of its own: other
+// runs lie up to 1 % apart as a whole).
 struct ClearArgs {
     int64_t n_dt, n_gt, n_cells, n_dt_frames, n_gt_frames, n_cand;
     int32_t n_cat, n_vis;
@@ -152,39 +159,13 @@ struct ClearArgs {
     long long *blk;                              // [n_gt_frames / TC_SCAN + 1]: the scan's block sums
     // the state of the cells that do not fit in LDS, n_dt + n_gt entries each:
     // cell c owns [cell_dt_off[c] + cell_gt_off[c], the next cell's)
-    long long *su, *sv, *sminv, *snpos, *sc0, *sc1, *stc0;
-    int32_t *sp, *sway, *sused, *sgidx, *sdidx, *sge, *sgf, *smark;
+    SearchStore store;
+    long long *snpos, *sc0, *sc1, *stc0;
+    int32_t *sgidx, *sdidx, *sge, *sgf, *smark;
     int32_t *scur, *send, *slast, *slstep, *smat, *sidsw, *sstart, *stn, *stbit, *sbit0;
 };
 
-struct ClearCell {
-    int64_t d0, D, g0, G;
-};
-
-__device__ __forceinline__ ClearCell clear_cell(const ClearArgs &a, int64_t cell)
-{
-    ClearCell c;
-    c.d0 = clamp64(a.cell_dt_off[cell], 0, a.n_dt);
-    c.D = clamp64(a.cell_dt_off[cell + 1], c.d0, a.n_dt) - c.d0;
-    c.g0 = clamp64(a.cell_gt_off[cell], 0, a.n_gt);
-    c.G = clamp64(a.cell_gt_off[cell + 1], c.g0, a.n_gt) - c.g0;
-    return c;
-}
-
-__device__ __forceinline__ bool clear_eligible(const ClearArgs &a, int64_t g)
-{
-    return !(a.gt_flags[g] & TAOAMD_GT_IGNORE);
-}
-
 // (offsets clamped to the tables: a bad CSR reads wrong entries, never past an end)
-__device__ __forceinline__ int64_t clear_fs(const ClearArgs &a, int64_t g)
-{
-    return clamp64(a.gfoff[g], 0, a.n_gt_frames);
-}
-__device__ __forceinline__ int64_t clear_fe(const ClearArgs &a, int64_t g)
-{
-    return clamp64(a.gfoff[g + 1], clear_fs(a, g), a.n_gt_frames);
-}
 __device__ __forceinline__ int64_t clear_c0(const ClearArgs &a, int64_t k)
 {
     return clamp64(a.cand_off[k], 0, a.n_cand);
@@ -221,8 +202,8 @@ __global__ __launch_bounds__(TC_TILE) void clear_cand_kernel(ClearArgs a)
     }
     const int32_t g = a.ft.frame_gt[k];
     const int32_t cell = g >= 0 ? a.ft.gt_cell[g] : -1;
-    if (cell >= 0 && clear_eligible(a, g)) {
-        const ClearCell c = clear_cell(a, cell);
+    if (cell >= 0 && track_eligible(a, g)) {
+        const TrackCell c = track_cell<false>(a, cell);
         const int64_t p = a.gfpos[k];
         const double4 B = a.gfbox[k];
         for (int64_t d = 0; d < c.D; d++) {
@@ -252,7 +233,8 @@ __global__ __launch_bounds__(TC_TILE) void clear_cand_kernel(ClearArgs a)
 // off[i] = the sum of cnt[0 .. i), off[n] the total, in three launches: the sums
 // within a block of TC_SCAN counts and the block's total; the totals' own sums by
 // one workgroup; their addition.  (One workgroup over all the frames, the first
-// form, took 4.8 ms at 3 million frames: more than the walk.)
+// form, took 4.8 ms at 3 million frames: more than the walk.  The scan itself is
+// written out in both kernels: the note at occ_scan_kernel, track_occlusion.hip.)
 __global__ __launch_bounds__(TC_SCAN) void clear_scan_tile_kernel(const int32_t *__restrict__ cnt,
                                                                   int64_t *__restrict__ off,
                                                                   long long *__restrict__ blk,
@@ -263,12 +245,7 @@ __global__ __launch_bounds__(TC_SCAN) void clear_scan_tile_kernel(const int32_t 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int64_t i = (int64_t)blockIdx.x * TC_SCAN + tid;
     const long long v = i < n ? cnt[i] : 0;
-    long long incl = v;
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const long long u = __shfl_up(incl, o, WAVE);
-        if (lane_id() >= o) incl += u;
-    }
+    const long long incl = wave_prefix(v);
     if (lane_id() == WAVE - 1) s_w[wave] = incl;
     __syncthreads();
     long long before = 0, total = 0;
@@ -329,14 +306,14 @@ __global__ __launch_bounds__(TC_SCAN) void clear_scan_add_kernel(int64_t *__rest
 // the chain
 // ---------------------------------------------------------------------------
 // The number of eligible rows of the cell and the first of them (uniform)
-__device__ __forceinline__ int64_t clear_count_eligible(const ClearArgs &a, const ClearCell &c,
+__device__ __forceinline__ int64_t clear_count_eligible(const ClearArgs &a, const TrackCell &c,
                                                         int64_t &first)
 {
     int64_t n = 0;
     first = -1;
     for (int64_t gb = 0; gb < c.G; gb += WAVE) {
         const int64_t o = gb + lane_id();
-        const uint64_t m = __ballot(o < c.G && clear_eligible(a, c.g0 + o));
+        const uint64_t m = __ballot(o < c.G && track_eligible(a, c.g0 + o));
         if (m && first < 0) first = gb + __builtin_ctzll(m);
         n += __popcll(m);
     }
@@ -383,11 +360,12 @@ __device__ __forceinline__ int64_t clear_one_row(const ClearArgs &a, int64_t D, 
 __global__ __launch_bounds__(WAVE) void clear_walk1_kernel(ClearArgs a)
 {
     const int lane = lane_id();
-    const ClearCell c = clear_cell(a, blockIdx.x);
+    const TrackCell c = track_cell<false>(a, blockIdx.x);
     int64_t o1;
     if (clear_count_eligible(a, c, o1) != 1) return;                     // (uniform)
     const int64_t g = c.g0 + o1;
-    const int64_t fs = clear_fs(a, g), fe = clear_fe(a, g);
+    const TrackSpan f = track_span(a.gfoff, g, a.n_gt_frames);
+    const int64_t fs = f.first, fe = f.end;
     int32_t last = -1, lstep = -1, stepno = 0, mat = 0, idsw = 0, start = 0;
     // the chunk's descriptors: the lane's frame {first candidate, end, step bit}
     int64_t x0 = 0, x1 = 0, nx0 = 0, nx1 = 0;
@@ -555,9 +533,8 @@ __device__ __forceinline__ void clear_take(const ClearArgs &a, const ClearState 
 
 __global__ __launch_bounds__(WAVE) void clear_walk_kernel(ClearArgs a)
 {
-    __shared__ long long l_u[TC_LDS], l_v[TC_LDS], l_minv[TC_LDS];
+    __shared__ SearchLds<TC_LDS> l_search;           // (idx0: gidx, idx1: didx)
     __shared__ long long l_npos[TC_LDS], l_c0[TC_LDS], l_c1[TC_LDS];
-    __shared__ int32_t l_p[TC_LDS], l_way[TC_LDS], l_used[TC_LDS], l_gidx[TC_LDS], l_didx[TC_LDS];
     __shared__ int32_t l_ge[TC_LDS], l_gf[TC_LDS], l_mark[TC_LDS];
     __shared__ int32_t l_cur[TC_LDS], l_end[TC_LDS], l_last[TC_LDS], l_lstep[TC_LDS];
     __shared__ int32_t l_mat[TC_LDS], l_idsw[TC_LDS], l_start[TC_LDS];
@@ -566,7 +543,7 @@ __global__ __launch_bounds__(WAVE) void clear_walk_kernel(ClearArgs a)
     __shared__ int32_t l_tn[TC_LDS], l_tbit[TC_LDS], l_bit0[1];
     const int lane = lane_id();
     const uint64_t below = (1ull << lane) - 1ull;
-    const ClearCell c = clear_cell(a, blockIdx.x);
+    const TrackCell c = track_cell<false>(a, blockIdx.x);
     int64_t o1;
     if (clear_count_eligible(a, c, o1) < 2) return;                      // (uniform)
     if ((c.G < c.D ? c.G : c.D) > TC_NMAX) {                             // (uniform)
@@ -577,14 +554,12 @@ __global__ __launch_bounds__(WAVE) void clear_walk_kernel(ClearArgs a)
     const int64_t base = c.d0 + c.g0;                // the cell's slice of the state arrays
     ClearState st;
     if (lds) {
-        st = {{l_u, l_v, l_minv, l_p, l_way, l_used, nullptr, nullptr},
-              l_gidx, l_didx, l_ge, l_gf, l_mark,
+        st = {l_search.search(), l_search.idx0, l_search.idx1, l_ge, l_gf, l_mark,
               l_cur, l_end, l_last, l_lstep, l_mat, l_idsw, l_start,
               l_npos, l_c0, l_c1, l_tc0, l_tn, l_tbit, l_bit0, l_s0, l_srow, l_sq};
     } else {
-        st = {{a.su + base, a.sv + base, a.sminv + base, a.sp + base, a.sway + base,
-               a.sused + base, nullptr, nullptr},
-              a.sgidx + base, a.sdidx + base, a.sge + base, a.sgf + base, a.smark + base,
+        st = {a.store.at(base), a.sgidx + base, a.sdidx + base, a.sge + base, a.sgf + base,
+              a.smark + base,
               a.scur + base, a.send + base, a.slast + base, a.slstep + base, a.smat + base,
               a.sidsw + base, a.sstart + base,
               a.snpos + base, a.sc0 + base, a.sc1 + base, a.stc0 + base, a.stn + base,
@@ -597,8 +572,9 @@ __global__ __launch_bounds__(WAVE) void clear_walk_kernel(ClearArgs a)
         const int64_t o = ob + lane;
         int64_t mine = 0;
         if (o < c.G) {
-            const int64_t fs = clear_fs(a, c.g0 + o), fe = clear_fe(a, c.g0 + o);
-            const bool el = clear_eligible(a, c.g0 + o);
+            const TrackSpan f = track_span(a.gfoff, c.g0 + o, a.n_gt_frames);
+            const int64_t fs = f.first, fe = f.end;
+            const bool el = track_eligible(a, c.g0 + o);
             st.cur[o] = (int32_t)fs;
             st.end[o] = (int32_t)fe;
             st.npos[o] = el && fs < fe ? (long long)a.gfpos[fs] : TC_END;
@@ -673,12 +649,7 @@ __global__ __launch_bounds__(WAVE) void clear_walk_kernel(ClearArgs a)
             mg += __popcll(m);
             total += wave_sum(x1 - x0);
             if (lds) {                                       // (ng <= TC_LDS = WAVE: one pass)
-                long long incl = x1 - x0;
-#pragma unroll
-                for (int o = 1; o < WAVE; o <<= 1) {
-                    const long long u = __shfl_up(incl, o, WAVE);
-                    if (lane >= o) incl += u;
-                }
+                const long long incl = wave_prefix(x1 - x0);
                 if (incl - (x1 - x0) <= TC_STAGE) l_s0[lane] = (int32_t)(incl - (x1 - x0));
                 if (lane == WAVE - 1 && incl <= TC_STAGE) l_s0[WAVE] = (int32_t)incl;
             }
@@ -773,35 +744,30 @@ __global__ __launch_bounds__(WAVE) void clear_walk_kernel(ClearArgs a)
         }
         __syncthreads();
         if (md == 0) continue;                                           // (uniform)
-        ClearWeight W = {a, c.D, st, staged, stepno, mg <= md};
-        const int n = W.rows_are_gt ? mg : md, m = W.rows_are_gt ? md : mg;
+        // the smaller side as rows, the ground truths when equal
+        const Sides sd = assign_sides(st.gidx, mg, st.didx, md);
         Search s = st.s;
-        s.ridx = W.rows_are_gt ? st.gidx : st.didx;
-        s.cidx = W.rows_are_gt ? st.didx : st.gidx;
-        if (!assign_solve(W, s, n, m)) {
+        s.ridx = sd.rows;
+        s.cidx = sd.cols;
+        const ClearWeight W = {a, c.D, st, staged, stepno, sd.first};
+        if (!assign_solve(W, s, sd.n, sd.m)) {
             if (lane == 0) *a.status = 1;
             __syncthreads();
             continue;
         }
         // the pairs with a positive w (distinct ground truths: a lane a pair)
-        for (int jb = 0; jb < m; jb += WAVE) {
-            const int j = jb + lane;
-            const int i = j < m ? s.p[j] : 0;
-            if (i > 0) {
-                const int64_t r = s.ridx[i - 1], cc = s.cidx[j];
-                const int64_t gi = W.rows_are_gt ? r : cc, d = W.rows_are_gt ? cc : r;
-                int64_t x = 0;
-                if (W.at(gi, d, x) > 0)
-                    clear_take(a, st, st.ge[gi], st.gf[gi], (int32_t)d, x, stepno);
-            }
-        }
+        assign_pairs(s, sd, [&](bool has, int64_t gi, int64_t d) {
+            int64_t x = 0;
+            if (has && W.at(gi, d, x) > 0)
+                clear_take(a, st, st.ge[gi], st.gf[gi], (int32_t)d, x, stepno);
+        });
         __syncthreads();
     }
     __syncthreads();
     for (int64_t o = lane; o < c.G; o += WAVE) {
-        if (!clear_eligible(a, c.g0 + o)) continue;
+        if (!track_eligible(a, c.g0 + o)) continue;
         int32_t *out = a.gt_clear + (c.g0 + o) * TC_NGT;
-        out[0] = (int32_t)(clear_fe(a, c.g0 + o) - clear_fs(a, c.g0 + o));
+        out[0] = (int32_t)track_span(a.gfoff, c.g0 + o, a.n_gt_frames).len();
         out[1] = st.mat[o];
         out[2] = st.idsw[o];
         out[3] = st.start[o];
@@ -817,9 +783,10 @@ __global__ __launch_bounds__(256) void clear_reduce_kernel(ClearArgs a)
                     + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
     if (g >= a.n_gt) return;                                 // (whole wavefronts)
     const int32_t cat = a.gt_cat[g];
-    if (!clear_eligible(a, g) || cat < 0 || cat >= a.n_cat) return;      // (uniform)
+    if (!track_eligible(a, g) || cat < 0 || cat >= a.n_cat) return;      // (uniform)
     const int lane = lane_id();
-    const int64_t fs = clear_fs(a, g), fe = clear_fe(a, g);
+    const TrackSpan f = track_span(a.gfoff, g, a.n_gt_frames);
+    const int64_t fs = f.first, fe = f.end;
     long long qsum = 0;
     int32_t vf[TC_VMAX], vm[TC_VMAX], vs[TC_VMAX];
     long long vq[TC_VMAX];
@@ -872,14 +839,14 @@ __global__ __launch_bounds__(256) void clear_reduce_kernel(ClearArgs a)
         }
     }
     if (lane == 0) {
-        const int32_t *t = a.gt_clear + g * TC_NGT;
-        const long long present = t[0], matched = t[1];
+        const int32_t *in = a.gt_clear + g * TC_NGT;
+        const long long present = in[0], matched = in[1];
         const bool mt = 5 * matched > 4 * present;
         const bool pt = !mt && 5 * matched >= present;
         unsigned long long *row = a.cat_counts + (int64_t)cat * TC_NCAT;
-        if (t[1] > 0) atomicAdd(row + 0, (unsigned long long)t[1]);
-        if (t[2] > 0) atomicAdd(row + 1, (unsigned long long)t[2]);
-        if (t[3] > 1) atomicAdd(row + 2, (unsigned long long)(t[3] - 1));
+        if (in[1] > 0) atomicAdd(row + 0, (unsigned long long)in[1]);
+        if (in[2] > 0) atomicAdd(row + 1, (unsigned long long)in[2]);
+        if (in[3] > 1) atomicAdd(row + 2, (unsigned long long)(in[3] - 1));
         atomicAdd(row + (mt ? 3 : (pt ? 4 : 5)), 1ull);
         if (qsum) atomicAdd(row + 6, (unsigned long long)qsum);
     }
@@ -889,93 +856,38 @@ __global__ __launch_bounds__(256) void clear_reduce_kernel(ClearArgs a)
 // the entry points
 // ---------------------------------------------------------------------------
 // The tables of all stages, in buffer order: a function of (n_dt, n_gt, n_gt_frames)
-static void clear_layout(Carve &c, int64_t n_dt, int64_t n_gt, int64_t n_gt_frames, ClearArgs &a)
+static void clear_layout(Carve &c, int64_t n_dt, int64_t n_gt, int64_t n_gt_frames,
+                         FrameTables &ft, ClearArgs &a)
 {
     const size_t n = (size_t)(n_dt + n_gt);
-    frames_layout(c, n_dt, n_gt, n_gt_frames, a.ft);
+    frames_layout(c, n_dt, n_gt, n_gt_frames, ft);
     a.n_cnt = c.take<int32_t>((size_t)n_gt_frames);
     a.blk = c.take<long long>((size_t)n_gt_frames / TC_SCAN + 1);
-    a.su = c.take<long long>(n);
-    a.sv = c.take<long long>(n);
-    a.sminv = c.take<long long>(n);
-    a.snpos = c.take<long long>(n);
-    a.sc0 = c.take<long long>(n);
-    a.sc1 = c.take<long long>(n);
-    a.stc0 = c.take<long long>(n);
-    a.sp = c.take<int32_t>(n);
-    a.sway = c.take<int32_t>(n);
-    a.sused = c.take<int32_t>(n);
-    a.sgidx = c.take<int32_t>(n);
-    a.sdidx = c.take<int32_t>(n);
-    a.sge = c.take<int32_t>(n);
-    a.sgf = c.take<int32_t>(n);
-    a.smark = c.take<int32_t>(n);
-    a.scur = c.take<int32_t>(n);
-    a.send = c.take<int32_t>(n);
-    a.stn = c.take<int32_t>(n);
-    a.stbit = c.take<int32_t>(n);
-    a.sbit0 = c.take<int32_t>(n);
-    a.slast = c.take<int32_t>(n);
-    a.slstep = c.take<int32_t>(n);
-    a.smat = c.take<int32_t>(n);
-    a.sidsw = c.take<int32_t>(n);
-    a.sstart = c.take<int32_t>(n);
-}
-
-static bool clear_sizes_ok(int64_t n_dt, int64_t n_gt, int64_t n_gt_frames)
-{
-    return n_dt >= 0 && n_dt <= 0x7fffffff && n_gt >= 0 && n_gt <= 0x7fffffff &&
-           n_gt_frames >= 0 && n_gt_frames < 0x7fffffff && n_dt + n_gt <= 0x7fffffff;
+    a.store.layout(c, n);
+    for (long long **q : {&a.snpos, &a.sc0, &a.sc1, &a.stc0}) *q = c.take<long long>(n);
+    for (int32_t **q : {&a.sgidx, &a.sdidx, &a.sge, &a.sgf, &a.smark, &a.scur, &a.send, &a.stn,
+                        &a.stbit, &a.sbit0, &a.slast, &a.slstep, &a.smat, &a.sidsw, &a.sstart})
+        *q = c.take<int32_t>(n);
 }
 
 extern "C" size_t taoamd_track_clear_workspace(int64_t n_dt, int64_t n_gt, int64_t n_gt_frames)
 {
-    if (!clear_sizes_ok(n_dt, n_gt, n_gt_frames)) return 0;
+    if (!track_sizes_ok(n_dt, n_gt, n_gt_frames, TT_STORE)) return 0;
     ClearArgs a;
-    return measure([&](Carve &c) { clear_layout(c, n_dt, n_gt, n_gt_frames, a); });
+    return measure([&](Carve &c) { clear_layout(c, n_dt, n_gt, n_gt_frames, a.ft, a); });
 }
 
-// What count and fill share: the refusals, the carved workspace, the tables
-static int clear_cand_args(ClearArgs &a, int64_t n_dt, int64_t n_gt, int64_t n_cells,
-                           int64_t n_dt_frames, int64_t n_gt_frames, double frame_thr,
-                           const int32_t *cell_dt_off, const int32_t *cell_gt_off,
-                           const uint8_t *gt_flags, const uint8_t *dt_keep,
-                           const int32_t *dt_frame_off, const int32_t *dt_frame_pos,
-                           const double *dt_frame_box, const int32_t *gt_frame_off,
-                           const int32_t *gt_frame_pos, const double *gt_frame_box,
-                           void *workspace, size_t workspace_bytes)
+// What the entry points share: the common refusals, the carved workspace and the
+// common fields of the kernels' block
+static int clear_args(ClearArgs &a, TrackTables &t, unsigned need, void *workspace,
+                      size_t workspace_bytes)
 {
-    if (!clear_sizes_ok(n_dt, n_gt, n_gt_frames) || n_cells < 0 || n_cells > 0x7fffffff ||
-        n_dt_frames < 0 || n_dt_frames > 0x7fffffff)
-        return TAOAMD_ERR_ARG;
-    if (!(frame_thr > 0.0 && frame_thr <= 1.0)) return TAOAMD_ERR_ARG;   // (a NaN compares false)
-    if (!workspace) return TAOAMD_ERR_ARG;
-    if (n_cells > 0 && (!cell_dt_off || !cell_gt_off)) return TAOAMD_ERR_ARG;
-    if (n_dt > 0 && !dt_frame_off) return TAOAMD_ERR_ARG;
-    if (n_dt_frames > 0 && (!dt_frame_pos || !dt_frame_box)) return TAOAMD_ERR_ARG;
-    if (n_gt > 0 && (!gt_frame_off || !gt_flags)) return TAOAMD_ERR_ARG;
-    if (n_gt_frames > 0 && (!gt_frame_pos || !gt_frame_box)) return TAOAMD_ERR_ARG;
-    Carve c(workspace);
     a = {};
-    clear_layout(c, n_dt, n_gt, n_gt_frames, a);
-    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
-    a.n_dt = n_dt; a.n_gt = n_gt; a.n_cells = n_cells;
-    a.n_dt_frames = n_dt_frames; a.n_gt_frames = n_gt_frames;
-    a.thr = frame_thr;
-    a.cell_dt_off = cell_dt_off; a.cell_gt_off = cell_gt_off;
-    a.gt_flags = gt_flags; a.dt_keep = dt_keep;
-    a.dfoff = dt_frame_off; a.dfpos = dt_frame_pos;
-    a.dfbox = reinterpret_cast<const double4 *>(dt_frame_box);
-    a.gfoff = gt_frame_off; a.gfpos = gt_frame_pos;
-    a.gfbox = reinterpret_cast<const double4 *>(gt_frame_box);
-    return TAOAMD_OK;
-}
-
-static int clear_index(const ClearArgs &a, hipStream_t s)
-{
-    const FrameSource src = {a.n_dt, a.n_gt, a.n_cells, a.n_dt_frames, a.n_gt_frames,
-                             a.cell_gt_off, a.dfoff, a.dfpos, a.gfoff};
-    return frames_build(src, a.ft, s);
+    const int st = track_args(
+        t, need | TT_GT_FLAGS | TT_STORE, workspace, workspace_bytes,
+        [&](Carve &c) { clear_layout(c, t.n_dt, t.n_gt, t.n_gt_frames, t.ft, a); });
+    track_fill<false>(a, t);
+    return st;
 }
 
 static unsigned clear_tiles(int64_t n_gt_frames)
@@ -992,13 +904,16 @@ extern "C" int taoamd_track_clear_count(
     void *workspace, size_t workspace_bytes, void *stream)
 {
     ClearArgs a;
+    TrackTables t = {n_dt, n_gt, n_cells, 0, n_dt_frames, n_gt_frames, cell_dt_off, cell_gt_off, nullptr,
+           nullptr, gt_flags, dt_frame_off, dt_frame_pos, track_boxes(dt_frame_box),
+           gt_frame_off, gt_frame_pos, track_boxes(gt_frame_box)};
     if (!cand_off || (n_gt_frames > 0 && !step)) return TAOAMD_ERR_ARG;
-    const int st = clear_cand_args(a, n_dt, n_gt, n_cells, n_dt_frames, n_gt_frames, frame_thr,
-                                   cell_dt_off, cell_gt_off, gt_flags, dt_keep, dt_frame_off,
-                                   dt_frame_pos, dt_frame_box, gt_frame_off, gt_frame_pos,
-                                   gt_frame_box, workspace, workspace_bytes);
+    if (!(frame_thr > 0.0 && frame_thr <= 1.0)) return TAOAMD_ERR_ARG;   // (a NaN compares false)
+    const int st = clear_args(a, t, TT_BOXES, workspace, workspace_bytes);
     if (st != TAOAMD_OK) return st;
     hipStream_t s = (hipStream_t)stream;
+    a.thr = frame_thr;
+    a.dt_keep = dt_keep;
     a.cand_off_out = cand_off;
     a.step_out = step;
     if (n_gt == 0 || n_gt_frames == 0) {
@@ -1006,7 +921,7 @@ extern "C" int taoamd_track_clear_count(
         if (n_gt_frames > 0) TAO_HIP(hipMemsetAsync(step, 0, (size_t)n_gt_frames, s));
         return TAOAMD_OK;
     }
-    const int si = clear_index(a, s);
+    const int si = track_index(t, s);
     if (si != TAOAMD_OK) return si;
     TAO_TIMED("clear_count_kernel", s,
               clear_cand_kernel<false><<<clear_tiles(n_gt_frames), TC_TILE, 0, s>>>(a));
@@ -1032,20 +947,23 @@ extern "C" int taoamd_track_clear_fill(
     size_t workspace_bytes, void *stream)
 {
     ClearArgs a;
+    TrackTables t = {n_dt, n_gt, n_cells, 0, n_dt_frames, n_gt_frames, cell_dt_off, cell_gt_off, nullptr,
+           nullptr, gt_flags, dt_frame_off, dt_frame_pos, track_boxes(dt_frame_box),
+           gt_frame_off, gt_frame_pos, track_boxes(gt_frame_box)};
     if (n_cand < 0 || !cand_off || (n_cand > 0 && (!cand_row || !cand_q))) return TAOAMD_ERR_ARG;
-    const int st = clear_cand_args(a, n_dt, n_gt, n_cells, n_dt_frames, n_gt_frames, frame_thr,
-                                   cell_dt_off, cell_gt_off, gt_flags, dt_keep, dt_frame_off,
-                                   dt_frame_pos, dt_frame_box, gt_frame_off, gt_frame_pos,
-                                   gt_frame_box, workspace, workspace_bytes);
+    if (!(frame_thr > 0.0 && frame_thr <= 1.0)) return TAOAMD_ERR_ARG;   // (a NaN compares false)
+    const int st = clear_args(a, t, TT_BOXES, workspace, workspace_bytes);
     if (st != TAOAMD_OK) return st;
     if (n_gt == 0 || n_gt_frames == 0 || n_cand == 0) return TAOAMD_OK;  // no candidate to store
     hipStream_t s = (hipStream_t)stream;
+    a.thr = frame_thr;
+    a.dt_keep = dt_keep;
     a.cand_off = cand_off;
     a.n_cand = n_cand;
     a.cand_row_out = cand_row;
     a.cand_q_out = cand_q;
     a.cand_iou_out = cand_iou;
-    const int si = clear_index(a, s);
+    const int si = track_index(t, s);
     if (si != TAOAMD_OK) return si;
     TAO_TIMED("clear_fill_kernel", s,
               clear_cand_kernel<true><<<clear_tiles(n_gt_frames), TC_TILE, 0, s>>>(a));
@@ -1061,23 +979,17 @@ extern "C" int taoamd_track_clear_walk(
     int32_t *match, double *match_iou, uint8_t *sw, int32_t *gt_clear, int32_t *status,
     void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!clear_sizes_ok(n_dt, n_gt, n_gt_frames) || n_cells < 0 || n_cells > 0x7fffffff ||
-        n_cand < 0)
-        return TAOAMD_ERR_ARG;
-    if (!status || !workspace || !cand_off) return TAOAMD_ERR_ARG;
-    if (n_cells > 0 && (!cell_dt_off || !cell_gt_off)) return TAOAMD_ERR_ARG;
-    if (n_gt > 0 && (!gt_frame_off || !gt_flags || !gt_clear)) return TAOAMD_ERR_ARG;
-    if (n_gt_frames > 0 && (!gt_frame_pos || !step || !match || !sw)) return TAOAMD_ERR_ARG;
+    ClearArgs a;
+    TrackTables t = {n_dt, n_gt, n_cells, 0, 0, n_gt_frames, cell_dt_off, cell_gt_off, nullptr, nullptr,
+           gt_flags, nullptr, nullptr, nullptr, gt_frame_off, gt_frame_pos, nullptr};
+    if (n_cand < 0 || !status || !cand_off) return TAOAMD_ERR_ARG;
+    if (n_gt > 0 && !gt_clear) return TAOAMD_ERR_ARG;
+    if (n_gt_frames > 0 && (!step || !match || !sw)) return TAOAMD_ERR_ARG;
     if (n_cand > 0 && (!cand_row || !cand_q)) return TAOAMD_ERR_ARG;
-    Carve c(workspace);
-    ClearArgs a = {};
-    clear_layout(c, n_dt, n_gt, n_gt_frames, a);
-    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
+    const int st = clear_args(a, t, TT_GT_POS, workspace, workspace_bytes);
+    if (st != TAOAMD_OK) return st;
     hipStream_t s = (hipStream_t)stream;
-    a.n_dt = n_dt; a.n_gt = n_gt; a.n_cells = n_cells; a.n_gt_frames = n_gt_frames;
     a.n_cand = n_cand;
-    a.cell_dt_off = cell_dt_off; a.cell_gt_off = cell_gt_off; a.gt_flags = gt_flags;
-    a.gfoff = gt_frame_off; a.gfpos = gt_frame_pos;
     a.cand_off = cand_off; a.cand_row = cand_row; a.cand_q = cand_q; a.cand_iou = cand_iou;
     a.step = step;
     a.match = match; a.match_iou = match_iou; a.sw = sw; a.gt_clear = gt_clear;
@@ -1106,22 +1018,19 @@ extern "C" int taoamd_track_clear_reduce(
     const int32_t *gt_clear, int64_t *cat_counts, int64_t *vis_counts, void *workspace,
     size_t workspace_bytes, void *stream)
 {
-    if (!clear_sizes_ok(n_dt, n_gt, n_gt_frames) || n_cand < 0 || n_cat <= 0)
-        return TAOAMD_ERR_ARG;
-    if (n_vis < 0 || n_vis > TC_VMAX) return TAOAMD_ERR_ARG;
+    ClearArgs a;
+    TrackTables t = {n_dt, n_gt, 0, 0, 0, n_gt_frames, nullptr, nullptr, nullptr, gt_cat, gt_flags,
+           nullptr, nullptr, nullptr, gt_frame_off, nullptr, nullptr};
+    if (n_cand < 0 || n_cat <= 0 || n_vis < 0 || n_vis > TC_VMAX) return TAOAMD_ERR_ARG;
     if (n_vis > 0 && (!gt_frame_vis || !vis_rng || !vis_counts)) return TAOAMD_ERR_ARG;
-    if (!cat_counts || !workspace || !cand_off) return TAOAMD_ERR_ARG;
-    if (n_gt > 0 && (!gt_cat || !gt_flags || !gt_frame_off || !gt_clear)) return TAOAMD_ERR_ARG;
+    if (!cat_counts || !cand_off || (n_gt > 0 && !gt_clear)) return TAOAMD_ERR_ARG;
     if (n_gt_frames > 0 && (!match || !sw)) return TAOAMD_ERR_ARG;
     if (n_cand > 0 && (!cand_row || !cand_q)) return TAOAMD_ERR_ARG;
-    Carve c(workspace);
-    ClearArgs a = {};
-    clear_layout(c, n_dt, n_gt, n_gt_frames, a);
-    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
+    const int st = clear_args(a, t, TT_GT_CAT, workspace, workspace_bytes);
+    if (st != TAOAMD_OK) return st;
     hipStream_t s = (hipStream_t)stream;
-    a.n_dt = n_dt; a.n_gt = n_gt; a.n_gt_frames = n_gt_frames; a.n_cand = n_cand;
+    a.n_cand = n_cand;
     a.n_cat = n_cat; a.n_vis = n_vis;
-    a.gt_cat = gt_cat; a.gt_flags = gt_flags; a.gfoff = gt_frame_off;
     a.gfvis = gt_frame_vis; a.vis_rng = vis_rng;
     a.cand_off = cand_off; a.cand_row = cand_row; a.cand_q = cand_q;
     a.match = const_cast<int32_t *>(match); a.sw = const_cast<uint8_t *>(sw);

@@ -1,8 +1,9 @@
 // The frame index of the passes over (ground-truth frame) x (the detection
-// tracks of its cell) -- the association (track_association.hip) and the
-// identity's share pass (track_identity.hip): three descriptor tables in the
-// pass's workspace, the one build of them, and the probe of a detection track's
-// frame list for a timeline position.  (assoc_pair_kernel has frames_find's lines
+// tracks of its cell) -- the association, the identity, HOTA and CLEAR: three
+// descriptor tables in the call's workspace, the one build of them (called
+// through track_index of track_tables.hpp, which holds what else those files
+// share), and the probe of a detection track's frame list for a timeline
+// position.  (assoc_pair_kernel has frames_find's lines
 // written out in its loop: calling it, or a form that takes the hit's body, cost
 // the kernel 38 VGPRs for 36 and, on an MI355X beside the written-out form in one
 // run, 0.351-0.354 ms for 0.347-0.349.  ident_share_kernel
@@ -12,8 +13,8 @@
 //                           last position} of its frame list, clamped to the tables
 //   frames_gt_cell_kernel   lane = cell: the cell of every ground-truth row
 //   frames_frame_gt_kernel  wavefront = ground-truth track: the track of every frame
-// HOTA (track_hota.hip) builds the same three and, beside them, a fourth table of
-// its own, the twin of dt_meta for the ground-truth tracks:
+// HOTA (track_hota.hip) builds, beside the three, a fourth table of its own, the
+// twin of dt_meta for the ground-truth tracks:
 //   frames_gt_meta_kernel   lane = ground-truth track (frames_build_gt_meta)
 //
 // EMPTY SIDES, the one rule: frames_build leaves every table complete whatever

@@ -3,20 +3,16 @@
 // 2016).  The reference has no such table; the definition is this library's,
 // stated in include/tao_amodal_hip.h and DESIGN.md section 8.
 //
-// Rows are those of the use_cats = 1 track table, cells and frame lists those of
-// the association (track_association.hip).  Two calls:
+// Rows, cells, frame lists and the entry points' common part are those of every
+// track analysis (track_tables.hpp, track_frames.hpp).  Two calls:
 //
 // taoamd_track_identity_share: share[cell_iou_off[cell] + d * G + g] = the frames
 // of ground-truth track g on which detection track d has a frame with box_iou >=
 // frame_thr -- per pair a COUNT, neither the 3D IoU's sum nor the association's
 // arg-max.
-//   frames_build         the frame index of the association's pass (a detection
-//                        track's frame range and positions, the cell of a ground-
-//                        truth row, the track of a frame; track_frames.hpp), built
-//                        into this call's workspace
 //   ident_share_kernel   lane = ground-truth frame, the whole table as one flat
-//                        list: the association's pair loop and its probe
-//                        (frames_find), but every candidate with an overlap
+//                        list: the association's pair loop with frames_find as
+//                        its probe, but every candidate with an overlap
 //                        >= frame_thr counts, not the greatest:
 //                        an integer atomic add per (pair, wavefront) with a hit,
 //                        the lanes of one pair found by ballot.  No LDS, no limit
@@ -33,38 +29,24 @@
 //                           of idx[]
 //                        2  lane = ground-truth track: the eligible ones with a
 //                           positive share in a compacted row are compacted
-//                        3  the smaller side becomes the rows (n <= m)
-//                        4  shortest augmenting paths (Hungarian in the Jonker-
-//                           Volgenant form, on cost = -weight; assign_solve.hpp,
-//                           shared with track_hota.hip): a row a time; a
-//                           step scans the free columns, lanes striding them
-//                           (ceil(m / 64) a lane), the minimum (value, column) by
-//                           a wavefront reduction -- the lowest column among
-//                           equal values, so the result is one function of the
-//                           input; potentials in 64 bits.  The search state (u,
-//                           v, minv, p, way, used, the two index lists) lives in
-//                           LDS where m <= TI_LDS, else in the cell's own slice
-//                           of workspace arrays of n_dt + n_gt entries.
-//                        Every loop has a bound known at entry: n rows, at most
-//                        m + 1 steps an augmentation, at most m + 1 edges of a
-//                        path.  A bound that runs out stores 1 to *status and
-//                        ends the cell with its pairs at -1; nothing spins.
+//                        3  the smaller side becomes the rows, the detections
+//                           when equal
+//                        4  assign_solve (assign_solve.hpp), its state in LDS
+//                           where m <= TI_LDS, else in the cell's slice of the
+//                           search store
+//                        A bound of the solver that runs out stores 1 to *status
+//                        and ends the cell with its pairs at -1; nothing spins.
 //                        A pair weighs share * (n + 1) + (share > 0): among equal
 //                        sums of shares the most pairs with a positive one, so
 //                        that `pairs` is unique as well.
 //                        The count tables are integer adds, one per (wavefront
 //                        step, category, column) (wave_add of common.hpp).
-// The wavefront is the workgroup, so __syncthreads() is the fence between its
-// lanes' stores and loads of the search state, in LDS and in global memory alike;
-// all control flow around it is uniform.
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950):
 //   ident_share_kernel 38 VGPRs, 30 SGPRs, 8 waves/SIMD, no scratch, no LDS;
 //   ident_assign_kernel 54 VGPRs, 11 264 B of LDS (a workgroup is one wavefront:
 //   14 cells a CU by LDS).
 #include "assign_solve.hpp"
-#include "common.hpp"
-#include "track_frames.hpp"
-#include "workspace.hpp"
+#include "track_tables.hpp"
 
 using namespace taoamd;
 
@@ -72,6 +54,9 @@ using namespace taoamd;
 #define TI_LDS 256          // columns (and rows) of a cell whose search state is in LDS
 #define TI_NCAT 6
 
+// The kernels' argument block is this file's own, the common fields where they
+// were (track_fill sets them): ident_assign_kernel measured slower over
+// { TrackTables t; ... } (the note in that kernel).
 struct IdentArgs {
     int64_t n_dt, n_gt, n_cells, n_iou, n_dt_frames, n_gt_frames;
     int32_t n_cat;
@@ -89,10 +74,8 @@ struct IdentArgs {
     int32_t *gt_ident, *dt_ident;    // [n_gt][2], [n_dt][2]
     int32_t *status;
     FrameTables ft;                  // the frame index (track_frames.hpp)
-    // the search state of the cells that do not fit in LDS, n_dt + n_gt entries
-    // each: cell c owns [cell_dt_off[c] + cell_gt_off[c], the next cell's)
-    long long *su, *sv, *sminv;
-    int32_t *sp, *sway, *sused, *sidx;
+    SearchStore store;               // the cells that do not fit in LDS
+    int32_t *sidx;                   // [n_dt + n_gt]: the cells' two index lists
 };
 
 __global__ __launch_bounds__(TI_TILE) void ident_share_kernel(IdentArgs a)
@@ -102,19 +85,16 @@ __global__ __launch_bounds__(TI_TILE) void ident_share_kernel(IdentArgs a)
     const int32_t g = a.ft.frame_gt[k];
     const int32_t cell = g >= 0 ? a.ft.gt_cell[g] : -1;
     if (cell < 0) return;
-    const int64_t d0 = clamp64(a.cell_dt_off[cell], 0, a.n_dt);
-    const int64_t d1 = clamp64(a.cell_dt_off[cell + 1], d0, a.n_dt);
-    const int64_t g0 = a.cell_gt_off[cell];
-    const int64_t G = (int64_t)a.cell_gt_off[cell + 1] - g0;
-    const int64_t col = a.cell_iou_off[cell] + (g - g0);
+    const TrackCell c = track_cell(a, cell);
+    const int64_t col = c.off + (g - c.g0);
     const int64_t p = a.gfpos[k];
     const double4 B = a.gfbox[k];
-    for (int64_t d = d0; d < d1; d++) {
+    for (int64_t d = c.d0; d < c.d0 + c.D; d++) {
         int64_t at = -1, lo;
         if (frames_find(a.dfpos, a.ft.dt_meta[d], p, lo)) {
             const double4 D = a.dfbox[lo];
             const double v = box_iou(D.x, D.y, D.z, D.w, B.x, B.y, B.z, B.w);
-            const int64_t i = col + (d - d0) * G;
+            const int64_t i = col + (d - c.d0) * c.G;
             // (a NaN compares false: no overlap)
             if (v >= a.thr && i >= 0 && i < a.n_iou) at = i;
         }
@@ -153,9 +133,9 @@ struct CellShare {
     }
 };
 
-// The weight of a pair for the shared solver (assign_solve.hpp): share * (n + 1) +
-// (share > 0) -- the sum of shares decides, among equal sums the number of pairs
-// with a positive share (fewer than n + 1), so that both numbers are unique.
+// The weight of a pair for the solver: share * (n + 1) + (share > 0) -- the sum
+// of shares decides, among equal sums the number of pairs with a positive share
+// (fewer than n + 1), so that both numbers are unique.
 struct IdentWeight {
     CellShare S;
     long long scale;                 // n + 1
@@ -169,6 +149,13 @@ struct IdentWeight {
 
 __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
 {
+    // (SearchLds, track_cell, assign_sides and assign_pairs, written out; the tie
+    // rule here is the other one: the detections become the rows when equal.
+    // With the shared forms the kernel compiles to other code -- the cell's offset
+    // loaded before the early return, the selects the other way round -- and
+    // measured 0.0545-0.0549 ms beside 0.0536-0.0541 of the parent, five runs each
+    // in turn on one MI355X (a run of its own).  These lines compile to the
+    // instructions the kernel had.)
     __shared__ long long l_u[TI_LDS], l_v[TI_LDS], l_minv[TI_LDS];
     __shared__ int32_t l_p[TI_LDS], l_way[TI_LDS], l_used[TI_LDS], l_ridx[TI_LDS], l_cidx[TI_LDS];
     const int64_t cell = blockIdx.x;
@@ -193,8 +180,8 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
         if (live)
             for (int64_t g = 0; g < G; g++) {
                 const int32_t v = S.at(d, g);
-                if (a.gt_flags[g0 + g] & TAOAMD_GT_IGNORE) mi = v > mi ? v : mi;
-                else me = v > me ? v : me;
+                if (track_eligible(a, g0 + g)) me = v > me ? v : me;
+                else mi = v > mi ? v : mi;
             }
         bool kept = false;
         int32_t cat = 0;
@@ -202,8 +189,7 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
         if (live) {
             kept = !(mi > me) && !((a.dt_flags[d0 + d] & TAOAMD_DT_IGNORE_UNMATCHED) && me == 0);
             cat = a.dt_cat[d0 + d];
-            const int64_t fs = clamp64(a.dfoff[d0 + d], 0, a.n_dt_frames);
-            frames = clamp64(a.dfoff[d0 + d + 1], fs, a.n_dt_frames) - fs;
+            frames = track_span(a.dfoff, d0 + d, a.n_dt_frames).len();
             a.dt_ident[(d0 + d) * 2 + 1] = kept;
         }
         const long long dt_cols[2] = {1, frames};                 // dt_tracks, dt_frames
@@ -220,15 +206,14 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
     for (int64_t gb = 0; gb < G; gb += WAVE) {
         const int64_t g = gb + lane;
         const bool live = g < G;
-        const bool elig = live && !(a.gt_flags[g0 + g] & TAOAMD_GT_IGNORE);
+        const bool elig = live && track_eligible(a, g0 + g);
         bool act = false;
         int32_t cat = 0;
         long long frames = 0;
         if (elig) {
-            for (int t = 0; t < nd && !act; t++) act = S.at(dlist[t], g) > 0;
+            for (int i = 0; i < nd && !act; i++) act = S.at(dlist[i], g) > 0;
             cat = a.gt_cat[g0 + g];
-            const int64_t fs = clamp64(a.gfoff[g0 + g], 0, a.n_gt_frames);
-            frames = clamp64(a.gfoff[g0 + g + 1], fs, a.n_gt_frames) - fs;
+            frames = track_span(a.gfoff, g0 + g, a.n_gt_frames).len();
         }
         const long long gt_cols[2] = {1, frames};                 // gt_tracks, gt_frames
         wave_add(a.cat_counts, TI_NCAT, elig && cat >= 0 && cat < a.n_cat, cat, gt_cols);
@@ -238,7 +223,7 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
     }
     __syncthreads();
     if (nd == 0 || ng == 0) return;                  // (uniform)
-    // 3: the smaller side as rows
+    // 3: the smaller side as rows, the detections when equal
     const bool rows_are_dt = nd <= ng;
     const int n = rows_are_dt ? nd : ng, m = rows_are_dt ? ng : nd;
     // a potential is a sum of at most n weights, each at most top * (n + 1) + 1: in
@@ -253,7 +238,9 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
         return;
     }
     const int32_t *rl = rows_are_dt ? dlist : glist, *cl = rows_are_dt ? glist : dlist;
-    // 4: the search, its state in LDS or in the cell's slice of the workspace
+    // 4: the search, its state in LDS or in the cell's slice of the store.  (One
+    // call on each side: inlined, the solver then knows which memory its state is
+    // in; one call behind the choice goes through flat addresses.)
     const IdentWeight W = {S, (long long)n + 1, rows_are_dt};
     Search s;
     bool ok;
@@ -263,8 +250,9 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
         s = {l_u, l_v, l_minv, l_p, l_way, l_used, l_ridx, l_cidx};
         ok = assign_solve(W, s, n, m);
     } else {
-        s = {a.su + base, a.sv + base, a.sminv + base, a.sp + base, a.sway + base,
-             a.sused + base, rl, cl};
+        s = a.store.at(base);
+        s.ridx = rl;
+        s.cidx = cl;
         ok = assign_solve(W, s, n, m);
     }
     if (!ok) {
@@ -292,30 +280,32 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
 }
 
 // The tables of both calls, in buffer order: a function of (n_dt, n_gt, n_gt_frames)
-static void ident_layout(Carve &c, int64_t n_dt, int64_t n_gt, int64_t n_gt_frames, IdentArgs &a)
+static void ident_layout(Carve &c, int64_t n_dt, int64_t n_gt, int64_t n_gt_frames,
+                         FrameTables &ft, IdentArgs &a)
 {
-    const size_t n = (size_t)(n_dt + n_gt);
-    frames_layout(c, n_dt, n_gt, n_gt_frames, a.ft);
-    a.su = c.take<long long>(n);
-    a.sv = c.take<long long>(n);
-    a.sminv = c.take<long long>(n);
-    a.sp = c.take<int32_t>(n);
-    a.sway = c.take<int32_t>(n);
-    a.sused = c.take<int32_t>(n);
-    a.sidx = c.take<int32_t>(n);
-}
-
-static bool ident_sizes_ok(int64_t n_dt, int64_t n_gt, int64_t n_gt_frames)
-{
-    return n_dt >= 0 && n_dt <= 0x7fffffff && n_gt >= 0 && n_gt <= 0x7fffffff &&
-           n_gt_frames >= 0 && n_gt_frames <= 0x7fffffff && n_dt + n_gt <= 0x7fffffff;
+    frames_layout(c, n_dt, n_gt, n_gt_frames, ft);
+    a.store.layout(c, (size_t)(n_dt + n_gt));
+    a.sidx = c.take<int32_t>((size_t)(n_dt + n_gt));
 }
 
 extern "C" size_t taoamd_track_identity_workspace(int64_t n_dt, int64_t n_gt, int64_t n_gt_frames)
 {
-    if (!ident_sizes_ok(n_dt, n_gt, n_gt_frames)) return 0;
+    if (!track_sizes_ok(n_dt, n_gt, n_gt_frames, TT_STORE)) return 0;
     IdentArgs a;
-    return measure([&](Carve &c) { ident_layout(c, n_dt, n_gt, n_gt_frames, a); });
+    return measure([&](Carve &c) { ident_layout(c, n_dt, n_gt, n_gt_frames, a.ft, a); });
+}
+
+// What the two entry points share: the common refusals, the carved workspace and
+// the common fields of the kernels' block
+static int ident_args(IdentArgs &a, TrackTables &t, unsigned need, void *workspace,
+                      size_t workspace_bytes)
+{
+    a = {};
+    const int st = track_args(
+        t, need | TT_IOU | TT_DT_OFF | TT_STORE, workspace, workspace_bytes,
+        [&](Carve &c) { ident_layout(c, t.n_dt, t.n_gt, t.n_gt_frames, t.ft, a); });
+    track_fill(a, t);
+    return st;
 }
 
 extern "C" int taoamd_track_identity_share(
@@ -326,39 +316,25 @@ extern "C" int taoamd_track_identity_share(
     const double *gt_frame_box, int32_t *share, void *workspace, size_t workspace_bytes,
     void *stream)
 {
-    if (!ident_sizes_ok(n_dt, n_gt, n_gt_frames) || n_cells < 0 || n_cells > 0x7fffffff ||
-        n_iou < 0 || n_dt_frames < 0 || n_dt_frames > 0x7fffffff)
-        return TAOAMD_ERR_ARG;
+    TrackTables t = {n_dt, n_gt, n_cells, n_iou, n_dt_frames, n_gt_frames, cell_dt_off,
+                     cell_gt_off, cell_iou_off, nullptr, nullptr, dt_frame_off, dt_frame_pos,
+                     track_boxes(dt_frame_box), gt_frame_off, gt_frame_pos,
+                     track_boxes(gt_frame_box)};
+    IdentArgs a;
     // (a NaN compares false both times)
     if (!(frame_thr > 0) || !(frame_thr <= 1)) return TAOAMD_ERR_ARG;
-    if (!workspace) return TAOAMD_ERR_ARG;
-    if (n_cells > 0 && (!cell_dt_off || !cell_gt_off || !cell_iou_off)) return TAOAMD_ERR_ARG;
-    if (n_dt > 0 && !dt_frame_off) return TAOAMD_ERR_ARG;
-    if (n_dt_frames > 0 && (!dt_frame_pos || !dt_frame_box)) return TAOAMD_ERR_ARG;
-    if (n_gt > 0 && !gt_frame_off) return TAOAMD_ERR_ARG;
-    if (n_gt_frames > 0 && (!gt_frame_pos || !gt_frame_box)) return TAOAMD_ERR_ARG;
     if (n_iou > 0 && !share) return TAOAMD_ERR_ARG;
-    Carve c(workspace);
-    IdentArgs a = {};
-    ident_layout(c, n_dt, n_gt, n_gt_frames, a);
-    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
+    const int st = ident_args(a, t, TT_BOXES, workspace, workspace_bytes);
+    if (st != TAOAMD_OK) return st;
     hipStream_t s = (hipStream_t)stream;
-    a.n_dt = n_dt; a.n_gt = n_gt; a.n_cells = n_cells; a.n_iou = n_iou;
-    a.n_dt_frames = n_dt_frames; a.n_gt_frames = n_gt_frames; a.thr = frame_thr;
-    a.cell_dt_off = cell_dt_off; a.cell_gt_off = cell_gt_off; a.cell_iou_off = cell_iou_off;
-    a.dfoff = dt_frame_off; a.dfpos = dt_frame_pos;
-    a.dfbox = reinterpret_cast<const double4 *>(dt_frame_box);
-    a.gfoff = gt_frame_off; a.gfpos = gt_frame_pos;
-    a.gfbox = reinterpret_cast<const double4 *>(gt_frame_box);
+    a.thr = frame_thr;
     a.share = share;
     if (n_iou > 0) TAO_HIP(hipMemsetAsync(share, 0, (size_t)n_iou * sizeof(int32_t), s));
     if (n_gt == 0) return TAOAMD_OK;
     // (empty sides: the rule of track_frames.hpp.  A ground-truth row no cell lists has
     // no candidates, a frame no track lists counts nowhere: share stays 0)
-    const FrameSource src = {n_dt, n_gt, n_cells, n_dt_frames, n_gt_frames,
-                             cell_gt_off, dt_frame_off, dt_frame_pos, gt_frame_off};
-    const int st = frames_build(src, a.ft, s);
-    if (st != TAOAMD_OK) return st;
+    const int si = track_index(t, s);
+    if (si != TAOAMD_OK) return si;
     if (n_gt_frames > 0)
         TAO_TIMED("ident_share_kernel", s,
                   ident_share_kernel<<<(unsigned)((n_gt_frames + TI_TILE - 1) / TI_TILE), TI_TILE,
@@ -375,24 +351,19 @@ extern "C" int taoamd_track_identity_assign(
     const int32_t *gt_frame_off, const int32_t *share, int64_t *cat_counts, int32_t *gt_ident,
     int32_t *dt_ident, int32_t *status, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!ident_sizes_ok(n_dt, n_gt, n_gt_frames) || n_cells < 0 || n_cells > 0x7fffffff ||
-        n_iou < 0 || n_dt_frames < 0 || n_dt_frames > 0x7fffffff || n_cat <= 0)
-        return TAOAMD_ERR_ARG;
-    if (!cat_counts || !status || !workspace) return TAOAMD_ERR_ARG;
-    if (n_cells > 0 && (!cell_dt_off || !cell_gt_off || !cell_iou_off)) return TAOAMD_ERR_ARG;
-    if (n_dt > 0 && (!dt_cat || !dt_flags || !dt_frame_off || !dt_ident)) return TAOAMD_ERR_ARG;
-    if (n_gt > 0 && (!gt_cat || !gt_flags || !gt_frame_off || !gt_ident)) return TAOAMD_ERR_ARG;
+    TrackTables t = {n_dt, n_gt, n_cells, n_iou, n_dt_frames, n_gt_frames, cell_dt_off,
+                     cell_gt_off, cell_iou_off, gt_cat, gt_flags, dt_frame_off, nullptr, nullptr,
+                     gt_frame_off, nullptr, nullptr};
+    IdentArgs a;
+    if (n_cat <= 0 || !cat_counts || !status) return TAOAMD_ERR_ARG;
+    if (n_dt > 0 && (!dt_cat || !dt_flags || !dt_ident)) return TAOAMD_ERR_ARG;
+    if (n_gt > 0 && !gt_ident) return TAOAMD_ERR_ARG;
     if (n_iou > 0 && !share) return TAOAMD_ERR_ARG;
-    Carve c(workspace);
-    IdentArgs a = {};
-    ident_layout(c, n_dt, n_gt, n_gt_frames, a);
-    if (!c.fits(workspace, workspace_bytes)) return TAOAMD_ERR_WORKSPACE;
+    const int st = ident_args(a, t, TT_GT_CAT | TT_GT_FLAGS, workspace, workspace_bytes);
+    if (st != TAOAMD_OK) return st;
     hipStream_t s = (hipStream_t)stream;
-    a.n_dt = n_dt; a.n_gt = n_gt; a.n_cells = n_cells; a.n_iou = n_iou;
-    a.n_dt_frames = n_dt_frames; a.n_gt_frames = n_gt_frames; a.n_cat = n_cat;
-    a.cell_dt_off = cell_dt_off; a.cell_gt_off = cell_gt_off; a.cell_iou_off = cell_iou_off;
-    a.gt_cat = gt_cat; a.gt_flags = gt_flags; a.dt_cat = dt_cat; a.dt_flags = dt_flags;
-    a.dfoff = dt_frame_off; a.gfoff = gt_frame_off;
+    a.n_cat = n_cat;
+    a.dt_cat = dt_cat; a.dt_flags = dt_flags;
     a.share = const_cast<int32_t *>(share);
     a.cat_counts = (unsigned long long *)cat_counts;
     a.gt_ident = gt_ident; a.dt_ident = dt_ident; a.status = status;

@@ -30,8 +30,7 @@
 //                     the nine columns of an episode as one 36-byte piece.
 //   occ_scan_kernel   one workgroup: the tracks' episode counts -> ep_off
 // Everything is an integer; every record has one place.
-#include "common.hpp"
-#include "workspace.hpp"
+#include "track_tables.hpp"
 
 using namespace taoamd;
 
@@ -96,9 +95,8 @@ __global__ __launch_bounds__(256) void occ_walk_kernel(OccArgs a)
                     + __builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
     if (g >= a.n_gt) return;                 // (whole wavefronts)
     const int lane = lane_id();
-    // (offsets clamped to the table: a bad CSR reads wrong frames, never past an end)
-    const int64_t s = clamp64(a.gfoff[g], 0, a.n_gt_frames);
-    const int64_t e = clamp64(a.gfoff[g + 1], s, a.n_gt_frames);
+    const TrackSpan f = track_span(a.gfoff, g, a.n_gt_frames);
+    const int64_t s = f.first, e = f.end;
     const int32_t L = (int32_t)(e - s);
     int64_t row0 = 0, row1 = 0;
     if (FILL) {
@@ -224,7 +222,13 @@ __global__ __launch_bounds__(256) void occ_walk_kernel(OccArgs a)
     }
 }
 
-// ep_off[i] = the sum of n_ep[0 .. i), ep_off[n] the total; one workgroup
+// ep_off[i] = the sum of n_ep[0 .. i), ep_off[n] the total; one workgroup.
+// (The 1024-lane scan stays written out here and in CLEAR's two scan kernels.  One
+// helper for the three was tried in two forms, parent and new build in turn on
+// one MI355X, five runs each: with the wavefront's number taken in the helper
+// this kernel took 0.0415-0.0420 ms beside 0.0337-0.0344, taken once outside
+// the loop 0.0341-0.0346 beside 0.0336-0.0338; clear_scan_tile_kernel
+// 0.0270-0.0274 beside 0.0215-0.0218.  Each pair is of one run; the runs differ.)
 __global__ __launch_bounds__(1024) void occ_scan_kernel(const int32_t *__restrict__ n_ep,
                                                         int64_t *__restrict__ ep_off, int64_t n)
 {
@@ -266,8 +270,7 @@ static void occ_layout(Carve &c, int64_t n_gt, OccArgs &a)
 
 static bool occ_sizes_ok(int64_t n_gt, int64_t n_gt_frames, int32_t n_len)
 {
-    return n_gt >= 0 && n_gt <= 0x7fffffff && n_gt_frames >= 0 && n_gt_frames <= 0x7fffffff &&
-           n_len >= 1 && n_len <= TO_LEN;
+    return track_sizes_ok(0, n_gt, n_gt_frames, 0) && n_len >= 1 && n_len <= TO_LEN;
 }
 
 extern "C" size_t taoamd_track_occlusion_workspace(int64_t n_gt, int64_t n_gt_frames,

@@ -593,7 +593,7 @@ class Workspace:
         self.assoc_frame_thr = None       # the frame_thr ws.assoc_best holds the followers of
         self.occ_ws = self.occ_gt = self.occ_off = self.occ_counts = self.occ_episodes = None
         self.ident_ws = self.ident_share = self.ident_cat_counts = None
-        self.ident_frame_thr = None       # the frame_thr ws.ident_dt holds the kept tracks of
+        self.ident_frame_thr = None       # the frame_thr ws.ident_keep holds the kept tracks of
         self.hota_ws = self.hota_mc = self.hota_lc = None
         self.clear_ws = self.clear_cand = self.clear_vis_counts = None
         self.occ_n = None                # episodes of the last stage_track_occlusion that read them
@@ -1363,6 +1363,21 @@ def _track_tables(dp, what):
     return sizes, cells, frames
 
 
+def _vis_windows(dp, vis_rng):
+    """The closed visibility windows of a stage that takes them, as float64[n_vis,
+    2], refused where the kernels cannot take them."""
+    vis_rng = np.ascontiguousarray(vis_rng if vis_rng is not None else [],
+                                   dtype=np.float64).reshape(-1, 2)
+    n_vis = len(vis_rng)
+    if n_vis > _lib.TRACK_ASSOCIATION_VIS:
+        raise _lib.TaoAmdError("%d visibility windows; the kernels take up to %d"
+                               % (n_vis, _lib.TRACK_ASSOCIATION_VIS))
+    if n_vis and dp.t.get("gt_frame_vis") is None:
+        raise _lib.TaoAmdError("visibility windows need the frames' visibility "
+                               "(engine.set_frame_visibility)")
+    return vis_rng
+
+
 def stage_track_association(dp, ws, frame_thr, vis_rng):
     """Per-frame followers of the ground-truth tracks (taoamd_track_association;
     the definition is in include/tao_amodal_hip.h): ws.assoc_follow[n_iou] in the
@@ -1376,15 +1391,8 @@ def stage_track_association(dp, ws, frame_thr, vis_rng):
     the first call and kept with the workspace."""
     sizes, cells, frames = _track_tables(dp, "association is")
     lib, t, dev = _lib.load(), dp.t, dp.device
-    vis_rng = np.ascontiguousarray(vis_rng if vis_rng is not None else [],
-                                   dtype=np.float64).reshape(-1, 2)
+    vis_rng = _vis_windows(dp, vis_rng)
     n_vis = len(vis_rng)
-    if n_vis > _lib.TRACK_ASSOCIATION_VIS:
-        raise _lib.TaoAmdError("%d visibility windows; the kernels take up to %d"
-                               % (n_vis, _lib.TRACK_ASSOCIATION_VIS))
-    if n_vis and t.get("gt_frame_vis") is None:
-        raise _lib.TaoAmdError("visibility windows need the frames' visibility "
-                               "(engine.set_frame_visibility)")
     n_gf = sizes[5]
     if ws.assoc_gt is None:
         ws.assoc_bytes = lib.taoamd_track_association_workspace(dp.n_dt, dp.n_gt, n_gf)
@@ -1478,13 +1486,14 @@ def stage_track_identity(dp, ws, frame_thr):
     frames with a box IoU >= `frame_thr` in (0, 1] --, ws.ident_cat_counts
     int64[n_cat, 6], ws.ident_gt int32[n_gt, 2] = {the assigned detection row or
     -1, its share}, ws.ident_dt int32[n_dt, 2] = {the assigned ground-truth row or
-    -1, kept}.  On request only.  Reads the track tables alone, like
+    -1, kept}, ws.ident_keep uint8[n_dt] = that `kept` column as the dt_keep table
+    HOTA and CLEAR read.  On request only.  Reads the track tables alone, like
     stage_track_association.  Raises if the assignment kernel reports a non-zero
     status (an exhausted loop bound, weights beyond 64-bit potentials): one
     synchronisation of the current stream.  Buffers are allocated
     on the first call and kept with the workspace: 4 bytes per pair of a cell, 8
-    per track, and a workspace of 56 bytes per detection track, 44 per ground-
-    truth track and 4 per ground-truth frame."""
+    per track and 1 more per detection track, and a workspace of 56 bytes per
+    detection track, 44 per ground-truth track and 4 per ground-truth frame."""
     sizes, cells, frames = _track_tables(dp, "identity is")
     lib, t, dev, s = _lib.load(), dp.t, dp.device, _stream()
     if ws.ident_ws is None:
@@ -1495,6 +1504,7 @@ def stage_track_identity(dp, ws, frame_thr):
                                           dtype=torch.int64, device=dev)
         ws.ident_gt = torch.empty((max(dp.n_gt, 1), 2), dtype=torch.int32, device=dev)
         ws.ident_dt = torch.empty((max(dp.n_dt, 1), 2), dtype=torch.int32, device=dev)
+        ws.ident_keep = torch.empty(max(dp.n_dt, 1), dtype=torch.uint8, device=dev)
         ws.ident_status = torch.empty(1, dtype=torch.int32, device=dev)
     _lib.check(lib.taoamd_track_identity_share(
         *sizes, float(frame_thr), *cells, *frames,
@@ -1506,6 +1516,7 @@ def stage_track_identity(dp, ws, frame_thr):
         _ptr(ws.ident_share), _ptr(ws.ident_cat_counts), _ptr(ws.ident_gt), _ptr(ws.ident_dt),
         _ptr(ws.ident_status), _ptr(ws.ident_ws), ws.ident_bytes, s),
         "taoamd_track_identity_assign")
+    ws.ident_keep.copy_(ws.ident_dt[:, 1])
     status = int(ws.ident_status.item())            # (synchronises)
     ws.ident_frame_thr = None
     if status:
@@ -1530,7 +1541,7 @@ def stage_track_hota(dp, ws, alphas, frame_thr):
     synchronisation of the current stream.  Buffers are allocated on the first
     call and kept with the workspace: 8 bytes per pair of a cell for pot and 12
     per (alpha, pair) for mc and lc, regrown where a call brings more alphas, 12
-    per ground-truth frame, 1 per detection track, and a workspace of 64 bytes
+    per ground-truth frame, and a workspace of 64 bytes
     per detection track, 68 per ground-truth track and 4 per ground-truth frame."""
     sizes, cells, frames = _track_tables(dp, "HOTA is")
     lib, t, dev, s = _lib.load(), dp.t, dp.device, _stream()
@@ -1547,7 +1558,6 @@ def stage_track_hota(dp, ws, alphas, frame_thr):
         ws.hota_bytes = lib.taoamd_track_hota_workspace(dp.n_dt, dp.n_gt, n_gf)
         ws.hota_ws = torch.empty(max(int(ws.hota_bytes), 256), dtype=torch.uint8, device=dev)
         ws.hota_pot = torch.empty(max(dp.n_iou, 1), dtype=torch.int64, device=dev)
-        ws.hota_keep = torch.empty(max(dp.n_dt, 1), dtype=torch.uint8, device=dev)
         ws.hota_match = torch.empty(max(n_gf, 1), dtype=torch.int32, device=dev)
         ws.hota_match_iou = torch.empty(max(n_gf, 1), dtype=torch.float64, device=dev)
         ws.hota_status = torch.empty(1, dtype=torch.int32, device=dev)
@@ -1558,8 +1568,7 @@ def stage_track_hota(dp, ws, alphas, frame_thr):
     ws.hota_tp = torch.empty((dp.n_cat, n_alpha), dtype=torch.int64, device=dev)
     ws.hota_loc = torch.empty((dp.n_cat, n_alpha), dtype=torch.int64, device=dev)
     ws.hota_ass = torch.empty((dp.n_cat, n_alpha, 3), dtype=torch.int64, device=dev)
-    ws.hota_keep.copy_(ws.ident_dt[:, 1])
-    tables = (*cells, _ptr(t["gt_flags"]), _ptr(ws.hota_keep), *frames)
+    tables = (*cells, _ptr(t["gt_flags"]), _ptr(ws.ident_keep), *frames)
     _lib.check(lib.taoamd_track_hota_align(
         *sizes, *tables, _ptr(ws.hota_pot), _ptr(ws.hota_ws), ws.hota_bytes, s),
         "taoamd_track_hota_align")
@@ -1593,20 +1602,13 @@ def stage_track_clear(dp, ws, frame_thr, vis_rng):
     read between count and fill, the status word at the end: two synchronisations
     of the current stream; a non-zero status raises.  Buffers are allocated on the
     first call and kept with the workspace: 22 bytes per ground-truth frame, 16
-    per candidate (regrown where a call finds more), 16 per ground-truth track, 1
-    per detection track, and a workspace of 144 bytes per detection track, 132 per
+    per candidate (regrown where a call finds more), 16 per ground-truth track,
+    and a workspace of 144 bytes per detection track, 132 per
     ground-truth track and 8 per ground-truth frame."""
     sizes, cells, frames = _track_tables(dp, "CLEAR is")
     lib, t, dev, s = _lib.load(), dp.t, dp.device, _stream()
-    vis_rng = np.ascontiguousarray(vis_rng if vis_rng is not None else [],
-                                   dtype=np.float64).reshape(-1, 2)
+    vis_rng = _vis_windows(dp, vis_rng)
     n_vis = len(vis_rng)
-    if n_vis > _lib.TRACK_ASSOCIATION_VIS:
-        raise _lib.TaoAmdError("%d visibility windows; the kernels take up to %d"
-                               % (n_vis, _lib.TRACK_ASSOCIATION_VIS))
-    if n_vis and t.get("gt_frame_vis") is None:
-        raise _lib.TaoAmdError("visibility windows need the frames' visibility "
-                               "(engine.set_frame_visibility)")
     frame_thr = float(frame_thr)
     if ws.ident_ws is None or ws.ident_frame_thr != frame_thr:
         stage_track_identity(dp, ws, frame_thr)
@@ -1614,7 +1616,6 @@ def stage_track_clear(dp, ws, frame_thr, vis_rng):
     if ws.clear_ws is None:
         ws.clear_bytes = lib.taoamd_track_clear_workspace(n_dt, n_gt, n_gf)
         ws.clear_ws = torch.empty(max(int(ws.clear_bytes), 256), dtype=torch.uint8, device=dev)
-        ws.clear_keep = torch.empty(max(n_dt, 1), dtype=torch.uint8, device=dev)
         ws.clear_off = torch.empty(n_gf + 1, dtype=torch.int64, device=dev)
         ws.clear_step = torch.empty(max(n_gf, 1), dtype=torch.uint8, device=dev)
         ws.clear_match = torch.empty(max(n_gf, 1), dtype=torch.int32, device=dev)
@@ -1630,9 +1631,8 @@ def stage_track_clear(dp, ws, frame_thr, vis_rng):
                                           dtype=torch.int64, device=dev)
     if not n_vis:
         ws.clear_vis_counts = None
-    ws.clear_keep.copy_(ws.ident_dt[:, 1])
     tables = (n_dt, n_gt, n_cells, n_df, n_gf, frame_thr, cells[0], cells[1],
-              _ptr(t["gt_flags"]), _ptr(ws.clear_keep), *frames)
+              _ptr(t["gt_flags"]), _ptr(ws.ident_keep), *frames)
     _lib.check(lib.taoamd_track_clear_count(
         *tables, _ptr(ws.clear_off), _ptr(ws.clear_step), _ptr(ws.clear_ws), ws.clear_bytes, s),
         "taoamd_track_clear_count")

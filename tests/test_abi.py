@@ -155,6 +155,11 @@ def _workspace_shapes():
         for n_cat in (1, 100, 1203):
             for n_rng in (6, 20):
                 yield "taoamd_accumulate_workspace", (n, n_cat, n_rng)
+        n_dt, n_gt, n_gf = n, n // 2, min(4 * n, 2 ** 31 - 2)
+        if n_dt + n_gt <= 2 ** 31 - 1:      # (the search stores hold n_dt + n_gt entries)
+            for name in ("association", "identity", "hota", "clear"):
+                yield "taoamd_track_%s_workspace" % name, (n_dt, n_gt, n_gf)
+            yield "taoamd_track_occlusion_workspace", (n_gt, n_gf, 3)
     for n_cat in (1, 100, 1203):
         for n_rng in (6, 20):
             for world in (1, 8):
@@ -162,6 +167,7 @@ def _workspace_shapes():
 
 
 # what the commit before the layout functions reported, in _workspace_shapes() order
+# (the track analyses: the commit before their shared search store)
 _WS_BYTES_BEFORE = {
     "taoamd_sort_workspace": [18688, 18688, 86272, 87296, 36767488, 524317440, 52613366016],
     "taoamd_sort_segments_workspace": [7168, 7168, 74752, 75776, 36551168, 521387520, 52320516096],
@@ -171,6 +177,11 @@ _WS_BYTES_BEFORE = {
     "taoamd_track_mask_iou_workspace": [256, 1024, 107264, 108032, 57000448, 813200384, 81604378880],
     "taoamd_accumulate_workspace": [65792, 212224, 5869312, 20033024, 70531328, 240871168, 71424, 234752, 5874944, 20055552, 70536960, 240893696, 129280, 466432, 5932800, 20287232, 70595072, 241125376, 134912, 488960, 5938432, 20309760, 70600704, 241147904, 34263808, 136934400, 40067584, 156755456, 104729600, 377593600, 487919872, 1950625792, 493723392, 1970446592, 558385664, 2191284736, 48955980544, 195723207680, 48961783808, 195743028480, 49026446080, 195963866624],
     "taoamd_exchange_workspace": [1792, 5888, 3072, 18432, 66304, 523776, 219136, 1744640, 787456, 6295040, 2623232, 20981248],
+    "taoamd_track_association_workspace": [256, 768, 231168, 231680, 123000320, 1754800384],
+    "taoamd_track_occlusion_workspace": [256, 256, 5888, 5888, 3000320, 42800384],
+    "taoamd_track_identity_workspace": [256, 2560, 264960, 267264, 141001472, 2011600896],
+    "taoamd_track_hota_workspace": [256, 3072, 321280, 324096, 171001856, 2439601152],
+    "taoamd_track_clear_workspace": [512, 7680, 681984, 689152, 363051776, 5179471616],
 }
 
 
@@ -254,6 +265,30 @@ def test_entry_points_refuse_a_workspace_below_the_reported_size():
     calls.append(("taoamd_flat_runs", (n, p, p, p, p, p, p, nb, None)))
     calls.append(("taoamd_flat_runs_by", (n, p, p, p, p, p, p, p, nb, None)))
     calls.append(("taoamd_flat_runs64_by", (n, p, p, p, p, p, p, p, nb, None)))
+    # the track analyses: (n_dt, n_gt, n_cells, n_iou, n_dt_frames, n_gt_frames) and the tables
+    n_dt, n_gt, n_gf = 1000, 70, 3000
+    sizes = (n_dt, n_gt, 50, 9000, 40000, n_gf)
+    nb = int(lib.taoamd_track_association_workspace(n_dt, n_gt, n_gf)) - 1
+    calls.append(("taoamd_track_association", (*sizes, K, 2, 0.5, *[p] * 20, nb, None)))
+    edges = np.array([1, 3, 6], dtype=np.int32)       # (read on the host: starts at 1, ascends)
+    nb = int(lib.taoamd_track_occlusion_workspace(n_gt, n_gf, 3)) - 1
+    occ = (n_gt, n_gf, K, 3, 3, 0.0, 0.1, edges.ctypes.data, p, p, p, p, p)
+    calls.append(("taoamd_track_occlusion_count", (*occ, p, p, p, p, nb, None)))
+    calls.append(("taoamd_track_occlusion_fill", (*occ, p, 10, p, p, nb, None)))
+    nb = int(lib.taoamd_track_identity_workspace(n_dt, n_gt, n_gf)) - 1
+    calls.append(("taoamd_track_identity_share", (*sizes, 0.5, *[p] * 11, nb, None)))
+    calls.append(("taoamd_track_identity_assign", (*sizes, K, *[p] * 15, nb, None)))
+    alphas = np.array([0.25, 0.5, 0.75])              # (read on the host: ascending)
+    nb = int(lib.taoamd_track_hota_workspace(n_dt, n_gt, n_gf)) - 1
+    calls.append(("taoamd_track_hota_align", (*sizes, *[p] * 13, nb, None)))
+    calls.append(("taoamd_track_hota_match", (*sizes, 3, alphas.ctypes.data, *[p] * 18, nb, None)))
+    calls.append(("taoamd_track_hota_reduce", (*sizes, K, 3, *[p] * 13, nb, None)))
+    nb = int(lib.taoamd_track_clear_workspace(n_dt, n_gt, n_gf)) - 1
+    cand = (n_dt, n_gt, 50, 40000, n_gf, 0.5, *[p] * 10)
+    calls.append(("taoamd_track_clear_count", (*cand, p, p, p, nb, None)))
+    calls.append(("taoamd_track_clear_fill", (*cand, p, 10, p, p, p, p, nb, None)))
+    calls.append(("taoamd_track_clear_walk", (n_dt, n_gt, 50, n_gf, 10, *[p] * 16, nb, None)))
+    calls.append(("taoamd_track_clear_reduce", (n_dt, n_gt, n_gf, 10, K, 2, *[p] * 14, nb, None)))
     for name, args in calls:
         assert getattr(lib, name)(*args) == 4, name
 

@@ -239,7 +239,8 @@ def test_all_three_on_the_seeded_table_twice(seeded):
 # the match alone on given pot tables: one-frame cells, each one frame group
 # ---------------------------------------------------------------------------
 SHAPES = [(1, 1), (1, 65), (2, 1), (2, 2), (3, 2), (2, 3), (63, 64), (64, 64), (65, 64),
-          (3, 256), (2, 257), (257, 2)]
+          (3, 256), (2, 257), (257, 2),
+          (3, 128), (3, 129), (129, 3)]     # the edge of TH_LDS: the state leaves LDS
 FAMILIES = [("dense", 1), ("dense", 19), ("dense", 32), ("sparse", 19), ("equal", 1),
             ("permutation", 32), ("zero_row_and_column", 19), ("w_zero", 32)]
 

@@ -445,7 +445,7 @@ def hota(a, res, dp, ws, timed):
              int(t["gt_frame_pos"].numel()))
     cells = (t["cell_dt_off"].data_ptr(), t["cell_gt_off"].data_ptr(),
              t["cell_iou_off"].data_ptr())
-    tables = (*cells, t["gt_flags"].data_ptr(), ws.hota_keep.data_ptr(),
+    tables = (*cells, t["gt_flags"].data_ptr(), ws.ident_keep.data_ptr(),
               t["dt_frame_off"].data_ptr(), t["dt_frame_pos"].data_ptr(),
               t["dt_frame_box"].data_ptr(), t["gt_frame_off"].data_ptr(),
               t["gt_frame_pos"].data_ptr(), t["gt_frame_box"].data_ptr())
@@ -540,7 +540,7 @@ def clear(a, res, gt, fl, dp, ws, timed):
     row, q, iou = ws.clear_cand
     rng_t = torch.from_numpy(windows).to(dp.device)
     tables = (dp.n_dt, dp.n_gt, dp.n_cells, n_df, n_gf, thr, t["cell_dt_off"].data_ptr(),
-              t["cell_gt_off"].data_ptr(), t["gt_flags"].data_ptr(), ws.clear_keep.data_ptr(),
+              t["cell_gt_off"].data_ptr(), t["gt_flags"].data_ptr(), ws.ident_keep.data_ptr(),
               t["dt_frame_off"].data_ptr(), t["dt_frame_pos"].data_ptr(),
               t["dt_frame_box"].data_ptr(), t["gt_frame_off"].data_ptr(),
               t["gt_frame_pos"].data_ptr(), t["gt_frame_box"].data_ptr())
