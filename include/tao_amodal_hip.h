@@ -1820,6 +1820,84 @@ int taoamd_track_clear_reduce(int64_t n_dt, int64_t n_gt, int64_t n_gt_frames, i
                               int64_t *vis_counts, void *workspace, size_t workspace_bytes,
                               void *stream);
 
+/* ---- track-level score thresholds (csrc/track_identity.hip) --------------------------
+ * The track tables hold every detection track up to the max_dets cut, whatever
+ * its score: Track-AP integrates over the ranking.  The identity, HOTA and CLEAR
+ * need an operating point -- "the tracks at or above a score".  WHOLE tracks are
+ * thresholded, by the score Track-AP ranks them by; a box is never dropped from
+ * a track.  The reference has no counterpart; the definition is this library's.
+ *
+ * The pass rule.  The score of detection track d is dt_score[d], the column of
+ * the track table (the mean the table build forms).  A threshold table is
+ * thr double[n_thr][n_cat] (device), 1 <= n_thr <= TAOAMD_TRACK_SCORE_THRS; a row
+ * is a LAYER.  d passes layer t iff
+ *     0 <= dt_cat[d] < n_cat,
+ *     dt_score[d] >= thr[t][dt_cat[d]]   (an IEEE comparison: a NaN on either
+ *                                         side does not pass, -inf passes every
+ *                                         score that is not a NaN, -0.0 >= 0.0
+ *                                         passes), and
+ *     base is NULL or base[d] != 0       (uint8[n_dt]: a column to AND with, as
+ *                                         the identity's kept column).
+ * taoamd_track_score_pass fills pass uint8[n_thr][n_dt] with 0 or 1 and writes
+ * nothing else; a lane per (layer, track).  n_dt = 0 is allowed (nothing is
+ * launched).  TAOAMD_ERR_ARG, before any device call: n_dt below 0 or beyond
+ * int32, n_cat <= 0, n_thr outside [1, TAOAMD_TRACK_SCORE_THRS], thr NULL, or
+ * n_dt > 0 and dt_score, dt_cat or pass NULL.  A layer of pass is a dt_keep
+ * column of taoamd_track_hota_* and taoamd_track_clear_*.
+ *
+ * The layered identity assignment.  taoamd_track_identity_assign_at takes the
+ * arguments of taoamd_track_identity_assign, n_thr after n_cat and dt_pass
+ * uint8[n_thr][n_dt] after dt_flags, and its outputs gain a leading layer axis:
+ * cat_counts int64[n_thr][n_cat][6], gt_ident int32[n_thr][n_gt][2] (may be
+ * NULL: not written), dt_ident int32[n_thr][n_dt][2].  Layer t is the
+ * identity's assignment over the detection tracks with dt_pass[t][d] != 0: a
+ * track that does not pass is neither a candidate nor counted, and its dt_ident
+ * is {-1, 0}.  The set-aside rules (a) and (b) read a track's OWN shares alone,
+ * so the tracks kept at layer t are those kept without a threshold AND passing:
+ *     kept_t[d] = kept[d] && dt_pass[t][d] != 0;
+ * the eligible ground truths and gt_tracks / gt_frames are the same in every
+ * layer.  EXACTLY: layer t is, word for word in cat_counts, gt_ident and
+ * dt_ident, what taoamd_track_identity_assign writes for the input in which the
+ * share rows of the tracks with dt_pass[t][d] == 0 are zeroed and
+ * TAOAMD_DT_IGNORE_UNMATCHED is set in their dt_flags (rule (b) sets them
+ * aside).  Word for word, not only in the counts, because rows without a
+ * positive share are compacted away before the solver runs: both inputs hand it
+ * the same rows and columns in the same order.
+ * The kernel is that of taoamd_track_identity_assign with the layer as the
+ * launch's second index: a wavefront per (cell, layer), the same LDS state per
+ * wavefront; the cells whose larger side exceeds 256 have a slice of the search
+ * store per layer, and every cell a slice of the index lists per layer.
+ * taoamd_track_identity_assign is the one-layer instance without a mask.  One
+ * int32 *status holds the GREATEST code any (cell, layer) stored (an atomic
+ * max), 0 otherwise.  No size limit, no TAOAMD_ERR_TOO_LARGE; every loop has a
+ * bound known at entry, and nothing spins.  share is read, never written: one
+ * taoamd_track_identity_share serves every layer.
+ * TAOAMD_ERR_ARG: what taoamd_track_identity_assign refuses (gt_ident excepted),
+ * n_thr outside [1, TAOAMD_TRACK_SCORE_THRS], n_dt > 0 and dt_pass NULL;
+ * TAOAMD_ERR_WORKSPACE: fewer bytes than
+ * taoamd_track_identity_layers_workspace(n_dt, n_gt, n_gt_frames, n_thr) (the
+ * identity's workspace with n_thr slices of the 40 + 4 bytes per row; it answers
+ * 0 to sizes it refuses, and for n_thr = 1 what taoamd_track_identity_workspace
+ * answers).  Both are answered before the first device call, with every output
+ * untouched. */
+#define TAOAMD_TRACK_SCORE_THRS 64          /* layers of a threshold table, at most */
+int taoamd_track_score_pass(int64_t n_dt, int32_t n_cat, int32_t n_thr, const double *dt_score,
+                            const int32_t *dt_cat, const double *thr, const uint8_t *base,
+                            uint8_t *pass, void *stream);
+size_t taoamd_track_identity_layers_workspace(int64_t n_dt, int64_t n_gt, int64_t n_gt_frames,
+                                              int32_t n_thr);
+int taoamd_track_identity_assign_at(int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou,
+                                    int64_t n_dt_frames, int64_t n_gt_frames, int32_t n_cat,
+                                    int32_t n_thr, const int32_t *cell_dt_off,
+                                    const int32_t *cell_gt_off, const int64_t *cell_iou_off,
+                                    const int32_t *gt_cat, const uint8_t *gt_flags,
+                                    const int32_t *dt_cat, const uint8_t *dt_flags,
+                                    const uint8_t *dt_pass, const int32_t *dt_frame_off,
+                                    const int32_t *gt_frame_off, const int32_t *share,
+                                    int64_t *cat_counts, int32_t *gt_ident, int32_t *dt_ident,
+                                    int32_t *status, void *workspace, size_t workspace_bytes,
+                                    void *stream);
+
 /* ---- multi-GPU result exchange (category-partitioned evaluation) -------------------
  * No reference counterpart (the reference is single-process); these carry the
  * tables of taoamd_accumulate_compact between ranks and end in the layout of

@@ -125,6 +125,7 @@ OCC_TRACK_COLUMNS = ("episodes", "frames", "kept", "switched_lost")
 OCC_COUNT_COLUMNS = ("episodes", "frames", "covered", "held", "start", "unfollowed", "end",
                      "kept", "switched", "lost", "gap")
 IDENT_CAT_COLUMNS = ("gt_tracks", "gt_frames", "dt_tracks", "dt_frames", "idtp", "pairs")
+TRACK_SCORE_THRS = _define("TRACK_SCORE_THRS")
 HOTA_ONE = _define("HOTA_ONE")
 TRACK_HOTA_ALPHAS = _define("TRACK_HOTA_ALPHAS")
 HOTA_RATIOS = ("hota", "deta", "assa", "detre", "detpr", "assre", "asspr", "loca")

@@ -187,7 +187,7 @@ extern "C" const char *taoamd_strerror(int status)
 
 extern "C" const char *taoamd_last_error(void) { return taoamd::g_err; }
 
-extern "C" int taoamd_version(void) { return 112; }
+extern "C" int taoamd_version(void) { return 113; }
 
 extern "C" int taoamd_thresholds_host(double *iou_thrs, double *rec_thrs)
 {

@@ -41,10 +41,18 @@
 //                        that `pairs` is unique as well.
 //                        The count tables are integer adds, one per (wavefront
 //                        step, category, column) (wave_add of common.hpp).
+//
+// taoamd_track_score_pass, taoamd_track_identity_assign_at (the header's section
+// "track-level score thresholds"): which detection tracks take part at a score.
+//   score_pass_kernel    lane = (layer, detection track): the pass rule
+//   ident_assign_kernel<true>  the kernel above with the layer as blockIdx.y: a
+//                        wavefront per (cell, layer); kept is kept AND pass; the
+//                        layer's slice of idx[], of the search store and of the
+//                        outputs; *status by an atomic max
 // Registers (hipcc -Rpass-analysis=kernel-resource-usage, gfx950):
 //   ident_share_kernel 38 VGPRs, 30 SGPRs, 8 waves/SIMD, no scratch, no LDS;
 //   ident_assign_kernel 54 VGPRs, 11 264 B of LDS (a workgroup is one wavefront:
-//   14 cells a CU by LDS).
+//   14 cells a CU by LDS), the same for both instances; score_pass_kernel 6 VGPRs.
 #include "assign_solve.hpp"
 #include "track_tables.hpp"
 
@@ -76,6 +84,10 @@ struct IdentArgs {
     FrameTables ft;                  // the frame index (track_frames.hpp)
     SearchStore store;               // the cells that do not fit in LDS
     int32_t *sidx;                   // [n_dt + n_gt]: the cells' two index lists
+    // the layered call alone (taoamd_track_identity_assign_at): layer t has the
+    // outputs, the store and sidx at t times their size, and reads dt_pass[t][.]
+    int32_t n_thr;
+    const uint8_t *dt_pass;          // [n_thr][n_dt]
 };
 
 __global__ __launch_bounds__(TI_TILE) void ident_share_kernel(IdentArgs a)
@@ -120,6 +132,31 @@ __global__ __launch_bounds__(256) void ident_init_kernel(IdentArgs a)
     if (i < a.n_dt) reinterpret_cast<int2 *>(a.dt_ident)[i] = make_int2(-1, 0);
 }
 
+// {-1, 0} into the rows of every layer: n_gi = n_thr * n_gt words of gt_ident (0
+// without one), n_di = n_thr * n_dt of dt_ident
+__global__ __launch_bounds__(256) void ident_init_layers_kernel(int2 *gt_ident, int64_t n_gi,
+                                                                int2 *dt_ident, int64_t n_di)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_gi) gt_ident[i] = make_int2(-1, 0);
+    if (i < n_di) dt_ident[i] = make_int2(-1, 0);
+}
+
+// The pass rule of the track-level score thresholds: lane = detection track,
+// blockIdx.y = layer.  A NaN on either side compares false.
+__global__ __launch_bounds__(256) void score_pass_kernel(int64_t n_dt, int32_t n_cat,
+                                                         const double *dt_score,
+                                                         const int32_t *dt_cat, const double *thr,
+                                                         const uint8_t *base, uint8_t *pass)
+{
+    const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= n_dt) return;
+    const int32_t cat = dt_cat[d];
+    bool on = cat >= 0 && cat < n_cat && (!base || base[d] != 0);
+    if (on) on = dt_score[d] >= thr[(int64_t)blockIdx.y * n_cat + cat];
+    pass[(int64_t)blockIdx.y * n_dt + d] = on ? 1 : 0;
+}
+
 // A cell's share matrix: entry (d, g) in-cell, 0 outside the table; a share is a
 // count, so a negative word reads as 0 too
 struct CellShare {
@@ -147,7 +184,9 @@ struct IdentWeight {
     }
 };
 
-__global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
+// AT: the layered call -- blockIdx.y is the layer, a wavefront per (cell, layer);
+// the one-layer, mask-free instance is the kernel as it was.
+template <bool AT> __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
 {
     // (SearchLds, track_cell, assign_sides and assign_pairs, written out; the tie
     // rule here is the other one: the detections become the rows when equal.
@@ -166,7 +205,16 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
     const int64_t G = clamp64(a.cell_gt_off[cell + 1], g0, a.n_gt) - g0;
     if (D == 0 && G == 0) return;
     CellShare S = {a.share, a.cell_iou_off[cell], G, a.n_iou};
-    const int64_t base = d0 + g0;                    // the cell's slice of the state arrays
+    int64_t base = d0 + g0;                          // the cell's slice of the state arrays
+    const uint8_t *pass = nullptr;
+    if constexpr (AT) {
+        const int64_t layer = blockIdx.y;
+        base += layer * (a.n_dt + a.n_gt);           // ... of the layer's slice
+        a.cat_counts += layer * a.n_cat * TI_NCAT;
+        if (a.gt_ident) a.gt_ident += layer * a.n_gt * 2;
+        a.dt_ident += layer * a.n_dt * 2;
+        pass = a.dt_pass + layer * a.n_dt;
+    }
     int32_t *dlist = a.sidx + base, *glist = a.sidx + base + D;
     const uint64_t below = (1ull << lane) - 1ull;
 
@@ -188,6 +236,11 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
         long long frames = 0;
         if (live) {
             kept = !(mi > me) && !((a.dt_flags[d0 + d] & TAOAMD_DT_IGNORE_UNMATCHED) && me == 0);
+            if constexpr (AT) {
+                // kept at a layer is kept AND pass: a track that does not pass is
+                // neither compacted nor counted, so no column is kept for its sake
+                if (!pass[d0 + d]) kept = false;
+            }
             cat = a.dt_cat[d0 + d];
             frames = track_span(a.dfoff, d0 + d, a.n_dt_frames).len();
             a.dt_ident[(d0 + d) * 2 + 1] = kept;
@@ -234,7 +287,10 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
     const unsigned long long nn = (unsigned long long)n * ((unsigned long long)n + 1);
     const unsigned long long ww = (unsigned long long)top + 1;
     if (__umul64hi(nn, ww) != 0 || nn * ww >= (1ull << 62)) {
-        if (lane == 0) *a.status = 2;
+        if (lane == 0) {
+            if constexpr (AT) atomicMax(a.status, 2);
+            else *a.status = 2;
+        }
         return;
     }
     const int32_t *rl = rows_are_dt ? dlist : glist, *cl = rows_are_dt ? glist : dlist;
@@ -256,7 +312,10 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
         ok = assign_solve(W, s, n, m);
     }
     if (!ok) {
-        if (lane == 0) *a.status = 1;
+        if (lane == 0) {
+            if constexpr (AT) atomicMax(a.status, 1);
+            else *a.status = 1;
+        }
         return;
     }
     // the pairs with a positive share
@@ -269,7 +328,8 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
             const int64_t d = rows_are_dt ? r : c, g = rows_are_dt ? c : r;
             w = S.at(d, g);
             if (w > 0) {
-                reinterpret_cast<int2 *>(a.gt_ident)[g0 + g] = make_int2((int32_t)(d0 + d), w);
+                if (!AT || a.gt_ident)
+                    reinterpret_cast<int2 *>(a.gt_ident)[g0 + g] = make_int2((int32_t)(d0 + d), w);
                 a.dt_ident[(d0 + d) * 2] = (int32_t)(g0 + g);
                 cat = a.gt_cat[g0 + g];
             }
@@ -279,13 +339,20 @@ __global__ __launch_bounds__(WAVE) void ident_assign_kernel(IdentArgs a)
     }
 }
 
-// The tables of both calls, in buffer order: a function of (n_dt, n_gt, n_gt_frames)
+// The tables of the calls, in buffer order: a function of (n_dt, n_gt, n_gt_frames)
+// and the layers (1 but for the layered assignment: a slice of the search store
+// and of the index lists per layer)
 static void ident_layout(Carve &c, int64_t n_dt, int64_t n_gt, int64_t n_gt_frames,
-                         FrameTables &ft, IdentArgs &a)
+                         FrameTables &ft, IdentArgs &a, int32_t n_thr = 1)
 {
     frames_layout(c, n_dt, n_gt, n_gt_frames, ft);
-    a.store.layout(c, (size_t)(n_dt + n_gt));
-    a.sidx = c.take<int32_t>((size_t)(n_dt + n_gt));
+    a.store.layout(c, (size_t)n_thr * (size_t)(n_dt + n_gt));
+    a.sidx = c.take<int32_t>((size_t)n_thr * (size_t)(n_dt + n_gt));
+}
+
+static inline bool ident_layers_ok(int32_t n_thr)
+{
+    return n_thr >= 1 && n_thr <= TAOAMD_TRACK_SCORE_THRS;
 }
 
 extern "C" size_t taoamd_track_identity_workspace(int64_t n_dt, int64_t n_gt, int64_t n_gt_frames)
@@ -295,15 +362,23 @@ extern "C" size_t taoamd_track_identity_workspace(int64_t n_dt, int64_t n_gt, in
     return measure([&](Carve &c) { ident_layout(c, n_dt, n_gt, n_gt_frames, a.ft, a); });
 }
 
-// What the two entry points share: the common refusals, the carved workspace and
+extern "C" size_t taoamd_track_identity_layers_workspace(int64_t n_dt, int64_t n_gt,
+                                                         int64_t n_gt_frames, int32_t n_thr)
+{
+    if (!track_sizes_ok(n_dt, n_gt, n_gt_frames, TT_STORE) || !ident_layers_ok(n_thr)) return 0;
+    IdentArgs a;
+    return measure([&](Carve &c) { ident_layout(c, n_dt, n_gt, n_gt_frames, a.ft, a, n_thr); });
+}
+
+// What the entry points share: the common refusals, the carved workspace and
 // the common fields of the kernels' block
 static int ident_args(IdentArgs &a, TrackTables &t, unsigned need, void *workspace,
-                      size_t workspace_bytes)
+                      size_t workspace_bytes, int32_t n_thr = 1)
 {
     a = {};
     const int st = track_args(
         t, need | TT_IOU | TT_DT_OFF | TT_STORE, workspace, workspace_bytes,
-        [&](Carve &c) { ident_layout(c, t.n_dt, t.n_gt, t.n_gt_frames, t.ft, a); });
+        [&](Carve &c) { ident_layout(c, t.n_dt, t.n_gt, t.n_gt_frames, t.ft, a, n_thr); });
     track_fill(a, t);
     return st;
 }
@@ -343,6 +418,57 @@ extern "C" int taoamd_track_identity_share(
     return TAOAMD_OK;
 }
 
+// Both assignments: n_thr layers read dt_pass (AT), or the one layer without a
+// mask that taoamd_track_identity_assign is (gt_ident is then required)
+template <bool AT>
+static int ident_assign(TrackTables &t, int32_t n_cat, int32_t n_thr, const int32_t *dt_cat,
+                        const uint8_t *dt_flags, const uint8_t *dt_pass, const int32_t *share,
+                        int64_t *cat_counts, int32_t *gt_ident, int32_t *dt_ident, int32_t *status,
+                        void *workspace, size_t workspace_bytes, void *stream)
+{
+    IdentArgs a;
+    if (n_cat <= 0 || !cat_counts || !status) return TAOAMD_ERR_ARG;
+    if (AT && !ident_layers_ok(n_thr)) return TAOAMD_ERR_ARG;
+    if (t.n_dt > 0 && (!dt_cat || !dt_flags || !dt_ident || (AT && !dt_pass)))
+        return TAOAMD_ERR_ARG;
+    if (!AT && t.n_gt > 0 && !gt_ident) return TAOAMD_ERR_ARG;
+    if (t.n_iou > 0 && !share) return TAOAMD_ERR_ARG;
+    const int st = ident_args(a, t, TT_GT_CAT | TT_GT_FLAGS, workspace, workspace_bytes, n_thr);
+    if (st != TAOAMD_OK) return st;
+    hipStream_t s = (hipStream_t)stream;
+    a.n_cat = n_cat;
+    a.dt_cat = dt_cat; a.dt_flags = dt_flags;
+    a.share = const_cast<int32_t *>(share);
+    a.cat_counts = (unsigned long long *)cat_counts;
+    a.gt_ident = gt_ident; a.dt_ident = dt_ident; a.status = status;
+    a.n_thr = n_thr; a.dt_pass = dt_pass;
+    TAO_HIP(hipMemsetAsync(cat_counts, 0, (size_t)n_thr * n_cat * TI_NCAT * sizeof(int64_t), s));
+    TAO_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
+    if constexpr (AT) {
+        const int64_t n_gi = gt_ident ? n_thr * t.n_gt : 0, n_di = n_thr * t.n_dt;
+        const int64_t rows = n_di > n_gi ? n_di : n_gi;
+        if (rows > 0)
+            TAO_TIMED("ident_init_layers_kernel", s,
+                      ident_init_layers_kernel<<<(unsigned)((rows + 255) / 256), 256, 0, s>>>(
+                          reinterpret_cast<int2 *>(gt_ident), n_gi,
+                          reinterpret_cast<int2 *>(dt_ident), n_di));
+        if (t.n_cells > 0)
+            TAO_TIMED("ident_assign_at_kernel", s,
+                      ident_assign_kernel<true><<<dim3((unsigned)t.n_cells, (unsigned)n_thr), WAVE,
+                                                  0, s>>>(a));
+    } else {
+        const int64_t rows = t.n_dt > t.n_gt ? t.n_dt : t.n_gt;
+        if (rows > 0)
+            TAO_TIMED("ident_init_kernel", s,
+                      ident_init_kernel<<<(unsigned)((rows + 255) / 256), 256, 0, s>>>(a));
+        if (t.n_cells > 0)
+            TAO_TIMED("ident_assign_kernel", s,
+                      ident_assign_kernel<false><<<(unsigned)t.n_cells, WAVE, 0, s>>>(a));
+    }
+    TAO_LAUNCH_CHECK();
+    return TAOAMD_OK;
+}
+
 extern "C" int taoamd_track_identity_assign(
     int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou, int64_t n_dt_frames,
     int64_t n_gt_frames, int32_t n_cat, const int32_t *cell_dt_off, const int32_t *cell_gt_off,
@@ -354,28 +480,39 @@ extern "C" int taoamd_track_identity_assign(
     TrackTables t = {n_dt, n_gt, n_cells, n_iou, n_dt_frames, n_gt_frames, cell_dt_off,
                      cell_gt_off, cell_iou_off, gt_cat, gt_flags, dt_frame_off, nullptr, nullptr,
                      gt_frame_off, nullptr, nullptr};
-    IdentArgs a;
-    if (n_cat <= 0 || !cat_counts || !status) return TAOAMD_ERR_ARG;
-    if (n_dt > 0 && (!dt_cat || !dt_flags || !dt_ident)) return TAOAMD_ERR_ARG;
-    if (n_gt > 0 && !gt_ident) return TAOAMD_ERR_ARG;
-    if (n_iou > 0 && !share) return TAOAMD_ERR_ARG;
-    const int st = ident_args(a, t, TT_GT_CAT | TT_GT_FLAGS, workspace, workspace_bytes);
-    if (st != TAOAMD_OK) return st;
+    return ident_assign<false>(t, n_cat, 1, dt_cat, dt_flags, nullptr, share, cat_counts, gt_ident,
+                               dt_ident, status, workspace, workspace_bytes, stream);
+}
+
+extern "C" int taoamd_track_identity_assign_at(
+    int64_t n_dt, int64_t n_gt, int64_t n_cells, int64_t n_iou, int64_t n_dt_frames,
+    int64_t n_gt_frames, int32_t n_cat, int32_t n_thr, const int32_t *cell_dt_off,
+    const int32_t *cell_gt_off, const int64_t *cell_iou_off, const int32_t *gt_cat,
+    const uint8_t *gt_flags, const int32_t *dt_cat, const uint8_t *dt_flags,
+    const uint8_t *dt_pass, const int32_t *dt_frame_off, const int32_t *gt_frame_off,
+    const int32_t *share, int64_t *cat_counts, int32_t *gt_ident, int32_t *dt_ident,
+    int32_t *status, void *workspace, size_t workspace_bytes, void *stream)
+{
+    TrackTables t = {n_dt, n_gt, n_cells, n_iou, n_dt_frames, n_gt_frames, cell_dt_off,
+                     cell_gt_off, cell_iou_off, gt_cat, gt_flags, dt_frame_off, nullptr, nullptr,
+                     gt_frame_off, nullptr, nullptr};
+    return ident_assign<true>(t, n_cat, n_thr, dt_cat, dt_flags, dt_pass, share, cat_counts,
+                              gt_ident, dt_ident, status, workspace, workspace_bytes, stream);
+}
+
+extern "C" int taoamd_track_score_pass(int64_t n_dt, int32_t n_cat, int32_t n_thr,
+                                       const double *dt_score, const int32_t *dt_cat,
+                                       const double *thr, const uint8_t *base, uint8_t *pass,
+                                       void *stream)
+{
+    if (n_dt < 0 || n_dt > 0x7fffffff || n_cat <= 0 || !ident_layers_ok(n_thr) || !thr)
+        return TAOAMD_ERR_ARG;
+    if (n_dt > 0 && (!dt_score || !dt_cat || !pass)) return TAOAMD_ERR_ARG;
+    if (n_dt == 0) return TAOAMD_OK;
     hipStream_t s = (hipStream_t)stream;
-    a.n_cat = n_cat;
-    a.dt_cat = dt_cat; a.dt_flags = dt_flags;
-    a.share = const_cast<int32_t *>(share);
-    a.cat_counts = (unsigned long long *)cat_counts;
-    a.gt_ident = gt_ident; a.dt_ident = dt_ident; a.status = status;
-    TAO_HIP(hipMemsetAsync(cat_counts, 0, (size_t)n_cat * TI_NCAT * sizeof(int64_t), s));
-    TAO_HIP(hipMemsetAsync(status, 0, sizeof(int32_t), s));
-    const int64_t rows = n_dt > n_gt ? n_dt : n_gt;
-    if (rows > 0)
-        TAO_TIMED("ident_init_kernel", s,
-                  ident_init_kernel<<<(unsigned)((rows + 255) / 256), 256, 0, s>>>(a));
-    if (n_cells > 0)
-        TAO_TIMED("ident_assign_kernel", s,
-                  ident_assign_kernel<<<(unsigned)n_cells, WAVE, 0, s>>>(a));
+    TAO_TIMED("score_pass_kernel", s,
+              score_pass_kernel<<<dim3((unsigned)((n_dt + 255) / 256), (unsigned)n_thr), 256, 0,
+                                  s>>>(n_dt, n_cat, dt_score, dt_cat, thr, base, pass));
     TAO_LAUNCH_CHECK();
     return TAOAMD_OK;
 }

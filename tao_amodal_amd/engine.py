@@ -594,6 +594,9 @@ class Workspace:
         self.occ_ws = self.occ_gt = self.occ_off = self.occ_counts = self.occ_episodes = None
         self.ident_ws = self.ident_share = self.ident_cat_counts = None
         self.ident_frame_thr = None       # the frame_thr ws.ident_keep holds the kept tracks of
+        # the thresholded identity's own (stage_track_identity_at), never the above
+        self.at_ws = self.at_share = self.at_pass = self.at_cat_counts = None
+        self.at_frame_thr = None          # the frame_thr ws.at_share holds the shares of
         self.hota_ws = self.hota_mc = self.hota_lc = None
         self.clear_ws = self.clear_cand = self.clear_vis_counts = None
         self.occ_n = None                # episodes of the last stage_track_occlusion that read them
@@ -1526,7 +1529,99 @@ def stage_track_identity(dp, ws, frame_thr):
     ws.ident_frame_thr = float(frame_thr)
 
 
-def stage_track_hota(dp, ws, alphas, frame_thr):
+def _thr_table(dp, thr_table):
+    """A table of track-level score thresholds as float64[n_thr, n_cat], refused
+    where the kernels cannot take it."""
+    thr = np.ascontiguousarray(thr_table, dtype=np.float64)
+    if thr.ndim != 2 or thr.shape[1] != dp.n_cat:
+        raise _lib.TaoAmdError("a threshold table of shape %s; [n_thr, %d] is the tables'"
+                               % (thr.shape, dp.n_cat))
+    if not 1 <= len(thr) <= _lib.TRACK_SCORE_THRS:
+        raise _lib.TaoAmdError("%d threshold layers; the kernels take 1 to %d"
+                               % (len(thr), _lib.TRACK_SCORE_THRS))
+    return thr
+
+
+def stage_track_score_pass(dp, ws, thr_table, base):
+    """Which detection tracks lie at or above a score (taoamd_track_score_pass;
+    the rule is in include/tao_amodal_hip.h, section "track-level score
+    thresholds"): ws.at_pass uint8[n_thr, n_dt], 1 where dt_score >= `thr_table`
+    [layer, the track's category] (float64[n_thr, n_cat], 1 to 64 layers) and
+    `base` -- a uint8[n_dt] device tensor or None -- is not 0 there.  Returns it.
+    On request only; a buffer of its own, regrown where a call brings more layers."""
+    _track_tables(dp, "score thresholds are")
+    lib, t, dev = _lib.load(), dp.t, dp.device
+    thr = _thr_table(dp, thr_table)
+    n_thr = len(thr)
+    if t["dt_score"].dtype != torch.float64:
+        raise _lib.TaoAmdError("dt_score is %s; the pass rule reads doubles" % t["dt_score"].dtype)
+    if ws.at_pass is None or ws.at_pass.shape[0] < n_thr:
+        ws.at_pass = torch.empty((n_thr, max(dp.n_dt, 1)), dtype=torch.uint8, device=dev)
+    thr_t = torch.from_numpy(thr).to(dev)
+    out = ws.at_pass[:n_thr]
+    _lib.check(lib.taoamd_track_score_pass(
+        dp.n_dt, dp.n_cat, n_thr, _ptr(t["dt_score"]), _ptr(t["dt_cat"]), _ptr(thr_t), _ptr(base),
+        _ptr(out), _stream()), "taoamd_track_score_pass")
+    ws.at_thr = thr_t      # (read by the kernel of this stream: alive until it ran)
+    return out
+
+
+def stage_track_identity_at(dp, ws, frame_thr, thr_table, per_track=False):
+    """The identity's assignment over the detection tracks at or above a score,
+    a layer per row of `thr_table` float64[n_thr, n_cat] in ONE launch
+    (taoamd_track_score_pass, taoamd_track_identity_assign_at; the definition is
+    in include/tao_amodal_hip.h, section "track-level score thresholds"):
+    ws.at_cat_counts int64[n_thr, n_cat, 6], ws.at_dt int32[n_thr, n_dt, 2],
+    ws.at_keep uint8[n_thr, n_dt] = the layers' kept columns (kept AND pass: what
+    stage_track_hota and stage_track_clear take as `keep`), and with
+    per_track=True ws.at_gt int32[n_thr, n_gt, 2] (None otherwise).  share runs
+    once for all layers, and not at all where the workspace holds it for
+    `frame_thr`: ws.ident_share of stage_track_identity (ws.ident_frame_thr), or
+    this stage's own ws.at_share (ws.at_frame_thr).  Every buffer is this
+    stage's own: nothing stage_track_identity left is written.  Raises on a
+    non-zero status: one synchronisation of the current stream.  The workspace
+    is the identity's with 44 bytes per track and layer."""
+    sizes, cells, frames = _track_tables(dp, "identity is")
+    lib, t, dev, s = _lib.load(), dp.t, dp.device, _stream()
+    thr = _thr_table(dp, thr_table)
+    n_thr, frame_thr = len(thr), float(frame_thr)
+    if ws.at_ws is None or ws.at_layers < n_thr:
+        ws.at_bytes = lib.taoamd_track_identity_layers_workspace(dp.n_dt, dp.n_gt, sizes[5], n_thr)
+        ws.at_ws = torch.empty(max(int(ws.at_bytes), 256), dtype=torch.uint8, device=dev)
+        ws.at_layers = n_thr
+        ws.at_status = torch.empty(1, dtype=torch.int32, device=dev)
+    if ws.ident_ws is not None and ws.ident_frame_thr == frame_thr:
+        share = ws.ident_share
+    else:
+        if ws.at_share is None:
+            ws.at_share = torch.empty(max(dp.n_iou, 1), dtype=torch.int32, device=dev)
+        if ws.at_frame_thr != frame_thr:
+            ws.at_frame_thr = None
+            _lib.check(lib.taoamd_track_identity_share(
+                *sizes, frame_thr, *cells, *frames, _ptr(ws.at_share), _ptr(ws.at_ws),
+                ws.at_bytes, s), "taoamd_track_identity_share")
+            ws.at_frame_thr = frame_thr
+        share = ws.at_share
+    passed = stage_track_score_pass(dp, ws, thr, None)
+    ws.at_cat_counts = torch.empty((n_thr, dp.n_cat, len(_lib.IDENT_CAT_COLUMNS)),
+                                   dtype=torch.int64, device=dev)
+    ws.at_dt = torch.empty((n_thr, max(dp.n_dt, 1), 2), dtype=torch.int32, device=dev)
+    ws.at_gt = torch.empty((n_thr, max(dp.n_gt, 1), 2), dtype=torch.int32, device=dev) \
+        if per_track else None
+    _lib.check(lib.taoamd_track_identity_assign_at(
+        *sizes, dp.n_cat, n_thr, *cells, _ptr(t["gt_cat"]), _ptr(t["gt_flags"]),
+        _ptr(t["dt_cat"]), _ptr(t["dt_flags"]), _ptr(passed), frames[0], frames[3], _ptr(share),
+        _ptr(ws.at_cat_counts), _ptr(ws.at_gt), _ptr(ws.at_dt), _ptr(ws.at_status),
+        _ptr(ws.at_ws), ws.at_bytes, s), "taoamd_track_identity_assign_at")
+    ws.at_keep = ws.at_dt[:, :, 1].to(torch.uint8).contiguous()
+    status = int(ws.at_status.item())               # (synchronises)
+    if status:
+        raise _lib.TaoAmdError("taoamd_track_identity_assign_at: status %d (%s)" % (
+            status, "a search ran out of its loop bound" if status == 1 else
+            "a cell's weights exceed 64-bit potentials"))
+
+
+def stage_track_hota(dp, ws, alphas, frame_thr, keep=None):
     """HOTA's integer tables from a one-to-one assignment per frame
     (taoamd_track_hota_align, taoamd_track_hota_match, taoamd_track_hota_reduce;
     the definition is in include/tao_amodal_hip.h): ws.hota_tp and ws.hota_loc
@@ -1536,7 +1631,10 @@ def stage_track_hota(dp, ws, alphas, frame_thr):
     localisation thresholds `alphas` (1 to 32 doubles, TrackEval's eps already
     subtracted).  The detection tracks that take part are the identity's kept
     ones at `frame_thr`: stage_track_identity runs first unless the workspace
-    holds it for that threshold (ws.ident_frame_thr).  On request only.  Raises
+    holds it for that threshold (ws.ident_frame_thr) -- or, with `keep`, the
+    tracks of that uint8[n_dt] device tensor (a layer of ws.at_keep of
+    stage_track_identity_at), and the identity is neither run nor read.  On
+    request only.  Raises
     if the match reports a non-zero status (an exhausted loop bound): one
     synchronisation of the current stream.  Buffers are allocated on the first
     call and kept with the workspace: 8 bytes per pair of a cell for pot and 12
@@ -1551,8 +1649,10 @@ def stage_track_hota(dp, ws, alphas, frame_thr):
         raise _lib.TaoAmdError("%d alphas; the kernels take 1 to %d"
                                % (n_alpha, _lib.TRACK_HOTA_ALPHAS))
     frame_thr = float(frame_thr)
-    if ws.ident_ws is None or ws.ident_frame_thr != frame_thr:
-        stage_track_identity(dp, ws, frame_thr)
+    if keep is None:
+        if ws.ident_ws is None or ws.ident_frame_thr != frame_thr:
+            stage_track_identity(dp, ws, frame_thr)
+        keep = ws.ident_keep
     n_gf = sizes[5]
     if ws.hota_ws is None:
         ws.hota_bytes = lib.taoamd_track_hota_workspace(dp.n_dt, dp.n_gt, n_gf)
@@ -1568,7 +1668,7 @@ def stage_track_hota(dp, ws, alphas, frame_thr):
     ws.hota_tp = torch.empty((dp.n_cat, n_alpha), dtype=torch.int64, device=dev)
     ws.hota_loc = torch.empty((dp.n_cat, n_alpha), dtype=torch.int64, device=dev)
     ws.hota_ass = torch.empty((dp.n_cat, n_alpha, 3), dtype=torch.int64, device=dev)
-    tables = (*cells, _ptr(t["gt_flags"]), _ptr(ws.ident_keep), *frames)
+    tables = (*cells, _ptr(t["gt_flags"]), _ptr(keep), *frames)
     _lib.check(lib.taoamd_track_hota_align(
         *sizes, *tables, _ptr(ws.hota_pot), _ptr(ws.hota_ws), ws.hota_bytes, s),
         "taoamd_track_hota_align")
@@ -1586,7 +1686,7 @@ def stage_track_hota(dp, ws, alphas, frame_thr):
                                "loop bound)" % status)
 
 
-def stage_track_clear(dp, ws, frame_thr, vis_rng):
+def stage_track_clear(dp, ws, frame_thr, vis_rng, keep=None):
     """CLEAR MOT's integer tables from a one-to-one assignment per step that
     depends on the step before (taoamd_track_clear_count, _fill, _walk, _reduce;
     the definition is in include/tao_amodal_hip.h): ws.clear_cat_counts
@@ -1598,7 +1698,8 @@ def stage_track_clear(dp, ws, frame_thr, vis_rng):
     `vis_rng` (up to 8 {lo, hi} pairs; they need set_frame_visibility).  The
     detection tracks that take part are the identity's kept ones at `frame_thr`:
     stage_track_identity runs first unless the workspace holds it for that
-    threshold (ws.ident_frame_thr).  On request only.  The number of candidates is
+    threshold (ws.ident_frame_thr) -- or, with `keep`, the tracks of that
+    uint8[n_dt] device tensor, as for stage_track_hota.  On request only.  The number of candidates is
     read between count and fill, the status word at the end: two synchronisations
     of the current stream; a non-zero status raises.  Buffers are allocated on the
     first call and kept with the workspace: 22 bytes per ground-truth frame, 16
@@ -1610,8 +1711,10 @@ def stage_track_clear(dp, ws, frame_thr, vis_rng):
     vis_rng = _vis_windows(dp, vis_rng)
     n_vis = len(vis_rng)
     frame_thr = float(frame_thr)
-    if ws.ident_ws is None or ws.ident_frame_thr != frame_thr:
-        stage_track_identity(dp, ws, frame_thr)
+    if keep is None:
+        if ws.ident_ws is None or ws.ident_frame_thr != frame_thr:
+            stage_track_identity(dp, ws, frame_thr)
+        keep = ws.ident_keep
     n_dt, n_gt, n_cells, _, n_df, n_gf = sizes
     if ws.clear_ws is None:
         ws.clear_bytes = lib.taoamd_track_clear_workspace(n_dt, n_gt, n_gf)
@@ -1632,7 +1735,7 @@ def stage_track_clear(dp, ws, frame_thr, vis_rng):
     if not n_vis:
         ws.clear_vis_counts = None
     tables = (n_dt, n_gt, n_cells, n_df, n_gf, frame_thr, cells[0], cells[1],
-              _ptr(t["gt_flags"]), _ptr(ws.ident_keep), *frames)
+              _ptr(t["gt_flags"]), _ptr(keep), *frames)
     _lib.check(lib.taoamd_track_clear_count(
         *tables, _ptr(ws.clear_off), _ptr(ws.clear_step), _ptr(ws.clear_ws), ws.clear_bytes, s),
         "taoamd_track_clear_count")

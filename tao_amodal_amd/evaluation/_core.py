@@ -431,14 +431,35 @@ class GpuRun:
                     "counts": ws.occ_counts.cpu().numpy(),
                     "episodes": ws.occ_episodes[:ws.occ_n].cpu().numpy()}
 
-    def identity_table(self, frame_thr):
+    def _layers(self, score_thr):
+        """A threshold per category in the tables' order (float64[K]) as the
+        one-layer table of the thresholded stages."""
+        thr = np.ascontiguousarray(score_thr, dtype=np.float64).reshape(1, -1)
+        if thr.shape[1] != self.dp.n_cat:
+            raise ValueError("score_thr: %d thresholds for the tables' %d categories"
+                             % (thr.shape[1], self.dp.n_cat))
+        return thr
+
+    def identity_table(self, frame_thr, score_thr=None):
         """The identity measures' tables (engine.stage_track_identity; the
         definition is in include/tao_amodal_hip.h) at the per-frame threshold
         `frame_thr`: dict(cat_counts int64[K, 6], gt_ident int32[n_gt, 2],
-        dt_ident int32[n_dt, 2], rows as table rows).  Reads the track tables
-        alone; refuses what association_table() refuses."""
+        dt_ident int32[n_dt, 2], rows as table rows).  With `score_thr`
+        (float64[K] in the tables' category order) over the detection tracks at
+        or above it (engine.stage_track_identity_at; section "track-level score
+        thresholds").  Reads the track tables alone; refuses what
+        association_table() refuses."""
         self._followers_at("identity()", None)
         dp, ws = self.dp, self.ws
+        if score_thr is not None:
+            with timed("kernels"):
+                self.engine.stage_track_identity_at(dp, ws, frame_thr, self._layers(score_thr),
+                                                    per_track=True)
+                self.torch.cuda.synchronize(self.device)
+            with timed("download"):
+                return {"cat_counts": ws.at_cat_counts[0].cpu().numpy(),
+                        "gt_ident": ws.at_gt[0, :dp.n_gt].cpu().numpy(),
+                        "dt_ident": ws.at_dt[0, :dp.n_dt].cpu().numpy()}
         with timed("kernels"):
             self.engine.stage_track_identity(dp, ws, frame_thr)
             self.torch.cuda.synchronize(self.device)
@@ -447,49 +468,97 @@ class GpuRun:
                     "gt_ident": ws.ident_gt[:dp.n_gt].cpu().numpy(),
                     "dt_ident": ws.ident_dt[:dp.n_dt].cpu().numpy()}
 
-    def hota_table(self, alphas, frame_thr):
+    def _hota_download(self, cat_counts):
+        ws = self.ws
+        n_gf = int(self.dp.t["gt_frame_pos"].numel())
+        return {"cat_counts": cat_counts.cpu().numpy(),
+                "tp": ws.hota_tp.cpu().numpy(), "loc": ws.hota_loc.cpu().numpy(),
+                "ass": ws.hota_ass.cpu().numpy(),
+                "match": ws.hota_match[:n_gf].cpu().numpy(),
+                "match_iou": ws.hota_match_iou[:n_gf].cpu().numpy()}
+
+    def hota_table(self, alphas, frame_thr, score_thr=None):
         """HOTA's integer tables (engine.stage_track_hota; the definition is in
         include/tao_amodal_hip.h) at the localisation thresholds `alphas` (eps
-        already subtracted) over the tracks identity_table(frame_thr) keeps:
-        dict(cat_counts int64[K, 6] of the identity, tp and loc int64[K, A], ass
-        int64[K, A, 3], match int32[n_gt_frames] as in-cell indices, match_iou).
-        Reads the track tables alone; refuses what identity_table() refuses."""
+        already subtracted) over the tracks identity_table(frame_thr, score_thr)
+        keeps: dict(cat_counts int64[K, 6] of that identity, tp and loc int64[K,
+        A], ass int64[K, A, 3], match int32[n_gt_frames] as in-cell indices,
+        match_iou).  Reads the track tables alone; refuses what identity_table()
+        refuses."""
         self._followers_at("hota()", None)
-        dp, ws = self.dp, self.ws
+        dp, ws, e = self.dp, self.ws, self.engine
         with timed("kernels"):
-            self.engine.stage_track_hota(dp, ws, alphas, frame_thr)
+            if score_thr is None:
+                e.stage_track_hota(dp, ws, alphas, frame_thr)
+                counts = ws.ident_cat_counts
+            else:
+                e.stage_track_identity_at(dp, ws, frame_thr, self._layers(score_thr))
+                e.stage_track_hota(dp, ws, alphas, frame_thr, keep=ws.at_keep[0])
+                counts = ws.at_cat_counts[0]
             self.torch.cuda.synchronize(self.device)
         with timed("download"):
-            n_gf = int(dp.t["gt_frame_pos"].numel())
-            return {"cat_counts": ws.ident_cat_counts.cpu().numpy(),
-                    "tp": ws.hota_tp.cpu().numpy(), "loc": ws.hota_loc.cpu().numpy(),
-                    "ass": ws.hota_ass.cpu().numpy(),
-                    "match": ws.hota_match[:n_gf].cpu().numpy(),
-                    "match_iou": ws.hota_match_iou[:n_gf].cpu().numpy()}
+            return self._hota_download(counts)
 
-    def clear_table(self, frame_thr, vis_rng, ann_vis):
+    def _clear_download(self, ident_counts, n_vis):
+        dp, ws = self.dp, self.ws
+        n_gf = int(dp.t["gt_frame_pos"].numel())
+        return {"ident_counts": ident_counts.cpu().numpy(),
+                "cat_counts": ws.clear_cat_counts.cpu().numpy(),
+                "vis_counts": ws.clear_vis_counts.cpu().numpy() if n_vis else
+                np.zeros((0, dp.n_cat, 4), dtype=np.int64),
+                "gt_clear": ws.clear_gt[:dp.n_gt].cpu().numpy(),
+                "match": ws.clear_match[:n_gf].cpu().numpy(),
+                "match_iou": ws.clear_match_iou[:n_gf].cpu().numpy(),
+                "sw": ws.clear_sw[:n_gf].cpu().numpy()}
+
+    def clear_table(self, frame_thr, vis_rng, ann_vis, score_thr=None):
         """CLEAR MOT's integer tables (engine.stage_track_clear; the definition is
         in include/tao_amodal_hip.h) at the per-frame threshold `frame_thr` and the
-        visibility windows `vis_rng`, over the tracks identity_table(frame_thr)
-        keeps: dict(ident_counts int64[K, 6] of the identity, cat_counts int64[K,
-        7], vis_counts int64[n_vis, K, 4], gt_clear int32[n_gt, 4], match
-        int32[n_gt_frames] as in-cell indices, match_iou, sw uint8).  `ann_vis` as
-        for association_table(); refuses what it refuses."""
+        visibility windows `vis_rng`, over the tracks identity_table(frame_thr,
+        score_thr) keeps: dict(ident_counts int64[K, 6] of that identity,
+        cat_counts int64[K, 7], vis_counts int64[n_vis, K, 4], gt_clear
+        int32[n_gt, 4], match int32[n_gt_frames] as in-cell indices, match_iou, sw
+        uint8).  `ann_vis` as for association_table(); refuses what it refuses."""
         self._followers_at("clear()", ann_vis)
-        dp, ws = self.dp, self.ws
+        dp, ws, e = self.dp, self.ws, self.engine
         with timed("kernels"):
-            self.engine.stage_track_clear(dp, ws, frame_thr, vis_rng)
+            if score_thr is None:
+                e.stage_track_clear(dp, ws, frame_thr, vis_rng)
+                counts = ws.ident_cat_counts
+            else:
+                e.stage_track_identity_at(dp, ws, frame_thr, self._layers(score_thr))
+                e.stage_track_clear(dp, ws, frame_thr, vis_rng, keep=ws.at_keep[0])
+                counts = ws.at_cat_counts[0]
             self.torch.cuda.synchronize(self.device)
         with timed("download"):
-            n_gf = int(dp.t["gt_frame_pos"].numel())
-            return {"ident_counts": ws.ident_cat_counts.cpu().numpy(),
-                    "cat_counts": ws.clear_cat_counts.cpu().numpy(),
-                    "vis_counts": ws.clear_vis_counts.cpu().numpy() if len(vis_rng) else
-                    np.zeros((0, dp.n_cat, 4), dtype=np.int64),
-                    "gt_clear": ws.clear_gt[:dp.n_gt].cpu().numpy(),
-                    "match": ws.clear_match[:n_gf].cpu().numpy(),
-                    "match_iou": ws.clear_match_iou[:n_gf].cpu().numpy(),
-                    "sw": ws.clear_sw[:n_gf].cpu().numpy()}
+            return self._clear_download(counts, len(vis_rng))
+
+    def curve_tables(self, frame_thr, thr_tables, alphas, measures):
+        """The integer tables of tracking_curve(): the identity over every layer
+        of `thr_tables` float64[T, K] (the tables' category order) in one launch
+        (engine.stage_track_identity_at), then -- for "hota" and "clear" in
+        `measures` -- a host loop of engine.stage_track_hota / stage_track_clear
+        over the layers' kept columns.  dict(cat_counts int64[T, K, 6], tp and loc
+        int64[T, K, A], ass int64[T, K, A, 3], clear int64[T, K, 7]; what was not
+        asked for is absent).  Refuses what identity_table() refuses."""
+        self._followers_at("tracking_curve()", None)
+        dp, ws, e = self.dp, self.ws, self.engine
+        out = {}
+        with timed("kernels"):
+            e.stage_track_identity_at(dp, ws, frame_thr, thr_tables)
+            out["cat_counts"] = ws.at_cat_counts.cpu().numpy()
+            keep = ws.at_keep
+            rows = {k: [] for k in ("tp", "loc", "ass", "clear")}
+            for t in range(len(keep)):
+                if "hota" in measures:
+                    e.stage_track_hota(dp, ws, alphas, frame_thr, keep=keep[t])
+                    for k, v in (("tp", ws.hota_tp), ("loc", ws.hota_loc), ("ass", ws.hota_ass)):
+                        rows[k].append(v.cpu().numpy())
+                if "clear" in measures:
+                    e.stage_track_clear(dp, ws, frame_thr, [], keep=keep[t])
+                    rows["clear"].append(ws.clear_cat_counts.cpu().numpy())
+        out.update({k: np.stack(v) for k, v in rows.items() if v})
+        return out
 
     def pointer_tables(self):
         """What eval['dt_pointers'] is read from: the detections' ids and

@@ -435,14 +435,17 @@ class DistRun:
     def occlusion_table(self, frame_thr, vis_rng, recover, len_edges, ann_vis):
         raise NotImplementedError("occlusions() in a multi-GPU run")
 
-    def identity_table(self, frame_thr):
+    def identity_table(self, frame_thr, score_thr=None):
         raise NotImplementedError("identity() in a multi-GPU run")
 
-    def hota_table(self, alphas, frame_thr):
+    def hota_table(self, alphas, frame_thr, score_thr=None):
         raise NotImplementedError("hota() in a multi-GPU run")
 
-    def clear_table(self, frame_thr, vis_rng, ann_vis):
+    def clear_table(self, frame_thr, vis_rng, ann_vis, score_thr=None):
         raise NotImplementedError("clear() in a multi-GPU run")
+
+    def curve_tables(self, frame_thr, thr_tables, alphas, measures):
+        raise NotImplementedError("tracking_curve() in a multi-GPU run")
 
     def pointer_tables(self):
         if self._pointers is None:

@@ -481,7 +481,7 @@ class TaoEval:
         frames, in per cent.  Returned, not printed."""
         return followers.occlusion_lines(self.occlusions(frame_thr, vis_rng, recover, len_edges))
 
-    def identity(self, frame_thr=0.5, per_track=False):
+    def identity(self, frame_thr=0.5, per_track=False, score_thr=None):
         """IDF1, IDP and IDR (Ristani et al., ECCV 2016; TrackEval's Identity):
         the identity measure beside Track-AP.  association() is many-to-one --
         one detection track may be the primary of several ground-truth tracks,
@@ -519,15 +519,25 @@ class TaoEval:
         ids, int64[n_dt, 3] = the assigned ground-truth track's id or -1, kept,
         frames).  Every count is exact and the same from run to run; where
         several assignments reach the optimum, the one reported is one of them.
-        Not available: iou_type="segm", use_cats = 0, multi-GPU runs."""
-        return followers.identity(self, frame_thr, per_track)
 
-    def identity_lines(self, frame_thr=0.5):
+        `score_thr`: the operating point.  The tables hold every track up to the
+        max_dets cut, whatever its score; with a threshold -- a float, or one per
+        category in the order of params.cat_ids -- only the detection tracks
+        whose score (the one Track-AP ranks them by) is >= it take part: whole
+        tracks, never single boxes.  A NaN lets no track of its category pass,
+        -inf every track.  None is the table as it is.  The result then holds
+        "score_thr": float64[K] and is cached per threshold as well; the rule is
+        in include/tao_amodal_hip.h, section "track-level score thresholds".
+        tracking_curve() finds the threshold.
+        Not available: iou_type="segm", use_cats = 0, multi-GPU runs."""
+        return followers.identity(self, frame_thr, per_track, score_thr)
+
+    def identity_lines(self, frame_thr=0.5, score_thr=None):
         """identity() as a small text table: the totals over the categories.
         Returned, not printed."""
-        return followers.identity_lines(self.identity(frame_thr))
+        return followers.identity_lines(self.identity(frame_thr, score_thr=score_thr))
 
-    def hota(self, alphas=None, frame_thr=0.5, per_frame=False):
+    def hota(self, alphas=None, frame_thr=0.5, per_frame=False, score_thr=None):
         """HOTA, DetA and AssA (Luiten et al., IJCV 2021; TrackEval's HOTA): the
         measure tracking papers print beside Track-AP and IDF1.  association()
         is a per-frame arg-max and identity() one assignment over whole tracks;
@@ -565,19 +575,21 @@ class TaoEval:
         scalars averaged over the categories that have frames (its class-
         averaged combination)}; with per_frame=True "frames": per ground-truth
         frame (the ground-truth track id, the image id, the matched detection
-        track's id or -1, its box IoU or 0).
+        track's id or -1, its box IoU or 0).  `score_thr` as for identity(): the
+        tracks that take part are identity(frame_thr, score_thr=score_thr)'s,
+        and the result holds "score_thr".
         Not available: iou_type="segm", use_cats = 0, multi-GPU runs, the
         command line; recall per visibility window is clear()'s "vis_re" (the
         per-frame output here carries what a breakdown of DetRe needs)."""
-        return followers.hota(self, alphas, frame_thr, per_frame)
+        return followers.hota(self, alphas, frame_thr, per_frame, score_thr)
 
-    def hota_lines(self, alphas=None, frame_thr=0.5):
+    def hota_lines(self, alphas=None, frame_thr=0.5, score_thr=None):
         """hota() as a small text table in per cent, in TrackEval's column order:
         the total and the class mean.  Returned, not printed."""
-        return followers.hota_lines(self.hota(alphas, frame_thr))
+        return followers.hota_lines(self.hota(alphas, frame_thr, score_thr=score_thr))
 
     def clear(self, frame_thr=0.5, vis_rng=None, vis_lbl=None, per_track=False,
-              per_frame=False):
+              per_frame=False, score_thr=None):
         """CLEAR MOT (Bernardin & Stiefelhagen, 2008; TrackEval's CLEAR): MOTA,
         MOTP, ID switches, fragmentations, mostly tracked / mostly lost -- the
         third of the measures printed beside Track-AP, with IDF1 (identity())
@@ -618,16 +630,58 @@ class TaoEval:
         lost / partly / mostly tracked; zeros for an ignored track); with
         per_frame=True "frames": per ground-truth frame (the ground-truth track
         id, the image id, the matched detection track's id or -1, its box IoU
-        or 0, the switch flag).
+        or 0, the switch flag).  `score_thr` as for identity(): the tracks that
+        take part are identity(frame_thr, score_thr=score_thr)'s, and the result
+        holds "score_thr".
         Not available: iou_type="segm", use_cats = 0, multi-GPU runs, the
         command line; FP per frame (no table holds a video's frame count)."""
-        return followers.clear(self, frame_thr, vis_rng, vis_lbl, per_track, per_frame)
+        return followers.clear(self, frame_thr, vis_rng, vis_lbl, per_track, per_frame,
+                               score_thr)
 
-    def clear_lines(self, frame_thr=0.5, vis_rng=None, vis_lbl=None):
+    def clear_lines(self, frame_thr=0.5, vis_rng=None, vis_lbl=None, score_thr=None):
         """clear() as a small text table in per cent, in TrackEval's CLEAR column
         order: the total and the class mean, then a line per visibility window
         with CLR_Re and IDSW.  Returned, not printed."""
-        return followers.clear_lines(self.clear(frame_thr, vis_rng, vis_lbl))
+        return followers.clear_lines(self.clear(frame_thr, vis_rng, vis_lbl,
+                                                score_thr=score_thr))
+
+    def tracking_curve(self, score_thrs=None, frame_thr=0.5, alphas=None,
+                       measures=("identity", "hota", "clear")):
+        """identity(), hota() and clear() at a list of score thresholds: at
+        which score is IDF1, HOTA or MOTA best?  None of them is monotone in the
+        threshold.  `score_thrs`: 1 to 64 strictly ascending doubles (ValueError
+        otherwise), each applied to every category; None takes the distinct
+        values of the 0 %, 10 %, ... 90 % quantiles (scores that occur) of the
+        finite scores of the table's detection tracks, so that the first row is
+        the table without a threshold whenever no score is a NaN.  The frames'
+        shares are counted once and the identity's assignment is solved for all
+        thresholds in one launch; HOTA and CLEAR run once per threshold.
+        `measures`: which of "identity", "hota", "clear" (the identity's counts
+        are formed in any case: the other two are computed over its tracks).
+        Callable after evaluate(); not cached.
+
+        Returns {"score_thrs": float64[T], "cat_counts": int64[T, K, 6], the
+        identity's, the category axis in the order of params.cat_ids, float64[T,
+        K] "idf1", "hota", "deta", "assa" (the means over alpha), "mota", "motp"
+        and int64[T, K] "idsw", NaN where the category has no frames, "total":
+        the [T] arrays of what identity()'s, hota()'s and clear()'s "total" hold
+        as one number each -- the counts (gt_tracks .. dt_frames, idtp, tp, idsw,
+        ...), "idf1", "idp", "idr", "HOTA", "DetA", "AssA", ..., "mota", "motp",
+        ... --, "mean": hota()'s and clear()'s class means alike, "best": for
+        "IDF1", "HOTA" and "MOTA" {"index", "score_thr", "value"} of the greatest
+        total (the lowest threshold among equal ones; NaN rows are skipped),
+        "best_per_category": for the same names float64[K], the maximising
+        threshold per category (NaN without frames), which can be passed back as
+        `score_thr`, "frame_thr", "alphas", "measures"}.  Row t holds exactly
+        the numbers of the single calls with score_thr=score_thrs[t].
+        Not available: iou_type="segm", use_cats = 0, multi-GPU runs."""
+        return followers.tracking_curve(self, score_thrs, frame_thr, alphas, measures)
+
+    def curve_lines(self, c):
+        """tracking_curve()'s result `c` as a small text table: a line per
+        threshold with dt_tracks, IDF1, HOTA, DetA, AssA, MOTA in per cent and
+        IDSW.  Returned, not printed."""
+        return followers.curve_lines(c)
 
     def impact_lines(self, iou_thr=0.5, bg_thr=0.1):
         """error_impact() as a small text table: a line per (area, time) range,

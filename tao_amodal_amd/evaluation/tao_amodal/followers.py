@@ -1,7 +1,7 @@
 """The analyses of TaoEval that read the track tables alone -- association(),
-occlusions(), identity(), hota(), clear() -- and their text tables: the class layer
-over GpuRun.association_table / occlusion_table / identity_table / hota_table /
-clear_table.  The track
+occlusions(), identity(), hota(), clear(), tracking_curve() -- and their text
+tables: the class layer over GpuRun.association_table / occlusion_table /
+identity_table / hota_table / clear_table / curve_tables.  The track
 level's alone; the methods of TaoEval carry the documentation and call in here
 with the evaluator `ev`."""
 import numpy as np
@@ -27,6 +27,45 @@ def _cached(cache, key, make, optional):
         hit = cache[key] = make()
     drop = [k for k, on in optional if not on]
     return {k: v for k, v in hit.items() if k not in drop}
+
+
+def score_thr_of(ev, score_thr):
+    """`score_thr` of identity(), hota() and clear() as None or float64[K] in the
+    order of params.cat_ids: a float is every category's.  A NaN is allowed (no
+    track of that category passes), so that tracking_curve()'s
+    "best_per_category" can be passed back."""
+    if score_thr is None:
+        return None
+    K = len(ev.params.cat_ids)
+    try:
+        a = np.asarray(score_thr, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("score_thr: {!r} is neither a float nor {} floats".format(score_thr, K))
+    if a.ndim == 0:
+        return np.full(K, float(a))
+    if a.shape != (K,):
+        raise ValueError("score_thr: {} values; a float or one per category of "
+                         "params.cat_ids ({})".format(a.size, K))
+    return np.ascontiguousarray(a)
+
+
+def _table_thr(ev, thr):
+    """Thresholds [..., K] in the order of params.cat_ids as the tables' [...,
+    K_table]: a category of the tables that params.cat_ids does not name gets
+    +inf (none of its tracks passes; its rows are not reported either)."""
+    if ev._cat_pos is None or not ev.params.use_cats:
+        return thr
+    out = np.full(thr.shape[:-1] + (len(ev.flat.cat_ids),), np.inf)
+    out[..., ev._cat_pos] = thr
+    return out
+
+
+def _thr_text(thr):
+    """" | score>=..." for the first line of a text table, "" without a threshold."""
+    if thr is None:
+        return ""
+    one = len(thr) and (thr == thr[0]).all()
+    return " | score>={}".format("{:g}".format(thr[0]) if one else "per category")
 
 
 def _track_ids(rows, ids):
@@ -187,31 +226,43 @@ def identity_ratios(idtp, gt_frames, dt_frames):
                 np.where(gt_frames > 0, idtp / gt_frames, np.nan))
 
 
-def identity(ev, frame_thr, per_track):
+def _identity_numbers(cat_counts):
+    """(idf1, idp, idr float64[K], the totals' dict) of the identity's int64[K, 6]."""
+    from ..._lib import IDENT_CAT_COLUMNS
+    idf1, idp, idr = identity_ratios(cat_counts[:, 4], cat_counts[:, 1], cat_counts[:, 3])
+    total = dict(zip(IDENT_CAT_COLUMNS, (int(x) for x in cat_counts.sum(0))))
+    total["idfn"] = total["gt_frames"] - total["idtp"]
+    total["idfp"] = total["dt_frames"] - total["idtp"]
+    for name, v in zip(("idf1", "idp", "idr"),
+                       identity_ratios(total["idtp"], total["gt_frames"], total["dt_frames"])):
+        total[name] = float(v)
+    return idf1, idp, idr, total
+
+
+def identity(ev, frame_thr, per_track, score_thr=None):
     frame_thr = _frame_thr(ev, frame_thr)
+    thr = score_thr_of(ev, score_thr)
 
     def make():
         from ..._lib import IDENT_CAT_COLUMNS
-        t = ev._run.identity_table(frame_thr)
+        t = ev._run.identity_table(frame_thr) if thr is None else \
+            ev._run.identity_table(frame_thr, _table_thr(ev, thr))
         flat = ev._run.flat
         cat_counts = _params_cats(ev, t["cat_counts"], 0)
-        idf1, idp, idr = identity_ratios(cat_counts[:, 4], cat_counts[:, 1], cat_counts[:, 3])
-        total = dict(zip(IDENT_CAT_COLUMNS, (int(x) for x in cat_counts.sum(0))))
-        total["idfn"] = total["gt_frames"] - total["idtp"]
-        total["idfp"] = total["dt_frames"] - total["idtp"]
-        for name, v in zip(("idf1", "idp", "idr"),
-                           identity_ratios(total["idtp"], total["gt_frames"], total["dt_frames"])):
-            total[name] = float(v)
+        idf1, idp, idr, total = _identity_numbers(cat_counts)
         dt_id, gt_id = (np.asarray(x, dtype=np.int64) for x in (flat.dt_id, flat.gt_id))
         gi, di = t["gt_ident"], t["dt_ident"]
         tracks = np.stack([_track_ids(gi[:, 0], dt_id), gi[:, 1].astype(np.int64),
                            np.diff(np.asarray(flat.gt_frame_off, dtype=np.int64))], axis=1)
         dt_tracks = np.stack([_track_ids(di[:, 0], gt_id), di[:, 1].astype(np.int64),
                               np.diff(np.asarray(flat.dt_frame_off, dtype=np.int64))], axis=1)
-        return {"columns": list(IDENT_CAT_COLUMNS), "cat_counts": cat_counts,
-                "idf1": idf1, "idp": idp, "idr": idr, "total": total, "frame_thr": frame_thr,
-                "tracks": (gt_id, tracks), "dt_tracks": (dt_id, dt_tracks)}
-    return _cached(ev._identity, frame_thr, make,
+        out = {"columns": list(IDENT_CAT_COLUMNS), "cat_counts": cat_counts,
+               "idf1": idf1, "idp": idp, "idr": idr, "total": total, "frame_thr": frame_thr,
+               "tracks": (gt_id, tracks), "dt_tracks": (dt_id, dt_tracks)}
+        if thr is not None:
+            out["score_thr"] = thr
+        return out
+    return _cached(ev._identity, frame_thr if thr is None else (frame_thr, thr.tobytes()), make,
                    (("tracks", per_track), ("dt_tracks", per_track)))
 
 
@@ -262,49 +313,69 @@ def hota_scalars(r):
     return out
 
 
-def hota(ev, alphas, frame_thr, per_frame):
+def _hota_numbers(counts, tp, loc, ass):
+    """What hota() forms from the integer tables in the order of params.cat_ids
+    (counts int64[K, 4], tp and loc [K, A], ass [K, A, 3]): dict(the HOTA_RATIOS
+    float64[K, A], NaN where a category has no frames; "per_cat": the scalars'
+    float64[K], masked alike; "total", "mean")."""
+    from ..._lib import HOTA_RATIOS
+    gt_frames, dt_frames = counts[:, 1:2], counts[:, 3:4]
+    r = hota_ratios(tp, loc, ass, gt_frames, dt_frames)
+    has = (counts[:, 1] + counts[:, 3]) > 0
+    out = {k: np.where(has[:, None], r[k], np.nan) for k in HOTA_RATIOS}
+    tot = counts.sum(0)
+    total = dict(zip(("gt_tracks", "gt_frames", "dt_tracks", "dt_frames"),
+                     (int(x) for x in tot)))
+    total.update(tp=tp.sum(0), fn=tot[1] - tp.sum(0), fp=tot[3] - tp.sum(0), loc=loc.sum(0),
+                 ass=ass.sum(0))
+    rt = hota_ratios(total["tp"], total["loc"], total["ass"], tot[1], tot[3])
+    total.update(rt)
+    total.update({k: float(v) for k, v in hota_scalars(rt).items()})
+    per_cat = hota_scalars(r)
+    mean = {k: float(v[has].mean()) if has.any() else float("nan")
+            for k, v in per_cat.items()}
+    out["per_cat"] = {k: np.where(has, v, np.nan) for k, v in per_cat.items()}
+    out["total"], out["mean"] = total, mean
+    return out
+
+
+def hota(ev, alphas, frame_thr, per_frame, score_thr=None):
     frame_thr = _frame_thr(ev, frame_thr)
     alphas = hota_alphas(alphas)
+    thr = score_thr_of(ev, score_thr)
 
     def make():
-        from ..._lib import HOTA_RATIOS
-        t = ev._run.hota_table(alphas - np.finfo(float).eps, frame_thr)
+        at = alphas - np.finfo(float).eps
+        t = ev._run.hota_table(at, frame_thr) if thr is None else \
+            ev._run.hota_table(at, frame_thr, _table_thr(ev, thr))
         flat = ev._run.flat
         counts = _params_cats(ev, t["cat_counts"], 0)[:, :4]
         tp, loc, ass = (_params_cats(ev, t[k], 0) for k in ("tp", "loc", "ass"))
         gt_frames, dt_frames = counts[:, 1:2], counts[:, 3:4]
         out = {"alphas": alphas, "frame_thr": frame_thr, "cat_counts": counts, "tp": tp,
                "fn": gt_frames - tp, "fp": dt_frames - tp, "loc": loc, "ass": ass}
-        r = hota_ratios(tp, loc, ass, gt_frames, dt_frames)
-        has = (counts[:, 1] + counts[:, 3]) > 0
-        for k in HOTA_RATIOS:
-            out[k] = np.where(has[:, None], r[k], np.nan)
-        tot = counts.sum(0)
-        total = dict(zip(("gt_tracks", "gt_frames", "dt_tracks", "dt_frames"),
-                         (int(x) for x in tot)))
-        total.update(tp=tp.sum(0), fn=tot[1] - tp.sum(0), fp=tot[3] - tp.sum(0), loc=loc.sum(0),
-                     ass=ass.sum(0))
-        rt = hota_ratios(total["tp"], total["loc"], total["ass"], tot[1], tot[3])
-        total.update(rt)
-        total.update({k: float(v) for k, v in hota_scalars(rt).items()})
-        per_cat = hota_scalars(r)
-        mean = {k: float(v[has].mean()) if has.any() else float("nan")
-                for k, v in per_cat.items()}
-        out["total"], out["mean"] = total, mean
+        numbers = _hota_numbers(counts, tp, loc, ass)
+        del numbers["per_cat"]
+        out.update(numbers)
         foff, cell, img = _gt_frame_tables(flat)
         g_of = np.repeat(np.arange(len(foff) - 1), np.diff(foff))
         out["frames"] = (np.asarray(flat.gt_id, dtype=np.int64)[g_of], img,
                          _follower_ids(flat, cell, t["match"]), t["match_iou"])
+        if thr is not None:
+            out["score_thr"] = thr
         return out
-    return _cached(ev._hota, (alphas.tobytes(), frame_thr), make, (("frames", per_frame),))
+    key = (alphas.tobytes(), frame_thr) if thr is None else \
+        (alphas.tobytes(), frame_thr, thr.tobytes())
+    return _cached(ev._hota, key, make, (("frames", per_frame),))
 
 
 def hota_lines(e):
     """TaoEval.hota()'s result `e` as a small text table, in per cent and in
     TrackEval's column order: the detection-averaged total and the class mean."""
     names = list(HOTA_SCALARS) + ["HOTA(0)", "LocA(0)", "HOTALocA(0)"]
-    lines = [" track HOTA @[ alphas={:0.2f}:{:0.2f} ({}) | frame IoU={:0.2f} ]".format(
-                 float(e["alphas"][0]), float(e["alphas"][-1]), len(e["alphas"]), e["frame_thr"]),
+    lines = [" track HOTA @[ alphas={:0.2f}:{:0.2f} ({}) | frame IoU={:0.2f}{} ]".format(
+                 float(e["alphas"][0]), float(e["alphas"][-1]), len(e["alphas"]), e["frame_thr"],
+                 _thr_text(e.get("score_thr"))),
              " " + "".ljust(10) + "".join(n.rjust(12) for n in names)]
     for label, row in (("total", e["total"]), ("class mean", e["mean"])):
         lines.append(" " + label.ljust(10) + "".join(_pct(row[n], width=12) for n in names))
@@ -334,39 +405,53 @@ def clear_ratios(cat_counts):
             "mtr": cc[..., 7] / tr, "ptr": cc[..., 8] / tr, "mlr": cc[..., 9] / tr}
 
 
-def clear(ev, frame_thr, vis_rng, vis_lbl, per_track, per_frame):
+def _clear_columns():
+    from ..._lib import CLEAR_CAT_COLUMNS, IDENT_CAT_COLUMNS
+    return list(IDENT_CAT_COLUMNS[:4]) + list(CLEAR_CAT_COLUMNS)
+
+
+def _clear_numbers(cc):
+    """What clear() forms from its int64[K, 11] table in the order of
+    params.cat_ids: dict(the CLEAR_RATIOS float64[K], NaN where a category has no
+    frames; "total" without the windows; "mean")."""
+    from ..._lib import CLEAR_RATIOS
+    r = clear_ratios(cc)
+    has = (cc[:, 1] + cc[:, 3]) > 0
+    out = {k: np.where(has, r[k], np.nan) for k in CLEAR_RATIOS}
+    tot = cc.sum(0)
+    total = dict(zip(_clear_columns(), (int(x) for x in tot)))
+    total.update(fn=int(tot[1] - tot[4]), fp=int(tot[3] - tot[4]))
+    total.update({k: float(v) for k, v in clear_ratios(tot).items()})
+    out["total"] = total
+    out["mean"] = {k: float(r[k][has].mean()) if has.any() else float("nan")
+                   for k in CLEAR_RATIOS}
+    return out
+
+
+def clear(ev, frame_thr, vis_rng, vis_lbl, per_track, per_frame, score_thr=None):
     frame_thr = _frame_thr(ev, frame_thr)
     rng, vis_lbl = _windows(ev, vis_rng, vis_lbl)
+    thr = score_thr_of(ev, score_thr)
 
     def make():
-        from ..._lib import (CLEAR_CAT_COLUMNS, CLEAR_RATIOS, CLEAR_VIS_COLUMNS,
-                             IDENT_CAT_COLUMNS)
-        t = ev._run.clear_table(frame_thr, rng, ev._gt_columns.ann_vis)
+        from ..._lib import CLEAR_VIS_COLUMNS
+        ann_vis = ev._gt_columns.ann_vis
+        t = ev._run.clear_table(frame_thr, rng, ann_vis) if thr is None else \
+            ev._run.clear_table(frame_thr, rng, ann_vis, _table_thr(ev, thr))
         flat = ev._run.flat
         cc = np.concatenate([_params_cats(ev, t["ident_counts"], 0)[:, :4],
                              _params_cats(ev, t["cat_counts"], 0)], axis=1)
         vis = _params_cats(ev, t["vis_counts"], 1)
-        columns = list(IDENT_CAT_COLUMNS[:4]) + list(CLEAR_CAT_COLUMNS)
         out = {"frame_thr": frame_thr, "cat_counts": cc, "fn": cc[:, 1] - cc[:, 4],
                "fp": cc[:, 3] - cc[:, 4], "vis_counts": vis, "vis_rng": rng.tolist(),
                "vis_lbl": list(vis_lbl),
-               "columns": {"cat_counts": columns, "vis_counts": list(CLEAR_VIS_COLUMNS),
+               "columns": {"cat_counts": _clear_columns(), "vis_counts": list(CLEAR_VIS_COLUMNS),
                            "tracks": ["present", "matched", "idsw", "frag", "tracked"]}}
-        r = clear_ratios(cc)
-        has = (cc[:, 1] + cc[:, 3]) > 0
-        for k in CLEAR_RATIOS:
-            out[k] = np.where(has, r[k], np.nan)
+        out.update(_clear_numbers(cc))
         with np.errstate(divide="ignore", invalid="ignore"):
             out["vis_re"] = np.where(vis[..., 0] > 0, vis[..., 1] / vis[..., 0].astype(np.float64),
                                      np.nan)
-        tot = cc.sum(0)
-        total = dict(zip(columns, (int(x) for x in tot)))
-        total.update(fn=int(tot[1] - tot[4]), fp=int(tot[3] - tot[4]))
-        total.update({k: float(v) for k, v in clear_ratios(tot).items()})
-        total["vis_counts"] = vis.sum(1)
-        out["total"] = total
-        out["mean"] = {k: float(r[k][has].mean()) if has.any() else float("nan")
-                       for k in CLEAR_RATIOS}
+        out["total"]["vis_counts"] = vis.sum(1)
         gc = t["gt_clear"].astype(np.int64)
         mt = 5 * gc[:, 1] > 4 * gc[:, 0]
         pt = ~mt & (5 * gc[:, 1] >= gc[:, 0])
@@ -378,8 +463,11 @@ def clear(ev, frame_thr, vis_rng, vis_lbl, per_track, per_frame):
         g_of = np.repeat(np.arange(len(foff) - 1), np.diff(foff))
         out["frames"] = (np.asarray(flat.gt_id, dtype=np.int64)[g_of], img,
                          _follower_ids(flat, cell, t["match"]), t["match_iou"], t["sw"])
+        if thr is not None:
+            out["score_thr"] = thr
         return out
-    return _cached(ev._clear, (frame_thr, rng.tobytes(), tuple(vis_lbl)), make,
+    key = (frame_thr, rng.tobytes(), tuple(vis_lbl))
+    return _cached(ev._clear, key if thr is None else key + (thr.tobytes(),), make,
                    (("tracks", per_track), ("frames", per_frame)))
 
 
@@ -390,7 +478,8 @@ def clear_lines(e):
     tot = e["total"]
     ints = {"CLR_TP": tot["tp"], "CLR_FN": tot["fn"], "CLR_FP": tot["fp"], "IDSW": tot["idsw"],
             "MT": tot["mt"], "PT": tot["pt"], "ML": tot["ml"], "Frag": tot["frag"]}
-    lines = [" track CLEAR @[ frame IoU={:0.2f} ]".format(e["frame_thr"]),
+    lines = [" track CLEAR @[ frame IoU={:0.2f}{} ]".format(e["frame_thr"],
+                                                           _thr_text(e.get("score_thr"))),
              " " + "".ljust(10) + "".join(n.rjust(9) for n in CLEAR_SCALARS + CLEAR_INTEGERS),
              " " + "total".ljust(10)
              + "".join(_pct(tot[n.lower()], width=9) for n in CLEAR_SCALARS)
@@ -408,6 +497,166 @@ def identity_lines(e):
     """TaoEval.identity()'s result `e` as a small text table: the totals over
     the categories."""
     t = e["total"]
-    return [" track identity @[ frame IoU={:0.2f} ]".format(e["frame_thr"]),
+    return [" track identity @[ frame IoU={:0.2f}{} ]".format(e["frame_thr"],
+                                                            _thr_text(e.get("score_thr"))),
             " IDF1={}  IDP={}  IDR={}".format(_pct(t["idf1"]), _pct(t["idp"]), _pct(t["idr"])),
             " " + "  ".join("{}={}".format(c, t[c]) for c in list(e["columns"]) + ["idfn", "idfp"])]
+
+
+# ---------------------------------------------------------------------------
+# tracking_curve(): identity, HOTA and CLEAR over a list of score thresholds
+# ---------------------------------------------------------------------------
+CURVE_MEASURES = ("identity", "hota", "clear")
+CURVE_BEST = (("IDF1", "identity", "idf1"), ("HOTA", "hota", "HOTA"), ("MOTA", "clear", "mota"))
+# the per-category [T, K] arrays: (entry, measure)
+CURVE_PER_CAT = (("idf1", "identity"), ("hota", "hota"), ("deta", "hota"), ("assa", "hota"),
+                 ("mota", "clear"), ("motp", "clear"), ("idsw", "clear"))
+
+
+def default_score_thrs(dt_score):
+    """tracking_curve()'s thresholds for None: the distinct values of the 0 %, 10 %,
+    ... 90 % quantiles (method="lower": scores that occur) of the finite scores,
+    ascending; [-inf] where no score is finite.  The first is the least finite
+    score: every track that is not a NaN (or -inf) passes it."""
+    s = np.asarray(dt_score, dtype=np.float64).reshape(-1)
+    s = s[np.isfinite(s)]
+    if not len(s):
+        return np.array([-np.inf])
+    return np.unique(np.quantile(s, np.arange(10) / 10.0, method="lower"))
+
+
+def curve_score_thrs(score_thrs, dt_score):
+    """The curve's thresholds as float64[T]: default_score_thrs(dt_score) for None,
+    else 1 to 64 strictly ascending doubles, none a NaN."""
+    if score_thrs is None:
+        return default_score_thrs(dt_score)
+    a = np.asarray(score_thrs, dtype=np.float64).reshape(-1)
+    if not 1 <= len(a) <= 64:
+        raise ValueError("score_thrs: {} values; 1 to 64".format(len(a)))
+    if np.isnan(a).any():
+        raise ValueError("score_thrs: {} hold a NaN".format(a.tolist()))
+    if (np.diff(a) <= 0).any():
+        raise ValueError("score_thrs: {} do not strictly ascend".format(a.tolist()))
+    return a
+
+
+def curve_measures(measures):
+    """`measures` as a tuple in the order of CURVE_MEASURES."""
+    if isinstance(measures, str):
+        measures = (measures,)
+    got = [str(m) for m in measures]
+    if not got or any(m not in CURVE_MEASURES for m in got) or len(set(got)) != len(got):
+        raise ValueError("measures: {} is not a choice of {}".format(
+            list(measures), list(CURVE_MEASURES)))
+    return tuple(m for m in CURVE_MEASURES if m in got)
+
+
+def best_index(values):
+    """The index of the greatest of `values` that is not a NaN, the FIRST among
+    equal maxima (the lowest threshold of an ascending list); -1 if all are NaN
+    or there are none."""
+    v = np.asarray(values, dtype=np.float64).reshape(-1)
+    ok = ~np.isnan(v)
+    if not ok.any():
+        return -1
+    return int(np.argmax(np.where(ok, v, -np.inf)))      # (argmax: the first of equals)
+
+
+def best_threshold(values, score_thrs):
+    """{"index", "score_thr", "value"} of best_index; index -1 and two NaN for none."""
+    i = best_index(values)
+    if i < 0:
+        return {"index": -1, "score_thr": float("nan"), "value": float("nan")}
+    return {"index": i, "score_thr": float(np.asarray(score_thrs)[i]),
+            "value": float(np.asarray(values)[i])}
+
+
+def best_per_category(values, score_thrs):
+    """float64[K]: per column of values[T, K] the threshold of best_index, NaN for
+    a column of NaNs (a category without frames)."""
+    v = np.asarray(values, dtype=np.float64)
+    thrs = np.asarray(score_thrs, dtype=np.float64)
+    idx = [best_index(v[:, k]) for k in range(v.shape[1])]
+    return np.array([thrs[i] if i >= 0 else np.nan for i in idx], dtype=np.float64)
+
+
+def curve_numbers(score_thrs, cat_counts, tp=None, loc=None, ass=None, clear_counts=None):
+    """tracking_curve()'s result from the integer tables in the order of
+    params.cat_ids: cat_counts int64[T, K, 6] of the identity, HOTA's tp and loc
+    [T, K, A] and ass [T, K, A, 3] and CLEAR's int64[T, K, 7], each None where the
+    measure was not asked for.  A row is formed by the functions identity(), hota()
+    and clear() form theirs with."""
+    T = len(score_thrs)
+    out = {"score_thrs": np.asarray(score_thrs, dtype=np.float64),
+           "cat_counts": np.asarray(cat_counts, dtype=np.int64)}
+    per_cat = {name: [] for name, _ in CURVE_PER_CAT}
+    totals, means = [], []
+    for t in range(T):
+        cc = out["cat_counts"][t]
+        idf1, _, _, total = _identity_numbers(cc)
+        per_cat["idf1"].append(idf1)
+        mean = {}
+        if tp is not None:
+            h = _hota_numbers(cc[:, :4], tp[t], loc[t], ass[t])
+            for name in ("hota", "deta", "assa"):
+                per_cat[name].append(h["per_cat"][{"hota": "HOTA", "deta": "DetA",
+                                                   "assa": "AssA"}[name]])
+            total.update({k: v for k, v in h["total"].items() if isinstance(v, float)})
+            mean.update(h["mean"])
+        if clear_counts is not None:
+            c = _clear_numbers(np.concatenate([cc[:, :4], clear_counts[t]], axis=1))
+            per_cat["mota"].append(c["mota"])
+            per_cat["motp"].append(c["motp"])
+            per_cat["idsw"].append(clear_counts[t][:, 1].astype(np.int64))
+            total.update(c["total"])
+            mean.update(c["mean"])
+        totals.append(total)
+        means.append(mean)
+    K = out["cat_counts"].shape[1]
+    for name, rows in per_cat.items():
+        if rows:
+            out[name] = np.stack(rows).reshape(T, K)
+    out["total"] = {k: np.array([row[k] for row in totals]) for k in totals[0]}
+    out["mean"] = {k: np.array([row[k] for row in means]) for k in means[0]}
+    out["best"], out["best_per_category"] = {}, {}
+    for name, _, key in CURVE_BEST:
+        if key in out["total"]:
+            out["best"][name] = best_threshold(out["total"][key], out["score_thrs"])
+            out["best_per_category"][name] = best_per_category(out[name.lower()],
+                                                               out["score_thrs"])
+    return out
+
+
+def tracking_curve(ev, score_thrs, frame_thr, alphas, measures):
+    frame_thr = _frame_thr(ev, frame_thr)
+    alphas = hota_alphas(alphas)
+    measures = curve_measures(measures)
+    thrs = curve_score_thrs(score_thrs, ev.flat.dt_score)
+    K = len(ev.params.cat_ids)
+    tables = _table_thr(ev, np.repeat(thrs[:, None], K, axis=1))
+    t = ev._run.curve_tables(frame_thr, tables, alphas - np.finfo(float).eps, measures)
+    cats = {k: _params_cats(ev, v, 1) for k, v in t.items()}
+    c = curve_numbers(thrs, cats["cat_counts"], cats.get("tp"), cats.get("loc"), cats.get("ass"),
+                      cats.get("clear"))
+    c.update(frame_thr=frame_thr, alphas=alphas, measures=measures)
+    return c
+
+
+def curve_lines(c):
+    """TaoEval.tracking_curve()'s result `c` as a small text table: a line per
+    threshold with the totals, "-" for a measure that was not asked for."""
+    tot = c["total"]
+    names = ("IDF1", "HOTA", "DetA", "AssA", "MOTA")
+    keys = ("idf1", "HOTA", "DetA", "AssA", "mota")
+    lines = [" tracking curve @[ frame IoU={:0.2f} | {} thresholds ]".format(
+                 c["frame_thr"], len(c["score_thrs"])),
+             " " + "score>=".rjust(12) + "dt_tracks".rjust(11)
+             + "".join(n.rjust(9) for n in names) + "IDSW".rjust(9)]
+    for t, thr in enumerate(c["score_thrs"].tolist()):
+        lines.append(" " + "{:.6g}".format(thr).rjust(12)
+                     + "{:>11d}".format(int(tot["dt_tracks"][t]))
+                     + "".join(_pct(tot[k][t], width=9) if k in tot else "-".rjust(9)
+                               for k in keys)
+                     + ("{:>9d}".format(int(tot["idsw"][t])) if "idsw" in tot
+                        else "-".rjust(9)))
+    return lines

@@ -5,7 +5,7 @@ events:
 
     python tools/time_error_types.py [--level image|track] [--config 3s] [--reps 20] [--warmup 3]
                                      [--impact] [--association] [--occlusions] [--identity]
-                                     [--hota] [--clear] [--confusion]
+                                     [--hota] [--clear] [--curve [N]] [--confusion]
 
 Times, on the image level's tables of that configuration, each alone on an idle
 stream: the fused match as a benchmark step runs it (the yardstick), the
@@ -40,6 +40,13 @@ taoamd_track_clear_reduce each alone between HIP events and the whole stage
 (engine.stage_track_clear) beside the identity and the HOTA stage in the same
 process, and reports the number of candidates, the share of steps with more than
 one ground truth and the sizes of the candidate store and the workspace.
+--level track --curve [N] times the track-level score thresholds at N (default
+10) thresholds, the default ones of tracking_curve(): taoamd_track_score_pass
+alone, taoamd_track_identity_assign_at over the N layers in ONE launch against
+the same layers as N launches of one layer each, the thresholded identity stage
+(engine.stage_track_identity_at) and the whole curve (that stage, then HOTA and
+CLEAR once per layer) beside the unthresholded identity, HOTA and CLEAR stages in
+the same process; reports the kept tracks, IDF1, HOTA and MOTA per threshold.
 --confusion
 (both levels) adds the confusion table: the level's links pass,
 taoamd_confusion_count and taoamd_confusion_fill, each alone between HIP events
@@ -135,6 +142,8 @@ def track_level(a, gt, dt, dev, V):
         return hota(a, res, dp, ws, timed)
     if a.clear:
         return clear(a, res, gt, fl, dp, ws, timed)
+    if a.curve:
+        return curve(a, res, fl, dp, ws, timed)
     res["match_fused"] = timed(lambda: engine.stage_match(dp, ws))
     # the first call builds the per-video lists and runs the match for match_gt
     engine.stage_track_error_types(dp, ws, 0, a.bg_thr)
@@ -622,6 +631,111 @@ def clear(a, res, gt, fl, dp, ws, timed):
     print(json.dumps(res))
 
 
+def curve(a, res, fl, dp, ws, timed):
+    """--level track --curve N: the track-level score thresholds at frame_thr 0.5
+    and N thresholds (the quantiles tracking_curve() takes by default, each applied
+    to every category): the pass kernel alone, the layered assignment in one
+    launch and as N launches of one layer, the thresholded identity stage, and the
+    whole curve -- that stage, then engine.stage_track_hota and stage_track_clear
+    per layer, as GpuRun.curve_tables runs them -- beside the unthresholded
+    stages in the same process."""
+    import torch
+    from tao_amodal_amd import _lib, engine
+    from tao_amodal_amd.evaluation.tao_amodal.followers import default_score_thrs
+    lib = _lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    thr = 0.5
+    alphas = np.ascontiguousarray(np.arange(0.05, 0.99, 0.05) - np.finfo(float).eps)
+    score = np.asarray(fl.dt_score, dtype=np.float64)
+    fin = score[np.isfinite(score)]
+    thrs = default_score_thrs(score) if a.curve == 10 else \
+        np.unique(np.quantile(fin, np.arange(a.curve) / float(a.curve), method="lower"))
+    T = len(thrs)
+    table = np.ascontiguousarray(np.repeat(thrs[:, None], dp.n_cat, axis=1))
+    # the first calls allocate the buffers of every stage
+    engine.stage_track_hota(dp, ws, alphas, thr)
+    engine.stage_track_clear(dp, ws, thr, [])
+    engine.stage_track_identity_at(dp, ws, thr, table)
+    torch.cuda.synchronize()
+    t = dp.t
+    sizes = (dp.n_dt, dp.n_gt, dp.n_cells, dp.n_iou, int(t["dt_frame_pos"].numel()),
+             int(t["gt_frame_pos"].numel()))
+    cells = (t["cell_dt_off"].data_ptr(), t["cell_gt_off"].data_ptr(),
+             t["cell_iou_off"].data_ptr())
+    table_t = torch.from_numpy(table).to(dp.device)
+    passed = torch.empty((T, max(dp.n_dt, 1)), dtype=torch.uint8, device=dp.device)
+    cat_counts = torch.empty((T, dp.n_cat, 6), dtype=torch.int64, device=dp.device)
+    dt_ident = torch.empty((T, max(dp.n_dt, 1), 2), dtype=torch.int32, device=dp.device)
+    status = torch.empty(1, dtype=torch.int32, device=dp.device)
+
+    def score_pass():
+        _lib.check(lib.taoamd_track_score_pass(
+            dp.n_dt, dp.n_cat, T, t["dt_score"].data_ptr(), t["dt_cat"].data_ptr(),
+            table_t.data_ptr(), None, passed.data_ptr(), stream), "taoamd_track_score_pass")
+
+    def assign_at(first, n):
+        _lib.check(lib.taoamd_track_identity_assign_at(
+            *sizes, dp.n_cat, n, *cells, t["gt_cat"].data_ptr(), t["gt_flags"].data_ptr(),
+            t["dt_cat"].data_ptr(), t["dt_flags"].data_ptr(), passed[first].data_ptr(),
+            t["dt_frame_off"].data_ptr(), t["gt_frame_off"].data_ptr(),
+            ws.ident_share.data_ptr(), cat_counts[first].data_ptr(), None,
+            dt_ident[first].data_ptr(), status.data_ptr(), ws.at_ws.data_ptr(), ws.at_bytes,
+            stream), "taoamd_track_identity_assign_at")
+
+    def looped():
+        for k in range(T):
+            assign_at(k, 1)
+
+    def whole():
+        engine.stage_track_identity_at(dp, ws, thr, table)
+        for k in range(T):
+            engine.stage_track_hota(dp, ws, alphas, thr, keep=ws.at_keep[k])
+            engine.stage_track_clear(dp, ws, thr, [], keep=ws.at_keep[k])
+    score_pass()
+    res["curve_thresholds"] = [float(x) for x in thrs]
+    res["identity_stage"] = timed(lambda: engine.stage_track_identity(dp, ws, thr))
+    res["hota_stage"] = timed(lambda: engine.stage_track_hota(dp, ws, alphas, thr))
+    res["clear_stage_no_windows"] = timed(lambda: engine.stage_track_clear(dp, ws, thr, []))
+    res["score_pass"] = timed(score_pass)
+    res["assign_at_one_launch"] = timed(lambda: assign_at(0, T))
+    one = cat_counts.clone()
+    res["assign_at_one_layer_per_launch"] = timed(looped)
+    res["assign_at_launches_agree"] = bool(torch.equal(one, cat_counts))
+    res["assign_one_layer"] = timed(lambda: assign_at(0, 1))
+    res["identity_at_stage"] = timed(
+        lambda: engine.stage_track_identity_at(dp, ws, thr, table))
+    res["curve_whole"] = timed_calls(whole, 1, max(a.reps // 4, 3))
+    _lib.kernel_timing(True)
+    for _ in range(a.reps):
+        score_pass()
+        assign_at(0, T)
+    res["kernels_ms"] = {k: round(ms / n, 4) for k, (ms, n) in _lib.kernel_timings().items()}
+    _lib.kernel_timing(False)
+    torch.cuda.synchronize()
+    res["curve_status"] = int(status.item())
+    res["curve_workspace_bytes"] = int(ws.at_bytes)
+    res["identity_workspace_bytes"] = int(ws.ident_bytes)
+    # what the curve says (untimed): the totals per threshold
+    rows = []
+    whole()
+    cc = ws.at_cat_counts.sum(1).tolist()
+    for k in range(T):
+        engine.stage_track_hota(dp, ws, alphas, thr, keep=ws.at_keep[k])
+        engine.stage_track_clear(dp, ws, thr, [], keep=ws.at_keep[k])
+        tp = ws.hota_tp.sum(0).double()
+        ass = ws.hota_ass.sum(0).double()[:, 0] / _lib.HOTA_ONE
+        deta = tp / torch.clamp(cc[k][1] + cc[k][3] - tp, min=1)
+        assa = ass / torch.clamp(tp, min=1)
+        tot = ws.clear_cat_counts.sum(0).tolist()
+        rows.append({"dt_tracks": cc[k][2],
+                     "idf1": round(2 * cc[k][4] / max(cc[k][1] + cc[k][3], 1), 6),
+                     "hota": round(float(torch.sqrt(deta * assa).mean().item()), 6),
+                     "mota": round((tot[0] - (cc[k][3] - tot[0]) - tot[1]) / max(cc[k][1], 1), 6),
+                     "idsw": tot[1]})
+    res["curve_rows"] = rows
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--level", choices=("image", "track"), default="image")
@@ -638,8 +752,14 @@ def main():
     ap.add_argument("--identity", action="store_true")
     ap.add_argument("--hota", action="store_true")
     ap.add_argument("--clear", action="store_true")
+    ap.add_argument("--curve", type=int, nargs="?", const=10, default=0,
+                    help="thresholds of the tracking curve (1 to 64; 10 when given bare)")
     ap.add_argument("--confusion", action="store_true")
     a = ap.parse_args()
+    if a.curve and a.level != "track":
+        ap.error("--curve is the track level's: --level track")
+    if not 0 <= a.curve <= 64:
+        ap.error("--curve takes 1 to 64 thresholds")
     if a.association and a.level != "track":
         ap.error("--association is the track level's: --level track")
     if a.occlusions and a.level != "track":
