@@ -581,26 +581,47 @@ class Workspace:
                 self.ious_out = torch.empty(max(dp.n_iou, 1),
                                             dtype=torch.float64, device=dev)
         # the on-request analyses (stage_scores, the error breakdown, its impact
-        # and its confusion, stage_track_association, stage_track_occlusion): allocated
-        # by their first call
+        # and its confusion; the track analyses: declare_track_products):
+        # allocated by their first call
         self.scores = None
         self.err_match_gt = self.err_dt_counts = self.err_gt_counts = self.err_dt_type = None
         self.err_link_same = self.err_link_other = self.err_held = None
         self.imp_ws = self.imp_precision = self.imp_num_gt = None
         self.conf_ws = self.conf_off = self.conf_gt_cat = self.conf_counts = None
         self.conf_n = 0                   # entries of the last stage_confusion
-        self.assoc_gt = self.assoc_vis_counts = None
-        self.assoc_frame_thr = None       # the frame_thr ws.assoc_best holds the followers of
-        self.occ_ws = self.occ_gt = self.occ_off = self.occ_counts = self.occ_episodes = None
-        self.ident_ws = self.ident_share = self.ident_cat_counts = None
-        self.ident_frame_thr = None       # the frame_thr ws.ident_keep holds the kept tracks of
-        # the thresholded identity's own (stage_track_identity_at), never the above
-        self.at_ws = self.at_share = self.at_pass = self.at_cat_counts = None
-        self.at_frame_thr = None          # the frame_thr ws.at_share holds the shares of
-        self.hota_ws = self.hota_mc = self.hota_lc = None
-        self.clear_ws = self.clear_cand = self.clear_vis_counts = None
-        self.occ_n = None                # episodes of the last stage_track_occlusion that read them
+        self.declare_track_products()
         self.pairs_counted = False        # stage_track_iou counted the pairs' common frames
+
+    # What the stages of the track analyses keep with the workspace (_buffer,
+    # _workspace) or leave as their last result: None until a first call.
+    # ident_share holds the LAST run of taoamd_track_identity_share, whichever
+    # stage asked for it (_identity_share): the shares at valid["share"], which
+    # need not be the threshold of ident_keep / ident_gt / ident_dt /
+    # ident_cat_counts (valid["identity"]).  The at_* are the thresholded
+    # identity's own (stage_track_identity_at); occ_n, clear_n: the episodes /
+    # candidates the last call read.
+    TRACK_PRODUCTS = (
+        "assoc_ws", "assoc_bytes", "assoc_follow", "assoc_gt", "assoc_cat_counts",
+        "assoc_vis_counts", "assoc_best", "assoc_best_iou", "assoc_vis_rng",
+        "occ_ws", "occ_bytes", "occ_gt", "occ_off", "occ_counts", "occ_episodes", "occ_n",
+        "ident_ws", "ident_bytes", "ident_status", "ident_share", "ident_cat_counts", "ident_gt",
+        "ident_dt", "ident_keep",
+        "at_ws", "at_bytes", "at_status", "at_pass", "at_thr", "at_cat_counts", "at_dt", "at_gt",
+        "at_keep",
+        "hota_ws", "hota_bytes", "hota_status", "hota_pot", "hota_mc", "hota_lc", "hota_match",
+        "hota_match_iou", "hota_tp", "hota_loc", "hota_ass",
+        "clear_ws", "clear_bytes", "clear_status", "clear_off", "clear_step", "clear_cand",
+        "clear_row", "clear_q", "clear_iou", "clear_n", "clear_match", "clear_match_iou",
+        "clear_sw", "clear_gt", "clear_cat_counts", "clear_vis_counts")
+
+    def declare_track_products(self):
+        for name in self.TRACK_PRODUCTS:
+            setattr(self, name, None)
+        # product -> the key it is valid for (_valid, _producing): "followers"
+        # (assoc_best and kin), "share" (ident_share), "identity" (ident_keep,
+        # ident_gt, ident_dt, ident_cat_counts), each at its frame_thr; and a
+        # stage's own buffers ("<stage> buffers": _stage_buffers) at their sizes
+        self.valid = {}
 
 
 def _order_of(ws):
@@ -1381,6 +1402,126 @@ def _vis_windows(dp, vis_rng):
     return vis_rng
 
 
+def _buffer(ws, dev, name, shape, dtype, exact=False):
+    """The buffer rule of the track stages: ws.<name> is allocated by the first
+    call that asks for it and kept with the workspace.  `shape`: an int or a
+    tuple.  By default at least shape[0] leading rows of the trailing shape: a
+    larger buffer stays, a smaller one is regrown, and the buffer is handed out
+    whole -- the kernels take its address; the leading rows are its [:shape[0]]
+    (no view is formed here: a slice costs the stages that do not want one
+    microseconds between two launches).  exact=True: a buffer of `shape` itself,
+    allocated anew where the shape differs, and None (ws.<name> too) for a table
+    of no rows: no windows."""
+    shape = (shape,) if isinstance(shape, int) else tuple(shape)
+    have = getattr(ws, name)
+    if have is not None and have.shape == shape:
+        return have
+    if exact:
+        have = torch.empty(shape, dtype=dtype, device=dev) if shape[0] else None
+        setattr(ws, name, have)
+        return have
+    if have is None or have.shape[0] < shape[0] or have.shape[1:] != shape[1:]:
+        have = torch.empty(shape, dtype=dtype, device=dev)
+        setattr(ws, name, have)
+    return have
+
+
+def _workspace(ws, dev, stage, nbytes):
+    """The workspace pair of a track stage: ws.<stage>_ws of ws.<stage>_bytes (256
+    at least), allocated by the first call and regrown where a call needs more
+    than it holds."""
+    if getattr(ws, stage + "_ws") is None or getattr(ws, stage + "_bytes") < nbytes:
+        setattr(ws, stage + "_bytes", int(nbytes))
+        setattr(ws, stage + "_ws",
+                torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev))
+
+
+def _stage_buffers(ws, dev, stage, key, nbytes, buffers):
+    """A stage's workspace and buffers under _workspace and _buffer, asked for
+    where the stage's last call on this workspace had other sizes `key` (the
+    product "<stage> buffers") and only then: nbytes() gives the workspace's
+    bytes, buffers() rows of (name, shape, dtype[, exact])."""
+    if not _valid(ws, stage + " buffers", key):
+        with _producing(ws, stage + " buffers", key):
+            _workspace(ws, dev, stage, nbytes())
+            for request in buffers():
+                _buffer(ws, dev, *request)
+
+
+def _valid(ws, product, key):
+    """Does the workspace hold `product` (a name of ws.valid) for `key`."""
+    return ws.valid.get(product) == key
+
+
+class _producing:
+    """The validity rule of what the track stages reuse, as a context around the
+    lines that write a product: the key is cleared before the first launch that
+    writes it and set after the last check passed, so the product is valid for
+    no key after the lines raised anywhere.  The products: the results a later
+    stage reads ("followers", "share", "identity", at their frame_thr) and each
+    stage's own buffers ("<stage> buffers", at the sizes they depend on beyond
+    the problem's: a call with the same sizes asks for none again)."""
+
+    def __init__(self, ws, product, key):
+        self.valid, self.product, self.key = ws.valid, product, key
+
+    def __enter__(self):
+        self.valid.pop(self.product, None)
+
+    def __exit__(self, raised, *_):
+        if raised is None:
+            self.valid[self.product] = self.key
+
+
+_SEARCH_BOUND = "a search ran out of its loop bound"
+
+
+def _raise_on_status(status, name, texts):
+    """Reads the status word a stage's kernels left (one synchronisation of the
+    current stream); a non-zero code raises in the name of the entry point, with
+    texts[code - 1] -- the last text for every greater code."""
+    code = int(status.item())
+    if code:
+        raise _lib.TaoAmdError("%s: status %d (%s)"
+                               % (name, code, texts[min(code, len(texts)) - 1]))
+
+
+def _vis_tables(dp, ws, name, vis_rng, columns):
+    """The windows' side of the association and of CLEAR: ws.<name> int64[n_vis,
+    n_cat, len(columns)] under the exact rule (None without windows), and the
+    arguments (the frames' visibility, the windows' upload, ws.<name>) as
+    pointers, None without windows.  Also returns the upload, which the caller
+    keeps alive until its kernels ran."""
+    n_vis = len(vis_rng)
+    rng_t = torch.from_numpy(vis_rng).to(dp.device) if n_vis else None
+    counts = _buffer(ws, dp.device, name, (n_vis, dp.n_cat, len(columns)), torch.int64,
+                     exact=True)
+    return (_ptr(dp.t["gt_frame_vis"]) if n_vis else None, _ptr(rng_t), _ptr(counts)), rng_t
+
+
+def _identity_share(dp, ws, frame_thr, tables, work):
+    """taoamd_track_identity_share at `frame_thr` into ws.ident_share int32[n_iou]
+    (the product "share"), in the workspace `work` = (pointer, bytes) of the
+    calling stage, which has asked for ws.ident_share: the frame index the call
+    builds there is read by its own kernel alone.  `tables` as of _track_tables."""
+    sizes, cells, frames = tables
+    with _producing(ws, "share", frame_thr):
+        _lib.check(_lib.load().taoamd_track_identity_share(
+            *sizes, frame_thr, *cells, *frames, _ptr(ws.ident_share), *work, _stream()),
+            "taoamd_track_identity_share")
+
+
+def kept_tracks(dp, ws, frame_thr, keep):
+    """The dt_keep table of HOTA and CLEAR: `keep` where the caller brings one,
+    else the identity's ws.ident_keep at `frame_thr` -- stage_track_identity
+    runs first unless the workspace holds it for that threshold."""
+    if keep is not None:
+        return keep
+    if not _valid(ws, "identity", frame_thr):
+        stage_track_identity(dp, ws, frame_thr)
+    return ws.ident_keep
+
+
 def stage_track_association(dp, ws, frame_thr, vis_rng):
     """Per-frame followers of the ground-truth tracks (taoamd_track_association;
     the definition is in include/tao_amodal_hip.h): ws.assoc_follow[n_iou] in the
@@ -1391,38 +1532,30 @@ def stage_track_association(dp, ws, frame_thr, vis_rng):
     {lo, hi} pairs; they need set_frame_visibility).  On request only.  Reads the
     track tables alone -- never ws.iou, never the match --, so it depends on
     neither the metric, the thresholds nor the ranges.  Buffers are allocated on
-    the first call and kept with the workspace."""
-    sizes, cells, frames = _track_tables(dp, "association is")
-    lib, t, dev = _lib.load(), dp.t, dp.device
-    vis_rng = _vis_windows(dp, vis_rng)
-    n_vis = len(vis_rng)
-    n_gf = sizes[5]
-    if ws.assoc_gt is None:
-        ws.assoc_bytes = lib.taoamd_track_association_workspace(dp.n_dt, dp.n_gt, n_gf)
-        ws.assoc_ws = torch.empty(max(int(ws.assoc_bytes), 256), dtype=torch.uint8, device=dev)
-        ws.assoc_follow = torch.empty(max(dp.n_iou, 1), dtype=torch.int32, device=dev)
-        ws.assoc_gt = torch.empty((max(dp.n_gt, 1), len(_lib.ASSOC_TRACK_COLUMNS)),
-                                  dtype=torch.int32, device=dev)
-        ws.assoc_cat_counts = torch.empty((dp.n_cat, len(_lib.ASSOC_CAT_COLUMNS)),
-                                          dtype=torch.int64, device=dev)
-        ws.assoc_best = torch.empty(max(n_gf, 1), dtype=torch.int32, device=dev)
-        ws.assoc_best_iou = torch.empty(max(n_gf, 1), dtype=torch.float64, device=dev)
-        ws.assoc_vis_counts = None
-    if n_vis and (ws.assoc_vis_counts is None or ws.assoc_vis_counts.shape[0] != n_vis):
-        ws.assoc_vis_counts = torch.empty((n_vis, dp.n_cat, len(_lib.ASSOC_VIS_COLUMNS)),
-                                          dtype=torch.int64, device=dev)
-    if not n_vis:
-        ws.assoc_vis_counts = None
-    rng_t = torch.from_numpy(vis_rng).to(dev) if n_vis else None
-    _lib.check(lib.taoamd_track_association(
-        *sizes, dp.n_cat, n_vis, float(frame_thr), *cells, _ptr(t["gt_cat"]), _ptr(t["gt_flags"]),
-        *frames, _ptr(t["gt_frame_vis"]) if n_vis else None, _ptr(rng_t),
-        _ptr(ws.assoc_follow), _ptr(ws.assoc_gt), _ptr(ws.assoc_cat_counts),
-        _ptr(ws.assoc_vis_counts), _ptr(ws.assoc_best), _ptr(ws.assoc_best_iou),
-        _ptr(ws.assoc_ws), ws.assoc_bytes, _stream()), "taoamd_track_association")
-    # (the windows' upload is read by the kernels of this stream: alive until they ran)
-    ws.assoc_vis_rng = rng_t
-    ws.assoc_frame_thr = float(frame_thr)
+    the first call and kept with the workspace.  The followers are the product
+    "followers" of ws.valid, at `frame_thr`."""
+    lib, t, dev, frame_thr = _lib.load(), dp.t, dp.device, float(frame_thr)
+    i32 = torch.int32
+    with _producing(ws, "followers", frame_thr):
+        sizes, cells, frames = _track_tables(dp, "association is")
+        vis_rng = _vis_windows(dp, vis_rng)
+        n_gf = sizes[5]
+        _stage_buffers(
+            ws, dev, "assoc", (),
+            lambda: lib.taoamd_track_association_workspace(dp.n_dt, dp.n_gt, n_gf), lambda: (
+                ("assoc_follow", max(dp.n_iou, 1), i32),
+                ("assoc_gt", (max(dp.n_gt, 1), len(_lib.ASSOC_TRACK_COLUMNS)), i32),
+                ("assoc_cat_counts", (dp.n_cat, len(_lib.ASSOC_CAT_COLUMNS)), torch.int64),
+                ("assoc_best", max(n_gf, 1), i32),
+                ("assoc_best_iou", max(n_gf, 1), torch.float64)))
+        # (the windows' upload is read by the kernels of this stream: alive until they ran)
+        (vis, rng, vis_counts), ws.assoc_vis_rng = _vis_tables(
+            dp, ws, "assoc_vis_counts", vis_rng, _lib.ASSOC_VIS_COLUMNS)
+        _lib.check(lib.taoamd_track_association(
+            *sizes, dp.n_cat, len(vis_rng), frame_thr, *cells, _ptr(t["gt_cat"]),
+            _ptr(t["gt_flags"]), *frames, vis, rng, _ptr(ws.assoc_follow), _ptr(ws.assoc_gt),
+            _ptr(ws.assoc_cat_counts), vis_counts, _ptr(ws.assoc_best), _ptr(ws.assoc_best_iou),
+            _ptr(ws.assoc_ws), ws.assoc_bytes, _stream()), "taoamd_track_association")
 
 
 def stage_track_occlusion(dp, ws, frame_thr, vis_lo, vis_hi, recover, len_edges, episodes=False):
@@ -1452,33 +1585,29 @@ def stage_track_occlusion(dp, ws, frame_thr, vis_lo, vis_hi, recover, len_edges,
         raise _lib.TaoAmdError("%d length buckets; the kernels take 1 to %d"
                                % (n_len, _lib.TRACK_OCCLUSION_LEN))
     frame_thr = float(frame_thr)
-    if ws.assoc_gt is None or ws.assoc_frame_thr != frame_thr:
+    if not _valid(ws, "followers", frame_thr):
         stage_track_association(dp, ws, frame_thr, [])
-    if ws.occ_ws is None:
-        ws.occ_bytes = lib.taoamd_track_occlusion_workspace(dp.n_gt, n_gf, n_len)
-        ws.occ_ws = torch.empty(max(int(ws.occ_bytes), 256), dtype=torch.uint8, device=dev)
-        ws.occ_gt = torch.empty((max(dp.n_gt, 1), len(_lib.OCC_TRACK_COLUMNS)),
-                                dtype=torch.int32, device=dev)
-        ws.occ_off = torch.empty(dp.n_gt + 1, dtype=torch.int64, device=dev)
-    if ws.occ_counts is None or ws.occ_counts.shape[1] != n_len:
-        ws.occ_counts = torch.empty((dp.n_cat, n_len, len(_lib.OCC_COUNT_COLUMNS)),
-                                    dtype=torch.int64, device=dev)
+    _stage_buffers(
+        ws, dev, "occ", n_len,
+        lambda: lib.taoamd_track_occlusion_workspace(dp.n_gt, n_gf, n_len), lambda: (
+            ("occ_gt", (max(dp.n_gt, 1), len(_lib.OCC_TRACK_COLUMNS)), torch.int32),
+            ("occ_off", dp.n_gt + 1, torch.int64),
+            ("occ_counts", (dp.n_cat, n_len, len(_lib.OCC_COUNT_COLUMNS)), torch.int64, True)))
+    work = (_ptr(ws.occ_ws), ws.occ_bytes, s)
     tables = (dp.n_gt, n_gf, dp.n_cat, n_len, int(recover), float(vis_lo), float(vis_hi),
               edges.ctypes.data, _ptr(t["gt_cat"]), _ptr(t["gt_flags"]),
               frames[3], _ptr(t["gt_frame_vis"]), _ptr(ws.assoc_best))
     _lib.check(lib.taoamd_track_occlusion_count(
-        *tables, _ptr(ws.occ_gt), _ptr(ws.occ_off), _ptr(ws.occ_counts), _ptr(ws.occ_ws),
-        ws.occ_bytes, s), "taoamd_track_occlusion_count")
+        *tables, _ptr(ws.occ_gt), _ptr(ws.occ_off), _ptr(ws.occ_counts), *work),
+        "taoamd_track_occlusion_count")
     ws.occ_n = None
     if not episodes:
         return
     ws.occ_n = int(ws.occ_off[-1].item())           # (synchronises)
-    if ws.occ_episodes is None or ws.occ_episodes.shape[0] < ws.occ_n:
-        ws.occ_episodes = torch.empty((max(ws.occ_n, 1), len(_lib.OCC_EPISODE_COLUMNS)),
-                                      dtype=torch.int32, device=dev)
+    ep = _buffer(ws, dev, "occ_episodes", (max(ws.occ_n, 1), len(_lib.OCC_EPISODE_COLUMNS)),
+                 torch.int32)
     _lib.check(lib.taoamd_track_occlusion_fill(
-        *tables, _ptr(ws.occ_off), ws.occ_n, _ptr(ws.occ_episodes), _ptr(ws.occ_ws),
-        ws.occ_bytes, s), "taoamd_track_occlusion_fill")
+        *tables, _ptr(ws.occ_off), ws.occ_n, _ptr(ep), *work), "taoamd_track_occlusion_fill")
 
 
 def stage_track_identity(dp, ws, frame_thr):
@@ -1490,43 +1619,38 @@ def stage_track_identity(dp, ws, frame_thr):
     int64[n_cat, 6], ws.ident_gt int32[n_gt, 2] = {the assigned detection row or
     -1, its share}, ws.ident_dt int32[n_dt, 2] = {the assigned ground-truth row or
     -1, kept}, ws.ident_keep uint8[n_dt] = that `kept` column as the dt_keep table
-    HOTA and CLEAR read.  On request only.  Reads the track tables alone, like
+    HOTA and CLEAR read.  The four tables of the assignment are the product
+    "identity" of ws.valid at `frame_thr`; ws.ident_share is a product of its
+    own ("share"), written by every call of this stage and by
+    stage_track_identity_at where it needs another threshold's.  On request
+    only.  Reads the track tables alone, like
     stage_track_association.  Raises if the assignment kernel reports a non-zero
     status (an exhausted loop bound, weights beyond 64-bit potentials): one
     synchronisation of the current stream.  Buffers are allocated
     on the first call and kept with the workspace: 4 bytes per pair of a cell, 8
     per track and 1 more per detection track, and a workspace of 56 bytes per
     detection track, 44 per ground-truth track and 4 per ground-truth frame."""
-    sizes, cells, frames = _track_tables(dp, "identity is")
-    lib, t, dev, s = _lib.load(), dp.t, dp.device, _stream()
-    if ws.ident_ws is None:
-        ws.ident_bytes = lib.taoamd_track_identity_workspace(dp.n_dt, dp.n_gt, sizes[5])
-        ws.ident_ws = torch.empty(max(int(ws.ident_bytes), 256), dtype=torch.uint8, device=dev)
-        ws.ident_share = torch.empty(max(dp.n_iou, 1), dtype=torch.int32, device=dev)
-        ws.ident_cat_counts = torch.empty((dp.n_cat, len(_lib.IDENT_CAT_COLUMNS)),
-                                          dtype=torch.int64, device=dev)
-        ws.ident_gt = torch.empty((max(dp.n_gt, 1), 2), dtype=torch.int32, device=dev)
-        ws.ident_dt = torch.empty((max(dp.n_dt, 1), 2), dtype=torch.int32, device=dev)
-        ws.ident_keep = torch.empty(max(dp.n_dt, 1), dtype=torch.uint8, device=dev)
-        ws.ident_status = torch.empty(1, dtype=torch.int32, device=dev)
-    _lib.check(lib.taoamd_track_identity_share(
-        *sizes, float(frame_thr), *cells, *frames,
-        _ptr(ws.ident_share), _ptr(ws.ident_ws), ws.ident_bytes, s),
-        "taoamd_track_identity_share")
-    _lib.check(lib.taoamd_track_identity_assign(
-        *sizes, dp.n_cat, *cells, _ptr(t["gt_cat"]), _ptr(t["gt_flags"]), _ptr(t["dt_cat"]),
-        _ptr(t["dt_flags"]), frames[0], frames[3],
-        _ptr(ws.ident_share), _ptr(ws.ident_cat_counts), _ptr(ws.ident_gt), _ptr(ws.ident_dt),
-        _ptr(ws.ident_status), _ptr(ws.ident_ws), ws.ident_bytes, s),
-        "taoamd_track_identity_assign")
-    ws.ident_keep.copy_(ws.ident_dt[:, 1])
-    status = int(ws.ident_status.item())            # (synchronises)
-    ws.ident_frame_thr = None
-    if status:
-        raise _lib.TaoAmdError("taoamd_track_identity_assign: status %d (%s)" % (
-            status, "a search ran out of its loop bound" if status == 1 else
-            "a cell's weights exceed 64-bit potentials"))
-    ws.ident_frame_thr = float(frame_thr)
+    lib, t, dev, frame_thr = _lib.load(), dp.t, dp.device, float(frame_thr)
+    i32 = torch.int32
+    with _producing(ws, "identity", frame_thr):
+        sizes, cells, frames = tables = _track_tables(dp, "identity is")
+        _stage_buffers(
+            ws, dev, "ident", (),
+            lambda: lib.taoamd_track_identity_workspace(dp.n_dt, dp.n_gt, sizes[5]), lambda: (
+                ("ident_share", max(dp.n_iou, 1), i32),
+                ("ident_cat_counts", (dp.n_cat, len(_lib.IDENT_CAT_COLUMNS)), torch.int64),
+                ("ident_gt", (max(dp.n_gt, 1), 2), i32), ("ident_dt", (max(dp.n_dt, 1), 2), i32),
+                ("ident_keep", max(dp.n_dt, 1), torch.uint8), ("ident_status", 1, i32)))
+        work = (_ptr(ws.ident_ws), ws.ident_bytes)
+        _identity_share(dp, ws, frame_thr, tables, work)
+        _lib.check(lib.taoamd_track_identity_assign(
+            *sizes, dp.n_cat, *cells, _ptr(t["gt_cat"]), _ptr(t["gt_flags"]), _ptr(t["dt_cat"]),
+            _ptr(t["dt_flags"]), frames[0], frames[3], _ptr(ws.ident_share),
+            _ptr(ws.ident_cat_counts), _ptr(ws.ident_gt), _ptr(ws.ident_dt),
+            _ptr(ws.ident_status), *work, _stream()), "taoamd_track_identity_assign")
+        ws.ident_keep.copy_(ws.ident_dt[:, 1])
+        _raise_on_status(ws.ident_status, "taoamd_track_identity_assign",
+                         (_SEARCH_BOUND, "a cell's weights exceed 64-bit potentials"))
 
 
 def _thr_table(dp, thr_table):
@@ -1555,10 +1679,8 @@ def stage_track_score_pass(dp, ws, thr_table, base):
     n_thr = len(thr)
     if t["dt_score"].dtype != torch.float64:
         raise _lib.TaoAmdError("dt_score is %s; the pass rule reads doubles" % t["dt_score"].dtype)
-    if ws.at_pass is None or ws.at_pass.shape[0] < n_thr:
-        ws.at_pass = torch.empty((n_thr, max(dp.n_dt, 1)), dtype=torch.uint8, device=dev)
+    out = _buffer(ws, dev, "at_pass", (n_thr, max(dp.n_dt, 1)), torch.uint8)[:n_thr]
     thr_t = torch.from_numpy(thr).to(dev)
-    out = ws.at_pass[:n_thr]
     _lib.check(lib.taoamd_track_score_pass(
         dp.n_dt, dp.n_cat, n_thr, _ptr(t["dt_score"]), _ptr(t["dt_cat"]), _ptr(thr_t), _ptr(base),
         _ptr(out), _stream()), "taoamd_track_score_pass")
@@ -1575,33 +1697,24 @@ def stage_track_identity_at(dp, ws, frame_thr, thr_table, per_track=False):
     ws.at_keep uint8[n_thr, n_dt] = the layers' kept columns (kept AND pass: what
     stage_track_hota and stage_track_clear take as `keep`), and with
     per_track=True ws.at_gt int32[n_thr, n_gt, 2] (None otherwise).  share runs
-    once for all layers, and not at all where the workspace holds it for
-    `frame_thr`: ws.ident_share of stage_track_identity (ws.ident_frame_thr), or
-    this stage's own ws.at_share (ws.at_frame_thr).  Every buffer is this
-    stage's own: nothing stage_track_identity left is written.  Raises on a
+    once for all layers, and not at all where ws.ident_share holds the shares at
+    `frame_thr` (the product "share": of stage_track_identity or of an earlier
+    call of this stage); it is the one buffer the two stages have in common,
+    and nothing else stage_track_identity left is written.  Raises on a
     non-zero status: one synchronisation of the current stream.  The workspace
-    is the identity's with 44 bytes per track and layer."""
-    sizes, cells, frames = _track_tables(dp, "identity is")
+    is the identity's with 44 bytes per track and layer, regrown where a call
+    brings more layers."""
+    sizes, cells, frames = tables = _track_tables(dp, "identity is")
     lib, t, dev, s = _lib.load(), dp.t, dp.device, _stream()
     thr = _thr_table(dp, thr_table)
     n_thr, frame_thr = len(thr), float(frame_thr)
-    if ws.at_ws is None or ws.at_layers < n_thr:
-        ws.at_bytes = lib.taoamd_track_identity_layers_workspace(dp.n_dt, dp.n_gt, sizes[5], n_thr)
-        ws.at_ws = torch.empty(max(int(ws.at_bytes), 256), dtype=torch.uint8, device=dev)
-        ws.at_layers = n_thr
-        ws.at_status = torch.empty(1, dtype=torch.int32, device=dev)
-    if ws.ident_ws is not None and ws.ident_frame_thr == frame_thr:
-        share = ws.ident_share
-    else:
-        if ws.at_share is None:
-            ws.at_share = torch.empty(max(dp.n_iou, 1), dtype=torch.int32, device=dev)
-        if ws.at_frame_thr != frame_thr:
-            ws.at_frame_thr = None
-            _lib.check(lib.taoamd_track_identity_share(
-                *sizes, frame_thr, *cells, *frames, _ptr(ws.at_share), _ptr(ws.at_ws),
-                ws.at_bytes, s), "taoamd_track_identity_share")
-            ws.at_frame_thr = frame_thr
-        share = ws.at_share
+    _stage_buffers(
+        ws, dev, "at", n_thr,
+        lambda: lib.taoamd_track_identity_layers_workspace(dp.n_dt, dp.n_gt, sizes[5], n_thr),
+        lambda: (("at_status", 1, torch.int32), ("ident_share", max(dp.n_iou, 1), torch.int32)))
+    work = (_ptr(ws.at_ws), ws.at_bytes)
+    if not _valid(ws, "share", frame_thr):
+        _identity_share(dp, ws, frame_thr, tables, work)
     passed = stage_track_score_pass(dp, ws, thr, None)
     ws.at_cat_counts = torch.empty((n_thr, dp.n_cat, len(_lib.IDENT_CAT_COLUMNS)),
                                    dtype=torch.int64, device=dev)
@@ -1610,15 +1723,12 @@ def stage_track_identity_at(dp, ws, frame_thr, thr_table, per_track=False):
         if per_track else None
     _lib.check(lib.taoamd_track_identity_assign_at(
         *sizes, dp.n_cat, n_thr, *cells, _ptr(t["gt_cat"]), _ptr(t["gt_flags"]),
-        _ptr(t["dt_cat"]), _ptr(t["dt_flags"]), _ptr(passed), frames[0], frames[3], _ptr(share),
-        _ptr(ws.at_cat_counts), _ptr(ws.at_gt), _ptr(ws.at_dt), _ptr(ws.at_status),
-        _ptr(ws.at_ws), ws.at_bytes, s), "taoamd_track_identity_assign_at")
+        _ptr(t["dt_cat"]), _ptr(t["dt_flags"]), _ptr(passed), frames[0], frames[3],
+        _ptr(ws.ident_share), _ptr(ws.at_cat_counts), _ptr(ws.at_gt), _ptr(ws.at_dt),
+        _ptr(ws.at_status), *work, s), "taoamd_track_identity_assign_at")
     ws.at_keep = ws.at_dt[:, :, 1].to(torch.uint8).contiguous()
-    status = int(ws.at_status.item())               # (synchronises)
-    if status:
-        raise _lib.TaoAmdError("taoamd_track_identity_assign_at: status %d (%s)" % (
-            status, "a search ran out of its loop bound" if status == 1 else
-            "a cell's weights exceed 64-bit potentials"))
+    _raise_on_status(ws.at_status, "taoamd_track_identity_assign_at",
+                     (_SEARCH_BOUND, "a cell's weights exceed 64-bit potentials"))
 
 
 def stage_track_hota(dp, ws, alphas, frame_thr, keep=None):
@@ -1631,9 +1741,9 @@ def stage_track_hota(dp, ws, alphas, frame_thr, keep=None):
     localisation thresholds `alphas` (1 to 32 doubles, TrackEval's eps already
     subtracted).  The detection tracks that take part are the identity's kept
     ones at `frame_thr`: stage_track_identity runs first unless the workspace
-    holds it for that threshold (ws.ident_frame_thr) -- or, with `keep`, the
-    tracks of that uint8[n_dt] device tensor (a layer of ws.at_keep of
-    stage_track_identity_at), and the identity is neither run nor read.  On
+    holds it for that threshold (the product "identity" of ws.valid) -- or, with
+    `keep`, the tracks of that uint8[n_dt] device tensor (a layer of ws.at_keep
+    of stage_track_identity_at), and the identity is neither run nor read.  On
     request only.  Raises
     if the match reports a non-zero status (an exhausted loop bound): one
     synchronisation of the current stream.  Buffers are allocated on the first
@@ -1648,42 +1758,30 @@ def stage_track_hota(dp, ws, alphas, frame_thr, keep=None):
     if not 1 <= n_alpha <= _lib.TRACK_HOTA_ALPHAS:
         raise _lib.TaoAmdError("%d alphas; the kernels take 1 to %d"
                                % (n_alpha, _lib.TRACK_HOTA_ALPHAS))
-    frame_thr = float(frame_thr)
-    if keep is None:
-        if ws.ident_ws is None or ws.ident_frame_thr != frame_thr:
-            stage_track_identity(dp, ws, frame_thr)
-        keep = ws.ident_keep
-    n_gf = sizes[5]
-    if ws.hota_ws is None:
-        ws.hota_bytes = lib.taoamd_track_hota_workspace(dp.n_dt, dp.n_gt, n_gf)
-        ws.hota_ws = torch.empty(max(int(ws.hota_bytes), 256), dtype=torch.uint8, device=dev)
-        ws.hota_pot = torch.empty(max(dp.n_iou, 1), dtype=torch.int64, device=dev)
-        ws.hota_match = torch.empty(max(n_gf, 1), dtype=torch.int32, device=dev)
-        ws.hota_match_iou = torch.empty(max(n_gf, 1), dtype=torch.float64, device=dev)
-        ws.hota_status = torch.empty(1, dtype=torch.int32, device=dev)
-        ws.hota_mc = None
-    if ws.hota_mc is None or ws.hota_mc.shape[0] < n_alpha:
-        ws.hota_mc = torch.empty((n_alpha, max(dp.n_iou, 1)), dtype=torch.int32, device=dev)
-        ws.hota_lc = torch.empty((n_alpha, max(dp.n_iou, 1)), dtype=torch.int64, device=dev)
+    keep = kept_tracks(dp, ws, float(frame_thr), keep)
+    n_gf, n_iou, i32, i64 = max(sizes[5], 1), max(dp.n_iou, 1), torch.int32, torch.int64
+    _stage_buffers(
+        ws, dev, "hota", n_alpha,
+        lambda: lib.taoamd_track_hota_workspace(dp.n_dt, dp.n_gt, sizes[5]), lambda: (
+            ("hota_pot", n_iou, i64), ("hota_mc", (n_alpha, n_iou), i32),
+            ("hota_lc", (n_alpha, n_iou), i64), ("hota_match", n_gf, i32),
+            ("hota_match_iou", n_gf, torch.float64), ("hota_status", 1, i32)))
     ws.hota_tp = torch.empty((dp.n_cat, n_alpha), dtype=torch.int64, device=dev)
     ws.hota_loc = torch.empty((dp.n_cat, n_alpha), dtype=torch.int64, device=dev)
     ws.hota_ass = torch.empty((dp.n_cat, n_alpha, 3), dtype=torch.int64, device=dev)
     tables = (*cells, _ptr(t["gt_flags"]), _ptr(keep), *frames)
-    _lib.check(lib.taoamd_track_hota_align(
-        *sizes, *tables, _ptr(ws.hota_pot), _ptr(ws.hota_ws), ws.hota_bytes, s),
-        "taoamd_track_hota_align")
+    work = (_ptr(ws.hota_ws), ws.hota_bytes, s)
+    _lib.check(lib.taoamd_track_hota_align(*sizes, *tables, _ptr(ws.hota_pot), *work),
+               "taoamd_track_hota_align")
     _lib.check(lib.taoamd_track_hota_match(
         *sizes, n_alpha, alphas.ctypes.data, *tables, _ptr(ws.hota_pot), _ptr(ws.hota_mc),
         _ptr(ws.hota_lc), _ptr(ws.hota_match), _ptr(ws.hota_match_iou), _ptr(ws.hota_status),
-        _ptr(ws.hota_ws), ws.hota_bytes, s), "taoamd_track_hota_match")
+        *work), "taoamd_track_hota_match")
     _lib.check(lib.taoamd_track_hota_reduce(
         *sizes, dp.n_cat, n_alpha, *cells, _ptr(t["gt_cat"]), _ptr(t["gt_flags"]), frames[0],
         frames[3], _ptr(ws.hota_mc), _ptr(ws.hota_lc), _ptr(ws.hota_tp), _ptr(ws.hota_loc),
-        _ptr(ws.hota_ass), _ptr(ws.hota_ws), ws.hota_bytes, s), "taoamd_track_hota_reduce")
-    status = int(ws.hota_status.item())             # (synchronises)
-    if status:
-        raise _lib.TaoAmdError("taoamd_track_hota_match: status %d (a search ran out of its "
-                               "loop bound)" % status)
+        _ptr(ws.hota_ass), *work), "taoamd_track_hota_reduce")
+    _raise_on_status(ws.hota_status, "taoamd_track_hota_match", (_SEARCH_BOUND,))
 
 
 def stage_track_clear(dp, ws, frame_thr, vis_rng, keep=None):
@@ -1698,8 +1796,9 @@ def stage_track_clear(dp, ws, frame_thr, vis_rng, keep=None):
     `vis_rng` (up to 8 {lo, hi} pairs; they need set_frame_visibility).  The
     detection tracks that take part are the identity's kept ones at `frame_thr`:
     stage_track_identity runs first unless the workspace holds it for that
-    threshold (ws.ident_frame_thr) -- or, with `keep`, the tracks of that
-    uint8[n_dt] device tensor, as for stage_track_hota.  On request only.  The number of candidates is
+    threshold (the product "identity" of ws.valid) -- or, with `keep`, the tracks
+    of that uint8[n_dt] device tensor, as for stage_track_hota.  On request
+    only.  The number of candidates is
     read between count and fill, the status word at the end: two synchronisations
     of the current stream; a non-zero status raises.  Buffers are allocated on the
     first call and kept with the workspace: 22 bytes per ground-truth frame, 16
@@ -1709,63 +1808,43 @@ def stage_track_clear(dp, ws, frame_thr, vis_rng, keep=None):
     sizes, cells, frames = _track_tables(dp, "CLEAR is")
     lib, t, dev, s = _lib.load(), dp.t, dp.device, _stream()
     vis_rng = _vis_windows(dp, vis_rng)
-    n_vis = len(vis_rng)
     frame_thr = float(frame_thr)
-    if keep is None:
-        if ws.ident_ws is None or ws.ident_frame_thr != frame_thr:
-            stage_track_identity(dp, ws, frame_thr)
-        keep = ws.ident_keep
+    keep = kept_tracks(dp, ws, frame_thr, keep)
     n_dt, n_gt, n_cells, _, n_df, n_gf = sizes
-    if ws.clear_ws is None:
-        ws.clear_bytes = lib.taoamd_track_clear_workspace(n_dt, n_gt, n_gf)
-        ws.clear_ws = torch.empty(max(int(ws.clear_bytes), 256), dtype=torch.uint8, device=dev)
-        ws.clear_off = torch.empty(n_gf + 1, dtype=torch.int64, device=dev)
-        ws.clear_step = torch.empty(max(n_gf, 1), dtype=torch.uint8, device=dev)
-        ws.clear_match = torch.empty(max(n_gf, 1), dtype=torch.int32, device=dev)
-        ws.clear_match_iou = torch.empty(max(n_gf, 1), dtype=torch.float64, device=dev)
-        ws.clear_sw = torch.empty(max(n_gf, 1), dtype=torch.uint8, device=dev)
-        ws.clear_gt = torch.empty((max(n_gt, 1), len(_lib.CLEAR_TRACK_COLUMNS)),
-                                  dtype=torch.int32, device=dev)
-        ws.clear_cat_counts = torch.empty((dp.n_cat, len(_lib.CLEAR_CAT_COLUMNS)),
-                                          dtype=torch.int64, device=dev)
-        ws.clear_status = torch.empty(1, dtype=torch.int32, device=dev)
-    if n_vis and (ws.clear_vis_counts is None or ws.clear_vis_counts.shape[0] != n_vis):
-        ws.clear_vis_counts = torch.empty((n_vis, dp.n_cat, len(_lib.CLEAR_VIS_COLUMNS)),
-                                          dtype=torch.int64, device=dev)
-    if not n_vis:
-        ws.clear_vis_counts = None
+    i32, f64, u8 = torch.int32, torch.float64, torch.uint8
+    _stage_buffers(
+        ws, dev, "clear", (), lambda: lib.taoamd_track_clear_workspace(n_dt, n_gt, n_gf), lambda: (
+            ("clear_off", n_gf + 1, torch.int64), ("clear_step", max(n_gf, 1), u8),
+            ("clear_match", max(n_gf, 1), i32), ("clear_match_iou", max(n_gf, 1), f64),
+            ("clear_sw", max(n_gf, 1), u8), ("clear_status", 1, i32),
+            ("clear_gt", (max(n_gt, 1), len(_lib.CLEAR_TRACK_COLUMNS)), i32),
+            ("clear_cat_counts", (dp.n_cat, len(_lib.CLEAR_CAT_COLUMNS)), torch.int64)))
+    work = (_ptr(ws.clear_ws), ws.clear_bytes, s)
+    off, step, match, sw, gt = (_ptr(ws.clear_off), _ptr(ws.clear_step), _ptr(ws.clear_match),
+                                _ptr(ws.clear_sw), _ptr(ws.clear_gt))
     tables = (n_dt, n_gt, n_cells, n_df, n_gf, frame_thr, cells[0], cells[1],
               _ptr(t["gt_flags"]), _ptr(keep), *frames)
-    _lib.check(lib.taoamd_track_clear_count(
-        *tables, _ptr(ws.clear_off), _ptr(ws.clear_step), _ptr(ws.clear_ws), ws.clear_bytes, s),
-        "taoamd_track_clear_count")
+    _lib.check(lib.taoamd_track_clear_count(*tables, off, step, *work),
+               "taoamd_track_clear_count")
     ws.clear_n = int(ws.clear_off[-1].item())       # (synchronises)
-    if ws.clear_cand is None or ws.clear_cand[0].numel() < ws.clear_n:
-        ws.clear_cand = (torch.empty(max(ws.clear_n, 1), dtype=torch.int32, device=dev),
-                         torch.empty(max(ws.clear_n, 1), dtype=torch.int32, device=dev),
-                         torch.empty(max(ws.clear_n, 1), dtype=torch.float64, device=dev))
-    row, q, iou = ws.clear_cand
-    _lib.check(lib.taoamd_track_clear_fill(
-        *tables, _ptr(ws.clear_off), ws.clear_n, _ptr(row), _ptr(q), _ptr(iou), _ptr(ws.clear_ws),
-        ws.clear_bytes, s), "taoamd_track_clear_fill")
-    store = (_ptr(ws.clear_off), _ptr(row), _ptr(q))
+    ws.clear_cand = tuple(_buffer(ws, dev, name, max(ws.clear_n, 1), dtype) for name, dtype in
+                          (("clear_row", i32), ("clear_q", i32), ("clear_iou", f64)))
+    row, q, iou = map(_ptr, ws.clear_cand)
+    _lib.check(lib.taoamd_track_clear_fill(*tables, off, ws.clear_n, row, q, iou, *work),
+               "taoamd_track_clear_fill")
     _lib.check(lib.taoamd_track_clear_walk(
         n_dt, n_gt, n_cells, n_gf, ws.clear_n, cells[0], cells[1], _ptr(t["gt_flags"]),
-        frames[3], frames[4], *store, _ptr(iou), _ptr(ws.clear_step), _ptr(ws.clear_match),
-        _ptr(ws.clear_match_iou), _ptr(ws.clear_sw), _ptr(ws.clear_gt), _ptr(ws.clear_status),
-        _ptr(ws.clear_ws), ws.clear_bytes, s), "taoamd_track_clear_walk")
-    rng_t = torch.from_numpy(vis_rng).to(dev) if n_vis else None
+        frames[3], frames[4], off, row, q, iou, step, match, _ptr(ws.clear_match_iou), sw, gt,
+        _ptr(ws.clear_status), *work), "taoamd_track_clear_walk")
+    (vis, rng, vis_counts), rng_t = _vis_tables(dp, ws, "clear_vis_counts", vis_rng,
+                                                _lib.CLEAR_VIS_COLUMNS)
     _lib.check(lib.taoamd_track_clear_reduce(
-        n_dt, n_gt, n_gf, ws.clear_n, dp.n_cat, n_vis, _ptr(t["gt_cat"]), _ptr(t["gt_flags"]),
-        frames[3], _ptr(t["gt_frame_vis"]) if n_vis else None, _ptr(rng_t), *store,
-        _ptr(ws.clear_match), _ptr(ws.clear_sw), _ptr(ws.clear_gt), _ptr(ws.clear_cat_counts),
-        _ptr(ws.clear_vis_counts), _ptr(ws.clear_ws), ws.clear_bytes, s),
-        "taoamd_track_clear_reduce")
-    status = int(ws.clear_status.item())            # (synchronises; the windows were read)
-    if status:
-        raise _lib.TaoAmdError("taoamd_track_clear_walk: status %d (%s)" % (
-            status, "a search ran out of its loop bound" if status == 1 else
-            "a cell's smaller side exceeds %d" % _lib.TRACK_CLEAR_NMAX))
+        n_dt, n_gt, n_gf, ws.clear_n, dp.n_cat, len(vis_rng), _ptr(t["gt_cat"]),
+        _ptr(t["gt_flags"]), frames[3], vis, rng, off, row, q, match, sw, gt,
+        _ptr(ws.clear_cat_counts), vis_counts, *work), "taoamd_track_clear_reduce")
+    # (synchronises: the windows' upload rng_t was read while this frame held it)
+    _raise_on_status(ws.clear_status, "taoamd_track_clear_walk", (
+        _SEARCH_BOUND, "a cell's smaller side exceeds %d" % _lib.TRACK_CLEAR_NMAX))
 
 
 def stage_track_iou_guarded(dp, ws):

@@ -403,14 +403,11 @@ class GpuRun:
             e.stage_track_association(dp, ws, frame_thr, vis_rng)
             self.torch.cuda.synchronize(self.device)
         with timed("download"):
-            n_gt, n_gf = dp.n_gt, int(dp.t["gt_frame_pos"].numel())
-            n_vis = len(vis_rng)
-            return {"gt_assoc": ws.assoc_gt[:n_gt].cpu().numpy(),
-                    "cat_counts": ws.assoc_cat_counts.cpu().numpy(),
-                    "vis_counts": ws.assoc_vis_counts.cpu().numpy() if n_vis else
-                    np.zeros((0, dp.n_cat, 3), dtype=np.int64),
-                    "best": ws.assoc_best[:n_gf].cpu().numpy(),
-                    "best_iou": ws.assoc_best_iou[:n_gf].cpu().numpy()}
+            n_gf = int(dp.t["gt_frame_pos"].numel())
+            return self._download(
+                gt_assoc=(ws.assoc_gt, dp.n_gt), cat_counts=ws.assoc_cat_counts,
+                vis_counts=(ws.assoc_vis_counts, (0, dp.n_cat, 3)),
+                best=(ws.assoc_best, n_gf), best_iou=(ws.assoc_best_iou, n_gf))
 
     def occlusion_table(self, frame_thr, vis_rng, recover, len_edges, ann_vis):
         """Whether the follower of a ground-truth track is kept through occlusion
@@ -427,18 +424,46 @@ class GpuRun:
                                               len_edges, episodes=True)
             self.torch.cuda.synchronize(self.device)
         with timed("download"):
-            return {"gt_occ": ws.occ_gt[:dp.n_gt].cpu().numpy(),
-                    "counts": ws.occ_counts.cpu().numpy(),
-                    "episodes": ws.occ_episodes[:ws.occ_n].cpu().numpy()}
+            return self._download(gt_occ=(ws.occ_gt, dp.n_gt), counts=ws.occ_counts,
+                                  episodes=(ws.occ_episodes, ws.occ_n))
 
-    def _layers(self, score_thr):
-        """A threshold per category in the tables' order (float64[K]) as the
-        one-layer table of the thresholded stages."""
-        thr = np.ascontiguousarray(score_thr, dtype=np.float64).reshape(1, -1)
-        if thr.shape[1] != self.dp.n_cat:
-            raise ValueError("score_thr: %d thresholds for the tables' %d categories"
-                             % (thr.shape[1], self.dp.n_cat))
-        return thr
+    @staticmethod
+    def _download(**tables):
+        """Device tables on the host: name=tensor (all of it), name=(tensor, n)
+        (its first n rows) or name=(tensor or None, shape) (for None the int64
+        zeros of `shape`: a table of no windows)."""
+        out = {}
+        for name, table in tables.items():
+            t, n = table if isinstance(table, tuple) else (table, None)
+            if t is None:
+                out[name] = np.zeros(n, dtype=np.int64)
+            else:
+                out[name] = (t if n is None or isinstance(n, tuple) else t[:n]).cpu().numpy()
+        return out
+
+    def _kept(self, frame_thr, score_thr, per_track=False, rerun=False):
+        """(keep uint8[T, n_dt], cat_counts int64[T, K, 6]) on the device: the
+        identity's kept column and counts at `frame_thr`, a row per layer --
+        what hota_table(), clear_table() and curve_tables() run over.
+        `score_thr` None: the one row of the unthresholded identity (views of
+        ws.ident_keep and ws.ident_cat_counts), reused where the workspace holds
+        it for `frame_thr` unless `rerun`.  float64[K]: a threshold per category
+        in the tables' order, one layer; float64[T, K]: a table of layers
+        (engine.stage_track_identity_at, in one launch; `per_track` as there)."""
+        e, dp, ws = self.engine, self.dp, self.ws
+        if score_thr is None:
+            if rerun:
+                e.stage_track_identity(dp, ws, frame_thr)
+            keep = e.kept_tracks(dp, ws, float(frame_thr), None)
+            return keep[None], ws.ident_cat_counts[None]
+        thr = np.ascontiguousarray(score_thr, dtype=np.float64)
+        if thr.ndim < 2:
+            thr = thr.reshape(1, -1)
+            if thr.shape[1] != dp.n_cat:
+                raise ValueError("score_thr: %d thresholds for the tables' %d categories"
+                                 % (thr.shape[1], dp.n_cat))
+        e.stage_track_identity_at(dp, ws, frame_thr, thr, per_track=per_track)
+        return ws.at_keep, ws.at_cat_counts
 
     def identity_table(self, frame_thr, score_thr=None):
         """The identity measures' tables (engine.stage_track_identity; the
@@ -451,31 +476,13 @@ class GpuRun:
         association_table() refuses."""
         self._followers_at("identity()", None)
         dp, ws = self.dp, self.ws
-        if score_thr is not None:
-            with timed("kernels"):
-                self.engine.stage_track_identity_at(dp, ws, frame_thr, self._layers(score_thr),
-                                                    per_track=True)
-                self.torch.cuda.synchronize(self.device)
-            with timed("download"):
-                return {"cat_counts": ws.at_cat_counts[0].cpu().numpy(),
-                        "gt_ident": ws.at_gt[0, :dp.n_gt].cpu().numpy(),
-                        "dt_ident": ws.at_dt[0, :dp.n_dt].cpu().numpy()}
         with timed("kernels"):
-            self.engine.stage_track_identity(dp, ws, frame_thr)
+            _, counts = self._kept(frame_thr, score_thr, per_track=True, rerun=True)
+            gt, dt = (ws.ident_gt, ws.ident_dt) if score_thr is None else (ws.at_gt[0], ws.at_dt[0])
             self.torch.cuda.synchronize(self.device)
         with timed("download"):
-            return {"cat_counts": ws.ident_cat_counts.cpu().numpy(),
-                    "gt_ident": ws.ident_gt[:dp.n_gt].cpu().numpy(),
-                    "dt_ident": ws.ident_dt[:dp.n_dt].cpu().numpy()}
-
-    def _hota_download(self, cat_counts):
-        ws = self.ws
-        n_gf = int(self.dp.t["gt_frame_pos"].numel())
-        return {"cat_counts": cat_counts.cpu().numpy(),
-                "tp": ws.hota_tp.cpu().numpy(), "loc": ws.hota_loc.cpu().numpy(),
-                "ass": ws.hota_ass.cpu().numpy(),
-                "match": ws.hota_match[:n_gf].cpu().numpy(),
-                "match_iou": ws.hota_match_iou[:n_gf].cpu().numpy()}
+            return self._download(cat_counts=counts[0], gt_ident=(gt, dp.n_gt),
+                                  dt_ident=(dt, dp.n_dt))
 
     def hota_table(self, alphas, frame_thr, score_thr=None):
         """HOTA's integer tables (engine.stage_track_hota; the definition is in
@@ -488,28 +495,14 @@ class GpuRun:
         self._followers_at("hota()", None)
         dp, ws, e = self.dp, self.ws, self.engine
         with timed("kernels"):
-            if score_thr is None:
-                e.stage_track_hota(dp, ws, alphas, frame_thr)
-                counts = ws.ident_cat_counts
-            else:
-                e.stage_track_identity_at(dp, ws, frame_thr, self._layers(score_thr))
-                e.stage_track_hota(dp, ws, alphas, frame_thr, keep=ws.at_keep[0])
-                counts = ws.at_cat_counts[0]
+            keep, counts = self._kept(frame_thr, score_thr)
+            e.stage_track_hota(dp, ws, alphas, frame_thr, keep=keep[0])
             self.torch.cuda.synchronize(self.device)
         with timed("download"):
-            return self._hota_download(counts)
-
-    def _clear_download(self, ident_counts, n_vis):
-        dp, ws = self.dp, self.ws
-        n_gf = int(dp.t["gt_frame_pos"].numel())
-        return {"ident_counts": ident_counts.cpu().numpy(),
-                "cat_counts": ws.clear_cat_counts.cpu().numpy(),
-                "vis_counts": ws.clear_vis_counts.cpu().numpy() if n_vis else
-                np.zeros((0, dp.n_cat, 4), dtype=np.int64),
-                "gt_clear": ws.clear_gt[:dp.n_gt].cpu().numpy(),
-                "match": ws.clear_match[:n_gf].cpu().numpy(),
-                "match_iou": ws.clear_match_iou[:n_gf].cpu().numpy(),
-                "sw": ws.clear_sw[:n_gf].cpu().numpy()}
+            n_gf = int(dp.t["gt_frame_pos"].numel())
+            return self._download(cat_counts=counts[0], tp=ws.hota_tp, loc=ws.hota_loc,
+                                  ass=ws.hota_ass, match=(ws.hota_match, n_gf),
+                                  match_iou=(ws.hota_match_iou, n_gf))
 
     def clear_table(self, frame_thr, vis_rng, ann_vis, score_thr=None):
         """CLEAR MOT's integer tables (engine.stage_track_clear; the definition is
@@ -522,16 +515,16 @@ class GpuRun:
         self._followers_at("clear()", ann_vis)
         dp, ws, e = self.dp, self.ws, self.engine
         with timed("kernels"):
-            if score_thr is None:
-                e.stage_track_clear(dp, ws, frame_thr, vis_rng)
-                counts = ws.ident_cat_counts
-            else:
-                e.stage_track_identity_at(dp, ws, frame_thr, self._layers(score_thr))
-                e.stage_track_clear(dp, ws, frame_thr, vis_rng, keep=ws.at_keep[0])
-                counts = ws.at_cat_counts[0]
+            keep, counts = self._kept(frame_thr, score_thr)
+            e.stage_track_clear(dp, ws, frame_thr, vis_rng, keep=keep[0])
             self.torch.cuda.synchronize(self.device)
         with timed("download"):
-            return self._clear_download(counts, len(vis_rng))
+            n_gf = int(dp.t["gt_frame_pos"].numel())
+            return self._download(
+                ident_counts=counts[0], cat_counts=ws.clear_cat_counts,
+                vis_counts=(ws.clear_vis_counts, (0, dp.n_cat, 4)), gt_clear=(ws.clear_gt, dp.n_gt),
+                match=(ws.clear_match, n_gf), match_iou=(ws.clear_match_iou, n_gf),
+                sw=(ws.clear_sw, n_gf))
 
     def curve_tables(self, frame_thr, thr_tables, alphas, measures):
         """The integer tables of tracking_curve(): the identity over every layer
@@ -545,9 +538,8 @@ class GpuRun:
         dp, ws, e = self.dp, self.ws, self.engine
         out = {}
         with timed("kernels"):
-            e.stage_track_identity_at(dp, ws, frame_thr, thr_tables)
-            out["cat_counts"] = ws.at_cat_counts.cpu().numpy()
-            keep = ws.at_keep
+            keep, counts = self._kept(frame_thr, thr_tables)
+            out["cat_counts"] = counts.cpu().numpy()
             rows = {k: [] for k in ("tp", "loc", "ass", "clear")}
             for t in range(len(keep)):
                 if "hota" in measures:

@@ -6,6 +6,7 @@ level's alone; the methods of TaoEval carry the documentation and call in here
 with the evaluator `ev`."""
 import numpy as np
 
+from ... import _lib
 from .._core import _params_cats
 
 
@@ -52,11 +53,24 @@ def score_thr_of(ev, score_thr):
 def _table_thr(ev, thr):
     """Thresholds [..., K] in the order of params.cat_ids as the tables' [...,
     K_table]: a category of the tables that params.cat_ids does not name gets
-    +inf (none of its tracks passes; its rows are not reported either)."""
-    if ev._cat_pos is None or not ev.params.use_cats:
+    +inf (none of its tracks passes; its rows are not reported either).  None
+    (no threshold) stays None."""
+    if thr is None or ev._cat_pos is None or not ev.params.use_cats:
         return thr
     out = np.full(thr.shape[:-1] + (len(ev.flat.cat_ids),), np.inf)
     out[..., ev._cat_pos] = thr
+    return out
+
+
+def _key(thr, *parts):
+    """The cache key of a result: `parts`, and the thresholds where the call had any."""
+    return parts if thr is None else parts + (thr.tobytes(),)
+
+
+def _with_score_thr(out, thr):
+    """The result `out` with "score_thr" where the call had one."""
+    if thr is not None:
+        out["score_thr"] = thr
     return out
 
 
@@ -111,8 +125,9 @@ def _windows(ev, vis_rng, vis_lbl):
         if vis_lbl is None:
             vis_lbl = lp.visibility_rng_lbl[:5]
     rng = np.asarray(vis_rng, dtype=np.float64).reshape(-1, 2)
-    if len(rng) > 8:
-        raise ValueError("vis_rng: up to 8 visibility windows")
+    if len(rng) > _lib.TRACK_ASSOCIATION_VIS:
+        raise ValueError("vis_rng: up to {} visibility windows".format(
+            _lib.TRACK_ASSOCIATION_VIS))
     if vis_lbl is None:
         vis_lbl = ["[{:g}, {:g}]".format(lo, hi) for lo, hi in rng.tolist()]
     vis_lbl = [str(x) for x in vis_lbl]
@@ -164,14 +179,15 @@ def occlusions(ev, frame_thr, vis_rng, recover, len_edges, per_track, per_episod
     rng = np.asarray(vis_rng, dtype=np.float64).reshape(-1)
     if len(rng) != 2 or not rng[0] <= rng[1]:
         raise ValueError("vis_rng: {} is not one window lo <= hi".format(vis_rng))
-    if int(recover) != recover or not 1 <= recover <= 64:
-        raise ValueError("recover: {} is not an integer in [1, 64]".format(recover))
+    if int(recover) != recover or not 1 <= recover <= _lib.TRACK_OCCLUSION_RECOVER:
+        raise ValueError("recover: {} is not an integer in [1, {}]".format(
+            recover, _lib.TRACK_OCCLUSION_RECOVER))
     edges = [int(x) for x in np.asarray(len_edges).reshape(-1).tolist()]
-    if not 1 <= len(edges) <= 8 or edges[0] != 1 \
+    if not 1 <= len(edges) <= _lib.TRACK_OCCLUSION_LEN or edges[0] != 1 \
             or any(a >= b for a, b in zip(edges, edges[1:])) \
             or edges != np.asarray(len_edges).reshape(-1).tolist():
-        raise ValueError("len_edges: {} is not 1 to 8 ascending integers that start at 1"
-                         .format(len_edges))
+        raise ValueError("len_edges: {} is not 1 to {} ascending integers that start at 1"
+                         .format(len_edges, _lib.TRACK_OCCLUSION_LEN))
     key = (frame_thr, float(rng[0]), float(rng[1]), int(recover), tuple(edges))
 
     def make():
@@ -245,8 +261,7 @@ def identity(ev, frame_thr, per_track, score_thr=None):
 
     def make():
         from ..._lib import IDENT_CAT_COLUMNS
-        t = ev._run.identity_table(frame_thr) if thr is None else \
-            ev._run.identity_table(frame_thr, _table_thr(ev, thr))
+        t = ev._run.identity_table(frame_thr, _table_thr(ev, thr))
         flat = ev._run.flat
         cat_counts = _params_cats(ev, t["cat_counts"], 0)
         idf1, idp, idr, total = _identity_numbers(cat_counts)
@@ -256,13 +271,11 @@ def identity(ev, frame_thr, per_track, score_thr=None):
                            np.diff(np.asarray(flat.gt_frame_off, dtype=np.int64))], axis=1)
         dt_tracks = np.stack([_track_ids(di[:, 0], gt_id), di[:, 1].astype(np.int64),
                               np.diff(np.asarray(flat.dt_frame_off, dtype=np.int64))], axis=1)
-        out = {"columns": list(IDENT_CAT_COLUMNS), "cat_counts": cat_counts,
-               "idf1": idf1, "idp": idp, "idr": idr, "total": total, "frame_thr": frame_thr,
-               "tracks": (gt_id, tracks), "dt_tracks": (dt_id, dt_tracks)}
-        if thr is not None:
-            out["score_thr"] = thr
-        return out
-    return _cached(ev._identity, frame_thr if thr is None else (frame_thr, thr.tobytes()), make,
+        return _with_score_thr(
+            {"columns": list(IDENT_CAT_COLUMNS), "cat_counts": cat_counts,
+             "idf1": idf1, "idp": idp, "idr": idr, "total": total, "frame_thr": frame_thr,
+             "tracks": (gt_id, tracks), "dt_tracks": (dt_id, dt_tracks)}, thr)
+    return _cached(ev._identity, _key(thr, frame_thr), make,
                    (("tracks", per_track), ("dt_tracks", per_track)))
 
 
@@ -271,12 +284,12 @@ HOTA_SCALARS = ("HOTA", "DetA", "AssA", "DetRe", "DetPr", "AssRe", "AssPr", "Loc
 
 def hota_alphas(alphas):
     """The localisation thresholds as float64: TrackEval's 19 for None, else 1 to
-    32 strictly ascending values in (0, 1]."""
+    _lib.TRACK_HOTA_ALPHAS (32) strictly ascending values in (0, 1]."""
     if alphas is None:
         return np.arange(0.05, 0.99, 0.05)
     a = np.asarray(alphas, dtype=np.float64).reshape(-1)
-    if not 1 <= len(a) <= 32:
-        raise ValueError("alphas: {} values; 1 to 32".format(len(a)))
+    if not 1 <= len(a) <= _lib.TRACK_HOTA_ALPHAS:
+        raise ValueError("alphas: {} values; 1 to {}".format(len(a), _lib.TRACK_HOTA_ALPHAS))
     if not ((a > 0) & (a <= 1)).all():
         raise ValueError("alphas: {} are not all in (0, 1]".format(a.tolist()))
     if (np.diff(a) <= 0).any():
@@ -345,9 +358,7 @@ def hota(ev, alphas, frame_thr, per_frame, score_thr=None):
     thr = score_thr_of(ev, score_thr)
 
     def make():
-        at = alphas - np.finfo(float).eps
-        t = ev._run.hota_table(at, frame_thr) if thr is None else \
-            ev._run.hota_table(at, frame_thr, _table_thr(ev, thr))
+        t = ev._run.hota_table(alphas - np.finfo(float).eps, frame_thr, _table_thr(ev, thr))
         flat = ev._run.flat
         counts = _params_cats(ev, t["cat_counts"], 0)[:, :4]
         tp, loc, ass = (_params_cats(ev, t[k], 0) for k in ("tp", "loc", "ass"))
@@ -361,12 +372,9 @@ def hota(ev, alphas, frame_thr, per_frame, score_thr=None):
         g_of = np.repeat(np.arange(len(foff) - 1), np.diff(foff))
         out["frames"] = (np.asarray(flat.gt_id, dtype=np.int64)[g_of], img,
                          _follower_ids(flat, cell, t["match"]), t["match_iou"])
-        if thr is not None:
-            out["score_thr"] = thr
-        return out
-    key = (alphas.tobytes(), frame_thr) if thr is None else \
-        (alphas.tobytes(), frame_thr, thr.tobytes())
-    return _cached(ev._hota, key, make, (("frames", per_frame),))
+        return _with_score_thr(out, thr)
+    return _cached(ev._hota, _key(thr, alphas.tobytes(), frame_thr), make,
+                   (("frames", per_frame),))
 
 
 def hota_lines(e):
@@ -435,9 +443,7 @@ def clear(ev, frame_thr, vis_rng, vis_lbl, per_track, per_frame, score_thr=None)
 
     def make():
         from ..._lib import CLEAR_VIS_COLUMNS
-        ann_vis = ev._gt_columns.ann_vis
-        t = ev._run.clear_table(frame_thr, rng, ann_vis) if thr is None else \
-            ev._run.clear_table(frame_thr, rng, ann_vis, _table_thr(ev, thr))
+        t = ev._run.clear_table(frame_thr, rng, ev._gt_columns.ann_vis, _table_thr(ev, thr))
         flat = ev._run.flat
         cc = np.concatenate([_params_cats(ev, t["ident_counts"], 0)[:, :4],
                              _params_cats(ev, t["cat_counts"], 0)], axis=1)
@@ -463,11 +469,8 @@ def clear(ev, frame_thr, vis_rng, vis_lbl, per_track, per_frame, score_thr=None)
         g_of = np.repeat(np.arange(len(foff) - 1), np.diff(foff))
         out["frames"] = (np.asarray(flat.gt_id, dtype=np.int64)[g_of], img,
                          _follower_ids(flat, cell, t["match"]), t["match_iou"], t["sw"])
-        if thr is not None:
-            out["score_thr"] = thr
-        return out
-    key = (frame_thr, rng.tobytes(), tuple(vis_lbl))
-    return _cached(ev._clear, key if thr is None else key + (thr.tobytes(),), make,
+        return _with_score_thr(out, thr)
+    return _cached(ev._clear, _key(thr, frame_thr, rng.tobytes(), tuple(vis_lbl)), make,
                    (("tracks", per_track), ("frames", per_frame)))
 
 
@@ -527,12 +530,12 @@ def default_score_thrs(dt_score):
 
 def curve_score_thrs(score_thrs, dt_score):
     """The curve's thresholds as float64[T]: default_score_thrs(dt_score) for None,
-    else 1 to 64 strictly ascending doubles, none a NaN."""
+    else 1 to _lib.TRACK_SCORE_THRS (64) strictly ascending doubles, none a NaN."""
     if score_thrs is None:
         return default_score_thrs(dt_score)
     a = np.asarray(score_thrs, dtype=np.float64).reshape(-1)
-    if not 1 <= len(a) <= 64:
-        raise ValueError("score_thrs: {} values; 1 to 64".format(len(a)))
+    if not 1 <= len(a) <= _lib.TRACK_SCORE_THRS:
+        raise ValueError("score_thrs: {} values; 1 to {}".format(len(a), _lib.TRACK_SCORE_THRS))
     if np.isnan(a).any():
         raise ValueError("score_thrs: {} hold a NaN".format(a.tolist()))
     if (np.diff(a) <= 0).any():

@@ -148,7 +148,7 @@ def _fake_eval(f, keep, vis, seen):
     f.tl_vid_start = np.arange(len(f.vid_ids), dtype=np.int64) * 1000
     f.tl_image_id = np.arange(len(f.vid_ids) * 1000, dtype=np.int64) + 7
 
-    def clear_table(frame_thr, vis_rng, ann_vis):
+    def clear_table(frame_thr, vis_rng, ann_vis, score_thr=None):
         seen.append((frame_thr, np.array(vis_rng)))
         cc, w = ref.table(f, frame_thr, keep, vis, vis_rng)
         ident = np.zeros((len(f.cat_ids), 6), np.int64)

@@ -109,7 +109,7 @@ def _fake_eval(f, keep, alphas_seen):
     f.tl_vid_start = np.arange(len(f.vid_ids), dtype=np.int64) * 1000
     f.tl_image_id = np.arange(len(f.vid_ids) * 1000, dtype=np.int64) + 7
 
-    def hota_table(alphas, frame_thr):
+    def hota_table(alphas, frame_thr, score_thr=None):
         alphas_seen.append(np.array(alphas))
         w = ref.stage(f, alphas, keep)
         cc = np.zeros((len(f.cat_ids), 6), np.int64)
