@@ -580,20 +580,22 @@ class Workspace:
             if dp.kind == "lvis":
                 self.ious_out = torch.empty(max(dp.n_iou, 1),
                                             dtype=torch.float64, device=dev)
-        # the on-request analyses (stage_scores, the error breakdown, its impact
-        # and its confusion; the track analyses: declare_track_products):
-        # allocated by their first call
-        self.scores = None
-        self.err_match_gt = self.err_dt_counts = self.err_gt_counts = self.err_dt_type = None
-        self.err_link_same = self.err_link_other = self.err_held = None
-        self.imp_ws = self.imp_precision = self.imp_num_gt = None
-        self.conf_ws = self.conf_off = self.conf_gt_cat = self.conf_counts = None
-        self.conf_n = 0                   # entries of the last stage_confusion
-        self.declare_track_products()
+        # the on-request analyses: allocated by their first call
+        self.declare_products()
         self.pairs_counted = False        # stage_track_iou counted the pairs' common frames
 
-    # What the stages of the track analyses keep with the workspace (_buffer,
-    # _workspace) or leave as their last result: None until a first call.
+    # What the on-request stages keep with the workspace (_buffer, _workspace)
+    # or leave as their last result: None until a first call.  stage_scores,
+    # the error breakdown, its impact and its confusion; *_order: the order[]
+    # of the last call, conf_n: the entries of the last stage_confusion.
+    ANALYSIS_PRODUCTS = (
+        "score_ws", "score_bytes", "scores", "score_order",
+        "err_ws", "err_bytes", "err_match_gt", "err_dt_counts", "err_gt_counts", "err_dt_type",
+        "err_link_same", "err_link_other", "err_held",
+        "imp_ws", "imp_bytes", "imp_precision", "imp_num_gt", "imp_order",
+        "conf_ws", "conf_bytes", "conf_off", "conf_gt_cat", "conf_counts", "conf_n")
+
+    # The track analyses.
     # ident_share holds the LAST run of taoamd_track_identity_share, whichever
     # stage asked for it (_identity_share): the shares at valid["share"], which
     # need not be the threshold of ident_keep / ident_gt / ident_dt /
@@ -614,14 +616,17 @@ class Workspace:
         "clear_row", "clear_q", "clear_iou", "clear_n", "clear_match", "clear_match_iou",
         "clear_sw", "clear_gt", "clear_cat_counts", "clear_vis_counts")
 
-    def declare_track_products(self):
-        for name in self.TRACK_PRODUCTS:
+    def declare_products(self):
+        for name in self.ANALYSIS_PRODUCTS + self.TRACK_PRODUCTS:
             setattr(self, name, None)
         # product -> the key it is valid for (_valid, _producing): "followers"
         # (assoc_best and kin), "share" (ident_share), "identity" (ident_keep,
-        # ident_gt, ident_dt, ident_cat_counts), each at its frame_thr; and a
+        # ident_gt, ident_dt, ident_cat_counts), each at its frame_thr; "match
+        # indices" (err_match_gt holds those of a completed match); and a
         # stage's own buffers ("<stage> buffers": _stage_buffers) at their sizes
         self.valid = {}
+
+    declare_track_products = declare_products     # (the name from before it set both tuples)
 
 
 def _order_of(ws):
@@ -1019,7 +1024,15 @@ def stage_match(dp, ws, scatter=True, groups=None, singles=None, match_gt=None):
     """`groups` / `singles`: (device table, first, count) -- a slice of a
     launch plan instead of the problem's whole plan (the phases of the
     multi-GPU exchange, dist.ShardedEval).  `match_gt`: a table for the in-cell
-    match indices of this one call, where the workspace keeps none."""
+    match indices of this one call, where the workspace keeps none; handed the
+    workspace's own error_match_gt(), the call produces "match indices"."""
+    if match_gt is not None and match_gt is ws.err_match_gt:
+        with _producing(ws, "match indices", ()):
+            return _match(dp, ws, scatter, groups, singles, match_gt)
+    return _match(dp, ws, scatter, groups, singles, match_gt)
+
+
+def _match(dp, ws, scatter, groups, singles, match_gt):
     if dp.n_dt == 0:        # nothing was detected: every cell is GT-only
         return
     lib, t, s = _lib.load(), dp.t, _stream()
@@ -1103,12 +1116,10 @@ def stage_scores(dp, ws):
     thread's thresholds.  Its buffers are allocated on the first call: a
     workspace that is never asked pays nothing."""
     lib, t, s = _lib.load(), dp.t, _stream()
-    if ws.scores is None:
-        ws.score_bytes = lib.taoamd_score_at_recall_workspace(dp.n_dt, dp.n_cat, dp.n_rng)
-        ws.score_ws = torch.empty(max(int(ws.score_bytes), 256), dtype=torch.uint8,
-                                  device=dp.device)
-        ws.scores = torch.empty((N_THR, N_REC, dp.n_cat, dp.n_rng), dtype=torch.float64,
-                                device=dp.device)
+    _stage_buffers(
+        ws, dp.device, "score", (), lambda: lib.taoamd_score_at_recall_workspace(
+            dp.n_dt, dp.n_cat, dp.n_rng),
+        lambda: (("scores", (N_THR, N_REC, dp.n_cat, dp.n_rng), torch.float64),))
     # the scores lie where the detections are; so do rows left in cell order,
     # rows scattered to their sorted places need order[] for the scores alone
     ws.score_order = ws.order        # (derived on demand: alive while the pass runs)
@@ -1134,11 +1145,12 @@ def error_match_gt(dp, ws):
     workspace keeps none of its own: int32[n_dt, n_rng * 10], allocated on the
     first call and kept with the workspace (240 bytes a row: 5.1 GB at 21.4 M
     rows; `ws.err_match_gt = None` gives it back).  A caller that runs the match
-    itself passes it as stage_match(match_gt=...) / run_guarded(match_gt=...)."""
+    itself passes it as stage_match(match_gt=...) / run_guarded(match_gt=...):
+    that match produces "match indices", the allocation alone does not."""
     if ws.err_match_gt is None:
-        ws.err_match_gt = torch.empty((max(dp.n_dt, 1), dp.n_rng * N_THR), dtype=torch.int32,
-                                      device=dp.device)
-    return ws.err_match_gt
+        ws.valid.pop("match indices", None)       # (a new table holds none)
+    return _buffer(ws, dp.device, "err_match_gt", (max(dp.n_dt, 1), dp.n_rng * N_THR),
+                   torch.int32)
 
 
 def _error_tabs(dp):
@@ -1165,36 +1177,59 @@ def _error_tabs(dp):
 def _error_buffers(dp, ws, lib, per_detection, links):
     """The breakdown's buffers, each allocated where first asked for: the
     counts and the level's workspace, ws.err_dt_type with `per_detection`, the
-    link tables and ws.err_held with `links`."""
-    dev = dp.device
-    if ws.err_dt_counts is None:
-        sized = lib.taoamd_error_types_workspace if dp.kind == "lvis" else \
-            lib.taoamd_track_error_types_workspace
-        ws.err_bytes = sized(dp.n_dt, dp.n_gt, dp.n_rng)
-        ws.err_ws = torch.empty(max(int(ws.err_bytes), 256), dtype=torch.uint8, device=dev)
-        ws.err_dt_counts = torch.empty((dp.n_rng, dp.n_cat, 7), dtype=torch.int64, device=dev)
-        ws.err_gt_counts = torch.empty((dp.n_rng, dp.n_cat, 3), dtype=torch.int64, device=dev)
-    shape = (max(dp.n_dt, 1), dp.n_rng)
-    if per_detection and ws.err_dt_type is None:
-        ws.err_dt_type = torch.empty(shape, dtype=torch.uint8, device=dev)
-    if links and ws.err_link_same is None:
-        ws.err_link_same = torch.empty(shape, dtype=torch.int32, device=dev)
-        ws.err_link_other = torch.empty(shape, dtype=torch.int32, device=dev)
-        ws.err_held = torch.empty((dp.n_rng, max(dp.n_gt, 1)), dtype=torch.uint8, device=dev)
+    link tables and ws.err_held with `links`.  What a caller may give back by
+    name (here the link tables) is under no key: asked for on every call."""
+    sized = lib.taoamd_error_types_workspace if dp.kind == "lvis" else \
+        lib.taoamd_track_error_types_workspace
+    dev, shape, u8, i64 = dp.device, (max(dp.n_dt, 1), dp.n_rng), torch.uint8, torch.int64
+    _stage_buffers(
+        ws, dev, "err", (bool(per_detection), bool(links)),
+        lambda: sized(dp.n_dt, dp.n_gt, dp.n_rng), lambda: (
+            ("err_dt_counts", (dp.n_rng, dp.n_cat, 7), i64),
+            ("err_gt_counts", (dp.n_rng, dp.n_cat, 3), i64))
+        + ((("err_dt_type", shape, u8),) if per_detection else ())
+        + ((("err_held", (dp.n_rng, max(dp.n_gt, 1)), u8),) if links else ()))
+    if links:
+        _buffer(ws, dev, "err_link_same", shape, torch.int32)
+        _buffer(ws, dev, "err_link_other", shape, torch.int32)
+
+
+def _impact_buffers(dp, ws, lib, name):
+    """The buffers of the sweep of the nine variants through the entry point `name`."""
+    sizes, fixes = (dp.n_cat, dp.n_rng), len(_lib.ERROR_FIXES)
+    _workspace(ws, dp.device, "imp", getattr(lib, name + "_workspace")(dp.n_dt, dp.n_gt, *sizes))
+    _buffer(ws, dp.device, "imp_precision", (fixes, N_REC) + sizes, torch.float64)
+    _buffer(ws, dp.device, "imp_num_gt", (fixes,) + sizes, torch.int32)
+
+
+def _confusion_buffers(dp, ws, lib):
+    """The histogram's workspace and its row offsets; the entries: _confusion_entries."""
+    _workspace(ws, dp.device, "conf",
+               lib.taoamd_confusion_workspace(dp.n_dt, dp.n_gt, dp.n_cat, dp.n_rng))
+    _buffer(ws, dp.device, "conf_off", dp.n_rng * dp.n_cat + 1, torch.int64)
+
+
+def _confusion_entries(dp, ws, n):
+    """ws.conf_n = n and room for n entries, regrown where a call finds more."""
+    ws.conf_n = n
+    _buffer(ws, dp.device, "conf_gt_cat", max(n, 1), torch.int32)
+    _buffer(ws, dp.device, "conf_counts", (max(n, 1), 4), torch.int32)
 
 
 def _error_match_gt(dp, ws):
     """The match indices the breakdown reads: the workspace's own table (detail
-    mode), else error_match_gt(), filled by one more match unless the caller's
-    match already wrote it."""
+    mode), else error_match_gt(), filled by one more match unless the workspace
+    holds "match indices": a completed match, this one or the caller's, wrote
+    the table that is there."""
     if ws.match_gt is not None:
         return ws.match_gt
-    if ws.err_match_gt is None and dp.n_dt:
-        stage_match(dp, ws, scatter=not ws.cell_order, match_gt=error_match_gt(dp, ws))
+    if dp.n_dt and (ws.err_match_gt is None or not _valid(ws, "match indices", ())):
+        with _producing(ws, "match indices", ()):
+            stage_match(dp, ws, scatter=not ws.cell_order, match_gt=error_match_gt(dp, ws))
     return ws.err_match_gt
 
 
-def _error_pass(dp, ws, slot, tb, per_detection, links, kind):
+def _error_pass(dp, ws, slot, tb, kind, per_detection=False, links=False):
     """stage_error_types (`kind` "lvis") / stage_track_error_types ("tao"):
     `kind` is the level the caller's name promises, refused where the problem
     is of the other.  `links`: through the level's *_links entry point, which
@@ -1240,16 +1275,10 @@ def _error_impact(dp, ws, slot, tb, kind):
     """stage_error_impact (`kind` "lvis") / stage_track_error_impact ("tao"): the
     level's links pass, then the sweep of the nine variants through the level's
     entry point -- the two share their signature."""
-    _error_pass(dp, ws, slot, tb, True, True, kind)
-    lib, t, dev = _lib.load(), dp.t, dp.device
+    _error_pass(dp, ws, slot, tb, kind, per_detection=True, links=True)
+    lib, t = _lib.load(), dp.t
     name = "taoamd_error_impact" if kind == "lvis" else "taoamd_track_error_impact"
-    if ws.imp_ws is None:
-        ws.imp_bytes = getattr(lib, name + "_workspace")(dp.n_dt, dp.n_gt, dp.n_cat, dp.n_rng)
-        ws.imp_ws = torch.empty(max(int(ws.imp_bytes), 256), dtype=torch.uint8, device=dev)
-        ws.imp_precision = torch.empty((len(_lib.ERROR_FIXES), N_REC, dp.n_cat, dp.n_rng),
-                                       dtype=torch.float64, device=dev)
-        ws.imp_num_gt = torch.empty((len(_lib.ERROR_FIXES), dp.n_cat, dp.n_rng),
-                                    dtype=torch.int32, device=dev)
+    _impact_buffers(dp, ws, lib, name)
     ws.imp_order = ws.order          # (derived on demand: alive while the pass runs)
     _lib.check(getattr(lib, name)(
         dp.n_dt, dp.n_gt, dp.n_cat, dp.n_rng, _ptr(t["cat_off"]), _ptr(ws.imp_order),
@@ -1271,7 +1300,7 @@ def stage_error_types(dp, ws, slot, tb, per_detection=False):
     error_match_gt(), filled here by one more match with match_gt requested
     unless the caller's match already wrote it.  Buffers are allocated on the
     first call."""
-    _error_pass(dp, ws, slot, tb, per_detection, False, "lvis")
+    _error_pass(dp, ws, slot, tb, "lvis", per_detection=per_detection)
 
 
 def stage_error_impact(dp, ws, slot, tb):
@@ -1303,7 +1332,7 @@ def stage_track_error_types(dp, ws, slot, tb, per_detection=False):
     workspace's own table (detail mode), else from error_match_gt() (800 bytes
     a row), filled here by one more match unless the caller's match already
     wrote it.  Buffers are allocated on the first call."""
-    _error_pass(dp, ws, slot, tb, per_detection, False, "tao")
+    _error_pass(dp, ws, slot, tb, "tao", per_detection=per_detection)
 
 
 def stage_track_error_impact(dp, ws, slot, tb):
@@ -1339,22 +1368,15 @@ def stage_confusion(dp, ws, slot, tb):
     (range, category); the entries 20 bytes each, regrown where a call finds
     more (`ws.conf_ws = ws.conf_off = ws.conf_gt_cat = ws.conf_counts = None`
     gives them back)."""
-    _error_pass(dp, ws, slot, tb, True, True, dp.kind)
-    lib, t, dev, s = _lib.load(), dp.t, dp.device, _stream()
-    n_rows = dp.n_rng * dp.n_cat
-    if ws.conf_ws is None:
-        ws.conf_bytes = lib.taoamd_confusion_workspace(dp.n_dt, dp.n_gt, dp.n_cat, dp.n_rng)
-        ws.conf_ws = torch.empty(max(int(ws.conf_bytes), 256), dtype=torch.uint8, device=dev)
-        ws.conf_off = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
+    _error_pass(dp, ws, slot, tb, dp.kind, per_detection=True, links=True)
+    lib, t, s = _lib.load(), dp.t, _stream()
+    _confusion_buffers(dp, ws, lib)
     tables = (dp.n_dt, dp.n_gt, dp.n_cat, dp.n_rng, _ptr(t["cat_off"]), _ptr(t["dt_score"]),
               _ptr(t["dt_cat"]), _ptr(ws.err_dt_type), _ptr(ws.err_link_other),
               _ptr(t["gt_cat"]), _ptr(ws.err_held), _ptr(ws.conf_off))
     _lib.check(lib.taoamd_confusion_count(*tables, _ptr(ws.conf_ws), ws.conf_bytes, s),
                "taoamd_confusion_count")
-    ws.conf_n = int(ws.conf_off[-1].item())         # (synchronises)
-    if ws.conf_gt_cat is None or ws.conf_gt_cat.numel() < ws.conf_n:
-        ws.conf_gt_cat = torch.empty(max(ws.conf_n, 1), dtype=torch.int32, device=dev)
-        ws.conf_counts = torch.empty((max(ws.conf_n, 1), 4), dtype=torch.int32, device=dev)
+    _confusion_entries(dp, ws, int(ws.conf_off[-1].item()))       # (synchronises)
     _lib.check(lib.taoamd_confusion_fill(
         *tables, ws.conf_n, _ptr(ws.conf_gt_cat), _ptr(ws.conf_counts), _ptr(ws.conf_ws),
         ws.conf_bytes, s), "taoamd_confusion_fill")
@@ -1403,7 +1425,7 @@ def _vis_windows(dp, vis_rng):
 
 
 def _buffer(ws, dev, name, shape, dtype, exact=False):
-    """The buffer rule of the track stages: ws.<name> is allocated by the first
+    """The buffer rule of the on-request stages: ws.<name> is allocated by the first
     call that asks for it and kept with the workspace.  `shape`: an int or a
     tuple.  By default at least shape[0] leading rows of the trailing shape: a
     larger buffer stays, a smaller one is regrown, and the buffer is handed out
@@ -1427,7 +1449,7 @@ def _buffer(ws, dev, name, shape, dtype, exact=False):
 
 
 def _workspace(ws, dev, stage, nbytes):
-    """The workspace pair of a track stage: ws.<stage>_ws of ws.<stage>_bytes (256
+    """The workspace pair of an on-request stage: ws.<stage>_ws of ws.<stage>_bytes (256
     at least), allocated by the first call and regrown where a call needs more
     than it holds."""
     if getattr(ws, stage + "_ws") is None or getattr(ws, stage + "_bytes") < nbytes:
@@ -1454,11 +1476,12 @@ def _valid(ws, product, key):
 
 
 class _producing:
-    """The validity rule of what the track stages reuse, as a context around the
+    """The validity rule of what the on-request stages reuse, as a context around the
     lines that write a product: the key is cleared before the first launch that
     writes it and set after the last check passed, so the product is valid for
     no key after the lines raised anywhere.  The products: the results a later
-    stage reads ("followers", "share", "identity", at their frame_thr) and each
+    stage reads ("followers", "share", "identity", at their frame_thr; "match
+    indices", the breakdown's, at ()) and each
     stage's own buffers ("<stage> buffers", at the sizes they depend on beyond
     the problem's: a call with the same sizes asks for none again)."""
 

@@ -184,7 +184,8 @@ def track_level(a, gt, dt, dev, V):
         engine.stage_track_error_impact(dp, ws, 0, a.bg_thr)
         torch.cuda.synchronize()
         res["track_error_types_links"] = timed(
-            lambda: engine._error_pass(dp, ws, 0, a.bg_thr, True, True, "tao"))
+            lambda: engine._error_pass(dp, ws, 0, a.bg_thr, dp.kind, per_detection=True,
+                                       links=True))
         res["track_error_impact_links_and_sweep"] = timed(
             lambda: engine.stage_track_error_impact(dp, ws, 0, a.bg_thr))
         _lib.kernel_timing(True)
@@ -232,7 +233,8 @@ def confusion(a, res, dp, ws, timed):
             *tables, ws.conf_n, ws.conf_gt_cat.data_ptr(), ws.conf_counts.data_ptr(),
             ws.conf_ws.data_ptr(), ws.conf_bytes, stream), "taoamd_confusion_fill")
     res["confusion_links_pass"] = timed(
-        lambda: engine._error_pass(dp, ws, 0, a.bg_thr, True, True, dp.kind))
+        lambda: engine._error_pass(dp, ws, 0, a.bg_thr, dp.kind, per_detection=True,
+                                   links=True))
     res["confusion_count"] = timed(count)
     res["confusion_fill"] = timed(fill)
     res["confusion_stage"] = timed(lambda: engine.stage_confusion(dp, ws, 0, a.bg_thr))
@@ -818,7 +820,8 @@ def main():
         engine.stage_error_impact(dp, ws, 0, a.bg_thr)
         torch.cuda.synchronize()
         res["error_types_links"] = timed(
-            lambda: engine._error_pass(dp, ws, 0, a.bg_thr, True, True, "lvis"))
+            lambda: engine._error_pass(dp, ws, 0, a.bg_thr, dp.kind, per_detection=True,
+                                       links=True))
         res["error_impact_links_and_sweep"] = timed(
             lambda: engine.stage_error_impact(dp, ws, 0, a.bg_thr))
         _lib.kernel_timing(True)
